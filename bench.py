@@ -21,6 +21,13 @@ FRESH set of rank processes in --mode replicas after a sharded failure, and the 
 carries config.sharded_error.
 
 Prints ONE JSON line on rank 0 (see the contract in the task description).
+
+A plain run (`python bench.py --gpus 1 --steps N --warmup W`) does only what the headline needs: it builds the text, warms
+up, times the N steps and prints the line (metric, value, unit, ms_per_step, ...).  --full adds everything else this file
+measures or checks, after the timed steps: the device-side verification of the last SA and its pinned hash, the per-class
+kernel profile and roofline, the host S -> host SA leg, the exact-order, --harsh and dm-size legs, the CPU baselines, the
+FM-index leg, and for sharded runs the extra phase-timed step and the scaling model.  --dump-outputs DIR writes what the
+last timed step computed (dump_outputs) so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -706,6 +713,28 @@ def dm_leg(ctx_factory, device, k=256, threads=24):
     return out
 
 
+DUMP_SAMPLE = 3_000_000  # suffix-array entries --dump-outputs writes at most: 2 x 24 MB as float64
+DUMP_SEED = 20_251_016   # the sampled positions depend on n and this seed only, never on the build
+
+
+def dump_outputs(dirname, SA, n):
+    """--dump-outputs: the suffix array the last timed step left for its caller (SA[0..n], u32 on the device), as
+    DIR/sa.npy (float64, exact for every u32) beside DIR/sa_positions.npy (the indices into SA those values were read
+    from).  Up to DUMP_SAMPLE entries the whole array; beyond, a fixed sample: sorted positions drawn with DUMP_SEED, plus
+    the first and the last entry."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    if n + 1 <= DUMP_SAMPLE:
+        pos = np.arange(n + 1, dtype=np.int64)
+        vals = SA[:n + 1].cpu().numpy()
+    else:
+        pos = np.random.default_rng(DUMP_SEED).integers(0, n + 1, DUMP_SAMPLE - 2, dtype=np.int64)
+        pos = np.unique(np.concatenate([pos, np.array([0, n], np.int64)]))
+        vals = SA[torch.from_numpy(pos).to(SA.device)].cpu().numpy()
+    np.save(os.path.join(dirname, "sa.npy"), vals.view(np.uint32).astype(np.float64))
+    np.save(os.path.join(dirname, "sa_positions.npy"), pos.astype(np.float64))
+
+
 class _DevArray:
     def __init__(self, ptr, count):
         self.__cuda_array_interface__ = {"shape": (int(count),), "typestr": "|u1", "data": (int(ptr), False), "version": 2}
@@ -714,8 +743,14 @@ class _DevArray:
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
-    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=3, help="timed steps (>= 1)")
+    ap.add_argument("--warmup", type=int, default=1, help="untimed steps before them (>= 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, every other figure and check of this file (see the module docstring); "
+                         "the options below that name a leg, a baseline, the profile or the verification act only with it")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the suffix array of the last timed step (a fixed sample of it beyond %d entries) to "
+                         "DIR/sa.npy and DIR/sa_positions.npy (float64)" % DUMP_SAMPLE)
     ap.add_argument("--text-len", dest="n", type=int, default=CHM13_N, help="text length (default: chm13v2.0 size)")
     ap.add_argument("--fasta", default=None,
                     help="sort this FASTA / plain-text file (e.g. a real chm13v2.0.fa) instead of the synthetic text: read, "
@@ -770,6 +805,13 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        # a plain run: set-up, warm-up, the timed steps, --dump-outputs and the line; nothing else
+        args.no_profile = args.no_verify = args.no_fnv = True
+        args.no_e2e = args.no_exact = args.no_sensitivity = args.no_dm = args.no_fm = True
+        args.cpu_sample = 0
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
         # no launcher above us: start the ranks ourselves -- before torch is imported or HIP is touched
@@ -941,12 +983,14 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=torch.device("cpu") if dist.get_backend() == "gloo" else device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, SA, n)  # before anything below writes SA again
 
     # sharded runs: ONE extra step after the timed region with a device synchronisation at every phase boundary (what
     # --sharded-timings does to every step): rank 0's phase times, the inputs of DESIGN.md 7's expected-curve table, in every
-    # N > 1 line -- so that a measured curve can be checked against the model phase by phase
+    # N > 1 --full line -- so that a measured curve can be checked against the model phase by phase
     phase_extra = None
-    if sharded and phase_ms is None:
+    if sharded and phase_ms is None and args.full:
         phase_extra = {}
         multi_gpu.sharded_suffix_sort(backend, n, SA=SA if rank == 0 else None, timings=phase_extra)
         barrier()
@@ -979,7 +1023,7 @@ def main():
         if phase_extra:
             out["config"]["sharded_phase_ms_rank0"] = dict(phase_extra)
             out["config"]["sharded_phase_ms_from"] = "one extra step after the timed region, phases closed by device synchronisations"
-        if sharded:
+        if sharded and args.full:
             out["config"]["scaling_model"] = scaling_model(world, n, last_stats["m"] if world == 1 else None)
         if multi is not None:
             out["config"]["parallelism"] = ("ONE process driving devices %s through kiss_hip_multi_* (LMS sort sharded by key "
@@ -987,7 +1031,8 @@ def main():
             out["config"]["multi_phase_ms"] = {kk: v / args.steps for kk, v in multi_phase.items()}
             # the model's expectation for as many DISTINCT devices as shares were asked for (shares of one GPU, the only
             # form a one-GPU box can run, compete for it: they price the mechanics, not the curve)
-            out["config"]["scaling_model"] = scaling_model(len(args.multi_abi.split(",")), n)
+            if args.full:
+                out["config"]["scaling_model"] = scaling_model(len(args.multi_abi.split(",")), n)
         if not args.no_verify:
             out.update(verify_leg(ctx, S, SA, n, k, args.seed, args.iid or data == "file", algo,
                                   with_fnv=(world == 1 and not args.no_fnv), harsh=args.harsh))

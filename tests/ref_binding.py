@@ -1,7 +1,8 @@
 """ctypes binding of oracle/_ref/libkiss_ref.so: the reference's OWN get_lms / PackedDNAString / put_lms_suffix /
 induced_sort compiled unmodified from /root/reference (oracle/ref_driver.cpp says what is and is not reference code).
 TEST INFRASTRUCTURE ONLY.  The .so is built in the container that holds /root/reference and travels to the GPU box as a
-binary; where neither the tree nor the binary exists, available() is False and the tests that need it skip."""
+binary; where neither the tree nor the binary exists, available() is False (tests/test_ref_pin.py reads what this
+library returned from tests/golden/ref_pin_record.json, written by tests/golden/make_ref_pin_record.py)."""
 import ctypes
 import os
 import subprocess

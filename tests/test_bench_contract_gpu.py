@@ -18,7 +18,7 @@ def run_bench(*extra):
         env.pop(k, None)
     env["MASTER_ADDR"] = "127.0.0.1"
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--text-len", "3000000", "--steps", "2",
-                        "--warmup", "1", *extra], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+                        "--warmup", "1", "--full", *extra], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, p.stdout  # stdout carries the result line and nothing else
@@ -103,8 +103,8 @@ def test_bench_takes_a_fasta_path(tmp_path):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--fasta", str(fa), "--steps", "2", "--warmup", "1",
-                        "--cpu-sample", "200000", "--no-fm", "--no-dm", "--no-e2e"], cwd=ROOT, env=env, capture_output=True,
-                       text=True, timeout=600)
+                        "--full", "--cpu-sample", "200000", "--no-fm", "--no-dm", "--no-e2e"], cwd=ROOT, env=env,
+                       capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     out = json.loads([ln for ln in p.stdout.splitlines() if ln.strip()][0])
     assert out["data"] == "file" and out["config"]["n"] == S.size and "g.fa" in out["config"]["workload"]
@@ -152,7 +152,7 @@ def test_the_two_rank_code_path_of_bench_with_both_ranks_on_the_one_gpu(launcher
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     bench_args = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--text-len", "30000000", "--steps", "2", "--warmup", "1",
-                  "--cpu-sample", "0", "--no-fnv", "--rank-timeout", "600"]
+                  "--full", "--cpu-sample", "0", "--no-fnv", "--rank-timeout", "600"]
     if launcher == "self":  # bench.py starts its two ranks itself
         cmd = [sys.executable] + bench_args
     else:  # the driver's form: one rank per process under torch.distributed.run
@@ -169,3 +169,42 @@ def test_the_two_rank_code_path_of_bench_with_both_ranks_on_the_one_gpu(launcher
     assert set(cfg["sharded_phase_ms_rank0"]) >= {"sort", "induce"} or len(cfg["sharded_phase_ms_rank0"]) >= 4
     assert cfg["scaling_model"]["gpus"] == 2
     assert j["value"] == pytest.approx(30000000 * 2 / (2 * j["ms_per_step"] / 1e3), rel=1e-6)
+
+
+@pytest.mark.gpu
+def test_a_plain_run_times_its_steps_and_dumps_the_suffix_array_it_computed(tmp_path):
+    """No --full: the line carries the headline and nothing measured or checked beside it; --dump-outputs writes the SA of
+    the last timed step (the whole array at this size), equal to the oracle's on the same text and the same in every run."""
+    import numpy as np
+    import torch
+    from tests import oracle_binding
+    sys.path.insert(0, ROOT)
+    import bench
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+        env.pop(k, None)
+    n, dumps = 2_000_000, []
+    for steps in ("3", "1"):
+        d = tmp_path / ("out_steps%s" % steps)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--text-len", str(n), "--steps", steps,
+                            "--warmup", "1", "--dump-outputs", str(d)], cwd=ROOT, env=env, capture_output=True, text=True,
+                           timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, p.stdout
+        out = json.loads(lines[0])
+        assert out["steps"] == int(steps) and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0
+        assert out["value"] == pytest.approx(n * int(steps) / (int(steps) * out["ms_per_step"] / 1e3), rel=1e-6)
+        assert out["metric"].startswith("bases/sec suffix_sort") and out["unit"] == "bases/s" and out["dtype"] == "u8"
+        assert out["higher_is_better"] is True
+        for leg in ("verified", "end_to_end", "exact_order", "sensitivity", "dm_size", "fm_query", "cpu_baseline_dm"):
+            assert leg not in out, leg
+        assert out["roofline"] is None and out["cpu_baseline"] is None
+        sa, pos = np.load(d / "sa.npy"), np.load(d / "sa_positions.npy")
+        assert sa.dtype == np.float64 and pos.dtype == np.float64 and sa.size == pos.size == n + 1
+        assert np.array_equal(pos, np.arange(n + 1))
+        dumps.append(sa)
+    assert np.array_equal(dumps[0], dumps[1])
+    S = bench.gen_text_device(n, 2, torch.device("cuda", 0)).cpu().numpy()
+    ref = oracle_binding.load().suffix_sort(S, 256)
+    assert np.array_equal(dumps[0], ref.astype(np.float64))

@@ -193,3 +193,30 @@ def test_ranks_agree_on_the_outcome_of_the_sharded_rehearsal():
         assert r2 is not None and r3 is not None  # both ranks fall back, whoever saw the failure
     assert got[1][2] == "rank 1: RuntimeError: boom" and "another rank" in got[0][2]
     assert "suffix array fails" in got[0][3] and "another rank" in got[1][3]
+
+
+def test_dump_outputs_writes_a_fixed_sample_of_a_large_suffix_array(tmp_path):
+    # bench.dump_outputs on a CPU tensor: beyond DUMP_SAMPLE entries the positions depend on n alone, include both ends,
+    # and the values are the array's at those positions, exact in float64 (u32 values above 2^31 included)
+    import numpy as np
+    import torch
+    bench = _bench()
+    n = bench.DUMP_SAMPLE + 12_345
+    vals = (np.arange(n + 1, dtype=np.uint64) * 2_654_435_761 % (1 << 32)).astype(np.uint32)
+    SA = torch.from_numpy(vals.view(np.int32).copy())
+    bench.dump_outputs(str(tmp_path / "a"), SA, n)
+    bench.dump_outputs(str(tmp_path / "b"), SA, n)
+    pos, sa = np.load(tmp_path / "a" / "sa_positions.npy"), np.load(tmp_path / "a" / "sa.npy")
+    assert pos.dtype == sa.dtype == np.float64 and pos.size == sa.size <= bench.DUMP_SAMPLE
+    assert (pos.nbytes + sa.nbytes) <= 64 << 20
+    assert pos[0] == 0 and pos[-1] == n and np.all(np.diff(pos) > 0)
+    assert np.array_equal(sa, vals[pos.astype(np.int64)].astype(np.float64)) and sa.max() >= 2 ** 31
+    assert np.array_equal(pos, np.load(tmp_path / "b" / "sa_positions.npy"))
+    assert np.array_equal(sa, np.load(tmp_path / "b" / "sa.npy"))
+
+
+def test_steps_below_one_are_refused_before_anything_runs():
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + bad, capture_output=True, text=True,
+                           timeout=120)
+        assert p.returncode == 2 and "--steps must be >= 1" in p.stderr and p.stdout.strip() == ""
