@@ -396,6 +396,47 @@ int kiss_hip_fmi_query_batch_host(const kiss_hip_fmi_view *fmi, const uint8_t *p
                                   uint32_t *beg, uint32_t *end, uint64_t *hit_count_total, uint64_t *checksum,
                                   uint32_t *offsets, uint64_t *offsets_index, uint64_t offsets_capacity, int device);
 
+/* ---- FM-index, any instantiation: FMIndex<SA_INTV, uint32_t, ...>{.LOOKUP_LEN} ---------------------------------
+ * SA_INTV in 1..KISS_HIP_FMI_MAX_SA_INTV, LOOKUP_LEN in 0..KISS_HIP_FMI_MAX_LOOKUP_LEN; anything else is
+ * KISS_HIP_E_UNSUPPORTED.  (SA_INTV, LOOKUP_LEN) = (4, 0) is the index of the calls above, byte for byte.
+ * .fmi layout (fm_index.hpp:591-646): cnt, pri, bwt, occ1, occ2, sa_, lookup_, then b_ and b_occ_ only if SA_INTV != 1.
+ *   sa_     : SA_INTV == 1: the whole SA (N entries); else the values SA[i] with SA[i] % SA_INTV == 0 in row order.
+ *   lookup_ : 4^LOOKUP_LEN + 1 entries; lookup_[K] = beg of the backward search of the K-th LOOKUP_LEN-mer (Codec::hash:
+ *             last character in the low bits) from (0, N), lookup_[4^LOOKUP_LEN] = N (build_lookup, :238-270). */
+#define KISS_HIP_FMI_MAX_SA_INTV 32u
+#define KISS_HIP_FMI_MAX_LOOKUP_LEN 14u
+typedef struct kiss_hip_fmi_view_ex {
+    kiss_hip_fmi_view base;  /* base.sa_intv = SA_INTV; base.b / base.b_occ NULL when SA_INTV == 1 */
+    uint32_t lookup_len;     /* LOOKUP_LEN */
+    const uint32_t *lookup;  /* 4^lookup_len + 1 entries */
+} kiss_hip_fmi_view_ex;
+typedef struct kiss_hip_fmi_sizes_ex {
+    kiss_hip_fmi_sizes base; /* sa_entries = ceil(N / SA_INTV); b_words = b_occ_entries = 0 when SA_INTV == 1 */
+    uint64_t lookup_entries; /* 4^LOOKUP_LEN + 1 */
+} kiss_hip_fmi_sizes_ex;
+int kiss_hip_fmi_sizes_ex_for(uint64_t n, uint32_t sa_intv, uint32_t lookup_len, kiss_hip_fmi_sizes_ex *out);
+/* build from a device text and its SA: the arrays of kiss_hip_fmi_build_dev plus lookup_ (d_lookup, lookup_entries);
+ * d_b / d_b_occ may be NULL when sa_intv == 1.  Device times under KISS_HIP_K_FM_BUILD. */
+int kiss_hip_fmi_build_ex_dev(kiss_hip_ctx *ctx, const uint8_t *d_S, uint64_t n, const uint32_t *d_SA, uint32_t sa_intv,
+                              uint32_t lookup_len, uint8_t *d_bwt, uint32_t *d_occ1, uint8_t *d_occ2, uint32_t *d_sa,
+                              uint64_t *d_b, uint32_t *d_b_occ, uint32_t *d_lookup, uint32_t cnt_out[4], uint32_t *pri_out,
+                              void *stream);
+/* get_range(pattern, stop_cnt) (fm_index.hpp:553-584) then get_offsets(beg, end) (:453-501) for every pattern; the
+ * arguments of kiss_hip_fmi_query_batch_dev plus stop_cnt (0: no early stop; 0xFFFFFFFF: stop_cnt + 1 wraps to 0, never
+ * stops) and offs (device, Q entries, may be NULL): get_range's third value, the characters left unmatched. */
+int kiss_hip_fmi_query_ex_dev(kiss_hip_ctx *ctx, const kiss_hip_fmi_view_ex *fmi, const uint8_t *patterns, uint32_t L,
+                              uint64_t Q, uint32_t stop_cnt, uint32_t *beg, uint32_t *end, uint32_t *offs,
+                              uint64_t *hit_count_total, uint64_t *checksum, uint32_t *offsets, uint64_t *offsets_index,
+                              uint64_t offsets_capacity, void *stream);
+/* host-pointer forms, as kiss_hip_fmi_build_host / kiss_hip_fmi_query_batch_host */
+int kiss_hip_fmi_build_ex_host(const uint8_t *S, uint64_t n, const uint32_t *SA_or_null, uint32_t sa_intv,
+                               uint32_t lookup_len, uint8_t *bwt, uint32_t *occ1, uint8_t *occ2, uint32_t *sa, uint64_t *b,
+                               uint32_t *b_occ, uint32_t *lookup, uint32_t cnt_out[4], uint32_t *pri_out, int device);
+int kiss_hip_fmi_query_ex_host(const kiss_hip_fmi_view_ex *fmi, const uint8_t *patterns, uint32_t L, uint64_t Q,
+                               uint32_t stop_cnt, uint32_t *beg, uint32_t *end, uint32_t *offs, uint64_t *hit_count_total,
+                               uint64_t *checksum, uint32_t *offsets, uint64_t *offsets_index, uint64_t offsets_capacity,
+                               int device);
+
 /* ---- General alphabet (bytes): exact suffix array ---------------------------------
  * Replaces KISS1Sorter::get_suffix_array -> kiss1_suffix_array (kiss1_core.hpp:270-311), reachable only from the
  * reference's tests / experiments.  For that entry only the k-order property is defined (its comparator has no

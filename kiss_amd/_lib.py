@@ -89,6 +89,19 @@ class FmiView(ctypes.Structure):
     ]
 
 
+class FmiViewEx(ctypes.Structure):
+    _fields_ = [("base", FmiView), ("lookup_len", ctypes.c_uint32), ("lookup", ctypes.c_void_p)]
+
+
+class FmiSizes(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_uint64) for k in ("n_sa", "bwt_bytes", "occ1_entries", "occ2_bytes", "sa_entries", "b_words",
+                                               "b_occ_entries")]
+
+
+class FmiSizesEx(ctypes.Structure):
+    _fields_ = [("base", FmiSizes), ("lookup_entries", ctypes.c_uint64)]
+
+
 class KissHipError(RuntimeError):
     def __init__(self, status, where, detail=""):
         self.status = status
@@ -182,6 +195,16 @@ def load(hooks=None):
     lib.kiss_hip_fmi_build_dev.argtypes = [
         vp, vp, ctypes.c_uint64, vp, ctypes.c_uint32, vp, vp, vp, vp, vp, vp,
         ctypes.POINTER(ctypes.c_uint32 * 4), ctypes.POINTER(ctypes.c_uint32), vp]
+    u32 = ctypes.c_uint32
+    lib.kiss_hip_fmi_sizes_ex_for.argtypes = [u64, u32, u32, ctypes.POINTER(FmiSizesEx)]
+    lib.kiss_hip_fmi_build_ex_dev.argtypes = [
+        vp, vp, u64, vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(u32 * 4), ctypes.POINTER(u32), vp]
+    lib.kiss_hip_fmi_query_ex_dev.argtypes = [
+        vp, ctypes.POINTER(FmiViewEx), vp, u32, u64, u32, vp, vp, vp, ctypes.POINTER(u64), ctypes.POINTER(u64), vp, vp,
+        u64, vp]
+    lib.kiss_hip_fmi_build_ex_host.argtypes = [vp, u64, vp, u32, u32] + [vp] * 9 + [ctypes.c_int]
+    lib.kiss_hip_fmi_query_ex_host.argtypes = [ctypes.POINTER(FmiViewEx), vp, u32, u64, u32, vp, vp, vp,
+                                               ctypes.POINTER(u64), ctypes.POINTER(u64), vp, vp, u64, ctypes.c_int]
     lib.kiss_hip_file_size.argtypes = [ctypes.c_char_p, ctypes.POINTER(u64)]
     lib.kiss_hip_ctx_parse_text_dev.argtypes = [vp, vp, u64, vp, ctypes.POINTER(u64), vp]
     lib.kiss_hip_ctx_load_text_file.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(vp), ctypes.POINTER(u64)]
@@ -206,7 +229,8 @@ def load(hooks=None):
                  "kiss_hip_ctx_create_sized", "kiss_hip_ctx_release_io_buffers", "kiss_hip_multi_create",
                  "kiss_hip_multi_destroy", "kiss_hip_multi_suffix_sort_dna_u32", "kiss_hip_multi_suffix_sort_dna_u32_dev",
                  "kiss_hip_multi_get_stats", "kiss_hip_suffix_sort_dna_u32_multi", "kiss_hip_stage_view",
-                 "kiss_hip_stage_reserve"):
+                 "kiss_hip_stage_reserve", "kiss_hip_fmi_sizes_ex_for", "kiss_hip_fmi_build_ex_dev",
+                 "kiss_hip_fmi_query_ex_dev", "kiss_hip_fmi_build_ex_host", "kiss_hip_fmi_query_ex_host"):
         getattr(lib, name).restype = ctypes.c_int
     _libs[hooks] = lib
     return lib
@@ -234,4 +258,6 @@ EXPORTED_SYMBOLS = [
     "kiss_hip_multi_suffix_sort_dna_u32_dev", "kiss_hip_multi_get_stats", "kiss_hip_multi_ctx",
     "kiss_hip_suffix_sort_dna_u32_multi", "kiss_hip_debug_splitters", "kiss_hip_debug_fail_alloc_over",
     "kiss_hip_has_hooks", "kiss_hip_release_cached_contexts", "kiss_hip_get_stats_sized",
+    "kiss_hip_fmi_sizes_ex_for", "kiss_hip_fmi_build_ex_dev", "kiss_hip_fmi_query_ex_dev", "kiss_hip_fmi_build_ex_host",
+    "kiss_hip_fmi_query_ex_host",
 ]

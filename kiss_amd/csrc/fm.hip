@@ -1,14 +1,19 @@
 // fm.hip -- FM-index kernels: batched backward search + locate, and index construction from (text, SA).
 //
-// Index = biovoltron FMIndex<SA_INTV = 4, uint32_t, KISS1Sorter<uint32_t>>{.LOOKUP_LEN = 0}
+// Index = biovoltron FMIndex<SA_INTV, uint32_t, KISS1Sorter<uint32_t>>{.LOOKUP_LEN}
 // (reference include/biovoltron/algo/align/exact_match/fm_index.hpp); array layout = the .fmi layout
-// (fm_index.hpp:591-615) so a loaded .fmi can be handed over as raw pointers.
+// (fm_index.hpp:591-615) so a loaded .fmi can be handed over as raw pointers.  The original entry points
+// (kiss_hip_fmi_build_dev / _query_batch_dev) are the CLI's instantiation, SA_INTV = 4 and LOOKUP_LEN = 0; the *_ex_*
+// entry points take SA_INTV in 1..32 and LOOKUP_LEN in 0..14 (SA_INTV = 1: the whole SA, no b_ / b_occ_).
 //
 //   occ(c, i)  = occ1[i/256][c] + occ2[i/16][c] + #{c in bwt[16*(i/16) .. i)} - [c == 0 && 16*(i/16) <= pri < i]
 //                                                                   (compute_occ, fm_index.hpp:166-182)
 //   lf(c, i)   = cnt[c] + occ(c, i)                                 (:184-187)
-//   range      : (0, N) then, right to left, beg = lf(c, beg), end = lf(c, end) while end - beg >= 1
+//   range      : (lookup_[K], lookup_[K + 1]) for K = hash of the last LOOKUP_LEN characters (or (0, N) for a shorter
+//                seed), then, right to left, beg = lf(c, beg), end = lf(c, end) while end - beg >= stop_cnt + 1
 //                                                                   (get_range/compute_range :553-584, 224-235)
+//   lookup     : lookup_[K] = beg of the backward search of the K-th LOOKUP_LEN-mer from (0, N) (build_lookup :238-270),
+//                built level by level: range(c w) = LF(c, range(w)) for all 4^d strings w of length d
 //   locate     : breadth-first over <= SA_INTV - 1 LF levels, emitting sa_[j] + depth for the sampled rows
 //                of every visited range, in the reference's FIFO order, stopping once end - beg offsets
 //                have been collected (get_offsets :453-501).
@@ -163,9 +168,11 @@ __global__ __launch_bounds__(FM_THREADS) void k_fm_blocks(FmiD f, uint64_t nbloc
     blk[2 * j] = c;
     blk[2 * j + 1] = w;
 }
-// compute_b_occ, fm_index.hpp:189-208
+// compute_b_occ, fm_index.hpp:189-208.  SA_INTV = 1 keeps no bit-vector (b == nullptr): every row is sampled and its
+// rank is the row itself, so the walk below emits sa_[beg, end) at depth 0 -- get_offsets' span (:455-456)
 __device__ __forceinline__ uint32_t fm_b_occ(const FmiD &f, uint64_t i)
 {
+    if (!f.b) return (uint32_t)i;
     const uint64_t w = i >> 6;
     const uint32_t r = (uint32_t)(i & 63);
     uint32_t c = f.b_occ[w];
@@ -174,30 +181,45 @@ __device__ __forceinline__ uint32_t fm_b_occ(const FmiD &f, uint64_t i)
 }
 
 // ---- backward search: one lane per pattern -------------------------------------------------------
+// lookup == nullptr: the LOOKUP_LEN = 0 index of the original entry point (range (0, N)).  stop_upper = stop_cnt + 1 in u32
+// arithmetic (1 for the original entry point; 0 never stops).  offs (may be null): the characters left unmatched.
+// fr_all: every pattern owns frontier slots (the workgroup walk of SA_INTV > 4 keeps its levels in global memory).
 __global__ __launch_bounds__(FM_THREADS) void k_fm_range(FmiD f, const uint8_t *__restrict__ pat, uint32_t L, uint64_t Q,
                                                         uint32_t *__restrict__ beg_out, uint32_t *__restrict__ end_out,
                                                         uint64_t *__restrict__ cap /* offset slots per pattern */,
                                                         uint64_t *__restrict__ fcap /* frontier slots per pattern */,
                                                         uint32_t *__restrict__ heavy_list, uint32_t *__restrict__ nheavy,
                                                         uint32_t *__restrict__ medium_list, uint32_t *__restrict__ nmedium,
-                                                        uint32_t FM_LIGHT, uint32_t fm_heavy)
+                                                        uint32_t FM_LIGHT, uint32_t fm_heavy,
+                                                        const uint32_t *__restrict__ lookup, uint32_t lookup_len,
+                                                        uint32_t stop_upper, uint32_t *__restrict__ offs_out, uint32_t fr_all)
 {
     uint64_t q = (uint64_t)blockIdx.x * FM_THREADS + threadIdx.x;
     const bool live = q < Q; // (no early return: the list appends below are wave-wide)
     uint64_t beg = 0, end = live ? f.N : 0;
     const uint8_t *p = pat + (live ? q : 0) * L;
     uint32_t len = live ? L : 0;
+    if (lookup && live && len >= lookup_len) { // get_range (fm_index.hpp:574-581): the last LOOKUP_LEN characters at once
+        uint32_t key = 0;
+        for (uint32_t i = len - lookup_len; i < len; i++) key = (key << 2) | (p[i] & 3u); // Codec::hash: last char lowest
+        beg = lookup[key];
+        end = lookup[key + 1];
+        len -= lookup_len;
+    }
+    uint32_t left = 0; // "offset" of get_range: 0 when the range is empty or the seed used up before the loop
     if (!(end == beg || len == 0)) {
         while (len > 0) {
-            if (end - beg < 1) break;
+            if ((uint32_t)(end - beg) < stop_upper) break;
             uint32_t c = p[len - 1] & 3u;
             fm_lf2(f, c, beg, end);
             len--;
         }
+        left = len;
     }
     if (live) {
         beg_out[q] = (uint32_t)beg;
         end_out[q] = (uint32_t)end;
+        if (offs_out) offs_out[q] = left;
     }
     // get_offsets (fm_index.hpp:472-482) tests `offsets.size() < end - beg` only BEFORE a range is taken from the queue
     // and then emits every sampled row of that range: on an index whose k-ordered SA ties long repeats (telomere-like
@@ -205,7 +227,7 @@ __global__ __launch_bounds__(FM_THREADS) void k_fm_range(FmiD f, const uint8_t *
     // before the last range and a range never holds more rows than the first one: at most 2 (end - beg) - 1 positions.
     if (live) {
         cap[q] = 2 * (end - beg) + 4;
-        fcap[q] = end - beg > FM_LIGHT ? 0 : (end - beg) + 4; // ranges of one level (rows of a level <= end - beg)
+        fcap[q] = end - beg > FM_LIGHT && !fr_all ? 0 : (end - beg) + 4; // ranges of one level (rows of a level <= end - beg)
     }
     // located by a workgroup / by a wave (the order of the lists is irrelevant); the appends are aggregated per wave
     const bool hv = live && end - beg > fm_heavy, md = live && !hv && end - beg > FM_LIGHT;
@@ -229,7 +251,8 @@ __global__ __launch_bounds__(FM_THREADS) void k_fm_locate(FmiD f, const uint32_t
                                                          uint2 *__restrict__ frontier0, uint2 *__restrict__ frontier1,
                                                          uint32_t *__restrict__ out, uint64_t *__restrict__ got_out,
                                                          unsigned long long *__restrict__ totals,
-                                                         const uint32_t *__restrict__ overflow, uint32_t FM_LIGHT)
+                                                         const uint32_t *__restrict__ overflow, uint32_t FM_LIGHT,
+                                                         int max_depth /* SA_INTV */)
 {
     uint64_t q = (uint64_t)blockIdx.x * FM_THREADS + threadIdx.x;
     unsigned long long got = 0, sum = 0;
@@ -243,7 +266,7 @@ __global__ __launch_bounds__(FM_THREADS) void k_fm_locate(FmiD f, const uint32_t
         uint64_t ncur = 1;
         if (e0 - b0 <= FM_LIGHT) cur[0] = make_uint2((uint32_t)b0, (uint32_t)e0); // (the others own no frontier slots)
         bool stop = false;
-        for (int dep = 0; dep < 4 && !stop; dep++) {
+        for (int dep = 0; dep < max_depth && !stop; dep++) {
             uint64_t nn = 0;
             for (uint64_t t = 0; t < ncur; t++) {
                 if (got >= want) {
@@ -259,7 +282,7 @@ __global__ __launch_bounds__(FM_THREADS) void k_fm_locate(FmiD f, const uint32_t
                     got++;
                     sum += v;
                 }
-                if (dep + 1 == 4) continue;
+                if (dep + 1 == max_depth) continue;
                 if (cb + 1 == ce) {
                     uint64_t nb = fm_lf(f, fm_bwt(f, cb), cb);
                     if (nn < fcapq) nxt[nn] = make_uint2((uint32_t)nb, (uint32_t)(nb + 1));
@@ -299,7 +322,7 @@ __global__ __launch_bounds__(FM_THREADS) void k_fm_locate(FmiD f, const uint32_t
 }
 
 // ---- locate for one heavy pattern per workgroup ------------------------------------------------------------
-// Same breadth-first walk and the same output order; a level has at most 4^depth <= 64 ranges, so wave 0 handles
+// Same breadth-first walk and the same output order; for SA_INTV <= 4 a level has at most 4^depth <= 64 ranges, so wave 0 handles
 // the ranges (one lane each: sampled-row counts, the stop rule, the children) and then all threads write the
 // level's offsets -- output o belongs to the range whose prefix count covers it.
 template <int THREADS> // FMH_THREADS: one workgroup per pattern; FMM_THREADS: one wave per pattern
@@ -310,7 +333,7 @@ __global__ __launch_bounds__(THREADS) void k_fm_locate_group(FmiD f, const uint3
                                                                 uint32_t *__restrict__ out, uint64_t *__restrict__ got_out,
                                                                 unsigned long long *__restrict__ totals,
                                                                 const uint32_t *__restrict__ nheavy, // device-side count
-                                                                const uint32_t *__restrict__ overflow)
+                                                                const uint32_t *__restrict__ overflow, int max_depth /* <= 4 */)
 {
     __shared__ uint2 fr[2][64];
     __shared__ uint32_t d_ob[64], d_pre[65];
@@ -331,7 +354,7 @@ __global__ __launch_bounds__(THREADS) void k_fm_locate_group(FmiD f, const uint3
     uint64_t got = 0; // uniform
     unsigned long long sum = 0;
     int cur = 0;
-    for (int dep = 0; dep < 4; dep++) {
+    for (int dep = 0; dep < max_depth; dep++) {
         const uint32_t ncur = s_n;
         __syncthreads();
         if (threadIdx.x < 64) {
@@ -364,7 +387,7 @@ __global__ __launch_bounds__(THREADS) void k_fm_locate_group(FmiD f, const uint3
             // children
             uint2 ch[4];
             uint32_t nch = 0;
-            if (proc && dep + 1 < 4) {
+            if (proc && dep + 1 < max_depth) {
                 if (cb + 1 == ce) {
                     const uint64_t nb = fm_lf(f, fm_bwt(f, cb), cb);
                     ch[nch++] = make_uint2((uint32_t)nb, (uint32_t)(nb + 1));
@@ -444,6 +467,164 @@ __global__ __launch_bounds__(THREADS) void k_fm_locate_group(FmiD f, const uint3
     // totals
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, 64);
+    if (lane_id() == 0) s_sum[threadIdx.x >> 6] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long s = 0;
+        for (int w = 0; w < THREADS / 64; w++) s += s_sum[w];
+        const uint64_t g = got < capq ? got : capq;
+        got_out[q] = g;
+        atomicAdd(&totals[0], (unsigned long long)g);
+        atomicAdd(&totals[1], s);
+    }
+    } // next heavy pattern of this workgroup
+}
+
+// ---- locate for one heavy pattern per workgroup, SA_INTV > 4 ------------------------------------------------
+// Past depth 3 a level can hold up to end - beg ranges (one per row), more than a shared array takes: the levels live in
+// the pattern's frontier slots in global memory (end - beg + 4 entries each, k_fm_range with fr_all) and wave 0 takes a
+// level 64 ranges at a time -- per chunk the same work, stop rule and output order as k_fm_locate_group.
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void k_fm_locate_group_deep(FmiD f, const uint32_t *__restrict__ beg_in,
+                                                                     const uint32_t *__restrict__ end_in,
+                                                                     const uint32_t *__restrict__ heavy_list,
+                                                                     const uint64_t *__restrict__ cap_index,
+                                                                     const uint64_t *__restrict__ fcap_index,
+                                                                     uint2 *frontier0, uint2 *frontier1,
+                                                                     uint32_t *__restrict__ out, uint64_t *__restrict__ got_out,
+                                                                     unsigned long long *__restrict__ totals,
+                                                                     const uint32_t *__restrict__ nheavy,
+                                                                     const uint32_t *__restrict__ overflow, int max_depth)
+{
+    __shared__ uint32_t d_ob[64], d_pre[65];
+    __shared__ uint32_t s_np, s_total, s_stop, s_nch;
+    __shared__ unsigned long long s_sum[THREADS / 64];
+    if (*overflow) return;
+    for (uint32_t hq = blockIdx.x; hq < *nheavy; hq += gridDim.x) {
+    __syncthreads(); // (the shared arrays of the previous pattern are dead)
+    const uint32_t q = heavy_list[hq];
+    const uint64_t b0 = beg_in[q], e0 = end_in[q];
+    const uint64_t want = e0 - b0, base = cap_index[q], capq = 2 * want + 4;
+    const uint64_t fbase = fcap_index[q], fcapq = want + 4;
+    uint2 *cur = frontier0 + fbase, *nxt = frontier1 + fbase;
+    if (threadIdx.x == 0) cur[0] = make_uint2((uint32_t)b0, (uint32_t)e0);
+    uint64_t ncur = 1, got = 0; // uniform
+    unsigned long long sum = 0;
+    bool stop = false;
+    for (int dep = 0; dep < max_depth && !stop && ncur; dep++) {
+        uint64_t nn = 0; // children of this level so far (uniform)
+        for (uint64_t c0 = 0; c0 < ncur && !stop; c0 += 64) {
+            __syncthreads(); // cur is complete; d_ob / d_pre of the previous chunk are dead
+            if (threadIdx.x < 64) {
+                const uint32_t t = threadIdx.x;
+                const uint32_t nvalid = ncur - c0 < 64 ? (uint32_t)(ncur - c0) : 64u;
+                const bool valid = t < nvalid;
+                uint64_t cb = 0, ce = 0;
+                uint32_t ob = 0, cnt = 0;
+                if (valid) {
+                    const uint2 r = cur[c0 + t];
+                    cb = r.x;
+                    ce = r.y;
+                    ob = fm_b_occ(f, cb);
+                    cnt = fm_b_occ(f, ce) - ob;
+                }
+                uint32_t inc = cnt;
+#pragma unroll
+                for (int d = 1; d < 64; d <<= 1) {
+                    const uint32_t o = __shfl_up(inc, d, 64);
+                    if ((int)t >= d) inc += o;
+                }
+                const uint32_t excl = inc - cnt;
+                const bool proc = valid && (got + excl < want); // the reference checks `got >= want` before every range
+                const uint64_t pm = __ballot(proc);
+                const uint32_t np = (uint32_t)__popcll(pm); // processed ranges form a prefix
+                const uint32_t totp = np ? __shfl(inc, (int)np - 1, 64) : 0u;
+                if (proc) {
+                    d_ob[t] = ob;
+                    d_pre[t] = excl;
+                }
+                uint2 ch[4];
+                uint32_t nch = 0;
+                if (proc && dep + 1 < max_depth) {
+                    if (cb + 1 == ce) {
+                        const uint64_t nb = fm_lf(f, fm_bwt(f, cb), cb);
+                        ch[nch++] = make_uint2((uint32_t)nb, (uint32_t)(nb + 1));
+                    } else {
+                        const FmBlock bb = fm_block(f, cb >> 6);
+                        const FmBlock be = (ce >> 6) == (cb >> 6) ? bb : fm_block(f, ce >> 6);
+#pragma unroll
+                        for (uint32_t c = 0; c < 4; c++) {
+                            const uint64_t nb = (uint64_t)f.cnt[c] + fm_occ_in(f, bb, c, cb), ne = (uint64_t)f.cnt[c] + fm_occ_in(f, be, c, ce);
+                            if (nb != ne) ch[nch++] = make_uint2((uint32_t)nb, (uint32_t)ne);
+                        }
+                    }
+                }
+                uint32_t cinc = nch;
+#pragma unroll
+                for (int d = 1; d < 64; d <<= 1) {
+                    const uint32_t o = __shfl_up(cinc, d, 64);
+                    if ((int)t >= d) cinc += o;
+                }
+                const uint32_t cex = cinc - nch;
+                const uint32_t ctot = __shfl(cinc, 63, 64);
+                for (uint32_t j = 0; j < nch; j++)
+                    if (nn + cex + j < fcapq) nxt[nn + cex + j] = ch[j]; // (a level never has more ranges than rows)
+                if (t == 0) {
+                    d_pre[np] = totp;
+                    s_np = np;
+                    s_total = totp;
+                    s_stop = (np < nvalid) ? 1u : 0u;
+                    s_nch = ctot;
+                }
+            }
+            __syncthreads();
+            const uint32_t total = s_total, np = s_np;
+            nn += s_nch;
+            stop = s_stop != 0;
+            uint32_t lo_hint = 0;
+            for (uint32_t o0 = threadIdx.x; o0 < total; o0 += 4u * THREADS) {
+                uint32_t v[4];
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const uint32_t o = o0 + (uint32_t)u * THREADS;
+                    v[u] = 0;
+                    if (o < total) {
+                        uint32_t lo = lo_hint;
+                        if (lo + 1 < np && d_pre[lo + 1] <= o) {
+                            lo++;
+                            if (lo + 1 < np && d_pre[lo + 1] <= o) {
+                                uint32_t hi = np;
+                                while (hi - lo > 1) {
+                                    const uint32_t mid = (lo + hi) >> 1;
+                                    if (d_pre[mid] <= o) lo = mid;
+                                    else hi = mid;
+                                }
+                            }
+                        }
+                        lo_hint = lo;
+                        v[u] = f.sa[d_ob[lo] + (o - d_pre[lo])] + (uint32_t)dep;
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const uint32_t o = o0 + (uint32_t)u * THREADS;
+                    if (o < total) {
+                        const uint64_t idx = got + o;
+                        if (idx < capq) out[base + idx] = v[u];
+                        sum += v[u];
+                    }
+                }
+            }
+            got += total;
+        }
+        uint2 *tmp = cur;
+        cur = nxt;
+        nxt = tmp;
+        ncur = nn < fcapq ? nn : fcapq;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, 64);
+    __syncthreads(); // (s_sum of the previous pattern is dead)
     if (lane_id() == 0) s_sum[threadIdx.x >> 6] = sum;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -543,7 +724,7 @@ __global__ __launch_bounds__(FM_THREADS) void k_fm_occ1(const uint32_t *__restri
 
 // one lane per 64-row word of the sampling bit-vector
 __global__ __launch_bounds__(FM_THREADS) void k_fm_bits(const uint32_t *__restrict__ SA, uint64_t N, uint64_t words,
-                                                       uint64_t nbocc, uint32_t sa_mask, uint64_t *__restrict__ b,
+                                                       uint64_t nbocc, uint32_t sa_intv, uint64_t *__restrict__ b,
                                                        uint32_t *__restrict__ wcnt)
 {
     uint64_t w = (uint64_t)blockIdx.x * FM_THREADS + threadIdx.x;
@@ -553,7 +734,7 @@ __global__ __launch_bounds__(FM_THREADS) void k_fm_bits(const uint32_t *__restri
         for (uint32_t k = 0; k < 64; k++) {
             uint64_t i = w * 64 + k;
             if (i >= N) break;
-            if ((SA[i] & sa_mask) == 0) bits |= 1ull << k;
+            if (SA[i] % sa_intv == 0) bits |= 1ull << k; // build_sa, fm_index.hpp:338-350
         }
         b[w] = bits;
     }
@@ -573,6 +754,38 @@ __global__ __launch_bounds__(FM_THREADS) void k_fm_sample(const uint32_t *__rest
         int k = __ffsll((unsigned long long)bits) - 1;
         bits &= bits - 1;
         sa_out[p++] = SA[w * 64 + k];
+    }
+}
+
+// ---- the LOOKUP_LEN k-mer table (build_lookup, fm_index.hpp:238-270) -----------------------------------------
+// Level d holds the ranges of all 4^d strings w of length d in key order (Codec::hash: the last character in the low
+// bits); the strings of level d + 1 are c w, key c 4^d + key(w), range LF(c, range(w)) -- the reference's own backward
+// search without early stop, one step per level, so the table is the same for any SA (k-ordered ties included).
+// One lane per w: its one or two rank blocks serve all four c.  prev == nullptr: level 0 = {(0, N)}; next == nullptr:
+// the last level, only the begs are kept (lookup_[K] = beg(K)).
+__global__ __launch_bounds__(FM_THREADS) void k_fm_lookup_level(FmiD f, const uint2 *__restrict__ prev, uint64_t nprev,
+                                                               uint2 *__restrict__ next, uint32_t *__restrict__ lookup)
+{
+    const uint64_t w = (uint64_t)blockIdx.x * FM_THREADS + threadIdx.x;
+    if (w >= nprev) return;
+    const uint2 r = prev ? prev[w] : make_uint2(0u, (uint32_t)f.N);
+    const FmBlock bb = fm_block(f, r.x >> 6);
+    if (next) {
+        const FmBlock be = (r.y >> 6) == (r.x >> 6) ? bb : fm_block(f, r.y >> 6);
+#pragma unroll
+        for (uint32_t c = 0; c < 4; c++)
+            next[c * nprev + w] = make_uint2(f.cnt[c] + fm_occ_in(f, bb, c, r.x), f.cnt[c] + fm_occ_in(f, be, c, r.y));
+    } else {
+#pragma unroll
+        for (uint32_t c = 0; c < 4; c++) lookup[c * nprev + w] = f.cnt[c] + fm_occ_in(f, bb, c, r.x);
+    }
+}
+// lookup_[4^L] = N (the push_back of :242); LOOKUP_LEN = 0 also gets lookup_[0] = 0
+__global__ void k_fm_lookup_ends(uint32_t *lookup, uint64_t keys, uint32_t N)
+{
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        if (keys == 1) lookup[0] = 0;
+        lookup[keys] = N;
     }
 }
 
@@ -628,15 +841,17 @@ struct DevBuf {
 
 } // namespace
 
-extern "C" {
+namespace {
 
-int kiss_hip_fmi_query_batch_dev(kiss_hip_ctx *ctx, const kiss_hip_fmi_view *fmi, const uint8_t *patterns, uint32_t L,
-                                 uint64_t Q, uint32_t *beg, uint32_t *end, uint64_t *hit_count_total,
-                                 uint64_t *checksum, uint32_t *offsets, uint64_t *offsets_index,
-                                 uint64_t offsets_capacity, void *stream)
+// the batched query of both entry points.  lookup == nullptr: LOOKUP_LEN = 0 (range (0, N)); stop_upper = stop_cnt + 1;
+// offs: optional per-pattern "offset" of get_range.  fmi->sa_intv (1..32) is the depth of the locate walk.
+int fmi_query(kiss_hip_ctx *ctx, const kiss_hip_fmi_view *fmi, const uint32_t *lookup, uint32_t lookup_len,
+              uint32_t stop_upper, uint32_t *offs, const uint8_t *patterns, uint32_t L, uint64_t Q, uint32_t *beg,
+              uint32_t *end, uint64_t *hit_count_total, uint64_t *checksum, uint32_t *offsets, uint64_t *offsets_index,
+              uint64_t offsets_capacity, void *stream)
 {
-    if (!ctx || !fmi || !beg || !end || (Q && !patterns)) return KISS_HIP_E_INVALID;
-    if (fmi->sa_intv != 4) return KISS_HIP_E_UNSUPPORTED; // the CLI's FMIndex<4, ...> (fmindex_build.hpp:27)
+    const int max_depth = (int)fmi->sa_intv;
+    const bool deep = max_depth > 4; // levels past 4^3 = 64 ranges: k_fm_locate_group_deep
     KCHECK(hipSetDevice(ctx->device));
     ctx->stream = stream ? (hipStream_t)stream : ctx->own_stream;
     KTRY(kiss_workspace_ready(ctx));
@@ -653,7 +868,7 @@ int kiss_hip_fmi_query_batch_dev(kiss_hip_ctx *ctx, const kiss_hip_fmi_view *fmi
     f.occ1 = fmi->occ1;
     f.occ2 = fmi->occ2;
     f.sa = fmi->sa;
-    f.b = fmi->b;
+    f.b = max_depth == 1 ? nullptr : fmi->b; // (SA_INTV = 1: every row sampled, fm_b_occ is the identity)
     f.b_occ = fmi->b_occ;
 
     DevBuf cap, capidx, fcap, fcapidx, got, gotidx, tot, fr0, fr1, scratch, heavy, medium, blocks;
@@ -704,7 +919,8 @@ int kiss_hip_fmi_query_batch_dev(kiss_hip_ctx *ctx, const kiss_hip_fmi_view *fmi
         if (timed) (void)hipEventRecord(sev[0], ctx->stream);
         hipLaunchKernelGGL(k_fm_range, dim3(grid), dim3(FM_THREADS), 0, ctx->stream, f, patterns, L, Q, beg, end,
                            (uint64_t *)cap.p, (uint64_t *)fcap.p, (uint32_t *)heavy.p + 1, (uint32_t *)heavy.p,
-                           (uint32_t *)medium.p + 1, (uint32_t *)medium.p, fm_light, fm_heavy);
+                           (uint32_t *)medium.p + 1, (uint32_t *)medium.p, fm_light, fm_heavy, lookup, lookup_len, stop_upper,
+                           offs, deep ? 1u : 0u);
         if (timed) (void)hipEventRecord(sev[1], ctx->stream);
         KCHECK(hipGetLastError());
     }
@@ -736,15 +952,28 @@ int kiss_hip_fmi_query_batch_dev(kiss_hip_ctx *ctx, const kiss_hip_fmi_view *fmi
             hipLaunchKernelGGL(k_fm_locate, dim3(grid), dim3(FM_THREADS), 0, ctx->stream, f, beg, end, Q,
                                (const uint64_t *)capidx.p, (const uint64_t *)fcapidx.p, (uint2 *)fr0.p, (uint2 *)fr1.p,
                                (uint32_t *)scratch.p, (uint64_t *)got.p, (unsigned long long *)tot.p, (const uint32_t *)d_over,
-                               fm_light);
+                               fm_light, max_depth);
             const unsigned hgrid = (unsigned)(Q < 2048 ? Q : 2048);
-            hipLaunchKernelGGL((k_fm_locate_group<FMH_THREADS>), dim3(hgrid), dim3(FMH_THREADS), 0, ctx->stream, f, beg, end,
-                               (const uint32_t *)heavy.p + 1, (const uint64_t *)capidx.p, (uint32_t *)scratch.p,
-                               (uint64_t *)got.p, (unsigned long long *)tot.p, (const uint32_t *)heavy.p, (const uint32_t *)d_over);
             const unsigned mgrid = (unsigned)(Q < 16384 ? Q : 16384); // one wave per pattern, walking the medium list
-            hipLaunchKernelGGL((k_fm_locate_group<FMM_THREADS>), dim3(mgrid), dim3(FMM_THREADS), 0, ctx->stream, f, beg, end,
-                               (const uint32_t *)medium.p + 1, (const uint64_t *)capidx.p, (uint32_t *)scratch.p,
-                               (uint64_t *)got.p, (unsigned long long *)tot.p, (const uint32_t *)medium.p, (const uint32_t *)d_over);
+            if (!deep) {
+                hipLaunchKernelGGL((k_fm_locate_group<FMH_THREADS>), dim3(hgrid), dim3(FMH_THREADS), 0, ctx->stream, f, beg, end,
+                                   (const uint32_t *)heavy.p + 1, (const uint64_t *)capidx.p, (uint32_t *)scratch.p,
+                                   (uint64_t *)got.p, (unsigned long long *)tot.p, (const uint32_t *)heavy.p, (const uint32_t *)d_over,
+                                   max_depth);
+                hipLaunchKernelGGL((k_fm_locate_group<FMM_THREADS>), dim3(mgrid), dim3(FMM_THREADS), 0, ctx->stream, f, beg, end,
+                                   (const uint32_t *)medium.p + 1, (const uint64_t *)capidx.p, (uint32_t *)scratch.p,
+                                   (uint64_t *)got.p, (unsigned long long *)tot.p, (const uint32_t *)medium.p, (const uint32_t *)d_over,
+                                   max_depth);
+            } else {
+                hipLaunchKernelGGL((k_fm_locate_group_deep<FMH_THREADS>), dim3(hgrid), dim3(FMH_THREADS), 0, ctx->stream, f, beg,
+                                   end, (const uint32_t *)heavy.p + 1, (const uint64_t *)capidx.p, (const uint64_t *)fcapidx.p,
+                                   (uint2 *)fr0.p, (uint2 *)fr1.p, (uint32_t *)scratch.p, (uint64_t *)got.p,
+                                   (unsigned long long *)tot.p, (const uint32_t *)heavy.p, (const uint32_t *)d_over, max_depth);
+                hipLaunchKernelGGL((k_fm_locate_group_deep<FMM_THREADS>), dim3(mgrid), dim3(FMM_THREADS), 0, ctx->stream, f, beg,
+                                   end, (const uint32_t *)medium.p + 1, (const uint64_t *)capidx.p, (const uint64_t *)fcapidx.p,
+                                   (uint2 *)fr0.p, (uint2 *)fr1.p, (uint32_t *)scratch.p, (uint64_t *)got.p,
+                                   (unsigned long long *)tot.p, (const uint32_t *)medium.p, (const uint32_t *)d_over, max_depth);
+            }
             if (timed) (void)hipEventRecord(sev[3], ctx->stream);
             KCHECK(hipGetLastError());
         }
@@ -782,14 +1011,31 @@ int kiss_hip_fmi_query_batch_dev(kiss_hip_ctx *ctx, const kiss_hip_fmi_view *fmi
     return KISS_HIP_OK;
 }
 
-int kiss_hip_fmi_build_dev(kiss_hip_ctx *ctx, const uint8_t *d_S, uint64_t n, const uint32_t *d_SA, uint32_t sa_intv,
-                           uint8_t *d_bwt, uint32_t *d_occ1, uint8_t *d_occ2, uint32_t *d_sa_sampled, uint64_t *d_b,
-                           uint32_t *d_b_occ, uint32_t cnt_out[4], uint32_t *pri_out, void *stream)
+} // namespace
+
+extern "C" {
+
+int kiss_hip_fmi_query_batch_dev(kiss_hip_ctx *ctx, const kiss_hip_fmi_view *fmi, const uint8_t *patterns, uint32_t L,
+                                 uint64_t Q, uint32_t *beg, uint32_t *end, uint64_t *hit_count_total,
+                                 uint64_t *checksum, uint32_t *offsets, uint64_t *offsets_index,
+                                 uint64_t offsets_capacity, void *stream)
 {
-    if (!ctx || !d_SA || (n && !d_S) || !d_bwt || !d_occ1 || !d_occ2 || !d_sa_sampled || !d_b || !d_b_occ || !cnt_out ||
-        !pri_out)
-        return KISS_HIP_E_INVALID;
-    if (sa_intv != 4) return KISS_HIP_E_UNSUPPORTED;
+    if (!ctx || !fmi || !beg || !end || (Q && !patterns)) return KISS_HIP_E_INVALID;
+    if (fmi->sa_intv != 4) return KISS_HIP_E_UNSUPPORTED; // the CLI's FMIndex<4, ...> (fmindex_build.hpp:27)
+    return fmi_query(ctx, fmi, nullptr, 0, 1u, nullptr, patterns, L, Q, beg, end, hit_count_total, checksum, offsets,
+                     offsets_index, offsets_capacity, stream);
+}
+
+} // extern "C"
+
+namespace {
+
+// FMIndex::build(ref, ori_sa) without the lookup table: bwt, occ, and the SA sampled every sa_intv (1..32; 1 copies the
+// SA and leaves d_b / d_b_occ untouched)
+int fmi_build(kiss_hip_ctx *ctx, const uint8_t *d_S, uint64_t n, const uint32_t *d_SA, uint32_t sa_intv, uint8_t *d_bwt,
+              uint32_t *d_occ1, uint8_t *d_occ2, uint32_t *d_sa_sampled, uint64_t *d_b, uint32_t *d_b_occ,
+              uint32_t cnt_out[4], uint32_t *pri_out, void *stream)
+{
     if (n > KISS_HIP_MAX_N) return KISS_HIP_E_INVALID;
     KCHECK(hipSetDevice(ctx->device));
     ctx->stream = stream ? (hipStream_t)stream : ctx->own_stream;
@@ -825,14 +1071,17 @@ int kiss_hip_fmi_build_dev(kiss_hip_ctx *ctx, const uint8_t *d_S, uint64_t n, co
                        (uint32_t *)blk_tot.p, blocks, base[0], base[1], base[2], base[3]);
     hipLaunchKernelGGL(k_fm_occ1, dim3((unsigned)div_up(blocks, FM_THREADS)), dim3(FM_THREADS), 0, ctx->stream,
                        (const uint32_t *)blk_tot.p, blocks, d_occ1);
-    // sampling bit-vector, its rank directory and the sampled SA
-    hipLaunchKernelGGL(k_fm_bits, dim3((unsigned)div_up(nbocc, FM_THREADS)), dim3(FM_THREADS), 0, ctx->stream, d_SA, N,
-                       words, nbocc, sa_intv - 1, d_b, (uint32_t *)wcnt.p);
-    KCHECK(hipGetLastError());
-    KTRY(kiss_scan_u32(ctx, (const uint32_t *)wcnt.p, d_b_occ, nbocc));
-    hipLaunchKernelGGL(k_fm_sample, dim3((unsigned)div_up(words, FM_THREADS)), dim3(FM_THREADS), 0, ctx->stream, d_SA, N,
-                       words, d_b, d_b_occ, d_sa_sampled);
-    KCHECK(hipGetLastError());
+    if (sa_intv == 1) { // build_sa, fm_index.hpp:331-335: sa_ = the whole SA, no b_ / b_occ_
+        KCHECK(hipMemcpyAsync(d_sa_sampled, d_SA, N * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+    } else { // sampling bit-vector, its rank directory and the sampled SA
+        hipLaunchKernelGGL(k_fm_bits, dim3((unsigned)div_up(nbocc, FM_THREADS)), dim3(FM_THREADS), 0, ctx->stream, d_SA, N,
+                           words, nbocc, sa_intv, d_b, (uint32_t *)wcnt.p);
+        KCHECK(hipGetLastError());
+        KTRY(kiss_scan_u32(ctx, (const uint32_t *)wcnt.p, d_b_occ, nbocc));
+        hipLaunchKernelGGL(k_fm_sample, dim3((unsigned)div_up(words, FM_THREADS)), dim3(FM_THREADS), 0, ctx->stream, d_SA, N,
+                           words, d_b, d_b_occ, d_sa_sampled);
+        KCHECK(hipGetLastError());
+    }
     uint32_t h_pri = 0;
     KCHECK(hipMemcpyAsync(&h_pri, pri.p, 4, hipMemcpyDeviceToHost, ctx->stream));
     KCHECK(hipStreamSynchronize(ctx->stream));
@@ -845,6 +1094,93 @@ int kiss_hip_fmi_build_dev(kiss_hip_ctx *ctx, const uint8_t *d_S, uint64_t n, co
         sum += tot;
     }
     return KISS_HIP_OK;
+}
+
+// lookup_ of an index whose bwt / occ arrays are built: 4^L + 1 entries into d_lookup (build_lookup, fm_index.hpp:238-270)
+int fmi_lookup(kiss_hip_ctx *ctx, uint64_t N, const uint32_t cnt[4], uint32_t pri, const uint8_t *d_bwt,
+               const uint32_t *d_occ1, const uint8_t *d_occ2, uint32_t lookup_len, uint32_t *d_lookup)
+{
+    FmiD f{};
+    f.N = N;
+    for (int c = 0; c < 4; c++) f.cnt[c] = cnt[c];
+    f.pri = pri;
+    f.bwt_bytes = (N + 3) / 4;
+    f.bwt = d_bwt;
+    f.occ1 = d_occ1;
+    f.occ2 = d_occ2;
+    const uint64_t keys = 1ull << (2 * lookup_len);
+    const uint64_t nblocks = N / 64 + 1;
+    DevBuf blocks, lv[2];
+    KTRY(blocks.alloc(ctx, nblocks * 32));
+    // the levels 1 .. L - 1 alternate between two buffers: the one of level L - 1 (4^(L-1) ranges) and the one of L - 2
+    if (lookup_len >= 2) KTRY(lv[(lookup_len - 1) & 1].alloc(ctx, (keys >> 2) * sizeof(uint2)));
+    if (lookup_len >= 3) KTRY(lv[lookup_len & 1].alloc(ctx, (keys >> 4) * sizeof(uint2)));
+    f.blk = (const uint4 *)blocks.p;
+    KTimer t(ctx, KISS_HIP_K_FM_BUILD, keys);
+    hipLaunchKernelGGL(k_fm_blocks, dim3((unsigned)div_up(nblocks, FM_THREADS)), dim3(FM_THREADS), 0, ctx->stream, f, nblocks,
+                       (uint4 *)blocks.p);
+    for (uint32_t d = 0; d < lookup_len; d++) { // level d -> level d + 1
+        const uint64_t nprev = 1ull << (2 * d);
+        const uint2 *prev = d == 0 ? nullptr : (const uint2 *)lv[d & 1].p;
+        const bool last = d + 1 == lookup_len;
+        hipLaunchKernelGGL(k_fm_lookup_level, dim3((unsigned)div_up(nprev, FM_THREADS)), dim3(FM_THREADS), 0, ctx->stream, f,
+                           prev, nprev, last ? nullptr : (uint2 *)lv[(d + 1) & 1].p, last ? d_lookup : nullptr);
+    }
+    hipLaunchKernelGGL(k_fm_lookup_ends, dim3(1), dim3(64), 0, ctx->stream, d_lookup, keys, (uint32_t)N);
+    KCHECK(hipGetLastError());
+    KCHECK(hipStreamSynchronize(ctx->stream)); // (the level buffers are freed on return)
+    return KISS_HIP_OK;
+}
+
+bool fm_params_ok(uint32_t sa_intv, uint32_t lookup_len)
+{
+    return sa_intv >= 1 && sa_intv <= KISS_HIP_FMI_MAX_SA_INTV && lookup_len <= KISS_HIP_FMI_MAX_LOOKUP_LEN;
+}
+
+} // namespace
+
+extern "C" {
+
+int kiss_hip_fmi_build_dev(kiss_hip_ctx *ctx, const uint8_t *d_S, uint64_t n, const uint32_t *d_SA, uint32_t sa_intv,
+                           uint8_t *d_bwt, uint32_t *d_occ1, uint8_t *d_occ2, uint32_t *d_sa_sampled, uint64_t *d_b,
+                           uint32_t *d_b_occ, uint32_t cnt_out[4], uint32_t *pri_out, void *stream)
+{
+    if (!ctx || !d_SA || (n && !d_S) || !d_bwt || !d_occ1 || !d_occ2 || !d_sa_sampled || !d_b || !d_b_occ || !cnt_out ||
+        !pri_out)
+        return KISS_HIP_E_INVALID;
+    if (sa_intv != 4) return KISS_HIP_E_UNSUPPORTED;
+    KTRY(fmi_build(ctx, d_S, n, d_SA, sa_intv, d_bwt, d_occ1, d_occ2, d_sa_sampled, d_b, d_b_occ, cnt_out, pri_out, stream));
+    KCHECK(hipStreamSynchronize(ctx->stream));
+    ktimer_collect(ctx); // the KISS_HIP_K_FM_BUILD times of this build into the stats now, not at the next query
+    return KISS_HIP_OK;
+}
+
+int kiss_hip_fmi_build_ex_dev(kiss_hip_ctx *ctx, const uint8_t *d_S, uint64_t n, const uint32_t *d_SA, uint32_t sa_intv,
+                              uint32_t lookup_len, uint8_t *d_bwt, uint32_t *d_occ1, uint8_t *d_occ2, uint32_t *d_sa,
+                              uint64_t *d_b, uint32_t *d_b_occ, uint32_t *d_lookup, uint32_t cnt_out[4], uint32_t *pri_out,
+                              void *stream)
+{
+    if (!fm_params_ok(sa_intv, lookup_len)) return KISS_HIP_E_UNSUPPORTED;
+    if (!ctx || !d_SA || (n && !d_S) || !d_bwt || !d_occ1 || !d_occ2 || !d_sa || !d_lookup || !cnt_out || !pri_out ||
+        (sa_intv != 1 && (!d_b || !d_b_occ)))
+        return KISS_HIP_E_INVALID;
+    KTRY(fmi_build(ctx, d_S, n, d_SA, sa_intv, d_bwt, d_occ1, d_occ2, d_sa, d_b, d_b_occ, cnt_out, pri_out, stream));
+    KTRY(fmi_lookup(ctx, n + 1, cnt_out, *pri_out, d_bwt, d_occ1, d_occ2, lookup_len, d_lookup));
+    ktimer_collect(ctx); // (fmi_lookup has synchronised)
+    return KISS_HIP_OK;
+}
+
+int kiss_hip_fmi_query_ex_dev(kiss_hip_ctx *ctx, const kiss_hip_fmi_view_ex *fmi, const uint8_t *patterns, uint32_t L,
+                              uint64_t Q, uint32_t stop_cnt, uint32_t *beg, uint32_t *end, uint32_t *offs,
+                              uint64_t *hit_count_total, uint64_t *checksum, uint32_t *offsets, uint64_t *offsets_index,
+                              uint64_t offsets_capacity, void *stream)
+{
+    if (!fmi) return KISS_HIP_E_INVALID;
+    if (!fm_params_ok(fmi->base.sa_intv, fmi->lookup_len)) return KISS_HIP_E_UNSUPPORTED;
+    if (!ctx || !beg || !end || (Q && !patterns) || !fmi->lookup || (fmi->base.sa_intv != 1 && (!fmi->base.b || !fmi->base.b_occ)))
+        return KISS_HIP_E_INVALID;
+    return fmi_query(ctx, &fmi->base, fmi->lookup, fmi->lookup_len, stop_cnt + 1u, offs, patterns, L, Q, beg, end,
+                     hit_count_total, checksum, offsets, offsets_index, offsets_capacity, stream);
 }
 
 // ---- host-pointer forms (hosts that do not link HIP: the CLI, cgo/ctypes callers) -----------------------
@@ -946,6 +1282,122 @@ int kiss_hip_fmi_query_batch_host(const kiss_hip_fmi_view *fmi, const uint8_t *p
             break;
         e = hipMemcpy(beg, dbeg.p, Q * 4, hipMemcpyDeviceToHost);
         if (e == hipSuccess) e = hipMemcpy(end, dend.p, Q * 4, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && want) e = hipMemcpy(offsets_index, didx.p, (Q + 1) * 8, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && want) e = hipMemcpy(offsets, doff.p, offsets_capacity * 4, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = KISS_HIP_E_HIP;
+    } while (0);
+    kiss_hip_ctx_destroy(ctx);
+    return rc;
+}
+int kiss_hip_fmi_sizes_ex_for(uint64_t n, uint32_t sa_intv, uint32_t lookup_len, kiss_hip_fmi_sizes_ex *out)
+{
+    if (!fm_params_ok(sa_intv, lookup_len)) return KISS_HIP_E_UNSUPPORTED;
+    if (!out) return KISS_HIP_E_INVALID;
+    KTRY(kiss_hip_fmi_sizes_for(n, &out->base));
+    const uint64_t N = n + 1;
+    out->base.sa_entries = (N + sa_intv - 1) / sa_intv;
+    if (sa_intv == 1) out->base.b_words = out->base.b_occ_entries = 0;
+    out->lookup_entries = (1ull << (2 * lookup_len)) + 1;
+    return KISS_HIP_OK;
+}
+
+int kiss_hip_fmi_build_ex_host(const uint8_t *S, uint64_t n, const uint32_t *SA_or_null, uint32_t sa_intv,
+                               uint32_t lookup_len, uint8_t *bwt, uint32_t *occ1, uint8_t *occ2, uint32_t *sa, uint64_t *b,
+                               uint32_t *b_occ, uint32_t *lookup, uint32_t cnt_out[4], uint32_t *pri_out, int device)
+{
+    if (!fm_params_ok(sa_intv, lookup_len)) return KISS_HIP_E_UNSUPPORTED;
+    if (!S || !bwt || !occ1 || !occ2 || !sa || !lookup || !cnt_out || !pri_out || n == 0 || (sa_intv != 1 && (!b || !b_occ)))
+        return KISS_HIP_E_INVALID;
+    kiss_hip_fmi_sizes_ex z;
+    KTRY(kiss_hip_fmi_sizes_ex_for(n, sa_intv, lookup_len, &z));
+    kiss_hip_ctx *ctx = nullptr;
+    int rc = kiss_hip_ctx_create(&ctx, device, n);
+    if (rc) return rc;
+    DevBuf dS, dSA, dbwt, docc1, docc2, dsa, db, dbocc, dlookup;
+    do {
+        if ((rc = dS.alloc(ctx, n)) || (rc = dSA.alloc(ctx, (n + 1) * 4)) || (rc = dbwt.alloc(ctx, z.base.bwt_bytes + 8)) ||
+            (rc = docc1.alloc(ctx, z.base.occ1_entries * 4)) || (rc = docc2.alloc(ctx, z.base.occ2_bytes)) ||
+            (rc = dsa.alloc(ctx, z.base.sa_entries * 4)) || (rc = db.alloc(ctx, z.base.b_words * 8 + 8)) ||
+            (rc = dbocc.alloc(ctx, z.base.b_occ_entries * 4)) || (rc = dlookup.alloc(ctx, z.lookup_entries * 4)))
+            break;
+        if (hipMemcpy(dS.p, S, n, hipMemcpyHostToDevice) != hipSuccess) { rc = KISS_HIP_E_HIP; break; }
+        if (SA_or_null) {
+            if (hipMemcpy(dSA.p, SA_or_null, (n + 1) * 4, hipMemcpyHostToDevice) != hipSuccess) { rc = KISS_HIP_E_HIP; break; }
+        } else if ((rc = kiss_hip_ctx_suffix_sort_dna_u32_dev(ctx, (const uint8_t *)dS.p, n, 32u, KISS_HIP_ALGO_PARALLEL_SORTING,
+                                                              (uint32_t *)dSA.p, nullptr))) {
+            break;
+        }
+        if ((rc = kiss_hip_fmi_build_ex_dev(ctx, (const uint8_t *)dS.p, n, (const uint32_t *)dSA.p, sa_intv, lookup_len,
+                                            (uint8_t *)dbwt.p, (uint32_t *)docc1.p, (uint8_t *)docc2.p, (uint32_t *)dsa.p,
+                                            (uint64_t *)db.p, (uint32_t *)dbocc.p, (uint32_t *)dlookup.p, cnt_out, pri_out,
+                                            nullptr)))
+            break;
+        hipError_t e = hipMemcpy(bwt, dbwt.p, z.base.bwt_bytes, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(occ1, docc1.p, z.base.occ1_entries * 4, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(occ2, docc2.p, z.base.occ2_bytes, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(sa, dsa.p, z.base.sa_entries * 4, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(lookup, dlookup.p, z.lookup_entries * 4, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && sa_intv != 1) e = hipMemcpy(b, db.p, z.base.b_words * 8, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && sa_intv != 1) e = hipMemcpy(b_occ, dbocc.p, z.base.b_occ_entries * 4, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = KISS_HIP_E_HIP;
+    } while (0);
+    kiss_hip_ctx_destroy(ctx);
+    return rc;
+}
+
+int kiss_hip_fmi_query_ex_host(const kiss_hip_fmi_view_ex *fmi, const uint8_t *patterns, uint32_t L, uint64_t Q,
+                               uint32_t stop_cnt, uint32_t *beg, uint32_t *end, uint32_t *offs, uint64_t *hit_count_total,
+                               uint64_t *checksum, uint32_t *offsets, uint64_t *offsets_index, uint64_t offsets_capacity,
+                               int device)
+{
+    if (!fmi) return KISS_HIP_E_INVALID;
+    const uint32_t sa_intv = fmi->base.sa_intv;
+    if (!fm_params_ok(sa_intv, fmi->lookup_len)) return KISS_HIP_E_UNSUPPORTED;
+    if (!beg || !end || (Q && !patterns) || fmi->base.n_sa == 0 || !fmi->lookup ||
+        (sa_intv != 1 && (!fmi->base.b || !fmi->base.b_occ)))
+        return KISS_HIP_E_INVALID;
+    kiss_hip_fmi_sizes_ex z;
+    KTRY(kiss_hip_fmi_sizes_ex_for(fmi->base.n_sa - 1, sa_intv, fmi->lookup_len, &z));
+    kiss_hip_ctx *ctx = nullptr;
+    uint64_t max_n = fmi->base.n_sa > 4 * Q ? fmi->base.n_sa : 4 * Q;
+    if (max_n < (1u << 20)) max_n = 1u << 20;
+    int rc = kiss_hip_ctx_create(&ctx, device, max_n);
+    if (rc) return rc;
+    DevBuf dbwt, docc1, docc2, dsa, db, dbocc, dlookup, dpat, dbeg, dend, doffs, doff, didx;
+    do {
+        if ((rc = dbwt.alloc(ctx, z.base.bwt_bytes + 8)) || (rc = docc1.alloc(ctx, z.base.occ1_entries * 4)) ||
+            (rc = docc2.alloc(ctx, z.base.occ2_bytes)) || (rc = dsa.alloc(ctx, z.base.sa_entries * 4)) ||
+            (rc = db.alloc(ctx, z.base.b_words * 8 + 8)) || (rc = dbocc.alloc(ctx, z.base.b_occ_entries * 4)) ||
+            (rc = dlookup.alloc(ctx, z.lookup_entries * 4)) || (rc = dpat.alloc(ctx, Q * L)) ||
+            (rc = dbeg.alloc(ctx, Q * 4)) || (rc = dend.alloc(ctx, Q * 4)) || (offs && (rc = doffs.alloc(ctx, Q * 4))))
+            break;
+        hipError_t e = hipMemcpy(dbwt.p, fmi->base.bwt, z.base.bwt_bytes, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(docc1.p, fmi->base.occ1, z.base.occ1_entries * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(docc2.p, fmi->base.occ2, z.base.occ2_bytes, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(dsa.p, fmi->base.sa, z.base.sa_entries * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(dlookup.p, fmi->lookup, z.lookup_entries * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess && sa_intv != 1) e = hipMemcpy(db.p, fmi->base.b, z.base.b_words * 8, hipMemcpyHostToDevice);
+        if (e == hipSuccess && sa_intv != 1) e = hipMemcpy(dbocc.p, fmi->base.b_occ, z.base.b_occ_entries * 4, hipMemcpyHostToDevice);
+        if (e == hipSuccess && Q) e = hipMemcpy(dpat.p, patterns, Q * L, hipMemcpyHostToDevice);
+        if (e != hipSuccess) { rc = KISS_HIP_E_HIP; break; }
+        kiss_hip_fmi_view_ex v = *fmi;
+        v.base.bwt = (const uint8_t *)dbwt.p;
+        v.base.occ1 = (const uint32_t *)docc1.p;
+        v.base.occ2 = (const uint8_t *)docc2.p;
+        v.base.sa = (const uint32_t *)dsa.p;
+        v.base.b = sa_intv == 1 ? nullptr : (const uint64_t *)db.p;
+        v.base.b_occ = sa_intv == 1 ? nullptr : (const uint32_t *)dbocc.p;
+        v.lookup = (const uint32_t *)dlookup.p;
+        const bool want = offsets && offsets_index && offsets_capacity;
+        if (want && ((rc = doff.alloc(ctx, offsets_capacity * 4)) || (rc = didx.alloc(ctx, (Q + 1) * 8)))) break;
+        if ((rc = kiss_hip_fmi_query_ex_dev(ctx, &v, (const uint8_t *)dpat.p, L, Q, stop_cnt, (uint32_t *)dbeg.p,
+                                            (uint32_t *)dend.p, offs ? (uint32_t *)doffs.p : nullptr, hit_count_total, checksum,
+                                            want ? (uint32_t *)doff.p : nullptr, want ? (uint64_t *)didx.p : nullptr,
+                                            want ? offsets_capacity : 0, nullptr)))
+            break;
+        e = hipMemcpy(beg, dbeg.p, Q * 4, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(end, dend.p, Q * 4, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && offs) e = hipMemcpy(offs, doffs.p, Q * 4, hipMemcpyDeviceToHost);
         if (e == hipSuccess && want) e = hipMemcpy(offsets_index, didx.p, (Q + 1) * 8, hipMemcpyDeviceToHost);
         if (e == hipSuccess && want) e = hipMemcpy(offsets, doff.p, offsets_capacity * 4, hipMemcpyDeviceToHost);
         if (e != hipSuccess) rc = KISS_HIP_E_HIP;

@@ -5,6 +5,8 @@
 //   suffix_sort    [-k NUM(=256, -1 = unbounded)] [-s PARALLEL_SORTING|PREFIX_DOUBLING]   (command/suffix_sort.hpp)
 //   fmindex_build  [-k NUM (ignored, like the reference)]  -> writes <fasta>.fmi            (command/fmindex_build.hpp)
 //   fmindex_query  [-q STR] [-n NUM(=10)] [-b patterns.bin]                                  (command/fmindex_query.hpp)
+//   (opt-in: fmindex_build --sa-intv N --lookup-len L, fmindex_query --sa-intv N: FMIndex<N>{.LOOKUP_LEN = L}; the
+//    defaults 4 and 0 are the reference CLI's; the query reads L from the file, which does not record N)
 // and its log fields ("n = …, k = …, suffix sorting elapsed …", "query = … found N times", "searching time",
 // "number of matched locations", "location checksum").  Extras (opt-in): --output-sa FILE (raw u32 LE, n+1
 // entries; the reference never writes the SA), --device N, and for suffix_sort --gpus N / --devices LIST (the LMS sort
@@ -47,11 +49,14 @@ void usage()
               << "  --gpus NUM (=1)                shard the LMS sort over NUM devices (--device, --device + 1, ...)\n"
               << "  --devices LIST                 the same with an explicit comma-separated device list\n\n"
               << "./kiss fmindex_build [--option ...] <FASTA filename/Text filename>\n"
-              << "  -k [ --kordered ] NUM (=256)   accepted and ignored (the index is built with k = 32)\n\n"
+              << "  -k [ --kordered ] NUM (=256)   accepted and ignored (the index is built with k = 32)\n"
+              << "  --sa-intv NUM (=4)             SA sampling interval, 1..32 (1: the whole SA)\n"
+              << "  --lookup-len NUM (=0)          k-mer lookup table of 4^NUM ranges, 0..14\n\n"
               << "./kiss fmindex_query [--option ...] <FASTA filename/Text filename>\n"
               << "  -q [ --query ] STR             content of the query string\n"
               << "  -n [ --headn ] NUM (=10)       output the first n locations in single query mode\n"
-              << "  -b [ --batch ] patterns.bin    batch query mode (u32 len, u32 count, then count x len bytes)\n";
+              << "  -b [ --batch ] patterns.bin    batch query mode (u32 len, u32 count, then count x len bytes)\n"
+              << "  --sa-intv NUM (=4)             the SA sampling interval the index was built with\n";
 }
 
 inline uint8_t to_code(unsigned char c)
@@ -120,6 +125,7 @@ struct Args {
     std::string command, fasta, query, batch, output_sa, algo = "PARALLEL_SORTING";
     long long k = 256;
     size_t headn = 10;
+    uint32_t sa_intv = 4, lookup_len = 0; // FMIndex<SA_INTV>{.LOOKUP_LEN}: the reference CLI's (fmindex_build.hpp:27-29)
     int device = 0, gpus = 1;
     std::vector<int> devices; // --devices; empty: device, device + 1, ... (gpus of them)
     bool verbose = false, generic = false;
@@ -147,6 +153,8 @@ Args parse(int argc, char **argv)
         else if (s == "-n" || s == "--headn") a.headn = (size_t)std::stoull(next("--headn"));
         else if (s == "-b" || s == "--batch") a.batch = next("--batch");
         else if (s == "--output-sa") a.output_sa = next("--output-sa");
+        else if (s == "--sa-intv") a.sa_intv = (uint32_t)std::stoul(next("--sa-intv"));
+        else if (s == "--lookup-len") a.lookup_len = (uint32_t)std::stoul(next("--lookup-len"));
         else if (s == "--gpus") a.gpus = std::stoi(next("--gpus"));
         else if (s == "--devices") {
             const std::string list = next("--devices");
@@ -165,6 +173,8 @@ Args parse(int argc, char **argv)
     }
     if (pos.empty()) { usage(); std::exit(1); }
     if (a.gpus < 1) throw std::runtime_error("--gpus must be >= 1");
+    if (a.sa_intv < 1 || a.sa_intv > KISS_HIP_FMI_MAX_SA_INTV) throw std::runtime_error("--sa-intv must be in 1..32");
+    if (a.lookup_len > KISS_HIP_FMI_MAX_LOOKUP_LEN) throw std::runtime_error("--lookup-len must be in 0..14");
     if (a.devices.empty())
         for (int g = 0; g < a.gpus; g++) a.devices.push_back(a.device + g);
     else
@@ -182,21 +192,28 @@ double seconds_since(std::chrono::steady_clock::time_point t0)
 }
 
 // ---- .fmi (fm_index.hpp:591-646; Serializer: u64 count + raw bytes, nothing when the count is 0) ----------
+// order: cnt, pri, bwt, occ1, occ2, sa_, lookup_, then b_ and b_occ_ only if SA_INTV != 1
 struct Fmi {
-    kiss_hip_fmi_sizes z{};
+    kiss_hip_fmi_sizes_ex zx{};
+    const kiss_hip_fmi_sizes &z = zx.base;
+    uint32_t sa_intv = 4, lookup_len = 0;
     uint32_t cnt[4]{}, pri = 0;
     std::vector<uint8_t> bwt, occ2;
-    std::vector<uint32_t> occ1, sa, b_occ;
+    std::vector<uint32_t> occ1, sa, b_occ, lookup;
     std::vector<uint64_t> b;
+    Fmi(uint32_t sa_intv_, uint32_t lookup_len_) : sa_intv(sa_intv_), lookup_len(lookup_len_) {}
+    bool classic() const { return sa_intv == 4 && lookup_len == 0; } // the original entry points
     void alloc(uint64_t n)
     {
-        check(kiss_hip_fmi_sizes_for(n, &z), "kiss_hip_fmi_sizes_for");
+        check(kiss_hip_fmi_sizes_ex_for(n, sa_intv, lookup_len, &zx), "kiss_hip_fmi_sizes_ex_for");
         bwt.assign(z.bwt_bytes, 0);
         occ1.assign(z.occ1_entries, 0);
         occ2.assign(z.occ2_bytes, 0);
         sa.assign(z.sa_entries, 0);
         b.assign(z.b_words, 0);
         b_occ.assign(z.b_occ_entries, 0);
+        lookup.assign(zx.lookup_entries, 0);
+        lookup.back() = (uint32_t)z.n_sa; // LOOKUP_LEN = 0: {0, N} (fm_index.hpp:238-258)
     }
     static void put(std::ofstream &o, uint64_t count, const void *p, uint64_t bytes)
     {
@@ -214,10 +231,11 @@ struct Fmi {
         put(o, z.occ1_entries / 4, occ1.data(), z.occ1_entries * 4);
         put(o, z.occ2_bytes / 4, occ2.data(), z.occ2_bytes);
         put(o, z.sa_entries, sa.data(), z.sa_entries * 4);
-        const uint32_t lookup[2] = {0u, (uint32_t)z.n_sa}; // LOOKUP_LEN = 0 (fm_index.hpp:238-258)
-        put(o, 2, lookup, 8);
-        put(o, z.n_sa, b.data(), z.b_words * 8);
-        put(o, z.b_occ_entries, b_occ.data(), z.b_occ_entries * 4);
+        put(o, lookup.size(), lookup.data(), lookup.size() * 4);
+        if (sa_intv != 1) {
+            put(o, z.n_sa, b.data(), z.b_words * 8);
+            put(o, z.b_occ_entries, b_occ.data(), z.b_occ_entries * 4);
+        }
     }
     static uint64_t get_count(std::ifstream &in)
     {
@@ -226,6 +244,8 @@ struct Fmi {
         if (!in) throw std::runtime_error("truncated .fmi");
         return c;
     }
+    // the file does not record SA_INTV (a template parameter of the reference): a file whose counts do not fit the
+    // caller's is an error; LOOKUP_LEN follows from the lookup_ count
     void load(const std::string &path)
     {
         std::ifstream in(path, std::ios::binary);
@@ -233,21 +253,38 @@ struct Fmi {
         in.read(reinterpret_cast<char *>(cnt), 16);
         in.read(reinterpret_cast<char *>(&pri), 4);
         const uint64_t N = get_count(in);
+        if (N == 0) throw std::runtime_error("empty .fmi");
+        std::vector<uint8_t> bwt_in((N + 3) / 4);
+        in.read(reinterpret_cast<char *>(bwt_in.data()), (std::streamsize)bwt_in.size());
+        const uint64_t c_occ1 = get_count(in);
+        std::vector<uint32_t> occ1_in(c_occ1 * 4);
+        in.read(reinterpret_cast<char *>(occ1_in.data()), (std::streamsize)(occ1_in.size() * 4));
+        const uint64_t c_occ2 = get_count(in);
+        std::vector<uint8_t> occ2_in(c_occ2 * 4);
+        in.read(reinterpret_cast<char *>(occ2_in.data()), (std::streamsize)occ2_in.size());
+        const uint64_t c_sa = get_count(in);
+        if (c_sa != (N + sa_intv - 1) / sa_intv)
+            throw std::runtime_error("sa_ of the .fmi does not fit --sa-intv " + std::to_string(sa_intv));
+        std::vector<uint32_t> sa_in(c_sa);
+        in.read(reinterpret_cast<char *>(sa_in.data()), (std::streamsize)(c_sa * 4));
+        const uint64_t c_lookup = get_count(in);
+        lookup_len = 0;
+        while (lookup_len <= KISS_HIP_FMI_MAX_LOOKUP_LEN && (1ull << (2 * lookup_len)) + 1 != c_lookup) lookup_len++;
+        if (lookup_len > KISS_HIP_FMI_MAX_LOOKUP_LEN) throw std::runtime_error("bad lookup size in .fmi (not 4^L + 1)");
         alloc(N - 1);
-        in.read(reinterpret_cast<char *>(bwt.data()), (std::streamsize)z.bwt_bytes);
-        if (get_count(in) * 4 != z.occ1_entries) throw std::runtime_error("bad occ1 size in .fmi");
-        in.read(reinterpret_cast<char *>(occ1.data()), (std::streamsize)(z.occ1_entries * 4));
-        if (get_count(in) * 4 != z.occ2_bytes) throw std::runtime_error("bad occ2 size in .fmi");
-        in.read(reinterpret_cast<char *>(occ2.data()), (std::streamsize)z.occ2_bytes);
-        if (get_count(in) != z.sa_entries) throw std::runtime_error("bad sa size in .fmi");
-        in.read(reinterpret_cast<char *>(sa.data()), (std::streamsize)(z.sa_entries * 4));
-        if (get_count(in) != 2) throw std::runtime_error("bad lookup size in .fmi (LOOKUP_LEN = 0 expected)");
-        uint32_t lookup[2];
-        in.read(reinterpret_cast<char *>(lookup), 8);
-        if (get_count(in) != N) throw std::runtime_error("bad b_ size in .fmi");
-        in.read(reinterpret_cast<char *>(b.data()), (std::streamsize)(z.b_words * 8));
-        if (get_count(in) != z.b_occ_entries) throw std::runtime_error("bad b_occ_ size in .fmi");
-        in.read(reinterpret_cast<char *>(b_occ.data()), (std::streamsize)(z.b_occ_entries * 4));
+        if (c_occ1 * 4 != z.occ1_entries) throw std::runtime_error("bad occ1 size in .fmi");
+        if (c_occ2 * 4 != z.occ2_bytes) throw std::runtime_error("bad occ2 size in .fmi");
+        bwt.swap(bwt_in);
+        occ1.swap(occ1_in);
+        occ2.swap(occ2_in);
+        sa.swap(sa_in);
+        in.read(reinterpret_cast<char *>(lookup.data()), (std::streamsize)(c_lookup * 4));
+        if (sa_intv != 1) {
+            if (get_count(in) != N) throw std::runtime_error("bad b_ size in .fmi");
+            in.read(reinterpret_cast<char *>(b.data()), (std::streamsize)(z.b_words * 8));
+            if (get_count(in) != z.b_occ_entries) throw std::runtime_error("bad b_occ_ size in .fmi");
+            in.read(reinterpret_cast<char *>(b_occ.data()), (std::streamsize)(z.b_occ_entries * 4));
+        }
         if (!in || in.peek() != EOF) throw std::runtime_error("trailing or missing bytes in .fmi"); // fm_index.hpp:642
     }
     kiss_hip_fmi_view view() const
@@ -256,14 +293,37 @@ struct Fmi {
         v.n_sa = z.n_sa;
         for (int c = 0; c < 4; c++) v.cnt[c] = cnt[c];
         v.pri = pri;
-        v.sa_intv = 4;
+        v.sa_intv = sa_intv;
         v.bwt = bwt.data();
         v.occ1 = occ1.data();
         v.occ2 = occ2.data();
         v.sa = sa.data();
-        v.b = b.data();
-        v.b_occ = b_occ.data();
+        v.b = sa_intv == 1 ? nullptr : b.data();
+        v.b_occ = sa_intv == 1 ? nullptr : b_occ.data();
         return v;
+    }
+    kiss_hip_fmi_view_ex view_ex() const
+    {
+        kiss_hip_fmi_view_ex v{};
+        v.base = view();
+        v.lookup_len = lookup_len;
+        v.lookup = lookup.data();
+        return v;
+    }
+    // the batched query of either entry point (host pointers)
+    void query(const uint8_t *pat, uint32_t L, uint64_t Q, uint32_t *beg, uint32_t *end, uint64_t *hits, uint64_t *chk,
+               uint32_t *offsets, uint64_t *offsets_index, uint64_t capacity, int device) const
+    {
+        if (classic()) {
+            const kiss_hip_fmi_view v = view();
+            check(kiss_hip_fmi_query_batch_host(&v, pat, L, Q, beg, end, hits, chk, offsets, offsets_index, capacity, device),
+                  "kiss_hip_fmi_query_batch_host");
+        } else {
+            const kiss_hip_fmi_view_ex v = view_ex();
+            check(kiss_hip_fmi_query_ex_host(&v, pat, L, Q, 0, beg, end, nullptr, hits, chk, offsets, offsets_index, capacity,
+                                             device),
+                  "kiss_hip_fmi_query_ex_host");
+        }
     }
 };
 
@@ -358,11 +418,17 @@ int fmindex_build_main(const Args &a)
         S = T.to_host();
     }
     if (S.empty()) throw std::runtime_error("empty sequence");
-    Fmi f;
+    Fmi f(a.sa_intv, a.lookup_len);
     f.alloc(S.size());
-    check(kiss_hip_fmi_build_host(S.data(), S.size(), nullptr, f.bwt.data(), f.occ1.data(), f.occ2.data(), f.sa.data(),
-                                  f.b.data(), f.b_occ.data(), f.cnt, &f.pri, a.device),
-          "kiss_hip_fmi_build_host");
+    if (f.classic())
+        check(kiss_hip_fmi_build_host(S.data(), S.size(), nullptr, f.bwt.data(), f.occ1.data(), f.occ2.data(), f.sa.data(),
+                                      f.b.data(), f.b_occ.data(), f.cnt, &f.pri, a.device),
+              "kiss_hip_fmi_build_host");
+    else
+        check(kiss_hip_fmi_build_ex_host(S.data(), S.size(), nullptr, f.sa_intv, f.lookup_len, f.bwt.data(), f.occ1.data(),
+                                         f.occ2.data(), f.sa.data(), f.b.data(), f.b_occ.data(), f.lookup.data(), f.cnt,
+                                         &f.pri, a.device),
+              "kiss_hip_fmi_build_ex_host");
     f.save(a.fasta + ".fmi");
     return 0;
 }
@@ -384,21 +450,18 @@ int fmindex_query_main(const Args &a)
         DeviceText T(a.fasta, a.device);
         S = T.to_host();
     }
-    Fmi f;
+    Fmi f(a.sa_intv, 0);
     f.load(a.fasta + ".fmi");
-    const kiss_hip_fmi_view v = f.view();
     if (!a.query.empty()) {
         std::vector<uint8_t> q;
         for (unsigned char c : a.query) q.push_back(to_code(c));
         uint32_t beg = 0, end = 0;
         uint64_t hits = 0, chk = 0;
-        check(kiss_hip_fmi_query_batch_host(&v, q.data(), (uint32_t)q.size(), 1, &beg, &end, &hits, &chk, nullptr, nullptr, 0,
-                                            a.device), "kiss_hip_fmi_query_batch_host");
+        f.query(q.data(), (uint32_t)q.size(), 1, &beg, &end, &hits, &chk, nullptr, nullptr, 0, a.device);
         std::vector<uint32_t> off(hits + 1);
         std::vector<uint64_t> idx(2);
         if (hits)
-            check(kiss_hip_fmi_query_batch_host(&v, q.data(), (uint32_t)q.size(), 1, &beg, &end, &hits, &chk, off.data(),
-                                                idx.data(), hits, a.device), "kiss_hip_fmi_query_batch_host");
+            f.query(q.data(), (uint32_t)q.size(), 1, &beg, &end, &hits, &chk, off.data(), idx.data(), hits, a.device);
         std::string qs;
         for (auto c : q) qs.push_back("ACGT"[c]);
         std::fprintf(stderr, "[info] query = %s found %llu times\n", qs.c_str(), (unsigned long long)hits);
@@ -423,8 +486,7 @@ int fmindex_query_main(const Args &a)
         std::vector<uint32_t> beg(Q), end(Q);
         uint64_t hits = 0, chk = 0;
         const auto t0 = std::chrono::steady_clock::now();
-        check(kiss_hip_fmi_query_batch_host(&v, pat.data(), L, Q, beg.data(), end.data(), &hits, &chk, nullptr, nullptr, 0,
-                                            a.device), "kiss_hip_fmi_query_batch_host");
+        f.query(pat.data(), L, Q, beg.data(), end.data(), &hits, &chk, nullptr, nullptr, 0, a.device);
         std::fprintf(stderr, "[info] searching time: %.6f seconds\n", seconds_since(t0));
         std::fprintf(stderr, "[info] number of matched locations: %llu\n", (unsigned long long)hits);
         std::fprintf(stderr, "[info] location checksum: %llu\n", (unsigned long long)chk);

@@ -1,6 +1,7 @@
-"""Host-side mirror of biovoltron::FMIndex<4, uint32_t, KISS1Sorter<uint32_t>>{.LOOKUP_LEN = 0}
-(reference include/biovoltron/algo/align/exact_match/fm_index.hpp; instantiated by
-include/command/fmindex_build.hpp:27-29 and fmindex_query.hpp:26-28).
+"""Host-side mirror of biovoltron::FMIndex<SA_INTV, uint32_t, KISS1Sorter<uint32_t>>{.LOOKUP_LEN}
+(reference include/biovoltron/algo/align/exact_match/fm_index.hpp).  The defaults, SA_INTV = 4 and LOOKUP_LEN = 0, are
+the instantiation of the reference CLI (include/command/fmindex_build.hpp:27-29 and fmindex_query.hpp:26-28) and run
+through the original entry points; FMIndex(sa_intv=1..32, lookup_len=0..14) runs through the kiss_hip_fmi_*_ex_* ones.
 
 Same member names and meaning: build(ref), save(path) / load(path) in the reference's `.fmi`
 byte layout (fm_index.hpp:591-646), get_range(seed), get_offsets(beg, end), plus
@@ -19,6 +20,7 @@ from . import _lib
 from .sorter import Context, _check
 
 SA_INTV = 4          # fmindex_build.hpp:27
+MAX_SA_INTV, MAX_LOOKUP_LEN = 32, 14  # KISS_HIP_FMI_MAX_SA_INTV / KISS_HIP_FMI_MAX_LOOKUP_LEN
 SORT_LEN = 32        # FMIndex::build sorts with k = 32 whatever the CLI flags say (fm_index.hpp:384-386)
 OCC1_INTV, OCC2_INTV, B_OCC_INTV = 256, 16, 64
 
@@ -30,38 +32,59 @@ def _torch():
     return torch
 
 
+def _check_params(sa_intv, lookup_len):
+    if not 1 <= sa_intv <= MAX_SA_INTV:
+        raise ValueError("sa_intv must be in 1..%d, got %d" % (MAX_SA_INTV, sa_intv))
+    if not 0 <= lookup_len <= MAX_LOOKUP_LEN:
+        raise ValueError("lookup_len must be in 0..%d, got %d" % (MAX_LOOKUP_LEN, lookup_len))
+
+
 class FMIndex:
-    def __init__(self, device=0):
+    def __init__(self, device=0, sa_intv=SA_INTV, lookup_len=0):
+        _check_params(int(sa_intv), int(lookup_len))
         self.device = int(device)
+        self.sa_intv = int(sa_intv)
+        self.lookup_len = int(lookup_len)
         self.N = 0
         self.cnt = np.zeros(4, np.uint32)
         self.pri = 0
-        self.bwt = self.occ1 = self.occ2 = self.sa = self.b = self.b_occ = None  # torch tensors on the GPU
+        # torch tensors on the GPU; b / b_occ stay None when sa_intv == 1 (the reference keeps no bit-vector)
+        self.bwt = self.occ1 = self.occ2 = self.sa = self.b = self.b_occ = self.lookup = None
         self._ctx = None
+
+    @property
+    def _classic(self):
+        """the CLI's instantiation, served by the original entry points"""
+        return self.sa_intv == SA_INTV and self.lookup_len == 0
 
     # ---- sizes of the .fmi arrays for an SA of N entries -------------------------------------------
     @staticmethod
-    def _sizes(N):
+    def _sizes(N, sa_intv=SA_INTV, lookup_len=0):
         return {
             "bwt": (N + 3) // 4,                      # bytes
             "occ1": (N // OCC1_INTV + 1) * 4,          # u32
             "occ2": (N // OCC2_INTV + 1) * 4,          # u8
-            "sa": (N + SA_INTV - 1) // SA_INTV,        # u32
-            "b": (N + 63) // 64,                       # u64
-            "b_occ": N // B_OCC_INTV + 1,              # u32
+            "sa": (N + sa_intv - 1) // sa_intv,        # u32
+            "lookup": 4 ** lookup_len + 1,             # u32
+            "b": (N + 63) // 64 if sa_intv != 1 else 0,        # u64
+            "b_occ": N // B_OCC_INTV + 1 if sa_intv != 1 else 0,  # u32
         }
 
     def _alloc(self, N):
         torch = _torch()
         dev = torch.device("cuda", self.device)
-        sz = self._sizes(N)
+        sz = self._sizes(N, self.sa_intv, self.lookup_len)
         self.N = N
         self.bwt = torch.zeros(sz["bwt"] + 8, dtype=torch.uint8, device=dev)
         self.occ1 = torch.zeros(sz["occ1"], dtype=torch.int32, device=dev)
         self.occ2 = torch.zeros(sz["occ2"], dtype=torch.uint8, device=dev)
         self.sa = torch.zeros(sz["sa"], dtype=torch.int32, device=dev)
-        self.b = torch.zeros(sz["b"] + 1, dtype=torch.int64, device=dev)
-        self.b_occ = torch.zeros(sz["b_occ"], dtype=torch.int32, device=dev)
+        self.lookup = torch.zeros(sz["lookup"], dtype=torch.int32, device=dev)
+        if self.sa_intv != 1:
+            self.b = torch.zeros(sz["b"] + 1, dtype=torch.int64, device=dev)
+            self.b_occ = torch.zeros(sz["b_occ"], dtype=torch.int32, device=dev)
+        else:
+            self.b = self.b_occ = None
 
     def _context(self, max_n):
         if self._ctx is None or self._ctx.max_n < max_n:
@@ -72,36 +95,54 @@ class FMIndex:
 
     # ---- build (fm_index.hpp:379-451) ------------------------------------------------------------------
     def build(self, ref, sa=None):
-        """ref: uint8 array with values 0..3.  Sorts with k = 32 (like the reference) unless `sa` is given."""
+        """ref: uint8 array with values 0..3.  Sorts with k = 32 (like the reference) unless `sa` is given.
+        ref / sa may also be device tensors of this device (uint8 / int32 holding the u32 values): used in place."""
         torch = _torch()
         dev = torch.device("cuda", self.device)
-        ref = np.ascontiguousarray(ref, dtype=np.uint8)
-        n = ref.size
-        ctx = self._context(n)
-        d_S = torch.from_numpy(ref).to(dev)
-        d_SA = torch.empty(n + 1, dtype=torch.int32, device=dev)
-        if sa is None:
-            ctx.suffix_sort_dev(d_S.data_ptr(), n, d_SA.data_ptr(), k=SORT_LEN)
+        if isinstance(ref, torch.Tensor) and ref.device == dev:
+            d_S = ref.contiguous()
         else:
+            d_S = torch.from_numpy(np.ascontiguousarray(ref, dtype=np.uint8)).to(dev)
+        n = d_S.numel()
+        ctx = self._context(n)
+        if sa is None:
+            d_SA = torch.empty(n + 1, dtype=torch.int32, device=dev)
+            ctx.suffix_sort_dev(d_S.data_ptr(), n, d_SA.data_ptr(), k=SORT_LEN)
+        elif isinstance(sa, torch.Tensor) and sa.device == dev:
+            d_SA = sa.contiguous()
+            if d_SA.numel() != n + 1 or d_SA.element_size() != 4:
+                raise ValueError("sa must hold n + 1 32-bit entries")
+        else:
+            d_SA = torch.empty(n + 1, dtype=torch.int32, device=dev)
             d_SA.copy_(torch.from_numpy(np.ascontiguousarray(sa, dtype=np.uint32).view(np.int32)))
         self._alloc(n + 1)
         cnt = (ctypes.c_uint32 * 4)()
         pri = ctypes.c_uint32()
         lib = _lib.load()
-        _check(lib.kiss_hip_fmi_build_dev(ctx._ctx, ctypes.c_void_p(d_S.data_ptr()), n,
-                                          ctypes.c_void_p(d_SA.data_ptr()), SA_INTV,
-                                          ctypes.c_void_p(self.bwt.data_ptr()), ctypes.c_void_p(self.occ1.data_ptr()),
-                                          ctypes.c_void_p(self.occ2.data_ptr()), ctypes.c_void_p(self.sa.data_ptr()),
-                                          ctypes.c_void_p(self.b.data_ptr()), ctypes.c_void_p(self.b_occ.data_ptr()),
-                                          ctypes.byref(cnt), ctypes.byref(pri), None),
-               "kiss_hip_fmi_build_dev", ctx._ctx)
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)  # noqa: E731
+        if self._classic:
+            _check(lib.kiss_hip_fmi_build_dev(ctx._ctx, ctypes.c_void_p(d_S.data_ptr()), n,
+                                              ctypes.c_void_p(d_SA.data_ptr()), SA_INTV,
+                                              ptr(self.bwt), ptr(self.occ1), ptr(self.occ2), ptr(self.sa), ptr(self.b),
+                                              ptr(self.b_occ), ctypes.byref(cnt), ctypes.byref(pri), None),
+                   "kiss_hip_fmi_build_dev", ctx._ctx)
+            self.lookup.copy_(torch.tensor([0, n + 1], dtype=torch.int64).to(torch.int32))  # LOOKUP_LEN = 0: {0, N}
+        else:
+            _check(lib.kiss_hip_fmi_build_ex_dev(ctx._ctx, ctypes.c_void_p(d_S.data_ptr()), n,
+                                                 ctypes.c_void_p(d_SA.data_ptr()), self.sa_intv, self.lookup_len,
+                                                 ptr(self.bwt), ptr(self.occ1), ptr(self.occ2), ptr(self.sa), ptr(self.b),
+                                                 ptr(self.b_occ), ptr(self.lookup), ctypes.byref(cnt), ctypes.byref(pri),
+                                                 None),
+                   "kiss_hip_fmi_build_ex_dev", ctx._ctx)
         self.cnt = np.array(list(cnt), dtype=np.uint32)
         self.pri = int(pri.value)
         return self
 
     # ---- .fmi serialisation (fm_index.hpp:591-646; Serializer: u64 count + raw bytes, nothing when empty) -----
+    # order: cnt, pri, bwt, occ1, occ2, sa_, lookup_, then b_ and b_occ_ only if SA_INTV != 1; no header (SA_INTV is a
+    # template parameter of the reference, LOOKUP_LEN follows from the lookup_ count)
     def to_bytes(self):
-        sz = self._sizes(self.N)
+        sz = self._sizes(self.N, self.sa_intv, self.lookup_len)
         N = self.N
         out = [self.cnt.astype("<u4").tobytes(), struct.pack("<I", self.pri)]
 
@@ -113,9 +154,10 @@ class FMIndex:
         vec(sz["occ1"] // 4, self.occ1.cpu().numpy().view(np.uint32).astype("<u4").tobytes())
         vec(sz["occ2"] // 4, self.occ2.cpu().numpy().tobytes())
         vec(sz["sa"], self.sa.cpu().numpy().view(np.uint32).astype("<u4").tobytes())
-        vec(2, np.array([0, N], dtype="<u4").tobytes())  # lookup_ for LOOKUP_LEN = 0 (fm_index.hpp:238-258)
-        vec(N, self.b[:sz["b"]].cpu().numpy().view(np.uint64).astype("<u8").tobytes())
-        vec(sz["b_occ"], self.b_occ.cpu().numpy().view(np.uint32).astype("<u4").tobytes())
+        vec(sz["lookup"], self.lookup.cpu().numpy().view(np.uint32).astype("<u4").tobytes())  # (fm_index.hpp:238-270)
+        if self.sa_intv != 1:
+            vec(N, self.b[:sz["b"]].cpu().numpy().view(np.uint64).astype("<u8").tobytes())
+            vec(sz["b_occ"], self.b_occ.cpu().numpy().view(np.uint32).astype("<u4").tobytes())
         return b"".join(out)
 
     def save(self, path):
@@ -123,31 +165,52 @@ class FMIndex:
             f.write(self.to_bytes())
 
     @classmethod
-    def from_bytes(cls, buf, device=0):
+    def from_bytes(cls, buf, device=0, sa_intv=SA_INTV):
+        """the file does not record SA_INTV: the caller names it, and a file whose vector counts do not fit it is
+        rejected; LOOKUP_LEN is read from the lookup_ count (4^L + 1)"""
         torch = _torch()
-        self = cls(device)
+        _check_params(int(sa_intv), 0)
         mv = memoryview(buf)
-        self.cnt = np.frombuffer(mv[:16], dtype="<u4").astype(np.uint32)
-        self.pri = struct.unpack_from("<I", mv, 16)[0]
+        cnt = np.frombuffer(mv[:16], dtype="<u4").astype(np.uint32)
+        pri = struct.unpack_from("<I", mv, 16)[0]
         off = 20
 
         def vec(elem_bytes_of_count):
             nonlocal off
+            if off + 8 > len(mv):
+                raise ValueError("truncated .fmi")
             count = struct.unpack_from("<Q", mv, off)[0]
             off += 8
             nbytes = elem_bytes_of_count(count)
+            if off + nbytes > len(mv):
+                raise ValueError("truncated .fmi")
             raw = bytes(mv[off:off + nbytes])
             off += nbytes
             return count, raw
         N, bwt = vec(lambda c: (c + 3) // 4)
-        _, occ1 = vec(lambda c: c * 16)
-        _, occ2 = vec(lambda c: c * 4)
-        _, sa = vec(lambda c: c * 4)
-        _, _lookup = vec(lambda c: c * 4)
-        _, b = vec(lambda c: ((c + 63) // 64) * 8)
-        _, b_occ = vec(lambda c: c * 4)
+        c_occ1, occ1 = vec(lambda c: c * 16)
+        c_occ2, occ2 = vec(lambda c: c * 4)
+        c_sa, sa = vec(lambda c: c * 4)
+        c_lookup, lookup = vec(lambda c: c * 4)
+        lookup_len = next((L for L in range(MAX_LOOKUP_LEN + 1) if 4 ** L + 1 == c_lookup), None)
+        if lookup_len is None:
+            raise ValueError("lookup_ has %d entries, not 4^L + 1 for any L in 0..%d" % (c_lookup, MAX_LOOKUP_LEN))
+        sz = cls._sizes(N, sa_intv, lookup_len)
+        if c_occ1 * 4 != sz["occ1"] or c_occ2 * 4 != sz["occ2"]:
+            raise ValueError("occ sizes of the .fmi do not fit N = %d" % N)
+        if c_sa != sz["sa"]:
+            raise ValueError("sa_ has %d entries; SA_INTV = %d needs %d" % (c_sa, sa_intv, sz["sa"]))
+        b = b_occ = None
+        if sa_intv != 1:
+            c_b, b = vec(lambda c: ((c + 63) // 64) * 8)
+            c_bocc, b_occ = vec(lambda c: c * 4)
+            if c_b != N or c_bocc != sz["b_occ"]:
+                raise ValueError("b_ / b_occ_ sizes of the .fmi do not fit N = %d" % N)
         if off != len(mv):
             raise ValueError("trailing bytes in .fmi (the reference asserts EOF, fm_index.hpp:642)")
+        self = cls(device, sa_intv=sa_intv, lookup_len=lookup_len)
+        self.cnt = cnt
+        self.pri = pri
         self._alloc(N)
         dev = self.bwt.device
 
@@ -160,14 +223,16 @@ class FMIndex:
         put(self.occ1, occ1, "<u4")
         put(self.occ2, occ2, "u1")
         put(self.sa, sa, "<u4")
-        put(self.b, b, "<u8")
-        put(self.b_occ, b_occ, "<u4")
+        put(self.lookup, lookup, "<u4")
+        if sa_intv != 1:
+            put(self.b, b, "<u8")
+            put(self.b_occ, b_occ, "<u4")
         return self
 
     @classmethod
-    def load(cls, path, device=0):
+    def load(cls, path, device=0, sa_intv=SA_INTV):
         with open(path, "rb") as f:
-            return cls.from_bytes(f.read(), device)
+            return cls.from_bytes(f.read(), device, sa_intv)
 
     # ---- queries -------------------------------------------------------------------------------------------
     def _view(self):
@@ -176,21 +241,26 @@ class FMIndex:
         for c in range(4):
             v.cnt[c] = int(self.cnt[c])
         v.pri = self.pri
-        v.sa_intv = SA_INTV
+        v.sa_intv = self.sa_intv
         v.bwt = self.bwt.data_ptr()
         v.occ1 = self.occ1.data_ptr()
         v.occ2 = self.occ2.data_ptr()
         v.sa = self.sa.data_ptr()
-        v.b = self.b.data_ptr()
-        v.b_occ = self.b_occ.data_ptr()
+        v.b = self.b.data_ptr() if self.b is not None else None
+        v.b_occ = self.b_occ.data_ptr() if self.b_occ is not None else None
         return v
 
-    def query_batch(self, patterns, want_offsets=True, d_patterns=None, keep_on_device=False):
+    def query_batch(self, patterns, want_offsets=True, d_patterns=None, keep_on_device=False, stop_cnt=0, want_offs=False):
         """patterns: (Q, L) uint8 array with values 0..3 (host) or a device tensor via d_patterns.
-        Returns dict(beg, end, total_hits, checksum[, offsets, offsets_index]); keep_on_device: beg / end stay device
-        tensors (int32 holding the u32 values) instead of being copied to the host."""
+        Returns dict(beg, end, total_hits, checksum[, offsets, offsets_index][, offs]); keep_on_device: beg / end (and
+        offs) stay device tensors (int32 holding the u32 values) instead of being copied to the host.
+        stop_cnt: get_range's early stop (0: none; 0xFFFFFFFF also never stops, stop_cnt + 1 wraps in u32);
+        want_offs: also get_range's third value, the characters left unmatched per pattern."""
         torch = _torch()
         dev = torch.device("cuda", self.device)
+        stop_cnt = int(stop_cnt)
+        if not 0 <= stop_cnt <= 0xFFFFFFFF:
+            raise ValueError("stop_cnt is a u32")
         if d_patterns is None:
             patterns = np.ascontiguousarray(patterns, dtype=np.uint8)
             d_patterns = torch.from_numpy(patterns).to(dev)
@@ -198,47 +268,60 @@ class FMIndex:
         ctx = self._context(max(self.N, 4 * Q))
         beg = torch.empty(Q, dtype=torch.int32, device=dev)
         end = torch.empty(Q, dtype=torch.int32, device=dev)
+        offs = torch.empty(Q, dtype=torch.int32, device=dev) if want_offs else None
         tot = ctypes.c_uint64()
         chk = ctypes.c_uint64()
         lib = _lib.load()
         view = self._view()
+        if self._classic and stop_cnt == 0 and not want_offs:
+            def call(offsets, index, cap):
+                _check(lib.kiss_hip_fmi_query_batch_dev(ctx._ctx, ctypes.byref(view), ctypes.c_void_p(d_patterns.data_ptr()),
+                                                        L, Q, ctypes.c_void_p(beg.data_ptr()),
+                                                        ctypes.c_void_p(end.data_ptr()), ctypes.byref(tot),
+                                                        ctypes.byref(chk), offsets, index, cap, None),
+                       "kiss_hip_fmi_query_batch_dev", ctx._ctx)
+        else:
+            vex = _lib.FmiViewEx()
+            vex.base = view
+            vex.lookup_len = self.lookup_len
+            vex.lookup = self.lookup.data_ptr()
+
+            def call(offsets, index, cap):
+                _check(lib.kiss_hip_fmi_query_ex_dev(ctx._ctx, ctypes.byref(vex), ctypes.c_void_p(d_patterns.data_ptr()),
+                                                     L, Q, stop_cnt, ctypes.c_void_p(beg.data_ptr()),
+                                                     ctypes.c_void_p(end.data_ptr()),
+                                                     ctypes.c_void_p(offs.data_ptr() if offs is not None else None),
+                                                     ctypes.byref(tot), ctypes.byref(chk), offsets, index, cap, None),
+                       "kiss_hip_fmi_query_ex_dev", ctx._ctx)
         res = {}
+        # first pass sizes the output; the library needs a capacity, so run ranges once to learn it
+        call(None, None, 0)
         if want_offsets:
-            # first pass sizes the output; the library needs a capacity, so run ranges once to learn it
-            _check(lib.kiss_hip_fmi_query_batch_dev(ctx._ctx, ctypes.byref(view), ctypes.c_void_p(d_patterns.data_ptr()),
-                                                    L, Q, ctypes.c_void_p(beg.data_ptr()),
-                                                    ctypes.c_void_p(end.data_ptr()), ctypes.byref(tot),
-                                                    ctypes.byref(chk), None, None, 0, None),
-                   "kiss_hip_fmi_query_batch_dev", ctx._ctx)
             cap = int(tot.value)
             offsets = torch.empty(max(cap, 1), dtype=torch.int32, device=dev)
             index = torch.empty(Q + 1, dtype=torch.int64, device=dev)
-            _check(lib.kiss_hip_fmi_query_batch_dev(ctx._ctx, ctypes.byref(view), ctypes.c_void_p(d_patterns.data_ptr()),
-                                                    L, Q, ctypes.c_void_p(beg.data_ptr()),
-                                                    ctypes.c_void_p(end.data_ptr()), ctypes.byref(tot),
-                                                    ctypes.byref(chk), ctypes.c_void_p(offsets.data_ptr()),
-                                                    ctypes.c_void_p(index.data_ptr()), cap, None),
-                   "kiss_hip_fmi_query_batch_dev", ctx._ctx)
+            call(ctypes.c_void_p(offsets.data_ptr()), ctypes.c_void_p(index.data_ptr()), cap)
             res["offsets"] = offsets[:cap].cpu().numpy().view(np.uint32)
             res["offsets_index"] = index.cpu().numpy().view(np.uint64)
-        else:
-            _check(lib.kiss_hip_fmi_query_batch_dev(ctx._ctx, ctypes.byref(view), ctypes.c_void_p(d_patterns.data_ptr()),
-                                                    L, Q, ctypes.c_void_p(beg.data_ptr()),
-                                                    ctypes.c_void_p(end.data_ptr()), ctypes.byref(tot),
-                                                    ctypes.byref(chk), None, None, 0, None),
-                   "kiss_hip_fmi_query_batch_dev", ctx._ctx)
         if keep_on_device:
             res["beg"], res["end"] = beg, end
+            if offs is not None:
+                res["offs"] = offs
         else:
             res["beg"] = beg.cpu().numpy().view(np.uint32)
             res["end"] = end.cpu().numpy().view(np.uint32)
+            if offs is not None:
+                res["offs"] = offs.cpu().numpy().view(np.uint32)
         res["total_hits"] = int(tot.value)
         res["checksum"] = int(chk.value)
         return res
 
-    def get_range(self, seed):
-        """(beg, end) of one pattern (fm_index.hpp:574-584)."""
-        r = self.query_batch(np.asarray(seed, dtype=np.uint8)[None, :], want_offsets=False)
+    def get_range(self, seed, stop_cnt=0, with_offset=False):
+        """(beg, end) of one pattern (fm_index.hpp:553-584); with_offset: (beg, end, offset), the reference's array"""
+        r = self.query_batch(np.asarray(seed, dtype=np.uint8)[None, :], want_offsets=False, stop_cnt=stop_cnt,
+                             want_offs=with_offset)
+        if with_offset:
+            return int(r["beg"][0]), int(r["end"][0]), int(r["offs"][0])
         return int(r["beg"][0]), int(r["end"][0])
 
     def get_offsets_of(self, seed):
