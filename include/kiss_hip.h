@@ -445,6 +445,45 @@ int kiss_hip_fmi_query_ex_host(const kiss_hip_fmi_view_ex *fmi, const uint8_t *p
 int kiss_hip_suffix_sort_u8(const uint8_t *S, uint64_t n, uint32_t *SA, int device);
 int kiss_hip_ctx_suffix_sort_u8_dev(kiss_hip_ctx *ctx, const uint8_t *d_S, uint64_t n, uint32_t *d_SA, void *stream);
 
+/* ---- LCP array of an exact suffix array (DNA and bytes) -------------------------------------------------------
+ * Input: a text S of n symbols and its EXACT suffix array SA (n + 1 entries, SA[0] = n: the convention of
+ * kiss_hip_suffix_sort_dna_u32 / kiss_hip_suffix_sort_u8).  Output: LCP, n + 1 u32, LCP[0] = 0 and for i >= 1 the length
+ * of the longest common prefix of suffixes SA[i-1] and SA[i] (so LCP[1] = 0: suffix SA[0] is the empty one).
+ *   _dna_u32: symbols 0..3, only the low 2 bits are used (as the sort);  _u8: the full byte range.
+ * SA[0] != n or an entry > n: KISS_HIP_E_INVALID (checked on the device, nothing is written to LCP).  An SA that is a
+ * permutation but not the exact order -- e.g. the k-ordered SA of PARALLEL_SORTING -- gives UNSPECIFIED values (the
+ * permuted-LCP relation the computation rests on holds for the exact order only); the call still stays inside its arrays
+ * and returns KISS_HIP_OK.  n = 0 gives LCP = {0}.
+ * Device time goes into the report below, never into kiss_hip_stats.  The calls take the per-device lock of the sorts.
+ * Work arrays: the ctx's own (the packed text, the context words, the LMS work arrays): after an exact sort of the same n
+ * on the ctx an LCP call allocates nothing; on a fresh ctx it allocates what that sort would have. */
+typedef struct kiss_hip_lcp_report {
+    uint64_t n;
+    uint64_t irreducible;     /* positions whose lcp was computed directly (the rest follow from their left neighbour) */
+    uint64_t long_pairs;      /* of those, pairs sent on from the one-lane compare to the cooperative one */
+    uint64_t lcp_sum;         /* sum of LCP[1..n] */
+    uint32_t max_lcp;
+    uint32_t reserved_;
+    float ms_total;           /* device time of the call (HIP events) */
+    float ms_phi;             /* text packing / padded copy + Phi scatter with the SA checks */
+    float ms_short;           /* irreducible test + one-lane compares */
+    float ms_long;            /* cooperative compares (one wave per pair, then the whole grid per pair) */
+    float ms_scan_gather;     /* max-scan to PLCP + LCP[i] = PLCP[SA[i]] */
+    uint32_t reserved2_;
+} kiss_hip_lcp_report;
+/* device-resident: d_S (n symbols), d_SA (n + 1), d_LCP (n + 1) on the ctx's device; d_LCP may be d_SA (the LCP then
+ * replaces the SA); report may be NULL.  stream: as kiss_hip_ctx_suffix_sort_dna_u32_dev; returns after the work is done. */
+int kiss_hip_ctx_lcp_dna_u32_dev(kiss_hip_ctx *ctx, const uint8_t *d_S, uint64_t n, const uint32_t *d_SA, uint32_t *d_LCP,
+                                 kiss_hip_lcp_report *report, void *stream);
+int kiss_hip_ctx_lcp_u8_dev(kiss_hip_ctx *ctx, const uint8_t *d_S, uint64_t n, const uint32_t *d_SA, uint32_t *d_LCP,
+                            kiss_hip_lcp_report *report, void *stream);
+/* host-pointer one-shots on the cached per-device context (as kiss_hip_suffix_sort_dna_u32): SA_or_null == NULL sorts in
+ * exact order first and writes that SA to SA_out (n + 1 entries; SA_out may be NULL as well).  With an SA given, SA_out
+ * (if not NULL) receives a copy of it. */
+int kiss_hip_lcp_dna_u32(const uint8_t *S, uint64_t n, const uint32_t *SA_or_null, uint32_t *SA_out, uint32_t *LCP,
+                         int device);
+int kiss_hip_lcp_u8(const uint8_t *S, uint64_t n, const uint32_t *SA_or_null, uint32_t *SA_out, uint32_t *LCP, int device);
+
 /* ---- FASTA / plain-text input parsed on the device (replaces read_sequence, include/utils/io.hpp:6-18, and the
  * `c % 4` of command/suffix_sort.hpp:33; record rules of biovoltron/file_io/fasta.hpp:117-151) ------------------
  * The file is FASTA iff its first byte is '>'.  Header lines are dropped, every other byte except '\n' is a base:

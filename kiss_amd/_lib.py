@@ -81,6 +81,18 @@ class VerifyReport(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved_"}
 
 
+class LcpReport(ctypes.Structure):
+    _fields_ = [
+        ("n", ctypes.c_uint64), ("irreducible", ctypes.c_uint64), ("long_pairs", ctypes.c_uint64),
+        ("lcp_sum", ctypes.c_uint64), ("max_lcp", ctypes.c_uint32), ("reserved_", ctypes.c_uint32),
+        ("ms_total", ctypes.c_float), ("ms_phi", ctypes.c_float), ("ms_short", ctypes.c_float), ("ms_long", ctypes.c_float),
+        ("ms_scan_gather", ctypes.c_float), ("reserved2_", ctypes.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
+
+
 class FmiView(ctypes.Structure):
     _fields_ = [
         ("n_sa", ctypes.c_uint64), ("cnt", ctypes.c_uint32 * 4), ("pri", ctypes.c_uint32),
@@ -216,6 +228,12 @@ def load(hooks=None):
     lib.kiss_hip_free_dev.argtypes = [vp]
     lib.kiss_hip_alloc_dev.argtypes = [ctypes.POINTER(vp), u64]
     lib.kiss_hip_alloc_dev.restype = ctypes.c_int
+    for name in ("kiss_hip_ctx_lcp_dna_u32_dev", "kiss_hip_ctx_lcp_u8_dev"):
+        getattr(lib, name).argtypes = [vp, vp, u64, vp, vp, ctypes.POINTER(LcpReport), vp]
+        getattr(lib, name).restype = ctypes.c_int
+    for name in ("kiss_hip_lcp_dna_u32", "kiss_hip_lcp_u8"):
+        getattr(lib, name).argtypes = [vp, u64, vp, vp, vp, ctypes.c_int]
+        getattr(lib, name).restype = ctypes.c_int
     for name in ("kiss_hip_file_size", "kiss_hip_ctx_parse_text_dev", "kiss_hip_ctx_load_text_file",
                  "kiss_hip_copy_to_host", "kiss_hip_free_dev"):
         getattr(lib, name).restype = ctypes.c_int
@@ -259,5 +277,6 @@ EXPORTED_SYMBOLS = [
     "kiss_hip_suffix_sort_dna_u32_multi", "kiss_hip_debug_splitters", "kiss_hip_debug_fail_alloc_over",
     "kiss_hip_has_hooks", "kiss_hip_release_cached_contexts", "kiss_hip_get_stats_sized",
     "kiss_hip_fmi_sizes_ex_for", "kiss_hip_fmi_build_ex_dev", "kiss_hip_fmi_query_ex_dev", "kiss_hip_fmi_build_ex_host",
-    "kiss_hip_fmi_query_ex_host",
+    "kiss_hip_fmi_query_ex_host", "kiss_hip_ctx_lcp_dna_u32_dev", "kiss_hip_ctx_lcp_u8_dev", "kiss_hip_lcp_dna_u32",
+    "kiss_hip_lcp_u8",
 ]

@@ -542,17 +542,10 @@ int kiss_tied_reserve(kiss_hip_ctx *ctx, uint64_t t_cap)
     return rc;
 }
 
-// Host S -> host SA around a device-resident sort on `ctx`'s device (the reference's own timed region,
-// command/suffix_sort.hpp:57-61): upload into the ctx-owned device copies, sort(arg, d_S, d_SA), download -- finished
-// stretches of SA leave while the sweeps still run when SA is page-locked and the order is bounded (xfer.hip).  Shared by
-// the single-device entry and the multi-device one (multi.hip: device 0 runs the induction, so the SA lives there).
-int kiss_host_sort(kiss_hip_ctx *ctx, const uint8_t *S, uint64_t n, uint32_t k, uint32_t *SA,
-                   int (*sort)(void *, const uint8_t *, uint32_t *), void *arg)
+// device-side copies of the caller's buffers for the host-pointer entry points: owned by the ctx, sized for max_n
+int kiss_io_reserve(kiss_hip_ctx *ctx, uint64_t n)
 {
-    KCHECK(hipSetDevice(ctx->device));
-    kiss_opts_refresh(ctx);
-    ctx->stream = ctx->own_stream;
-    if (!ctx->io_S || !ctx->io_SA || ctx->io_cap < n) { // device-side copies of the caller's buffers: owned by the ctx, sized for max_n
+    if (!ctx->io_S || !ctx->io_SA || ctx->io_cap < n) {
         if (ctx->io_S) (void)hipFree(ctx->io_S);
         if (ctx->io_SA) (void)hipFree(ctx->io_SA);
         ctx->io_S = nullptr;
@@ -574,6 +567,20 @@ int kiss_host_sort(kiss_hip_ctx *ctx, const uint8_t *S, uint64_t n, uint32_t k, 
         ctx->io_cap = cap;
         ctx->ws_bytes += 5 * cap + 4;
     }
+    return KISS_HIP_OK;
+}
+
+// Host S -> host SA around a device-resident sort on `ctx`'s device (the reference's own timed region,
+// command/suffix_sort.hpp:57-61): upload into the ctx-owned device copies, sort(arg, d_S, d_SA), download -- finished
+// stretches of SA leave while the sweeps still run when SA is page-locked and the order is bounded (xfer.hip).  Shared by
+// the single-device entry and the multi-device one (multi.hip: device 0 runs the induction, so the SA lives there).
+int kiss_host_sort(kiss_hip_ctx *ctx, const uint8_t *S, uint64_t n, uint32_t k, uint32_t *SA,
+                   int (*sort)(void *, const uint8_t *, uint32_t *), void *arg)
+{
+    KCHECK(hipSetDevice(ctx->device));
+    kiss_opts_refresh(ctx);
+    ctx->stream = ctx->own_stream;
+    KTRY(kiss_io_reserve(ctx, n));
     using clk = std::chrono::steady_clock;
     const auto t0 = clk::now();
     KTRY(kiss_xfer_h2d(ctx, ctx->io_S, S, n));
@@ -966,3 +973,21 @@ int kiss_hip_ctx_get_stage_outputs(kiss_hip_ctx *ctx, uint32_t *lms_ascending, u
 }
 
 } // extern "C"
+
+// fn(ctx, arg) on the device's cached one-shot context grown to n bases, under the cache lock (the one-shot entries of
+// other files: lcp.hip)
+int kiss_cached_ctx_run(int device, uint64_t n, int (*fn)(kiss_hip_ctx *, void *), void *arg)
+{
+    if (device < 0 || device >= 64) return KISS_HIP_E_NO_DEVICE;
+    CachedCtx &c = *cached_ctx(device);
+    std::lock_guard<std::mutex> lock(c.m);
+    kiss_hip_ctx *ctx = nullptr;
+    int rc = cached_ctx_for(c, device, n, &ctx);
+    if (rc) return rc;
+    rc = fn(ctx, arg);
+    if (rc == KISS_HIP_E_NOMEM || rc == KISS_HIP_E_HIP) { // as kiss_hip_suffix_sort_dna_u32
+        kiss_hip_ctx_destroy(c.ctx);
+        c.ctx = nullptr;
+    }
+    return rc;
+}

@@ -9,7 +9,7 @@
 //    defaults 4 and 0 are the reference CLI's; the query reads L from the file, which does not record N)
 // and its log fields ("n = …, k = …, suffix sorting elapsed …", "query = … found N times", "searching time",
 // "number of matched locations", "location checksum").  Extras (opt-in): --output-sa FILE (raw u32 LE, n+1
-// entries; the reference never writes the SA), --device N, and for suffix_sort --gpus N / --devices LIST (the LMS sort
+// entries; the reference never writes the SA), --output-lcp FILE (the LCP array of an exact suffix array, same format), --device N, and for suffix_sort --gpus N / --devices LIST (the LMS sort
 // sharded over several GPUs of the node by ONE process, kiss_hip_multi_*; include/kiss_hip.h).
 // Input handling as utils/io.hpp:6-18 + suffix_sort.hpp:33: FASTA if the first byte is '>' (all records
 // concatenated), else plain text lines; ACGT/acgt -> 0..3, every other character -> 4 % 4 = 0 (A).
@@ -46,6 +46,7 @@ void usage()
               << "  -k [ --kordered ] NUM (=256)   k-ordered value; -1 indicates unbounded sorting\n"
               << "  -s [ --sorting-algorithm ] ALGO (=PARALLEL_SORTING)   PARALLEL_SORTING or PREFIX_DOUBLING\n"
               << "  --output-sa FILE               also write the suffix array (raw uint32 LE, n+1 entries)\n"
+              << "  --output-lcp FILE              also write the LCP array (raw uint32 LE, n+1 entries); exact order only (-k -1)\n"
               << "  --gpus NUM (=1)                shard the LMS sort over NUM devices (--device, --device + 1, ...)\n"
               << "  --devices LIST                 the same with an explicit comma-separated device list\n\n"
               << "./kiss fmindex_build [--option ...] <FASTA filename/Text filename>\n"
@@ -122,7 +123,7 @@ struct DeviceText {
 };
 
 struct Args {
-    std::string command, fasta, query, batch, output_sa, algo = "PARALLEL_SORTING";
+    std::string command, fasta, query, batch, output_sa, output_lcp, algo = "PARALLEL_SORTING";
     long long k = 256;
     size_t headn = 10;
     uint32_t sa_intv = 4, lookup_len = 0; // FMIndex<SA_INTV>{.LOOKUP_LEN}: the reference CLI's (fmindex_build.hpp:27-29)
@@ -153,6 +154,7 @@ Args parse(int argc, char **argv)
         else if (s == "-n" || s == "--headn") a.headn = (size_t)std::stoull(next("--headn"));
         else if (s == "-b" || s == "--batch") a.batch = next("--batch");
         else if (s == "--output-sa") a.output_sa = next("--output-sa");
+        else if (s == "--output-lcp") a.output_lcp = next("--output-lcp");
         else if (s == "--sa-intv") a.sa_intv = (uint32_t)std::stoul(next("--sa-intv"));
         else if (s == "--lookup-len") a.lookup_len = (uint32_t)std::stoul(next("--lookup-len"));
         else if (s == "--gpus") a.gpus = std::stoi(next("--gpus"));
@@ -189,6 +191,20 @@ Args parse(int argc, char **argv)
 double seconds_since(std::chrono::steady_clock::time_point t0)
 {
     return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// `total` u32 of a device buffer into a file (raw little-endian), in pieces
+void write_dev_u32(const std::string &path, const void *d_src, uint64_t total)
+{
+    std::ofstream o(path, std::ios::binary);
+    if (!o) throw std::runtime_error("cannot write " + path);
+    const uint64_t chunk = 64ull << 20; // entries per piece
+    std::vector<uint32_t> buf((size_t)std::min<uint64_t>(total, chunk));
+    for (uint64_t off = 0; off < total; off += chunk) {
+        const uint64_t c = std::min<uint64_t>(chunk, total - off);
+        check(kiss_hip_copy_to_host(buf.data(), (const uint32_t *)d_src + off, c * sizeof(uint32_t)), "kiss_hip_copy_to_host");
+        o.write(reinterpret_cast<const char *>(buf.data()), (std::streamsize)(c * sizeof(uint32_t)));
+    }
 }
 
 // ---- .fmi (fm_index.hpp:591-646; Serializer: u64 count + raw bytes, nothing when the count is 0) ----------
@@ -327,8 +343,62 @@ struct Fmi {
     }
 };
 
+// bases of a FASTA / plain-text file by the device parser's rule (fasta.hip) -- on the host, without a device, so that
+// --output-lcp with a bounded k is decided before anything else happens.  FASTA iff the first byte is '>'; there a line
+// that BEGINS with '>' is a header unless the line before it was one (the line after a header is always sequence: in a
+// run of '>' lines the 1st, 3rd, ... are headers); every byte of the other lines except '\n' is a base.
+uint64_t count_bases_host(const std::string &path)
+{
+    std::ifstream in(path, std::ios::binary);
+    if (!in) throw std::runtime_error("cannot open " + path);
+    std::vector<char> buf(1 << 20);
+    uint64_t n = 0;
+    bool first = true, fasta = false, line_start = true, header = false, prev_header = false;
+    while (in) {
+        in.read(buf.data(), (std::streamsize)buf.size());
+        const std::streamsize got = in.gcount();
+        for (std::streamsize i = 0; i < got; i++) {
+            const char c = buf[(size_t)i];
+            if (first) {
+                fasta = c == '>';
+                first = false;
+            }
+            if (line_start) {
+                header = fasta && c == '>' && !prev_header;
+                line_start = false;
+            }
+            if (c == '\n') {
+                prev_header = header;
+                header = false;
+                line_start = true;
+            } else if (!header) {
+                n++;
+            }
+        }
+    }
+    return n;
+}
+
+// --output-lcp needs the exact order: k = -1 or k >= n (n bounded by the file size first, counted only when that does not decide)
+[[noreturn]] void refuse_lcp(long long k)
+{
+    throw std::runtime_error("--output-lcp needs the exact suffix array: sort with -k -1 (k = " + std::to_string(k) +
+                             " is shorter than the text; the LCP array of a k-ordered suffix array is not defined)");
+}
+void check_lcp_request(const Args &a)
+{
+    if (a.output_lcp.empty()) return;
+    if (a.devices.size() > 1) throw std::runtime_error("--output-lcp: one device only (not with --gpus / --devices)");
+    if (a.k < 0) return;
+    uint64_t bytes = 0;
+    if (kiss_hip_file_size(a.fasta.c_str(), &bytes) != KISS_HIP_OK) throw std::runtime_error("cannot open " + a.fasta);
+    if ((uint64_t)a.k >= bytes || (uint64_t)a.k >= count_bases_host(a.fasta)) return;
+    refuse_lcp(a.k);
+}
+
 int suffix_sort_main(const Args &a)
 {
+    check_lcp_request(a); // (before any device work)
     const bool multi = a.devices.size() > 1;
     kiss_hip_multi *mc = nullptr;
     double multi_create_s = 0;
@@ -359,6 +429,7 @@ int suffix_sort_main(const Args &a)
     else if (a.algo == "PREFIX_DOUBLING") algo = KISS_HIP_ALGO_PREFIX_DOUBLING;
     else throw std::invalid_argument("Invalid sorting algorithm");
     const uint32_t k = (uint32_t)(uint64_t)a.k; // -1 -> size_t max -> truncated to 0xFFFFFFFF (suffix_sort.hpp:35-37)
+    if (!a.output_lcp.empty() && a.k >= 0 && (uint64_t)a.k < T.n) refuse_lcp(a.k); // (the parsed n: still before the sort)
     void *d_SA = nullptr;
     const auto ta = std::chrono::steady_clock::now();
     check(kiss_hip_alloc_dev(&d_SA, (T.n + 1) * sizeof(uint32_t)), "kiss_hip_alloc_dev");
@@ -393,16 +464,17 @@ int suffix_sort_main(const Args &a)
                      st.ms_pack, st.ms_classify, st.ms_lms_sort, st.ms_place, st.ms_induce, st.ms_refine, st.ms_total,
                      (unsigned long long)st.m, st.lms_rounds, st.doubling_rounds, st.induce_passes);
     }
-    if (!a.output_sa.empty()) {
-        std::ofstream o(a.output_sa, std::ios::binary);
-        if (!o) throw std::runtime_error("cannot write " + a.output_sa);
-        const uint64_t total = T.n + 1, chunk = 64ull << 20; // entries per piece
-        std::vector<uint32_t> buf((size_t)std::min<uint64_t>(total, chunk));
-        for (uint64_t off = 0; off < total; off += chunk) {
-            const uint64_t c = std::min<uint64_t>(chunk, total - off);
-            check(kiss_hip_copy_to_host(buf.data(), (const uint32_t *)d_SA + off, c * sizeof(uint32_t)), "kiss_hip_copy_to_host");
-            o.write(reinterpret_cast<const char *>(buf.data()), (std::streamsize)(c * sizeof(uint32_t)));
-        }
+    if (!a.output_sa.empty()) write_dev_u32(a.output_sa, d_SA, T.n + 1);
+    if (!a.output_lcp.empty()) { // in place: the SA buffer becomes the LCP array
+        kiss_hip_lcp_report rep{};
+        const auto tl = std::chrono::steady_clock::now();
+        check(kiss_hip_ctx_lcp_dna_u32_dev(T.ctx, T.d_S, T.n, (const uint32_t *)d_SA, (uint32_t *)d_SA, &rep, nullptr),
+              "kiss_hip_ctx_lcp_dna_u32_dev");
+        std::fprintf(stderr, "[info] LCP array elapsed %.6f (device %.3f ms: phi %.3f, short %.3f, long %.3f, scan + gather %.3f; "
+                             "irreducible %llu, long pairs %llu, max lcp %u)\n",
+                     seconds_since(tl), rep.ms_total, rep.ms_phi, rep.ms_short, rep.ms_long, rep.ms_scan_gather,
+                     (unsigned long long)rep.irreducible, (unsigned long long)rep.long_pairs, rep.max_lcp);
+        write_dev_u32(a.output_lcp, d_SA, T.n + 1);
     }
     const auto tf = std::chrono::steady_clock::now();
     kiss_hip_free_dev(d_SA);

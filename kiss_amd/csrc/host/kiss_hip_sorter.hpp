@@ -125,6 +125,35 @@ struct KissHipSorter {
       check(kiss_hip_suffix_sort_u8(S.data(), S.size(), SA, device()), "kiss_hip_suffix_sort_u8");
     });
   }
+
+  // LCP array (n + 1 entries: LCP[0] = 0, LCP[i] = lcp of suffixes SA[i-1] and SA[i]) of a text and its EXACT suffix array
+  // (get_suffix_array_dna with k = -1, get_suffix_array); an empty SA sorts in exact order first.  A k-ordered SA gives
+  // unspecified values.  kiss_hip_lcp_dna_u32 / kiss_hip_lcp_u8 on device().
+  static SA_t get_lcp_array_dna(const std::vector<std::uint8_t>& S, const SA_t& SA) {
+    return lcp_of(S, SA, kiss_hip_lcp_dna_u32, "kiss_hip_lcp_dna_u32");
+  }
+  static SA_t get_lcp_array(const std::ranges::random_access_range auto& ref, const SA_t& SA) {
+    return lcp_of(prepare_aligned_ref(ref), SA, kiss_hip_lcp_u8, "kiss_hip_lcp_u8");
+  }
+
+ private:
+  using lcp_fn = int (*)(const std::uint8_t*, std::uint64_t, const std::uint32_t*, std::uint32_t*, std::uint32_t*, int);
+  static SA_t lcp_of(const std::vector<std::uint8_t>& S, const SA_t& SA, lcp_fn fn, const char* where) {
+    if (!SA.empty() && SA.size() != S.size() + 1) throw std::invalid_argument(std::string(where) + ": SA must have n + 1 entries");
+    std::vector<std::uint32_t> sa32;
+    const std::uint32_t* sa = nullptr;
+    if (!SA.empty()) {
+      if constexpr (sizeof(size_type) == 4) {
+        sa = reinterpret_cast<const std::uint32_t*>(SA.data());
+      } else {
+        for (auto v : SA)
+          if (v > 0xFFFFFFFFull) throw std::invalid_argument(std::string(where) + ": SA entry beyond 32 bits");
+        sa32.assign(SA.begin(), SA.end());
+        sa = sa32.data();
+      }
+    }
+    return with_u32(S.size(), [&](std::uint32_t* LCP) { check(fn(S.data(), S.size(), sa, nullptr, LCP, device()), where); });
+  }
 };
 
 // KISS2 (PREFIX_DOUBLING): k >= n gives the exact suffix array by rank doubling; a bounded k gives the same

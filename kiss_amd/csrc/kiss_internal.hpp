@@ -321,6 +321,10 @@ void kiss_tie_trace_report(kiss_hip_ctx *ctx); // place.hip
 int kiss_place_lms(kiss_hip_ctx *ctx, uint64_t n, uint32_t k, uint64_t depth);
 // host <-> device legs of the host-pointer entry points (xfer.hip); both return after the bytes have arrived
 int kiss_xfer_h2d(kiss_hip_ctx *ctx, void *d_dst, const void *h_src, uint64_t bytes);
+// api.hip: the device-side copies ctx->io_S / ctx->io_SA of the host-pointer entry points, allocated for max_n on first use
+int kiss_io_reserve(kiss_hip_ctx *ctx, uint64_t n);
+// api.hip: fn(ctx, arg) on the one-shot context the library keeps for `device`, grown to n bases, under its lock
+int kiss_cached_ctx_run(int device, uint64_t n, int (*fn)(kiss_hip_ctx *, void *), void *arg);
 int kiss_xfer_d2h(kiss_hip_ctx *ctx, void *h_dst, const void *d_src, uint64_t bytes);
 void kiss_xfer_free(kiss_hip_ctx *ctx);
 // induced sort sweeps -> d_SA

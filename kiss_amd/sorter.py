@@ -161,6 +161,17 @@ class Context:
                                                     ctypes.c_void_p(stream or 0)), "kiss_hip_ctx_verify_sa_dev", self._ctx)
         return rep.as_dict()
 
+    def lcp_dev(self, d_S_ptr, n, d_SA_ptr, d_LCP_ptr, alphabet="dna", stream=None):
+        """LCP array of a text and its EXACT suffix array, all device resident (kiss_hip_ctx_lcp_dna_u32_dev /
+        kiss_hip_ctx_lcp_u8_dev): d_LCP receives n + 1 u32 (it may be d_SA).  alphabet "dna" (codes 0..3) or "bytes".
+        Returns the report as a dict.  A k-ordered (not exact) SA gives unspecified values."""
+        fn = {"dna": "kiss_hip_ctx_lcp_dna_u32_dev", "bytes": "kiss_hip_ctx_lcp_u8_dev"}[alphabet]
+        rep = _lib.LcpReport()
+        _check(getattr(self._lib, fn)(self._ctx, ctypes.c_void_p(d_S_ptr), int(n), ctypes.c_void_p(d_SA_ptr),
+                                      ctypes.c_void_p(d_LCP_ptr), ctypes.byref(rep), ctypes.c_void_p(stream or 0)),
+               fn, self._ctx)
+        return rep.as_dict()
+
     def stage_outputs(self):
         """(ascending LMS positions, k-ordered LMS positions, counts[12]) of the last sort."""
         st = self.stats()
@@ -281,6 +292,35 @@ def suffix_array_bytes(data, device=0, hooks=None):
     _check(lib.kiss_hip_suffix_sort_u8(S.ctypes.data if S.size else None, S.size, SA.ctypes.data, int(device)),
            "kiss_hip_suffix_sort_u8")
     return SA
+
+
+def _lcp_host(fn, S, SA, device, hooks):
+    n = S.size
+    SA_out = np.empty(n + 1, dtype=np.uint32)
+    LCP = np.empty(n + 1, dtype=np.uint32)
+    if SA is not None:
+        SA = np.ascontiguousarray(SA, dtype=np.uint32)
+        if SA.size != n + 1:
+            raise ValueError("SA must have n + 1 = %d entries, not %d" % (n + 1, SA.size))
+    lib = _lib.load(hooks)
+    _check(getattr(lib, fn)(S.ctypes.data if n else None, n, SA.ctypes.data if SA is not None else None,
+                            SA_out.ctypes.data, LCP.ctypes.data, int(device)), fn)
+    return SA_out, LCP
+
+
+def lcp_array(S, SA=None, device=0, hooks=None):
+    """(SA, LCP) of a DNA text (uint8 codes 0..3): SA exact (n + 1 entries, SA[0] = n), LCP[0] = 0 and LCP[i] = lcp of
+    suffixes SA[i-1], SA[i].  SA=None sorts on the device first; a given SA must be the exact one (a k-ordered SA gives
+    unspecified values).  kiss_hip_lcp_dna_u32."""
+    S = np.ascontiguousarray(S, dtype=np.uint8)
+    return _lcp_host("kiss_hip_lcp_dna_u32", S, SA, device, hooks)
+
+
+def lcp_array_bytes(data, SA=None, device=0, hooks=None):
+    """the same for a text over the byte alphabet (kiss_hip_lcp_u8; SA=None: suffix_array_bytes' order)"""
+    S = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else data,
+                             dtype=np.uint8)
+    return _lcp_host("kiss_hip_lcp_u8", S, SA, device, hooks)
 
 
 class KISS2Sorter(KISS1Sorter):
