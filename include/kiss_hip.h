@@ -234,7 +234,9 @@ int kiss_hip_suffix_sort_dna_u32_multi(const uint8_t *S, uint64_t n, uint32_t k,
  * For k >= n the stronger linear-time proof of exactness is used instead (inverse SA; first character, then the rank
  * of the following suffix), which holds iff d_SA is THE suffix array.  Text bytes compare as unsigned values, so the
  * call serves both the DNA codes 0..3 and byte texts (kiss_hip_suffix_sort_u8).  `digest` is an order-sensitive
- * 64-bit sum that any host can recompute (kiss_hip_sa_digest_host).  Allocates its own scratch (n/8 bytes, plus
+ * 64-bit sum that any host can recompute (kiss_hip_sa_digest_host).  order_violations is meaningful only when SA is a
+ * permutation of [0, n] (the k >= n proof reads ranks that a non-permutation never wrote; ok = 0 either way, and
+ * out_of_range, duplicates and sa0_ok are exact for every input).  Allocates its own scratch (n/8 bytes, plus
  * 4(n+1) bytes for k >= n) and frees it before returning; the ctx is only used for the device and the stream. */
 typedef struct kiss_hip_verify_report {
     uint64_t n;

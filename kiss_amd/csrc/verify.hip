@@ -48,13 +48,13 @@ __global__ __launch_bounds__(256) void k_vfy_perm(const uint32_t *__restrict__ S
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
         const uint32_t v = SA[i];
         dig += mix64((i << 32) ^ (uint64_t)v ^ 0x5851F42D4C957F2Dull * i);
+        if (i == 0 && (uint64_t)v != total - 1) atomicAdd(&c[6], 1ull); // (before the range check: SA[0] > n is not n either)
         if ((uint64_t)v >= total) {
             bad_range++;
             continue;
         }
         const uint32_t bit = 1u << (v & 31u);
         if (atomicOr(&bitmap[v >> 5], bit) & bit) dup++;
-        if (i == 0 && (uint64_t)v != total - 1) atomicAdd(&c[6], 1ull);
     }
     bad_range = wave_sum64(bad_range);
     dup = wave_sum64(dup);

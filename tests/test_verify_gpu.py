@@ -5,7 +5,7 @@ Includes BASELINE.json configs[1] and configs[3] at FULL size (n = 3 117 292 070
 import numpy as np
 import pytest
 
-from tests import gen
+from tests import gen, verify_model
 
 pytestmark = pytest.mark.gpu
 
@@ -45,6 +45,7 @@ def test_verifier_accepts_oracle_sa_and_digest_matches_host(ctx, torch_dev, orac
     assert rep["ok"] == 1 and rep["order_violations"] == 0 and rep["duplicates"] == 0 and rep["out_of_range"] == 0, rep
     assert rep["exact"] == (1 if k >= S.size else 0)
     assert rep["digest"] == sorter.sa_digest(SA)
+    assert rep["digest"] == verify_model.digest(SA)  # the formula restated in numpy, not the library's own helper
     if k >= S.size:
         # the exact SA also passes every bounded-k property check
         assert dev_verify(ctx, torch_dev, S, SA, 256)["ok"] == 1 or S.size <= 256
@@ -60,27 +61,32 @@ def test_verifier_rejects_what_it_should(ctx, torch_dev, oracle):
     assert dev_verify(ctx, torch_dev, S, SA, 256)["ok"] == 1
     rep = dev_verify(ctx, torch_dev, S, SA, 0xFFFFFFFF)
     assert rep["ok"] == 0 and rep["order_violations"] > 0 and rep["duplicates"] == 0
+    assert not verify_model.mismatches(rep, verify_model.report(S, SA, 0xFFFFFFFF)), rep
     # a swapped adjacent pair that differs within k bases
     b = S.tobytes()
     i = next(i for i in range(1000, n) if b[SA[i - 1]:SA[i - 1] + 256] != b[SA[i]:SA[i] + 256])
     bad = SA.copy()
     bad[i - 1], bad[i] = SA[i], SA[i - 1]
     rep = dev_verify(ctx, torch_dev, S, bad, 256)
-    assert rep["ok"] == 0 and 1 <= rep["order_violations"] <= 3 and rep["first_violation"] in (i - 1, i, i + 1)
+    assert rep["ok"] == 0 and rep["order_violations"] == 1 and rep["first_violation"] == i  # (the neighbours stay in order)
+    assert not verify_model.mismatches(rep, verify_model.report(S, bad, 256)), rep
     # a duplicated value (and hence a missing one)
     bad = SA.copy()
     bad[5000] = bad[6000]
     rep = dev_verify(ctx, torch_dev, S, bad, 256)
     assert rep["ok"] == 0 and rep["duplicates"] == 1
+    assert not verify_model.mismatches(rep, verify_model.report(S, bad, 256)), rep
     # sentinel not first / out of range
     bad = SA.copy()
     bad[0], bad[1] = SA[1], SA[0]
     rep = dev_verify(ctx, torch_dev, S, bad, 256)
     assert rep["ok"] == 0 and rep["sa0_ok"] == 0
+    assert not verify_model.mismatches(rep, verify_model.report(S, bad, 256)), rep
     bad = SA.copy()
     bad[77] = n + 5
     rep = dev_verify(ctx, torch_dev, S, bad, 256)
     assert rep["ok"] == 0 and rep["out_of_range"] == 1
+    assert not verify_model.mismatches(rep, verify_model.report(S, bad, 256)), rep
     # a tie at depth k may stand in either order for the property: swapping two entries equal through 256 bases passes
     ties = [i for i in range(1, n) if b[SA[i - 1]:SA[i - 1] + 256] == b[SA[i]:SA[i] + 256]
             and SA[i - 1] + 256 <= n and SA[i] + 256 <= n]
@@ -88,7 +94,9 @@ def test_verifier_rejects_what_it_should(ctx, torch_dev, oracle):
     ok = SA.copy()
     j = ties[0]
     ok[j - 1], ok[j] = SA[j], SA[j - 1]
-    assert dev_verify(ctx, torch_dev, S, ok, 256)["ok"] == 1
+    rep = dev_verify(ctx, torch_dev, S, ok, 256)
+    assert rep["ok"] == 1
+    assert not verify_model.mismatches(rep, verify_model.report(S, ok, 256)), rep
 
 
 @pytest.mark.parametrize("n,seed", [(150_000, 101), (15_000_000, 102)])
