@@ -72,6 +72,7 @@ void kiss_opts_refresh(kiss_hip_ctx *ctx)
     o.no_taint = env_on("KISS_HIP_NO_TAINT");
     o.isa_direct = env_on("KISS_HIP_ISA_DIRECT");
     o.no_onesweep = env_on("KISS_HIP_NO_ONESWEEP");
+    o.rx_one_tile = env_on("KISS_HIP_RX_ONE_TILE");
     o.merge_lms = env_on("KISS_HIP_MERGE_LMS");
     o.no_small_alphabet = env_on("KISS_HIP_NO_SMALL_ALPHABET");
     o.induce_one_pass = env_on("KISS_HIP_INDUCE_ONE_PASS");

@@ -32,6 +32,7 @@ struct KissOpts {
     bool no_taint = false;         // KISS_HIP_NO_TAINT: the suffix-array form compares every neighbour pair
     bool isa_direct = false;       // KISS_HIP_ISA_DIRECT: inverse SA by plain random scatter
     bool no_onesweep = false;      // KISS_HIP_NO_ONESWEEP: histogram + offsets + scatter radix passes
+    bool rx_one_tile = false;      // KISS_HIP_RX_ONE_TILE: every one-sweep pass by k_radix_scatter (one tile per CU)
     bool merge_lms = false;        // KISS_HIP_MERGE_LMS: the merged copy of the LMS list (round-1 form)
     bool no_small_alphabet = false;// KISS_HIP_NO_SMALL_ALPHABET (general.hip)
     bool induce_one_pass = false;  // KISS_HIP_INDUCE_ONE_PASS: a source segment partitioned in one pass with a look-back (slower: DESIGN.md 4)

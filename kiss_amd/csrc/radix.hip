@@ -18,7 +18,7 @@ constexpr int RX_THREADS = 1024;
 constexpr int RX_ITEMS = 16;
 constexpr int RX_WAVES = RX_THREADS / 64;
 constexpr int RX_WAVE_TILE = RX_ITEMS * 64;        // 1024
-constexpr int RX_TILE = RX_THREADS * RX_ITEMS;     // 8192
+constexpr int RX_TILE = RX_THREADS * RX_ITEMS;     // 16384
 
 template <int SRC>
 __device__ __forceinline__ uint32_t digit_of(uint64_t key, uint32_t seg, int shift)
@@ -213,17 +213,11 @@ __device__ __forceinline__ uint32_t rx_lookback(uint64_t *__restrict__ desc, uin
     // any has its prefix, goes three times as far back (32 descriptors) and ends up slower, as did a 16-lane walk.
     uint32_t excl = 0;
     uint32_t t = tile;
-#ifdef RX_PROF
-    uint32_t hops_ = 0, polls_ = 0;
-#endif
     while (t > 0) {
         t--;
         const uint64_t *q = desc + (uint64_t)t * 256 + d;
         uint64_t v = rx_desc_load(q);
         uint32_t spins = 0;
-#ifdef RX_PROF
-        hops_++;
-#endif
         while ((v >> 62) == 0 || (v & (0x3FFFFFFFull << 32)) != tag) {
             if (++spins > RX_SPIN_LIMIT) {
                 *err = 1; // a predecessor never published: give up with what we have (writes stay in range)
@@ -233,17 +227,14 @@ __device__ __forceinline__ uint32_t rx_lookback(uint64_t *__restrict__ desc, uin
             __builtin_amdgcn_s_sleep(1);
             v = rx_desc_load(q);
 #ifdef RX_PROF
-            polls_++;
+            if (d == 0) atomicAdd(&rx_prof[14], 1ull); // (no counter carried through the walk: registers)
 #endif
         }
         excl += (uint32_t)v;
         if ((v >> 62) == 2) break;
     }
 #ifdef RX_PROF
-    if (d == 0) {
-        atomicAdd(&rx_prof[13], (unsigned long long)hops_);
-        atomicAdd(&rx_prof[14], (unsigned long long)polls_);
-    }
+    if (d == 0) atomicAdd(&rx_prof[13], (unsigned long long)(tile - t)); // descriptors visited
 #endif
     rx_desc_store(mine, (2ull << 62) | tag | (excl + tot));
     return excl;
@@ -252,7 +243,8 @@ __device__ __forceinline__ uint32_t rx_lookback(uint64_t *__restrict__ desc, uin
 // Scatter.  LDS holds ONE 128 KiB staging buffer that the key, position and segment columns pass through in
 // turn (each column is reordered locally and leaves as coalesced per-digit runs): one workgroup of 16 waves per CU.
 // (Measured: 8192-item tiles with two workgroups per CU are 18 % slower -- run length per digit matters more
-//  than overlap between workgroups.)
+//  than overlap between workgroups.  The round-0 shape <0, false, true> with many tiles goes to k_radix_scatter_win
+//  below, which keeps the 16384-item tile and gets two workgroups per CU out of a smaller staging buffer.)
 // ONE = false: tile_off holds the scanned per-(tile, digit) offsets (histogram pass + matrix scan ran before);
 // ONE = true : tile_off holds the 256 global digit bases of this pass, tiles are numbered by ticket and find their
 //              offsets by look-back over `desc`
@@ -506,6 +498,244 @@ __global__ __launch_bounds__(RX_THREADS, 4) void k_radix_scatter(const uint64_t 
 #endif
 }
 
+// Windowed scatter for the round-0 shape (keys carry the digit, no segment column, look-back): the same tile, item
+// order, ranks, descriptors and ticket as k_radix_scatter<0, false, true>, but the staging buffer is HALF of what
+// a whole tile of keys needs: the keys leave in two windows of 8192 slots, the positions in one pass through the
+// same 64 KiB.  With the wave counters placed inside that buffer the workgroup needs 66 KiB of LDS, and at 64 VGPRs
+// per lane TWO tiles are resident on a CU, so that one tile's ranking and look-back overlap the other's loads and
+// stores.  What keeps it at 64 registers without scratch: nothing is carried that can be had again
+// (an item's digit comes from its key, the digit totals are read from wcnt twice), the local positions are packed
+// two per register, a thread remembers the digits of the 16 slots it writes (4 registers) instead of their global
+// offsets, and the positions are loaded when the keys have left the registers.  tests/test_radix_resources.py pins
+// these figures.
+// The compiler would unpack the 16-bit fields once and carry 16 registers through the windows; an empty asm that
+// "rewrites" the packed words makes it extract a field where it is used.
+#define RX_OPAQUE(v) asm volatile("" : "+v"(v))
+#define RX_KEEP_PACKED(a)                                                                                              \
+    _Pragma("unroll") for (unsigned i_ = 0; i_ < sizeof(a) / sizeof(a[0]); i_++) RX_OPAQUE(a[i_])
+constexpr int RX_WINDOWS = 2;
+// Two tiles per CU only pay when there are more tiles than one round of them on 256 CUs: below that the windowed
+// form has nothing to overlap with and the one-buffer kernel has fewer barriers.
+constexpr uint64_t RX_WIN_MIN_TILES = 513;
+constexpr int RX_WIN = RX_TILE / RX_WINDOWS;          // 8192 slots
+constexpr int RX_WIN_ROUNDS = RX_ITEMS / RX_WINDOWS;  // slots a thread writes out per window
+
+__global__ __launch_bounds__(RX_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_radix_scatter_win(
+    const uint64_t *__restrict__ key_in, const uint32_t *__restrict__ pos_in, uint64_t *__restrict__ key_out,
+    uint32_t *__restrict__ pos_out, uint64_t count, int shift, const uint32_t *__restrict__ tile_off,
+    uint64_t *__restrict__ desc, uint32_t *__restrict__ ctl, uint32_t ticket_base, uint64_t epoch)
+{
+    __shared__ uint64_t win64[RX_WIN]; // key window; whole tile of positions; wave counters until the staging starts
+    __shared__ uint32_t gbase[256];
+    __shared__ uint32_t wsum[RX_WAVES + 1];
+    __shared__ uint32_t s_tile;
+    uint32_t *const win32 = reinterpret_cast<uint32_t *>(win64);
+    uint32_t(*const wcnt)[256] = reinterpret_cast<uint32_t(*)[256]>(win64);
+    static_assert(sizeof(uint32_t) * RX_WAVES * 256 <= sizeof(uint64_t) * RX_WIN, "wave counters inside the window");
+    static_assert(sizeof(uint32_t) * RX_TILE <= sizeof(uint64_t) * RX_WIN, "a tile of positions inside the window");
+    constexpr bool ONE = true; // (RX_MARK)
+    (void)ONE;
+
+    const int wave = threadIdx.x >> 6;
+    const uint32_t lane = lane_id();
+#ifdef RX_PROF
+    __shared__ unsigned long long t_prev_; // (thread 0 only; in LDS: registers are what this kernel does not have)
+    if (threadIdx.x == 0) t_prev_ = wall_clock64();
+#endif
+    if (threadIdx.x == 0) s_tile = atomicAdd(&ctl[0], 1u) - ticket_base;
+    __syncthreads();
+    RX_MARK(0);
+    const uint32_t tile = s_tile;
+    const uint64_t tile_base = (uint64_t)tile * RX_TILE;
+    const uint32_t tile_count = (uint32_t)((count - tile_base) < (uint64_t)RX_TILE ? (count - tile_base) : RX_TILE);
+    const bool full = tile_count == RX_TILE;
+
+    if (threadIdx.x < 256) {
+#pragma unroll
+        for (int w = 0; w < RX_WAVES; w++) wcnt[w][threadIdx.x] = 0;
+    }
+    __syncthreads();
+
+    uint64_t k[RX_ITEMS];
+    uint32_t p[RX_ITEMS];
+    uint32_t lp[RX_ITEMS / 2]; // two 16-bit fields: rank inside the wave, later the local position; 0xFFFF = invalid
+    uint32_t dg[RX_ITEMS / 4]; // digits of the slots threadIdx.x + 1024 * r, four per register
+
+    const uint32_t wbase = (uint32_t)wave * RX_WAVE_TILE + lane;
+    const uint64_t *const kin = key_in + tile_base;
+    const uint32_t *const pin = pos_in + tile_base;
+    if (full) {
+#pragma unroll
+        for (int j = 0; j < RX_ITEMS; j++) k[j] = kin[wbase + (uint32_t)j * 64];
+    } else {
+#pragma unroll
+        for (int j = 0; j < RX_ITEMS; j++) {
+            const uint32_t li = wbase + (uint32_t)j * 64;
+            k[j] = li < tile_count ? kin[li] : 0ull;
+        }
+    }
+#ifdef RX_PROF
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    RX_MARK(1);
+#endif
+    // the ranking of k_radix_scatter, instruction for instruction
+    uint32_t *const wc = wcnt[wave];
+    auto rank_items = [&](auto full_tag) {
+        constexpr bool FULL = decltype(full_tag)::value;
+#pragma unroll
+        for (int j = 0; j < RX_ITEMS; j++) {
+            const bool valid = FULL || wbase + (uint32_t)j * 64 < tile_count;
+            const uint32_t d = (uint32_t)(k[j] >> shift) & 255u;
+            uint32_t plo = ~0u, phi = ~0u;
+            if (!FULL) {
+                const uint64_t vm = __ballot(valid);
+                plo = (uint32_t)vm;
+                phi = (uint32_t)(vm >> 32);
+            }
+#pragma unroll
+            for (int b = 0; b < 8; b++) {
+                const int sel = __builtin_amdgcn_sbfe((int)d, b, 1); // 0 or ~0
+                const uint64_t bm = __ballot(sel < 0);
+                plo = __builtin_amdgcn_bitop3_b32(plo, (uint32_t)bm, (uint32_t)sel, 0x90);
+                phi = __builtin_amdgcn_bitop3_b32(phi, (uint32_t)(bm >> 32), (uint32_t)sel, 0x90);
+            }
+            const uint32_t below = __builtin_amdgcn_mbcnt_hi(phi, __builtin_amdgcn_mbcnt_lo(plo, 0u));
+            const uint32_t old = wc[d];
+            if (below == 0 && valid) wc[d] = old + (uint32_t)__popc(plo) + (uint32_t)__popc(phi);
+            const uint32_t r = valid ? old + below : 0xFFFFu; // a rank is < 1024
+            if (j & 1) {
+                lp[j >> 1] |= r << 16;
+                RX_OPAQUE(lp[j >> 1]); // packed now, not when the last counter has come back from LDS
+            } else {
+                lp[j >> 1] = r;
+            }
+        }
+    };
+    if (full) rank_items(std::true_type{});
+    else rank_items(std::false_type{});
+    RX_KEEP_PACKED(lp);
+    RX_MARK(2);
+    __syncthreads();
+    RX_MARK(3);
+
+    // per digit (threads 0..255): totals over waves, exclusive prefix over waves, exclusive scan over digits
+    const uint32_t d = threadIdx.x & 255u;
+    const bool dig = threadIdx.x < 256;
+    uint32_t tot = 0;
+    if (dig) { // (four counters in flight at a time: sixteen would set the register peak of the kernel)
+#pragma unroll 4
+        for (int w = 0; w < RX_WAVES; w++) tot += wcnt[w][d];
+    }
+    uint32_t inc = tot;
+#pragma unroll
+    for (int dd = 1; dd < 64; dd <<= 1) {
+        uint32_t o = __shfl_up(inc, dd, 64);
+        if ((int)lane >= dd) inc += o;
+    }
+    if (lane == 63 && dig) wsum[wave] = inc;
+    __syncthreads();
+    RX_MARK(4);
+    uint32_t start = inc - tot;
+    if (dig) {
+        for (int w = 0; w < wave; w++) start += wsum[w];
+        uint32_t run = start;
+#pragma unroll 4
+        for (int w = 0; w < RX_WAVES; w++) {
+            const uint32_t c = wcnt[w][d];
+            wcnt[w][d] = run;
+            run += c;
+        }
+    }
+    __syncthreads();
+    // local positions of this thread's items; after the barrier behind them the counters' LDS is the window's
+#pragma unroll
+    for (int j = 0; j < RX_ITEMS; j++) {
+        const uint32_t r = (lp[j >> 1] >> (16 * (j & 1))) & 0xFFFFu;
+        const uint32_t l = r == 0xFFFFu ? r : wc[(uint32_t)(k[j] >> shift) & 255u] + r;
+        if (j & 1) lp[j >> 1] = (lp[j >> 1] & 0xFFFFu) | (l << 16);
+        else lp[j >> 1] = (lp[j >> 1] & 0xFFFF0000u) | l;
+    }
+    RX_KEEP_PACKED(lp);
+    lds_barrier();
+    RX_MARK(5);
+    // waves 0..3 look back; the others stage their keys meanwhile
+    if (dig) gbase[d] = tile_off[d] + rx_lookback(desc, tile, d, tot, epoch, &ctl[1]) - start;
+    RX_MARK(6);
+
+    // ---- keys: window win holds the slots [win * RX_WIN, (win + 1) * RX_WIN).  Slot idx = threadIdx.x + 1024 * r is
+    // written by the thread and in the order k_radix_scatter does, so a wave's stores cover the same runs.
+    // The read-out has no per-lane branch: in the last tile a slot past the end is clamped to the last valid one
+    // and writes that item once more.  (Exec-masked regions around the stores make the compiler wait for ALL
+    // outstanding memory operations, the stores of the slot before included, wherever it reuses a register that a
+    // load wrote on some path.)
+    const uint32_t last = tile_count - 1;
+#pragma unroll
+    for (int win = 0; win < RX_WINDOWS; win++) {
+        RX_KEEP_PACKED(lp);
+#pragma unroll
+        for (int j = 0; j < RX_ITEMS; j++) {
+            const uint32_t l = (lp[j >> 1] >> (16 * (j & 1))) & 0xFFFFu;
+            if ((l >> 13) == (uint32_t)win) win64[l & (RX_WIN - 1)] = k[j]; // (invalid items: 7)
+        }
+        if (win == RX_WINDOWS - 1) { // the keys have left the registers: the positions arrive under the key stores
+            if (full) {
+#pragma unroll
+                for (int j = 0; j < RX_ITEMS; j++) p[j] = pin[wbase + (uint32_t)j * 64];
+            } else {
+#pragma unroll
+                for (int j = 0; j < RX_ITEMS; j++) {
+                    const uint32_t li = wbase + (uint32_t)j * 64;
+                    p[j] = li < tile_count ? pin[li] : 0u;
+                }
+            }
+        }
+        lds_barrier(); // (window 0: also orders gbase[] of the look-back threads)
+        RX_MARK(7);
+        uint32_t tid = threadIdx.x;
+        RX_OPAQUE(tid); // (slot numbers are made where they are used, not carried from phase to phase)
+#pragma unroll
+        for (int r = 0; r < RX_WIN_ROUNDS; r++) {
+            const int rr = win * RX_WIN_ROUNDS + r;
+            uint32_t dd = 0;
+            if ((uint32_t)rr * RX_THREADS <= last) { // (uniform: a round of 1024 slots with at least one item)
+                uint32_t idx = (uint32_t)rr * RX_THREADS + tid;
+                idx = idx < last ? idx : last;
+                const uint64_t kk = win64[idx - (uint32_t)win * RX_WIN];
+                dd = (uint32_t)(kk >> shift) & 255u;
+                key_out[gbase[dd] + idx] = kk;
+            }
+            if (rr & 3) dg[rr >> 2] |= dd << (8 * (rr & 3));
+            else dg[rr >> 2] = dd;
+        }
+        RX_MARK(8);
+        lds_barrier(); // the window is free again
+        RX_MARK(9);
+    }
+    // ---- positions: the whole tile in one pass through the same LDS (invalid items: the last slot, which is past
+    // the end of a tile that has any)
+    RX_KEEP_PACKED(lp);
+#pragma unroll
+    for (int j = 0; j < RX_ITEMS; j++) {
+        const uint32_t l = (lp[j >> 1] >> (16 * (j & 1))) & 0xFFFFu;
+        win32[l & (RX_TILE - 1)] = p[j];
+    }
+    lds_barrier();
+    RX_MARK(10);
+    uint32_t tid = threadIdx.x;
+    RX_OPAQUE(tid);
+#pragma unroll
+    for (int r = 0; r < RX_ITEMS; r++) {
+        if ((uint32_t)r * RX_THREADS > last) break; // (uniform)
+        uint32_t idx = tid + (uint32_t)r * RX_THREADS;
+        idx = idx < last ? idx : last;
+        pos_out[gbase[(dg[r >> 2] >> (8 * (r & 3))) & 255u] + idx] = win32[idx];
+    }
+#ifdef RX_PROF
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    RX_MARK(11);
+#endif
+}
+
 // ---- digit-major exclusive scan of the tile-major histogram matrix hist[tile][256] ------------------
 // offset(tile, d) = sum over digits d' < d of total[d'] + sum over tiles t' < tile of hist[t'][d].
 // k_col_sum: per chunk of RX_CHUNK tiles, column sums -> digit-major chunk matrix csum[d][chunk];
@@ -606,9 +836,17 @@ int radix_pass_one(kiss_hip_ctx *ctx, RadixBufs &b, int src, uint64_t count, int
     const int dst = src ^ 1;
     KTimer t(ctx, KISS_HIP_K_RADIX_SCATTER, count);
     ctx->rx_epoch++;
-    hipLaunchKernelGGL((k_radix_scatter<SRC, HAS_SEG, true>), dim3((unsigned)tiles), dim3(RX_THREADS), 0, ctx->stream,
-                       b.key[src], b.seg[src], pos_in, b.key[dst], b.seg[dst], b.pos[dst], count, shift,
-                       ctx->rx_ghist + 256 * p, tiles, ctx->rx_desc, ctx->rx_ctl, ctx->rx_ticket_base, ctx->rx_epoch);
+    // (rx_one_tile: A-B switch of the hooks build)
+    if (SRC == 0 && !HAS_SEG && tiles >= RX_WIN_MIN_TILES && !ctx->opts.rx_one_tile) {
+        hipLaunchKernelGGL(k_radix_scatter_win, dim3((unsigned)tiles), dim3(RX_THREADS), 0, ctx->stream, b.key[src],
+                           pos_in, b.key[dst], b.pos[dst], count, shift, ctx->rx_ghist + 256 * p, ctx->rx_desc,
+                           ctx->rx_ctl, ctx->rx_ticket_base, ctx->rx_epoch);
+    } else {
+        hipLaunchKernelGGL((k_radix_scatter<SRC, HAS_SEG, true>), dim3((unsigned)tiles), dim3(RX_THREADS), 0,
+                           ctx->stream, b.key[src], b.seg[src], pos_in, b.key[dst], b.seg[dst], b.pos[dst], count, shift,
+                           ctx->rx_ghist + 256 * p, tiles, ctx->rx_desc, ctx->rx_ctl, ctx->rx_ticket_base,
+                           ctx->rx_epoch);
+    }
     KCHECK(hipGetLastError());
     ctx->rx_ticket_base += (uint32_t)tiles;
     return KISS_HIP_OK;
