@@ -439,6 +439,48 @@ int kiss_hip_fmi_query_ex_host(const kiss_hip_fmi_view_ex *fmi, const uint8_t *p
                                uint64_t *checksum, uint32_t *offsets, uint64_t *offsets_index, uint64_t offsets_capacity,
                                int device);
 
+/* ---- FM-index: batched search with up to KISS_HIP_FMI_MAX_MISMATCHES substitutions (no reference counterpart) --------
+ * For a batch of Q patterns of one length L and a bound e = max_mismatches, a hit of pattern P is a text position p in
+ * [0, n - L] whose Hamming distance to P, d = #{j : S[p + j] != P[j]}, is at most e (substitutions only; pattern bytes are
+ * used & 3).  Backward search that branches, then locate, then a sort into the one canonical order.
+ *   counts     : Q x (e + 1) u32: counts[q * (e + 1) + j] = hits of pattern q with exactly j mismatches.
+ *   positions / mismatches / index : optional (all three or none; none: capacity = 0).  index has Q + 1 entries; the hits of
+ *                pattern q are (positions[i], mismatches[i]) for i in [index[q], index[q + 1]) in ASCENDING position.
+ *   capacity   : entries available in positions / mismatches.  Smaller than the total: KISS_HIP_E_INVALID with the totals
+ *                in report->hits (call again with room, as with kiss_hip_fmi_query_batch_dev).
+ * Domain.  COUNTS are defined for L <= the order of the suffix array the index was built from: 32 for the default build
+ * (kiss_hip_fmi_build_host with SA_or_null == NULL), any L for an index built from the exact suffix array -- the domain of
+ * get_range.  POSITIONS are defined only for an index built from the EXACT suffix array (k = 0xFFFFFFFF): on a k-ordered
+ * one the LF walk of a tied row lands on another suffix's row.  The walk is bounded (at most SA_INTV - 1 steps, never from the
+ * primary row), so the call returns whatever arrays it is handed; a row that reaches no sampled row inside the bound is
+ * counted in walk_failures and the call returns KISS_HIP_E_INVALID, promising nothing about positions.  THE BOUND DOES NOT
+ * CATCH EVERY NON-EXACT INDEX: a tied row can reach a sampled row of the wrong suffix in time; walk_failures == 0 proves
+ * nothing.  Build with the exact order when positions are wanted.
+ * Limits: max_mismatches > KISS_HIP_FMI_MAX_MISMATCHES or sa_intv outside 1..32: KISS_HIP_E_UNSUPPORTED.  L == 0 or a
+ * required pointer NULL: KISS_HIP_E_INVALID.  L > n or Q == 0: KISS_HIP_OK, no hits.  The hits of a call are sorted in the
+ * ctx's LMS work arrays (their contents are lost; about 0.32 x the ctx's max_n entries): more hits than those hold is
+ * KISS_HIP_E_UNSUPPORTED with the totals in the report -- split the batch.
+ * Device times: report->ms_* always; the kernels also count under KISS_HIP_K_FM_QUERY when that class is profiled. */
+#define KISS_HIP_FMI_MAX_MISMATCHES 3u
+typedef struct kiss_hip_fmi_mm_report {
+    uint64_t Q;
+    uint32_t L, max_mismatches;
+    uint64_t hits[4];        /* by number of mismatches */
+    uint64_t ranges;         /* SA ranges (leaves) the search emitted */
+    uint64_t lf_pairs;       /* fm_lf2-equivalents ((range, base) pairs) evaluated by the search: the denominator of its rate */
+    uint64_t walk_failures;  /* rows that reached no sampled row within SA_INTV - 1 steps (index not from an exact SA) */
+    uint64_t checksum;       /* sum of all hit positions (0 without positions) */
+    float ms_total, ms_search, ms_locate, ms_sort;
+} kiss_hip_fmi_mm_report;
+/* every pointer except report is a device pointer; report may be NULL */
+int kiss_hip_fmi_query_mm_dev(kiss_hip_ctx *ctx, const kiss_hip_fmi_view *fmi, const uint8_t *patterns, uint32_t L, uint64_t Q,
+                              uint32_t max_mismatches, uint32_t *counts, uint32_t *positions, uint8_t *mismatches,
+                              uint64_t *index, uint64_t capacity, kiss_hip_fmi_mm_report *report, void *stream);
+/* the same with host pointers, as kiss_hip_fmi_query_ex_host (creates a ctx on `device`, uploads, runs, downloads) */
+int kiss_hip_fmi_query_mm_host(const kiss_hip_fmi_view *fmi, const uint8_t *patterns, uint32_t L, uint64_t Q,
+                               uint32_t max_mismatches, uint32_t *counts, uint32_t *positions, uint8_t *mismatches,
+                               uint64_t *index, uint64_t capacity, kiss_hip_fmi_mm_report *report, int device);
+
 /* ---- General alphabet (bytes): exact suffix array ---------------------------------
  * Replaces KISS1Sorter::get_suffix_array -> kiss1_suffix_array (kiss1_core.hpp:270-311), reachable only from the
  * reference's tests / experiments.  For that entry only the k-order property is defined (its comparator has no

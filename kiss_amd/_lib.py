@@ -114,6 +114,22 @@ class FmiSizesEx(ctypes.Structure):
     _fields_ = [("base", FmiSizes), ("lookup_entries", ctypes.c_uint64)]
 
 
+class FmiMmReport(ctypes.Structure):
+    """kiss_hip_fmi_mm_report"""
+    _fields_ = [
+        ("Q", ctypes.c_uint64), ("L", ctypes.c_uint32), ("max_mismatches", ctypes.c_uint32),
+        ("hits", ctypes.c_uint64 * 4), ("ranges", ctypes.c_uint64), ("lf_pairs", ctypes.c_uint64),
+        ("walk_failures", ctypes.c_uint64), ("checksum", ctypes.c_uint64),
+        ("ms_total", ctypes.c_float), ("ms_search", ctypes.c_float), ("ms_locate", ctypes.c_float),
+        ("ms_sort", ctypes.c_float),
+    ]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "hits"}
+        d["hits"] = [int(x) for x in self.hits]
+        return d
+
+
 class KissHipError(RuntimeError):
     def __init__(self, status, where, detail=""):
         self.status = status
@@ -217,6 +233,11 @@ def load(hooks=None):
     lib.kiss_hip_fmi_build_ex_host.argtypes = [vp, u64, vp, u32, u32] + [vp] * 9 + [ctypes.c_int]
     lib.kiss_hip_fmi_query_ex_host.argtypes = [ctypes.POINTER(FmiViewEx), vp, u32, u64, u32, vp, vp, vp,
                                                ctypes.POINTER(u64), ctypes.POINTER(u64), vp, vp, u64, ctypes.c_int]
+    lib.kiss_hip_fmi_query_mm_dev.argtypes = [vp, ctypes.POINTER(FmiView), vp, u32, u64, u32, vp, vp, vp, vp, u64,
+                                              ctypes.POINTER(FmiMmReport), vp]
+    lib.kiss_hip_fmi_query_mm_host.argtypes = [ctypes.POINTER(FmiView), vp, u32, u64, u32, vp, vp, vp, vp, u64,
+                                               ctypes.POINTER(FmiMmReport), ctypes.c_int]
+    lib.kiss_hip_fmi_query_mm_dev.restype = lib.kiss_hip_fmi_query_mm_host.restype = ctypes.c_int
     lib.kiss_hip_file_size.argtypes = [ctypes.c_char_p, ctypes.POINTER(u64)]
     lib.kiss_hip_ctx_parse_text_dev.argtypes = [vp, vp, u64, vp, ctypes.POINTER(u64), vp]
     lib.kiss_hip_ctx_load_text_file.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(vp), ctypes.POINTER(u64)]
@@ -278,5 +299,5 @@ EXPORTED_SYMBOLS = [
     "kiss_hip_has_hooks", "kiss_hip_release_cached_contexts", "kiss_hip_get_stats_sized",
     "kiss_hip_fmi_sizes_ex_for", "kiss_hip_fmi_build_ex_dev", "kiss_hip_fmi_query_ex_dev", "kiss_hip_fmi_build_ex_host",
     "kiss_hip_fmi_query_ex_host", "kiss_hip_ctx_lcp_dna_u32_dev", "kiss_hip_ctx_lcp_u8_dev", "kiss_hip_lcp_dna_u32",
-    "kiss_hip_lcp_u8",
+    "kiss_hip_lcp_u8", "kiss_hip_fmi_query_mm_dev", "kiss_hip_fmi_query_mm_host",
 ]

@@ -88,6 +88,8 @@ void kiss_opts_refresh(kiss_hip_ctx *ctx)
     o.collapse_n = env_u64("KISS_HIP_COLLAPSE_N", 0);
     o.fm_heavy = (uint32_t)env_u64("KISS_HIP_FM_HEAVY", 0);
     o.fm_light = (uint32_t)env_u64("KISS_HIP_FM_LIGHT", 0);
+    o.fm_mm_wave = env_on("KISS_HIP_FM_MM_WAVE");
+    o.fm_mm_budget = env_u64("KISS_HIP_FM_MM_BUDGET", 0);
     o.isa_direct_max = env_u64("KISS_HIP_ISA_DIRECT_MAX", 0);
     o.lx_sync_points = (unsigned)env_u64("KISS_HIP_LX_SYNC_POINTS", 0);
     o.tie_trace = (unsigned)env_u64("KISS_HIP_TIE_TRACE", 0);
@@ -244,6 +246,8 @@ void free_all(kiss_hip_ctx *ctx)
         if (p) (void)hipFree(p);
     for (void *p : ctx->fm_pool)
         if (p) (void)hipFree(p);
+    for (hipEvent_t e : ctx->fm_mm_ev)
+        if (e) (void)hipEventDestroy(e);
 #ifdef KISS_HIP_HOOKS
     if (ctx->tie_dbg) (void)hipFree(ctx->tie_dbg);
 #endif

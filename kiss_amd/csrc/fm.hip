@@ -25,7 +25,7 @@
 // compute_occ.  The .fmi arrays are only read by that pass and by the locate's sampled-SA / bit-vector look-ups.
 // Locate: patterns with more than FM_HEAVY occurrences (tandem repeats reach 10^6) get a workgroup of their own,
 // the rest stay one lane per pattern; both produce the reference's output order.
-#include "kiss_internal.hpp"
+#include "fm_internal.hpp"
 #include <cstdlib>
 
 namespace {
@@ -47,20 +47,6 @@ constexpr int FMH_THREADS = 512;
 // switched off (FM_LIGHT = FM_HEAVY: no pattern is "medium"); KISS_HIP_FM_LIGHT (1 .. 256) is the A-B hook.
 // (default: FM_LIGHT = the workgroup threshold, i.e. no wave tier)
 constexpr int FMM_THREADS = 64;
-
-struct FmiD {
-    uint64_t N;
-    uint32_t cnt[4];
-    uint32_t pri;
-    uint64_t bwt_bytes;
-    const uint8_t *bwt;
-    const uint32_t *occ1;
-    const uint8_t *occ2;
-    const uint32_t *sa;
-    const uint64_t *b;
-    const uint32_t *b_occ;
-    const uint4 *blk; // interleaved rank blocks: [2 * j] = counts of A, C, G, T in bwt[0, 64 j), [2 * j + 1] = the 64 dibits
-};
 
 // the 16 dibits of chunk i/16 as one u32 (dibit t at bits 2t); the index may end inside the word
 __device__ __forceinline__ uint32_t bwt_word(const FmiD &f, uint64_t chunk)
@@ -93,61 +79,6 @@ __device__ __forceinline__ uint32_t fm_occ_disk(const FmiD &f, uint32_t c, uint6
     return f.occ1[o1 * 4 + c] + (uint32_t)f.occ2[o2 * 4 + c] + cnt - pass_pri;
 }
 
-// one 32-byte block: counts before the block + the block's dibits
-struct FmBlock {
-    uint4 cnt;
-    uint4 bw; // dibit t of the block at bits 2 (t % 16) of word t / 16
-};
-__device__ __forceinline__ FmBlock fm_block(const FmiD &f, uint64_t j)
-{
-    FmBlock b;
-    b.cnt = f.blk[2 * j];
-    b.bw = f.blk[2 * j + 1];
-    return b;
-}
-// occ(c, i) for a row i of block j = i / 64 (the block already loaded): the same sum as compute_occ with the block start in
-// the place of the 16-row chunk start -- counts before the block + matching dibits in [64 j, i) - the primary row's
-// placeholder 'A' when it lies in that stretch
-__device__ __forceinline__ uint32_t fm_occ_in(const FmiD &f, const FmBlock &b, uint32_t c, uint64_t i)
-{
-    const uint32_t r = (uint32_t)(i & 63u);
-    const uint32_t pat = c * 0x55555555u;
-    const uint32_t w[4] = {b.bw.x, b.bw.y, b.bw.z, b.bw.w};
-    uint32_t cnt = 0;
-#pragma unroll
-    for (uint32_t t = 0; t < 4; t++) {
-        const uint32_t x = w[t] ^ pat;
-        uint32_t m = ~(x | (x >> 1)) & 0x55555555u; // bit 2 u set <=> dibit u of this word == c
-        const int left = (int)r - (int)(16 * t);     // rows of this word below i
-        m = left >= 16 ? m : (left <= 0 ? 0u : (m & ((1u << (2 * left)) - 1u)));
-        cnt += (uint32_t)__popc(m);
-    }
-    const uint32_t base = c == 0 ? b.cnt.x : (c == 1 ? b.cnt.y : (c == 2 ? b.cnt.z : b.cnt.w));
-    const uint64_t start = i & ~63ull;
-    const uint32_t pass_pri = (c == 0 && start <= f.pri && f.pri < i) ? 1u : 0u;
-    return base + cnt - pass_pri;
-}
-__device__ __forceinline__ uint32_t fm_occ(const FmiD &f, uint32_t c, uint64_t i)
-{
-    return fm_occ_in(f, fm_block(f, i >> 6), c, i);
-}
-__device__ __forceinline__ uint64_t fm_lf(const FmiD &f, uint32_t c, uint64_t i) { return (uint64_t)f.cnt[c] + fm_occ(f, c, i); }
-// both ends of a range: one block load when they fall into the same 64 rows (the usual case once the range is narrow)
-__device__ __forceinline__ void fm_lf2(const FmiD &f, uint32_t c, uint64_t &beg, uint64_t &end)
-{
-    const uint64_t jb = beg >> 6, je = end >> 6;
-    const FmBlock bb = fm_block(f, jb);
-    const uint32_t ob = fm_occ_in(f, bb, c, beg);
-    const uint32_t oe = je == jb ? fm_occ_in(f, bb, c, end) : fm_occ_in(f, fm_block(f, je), c, end);
-    beg = (uint64_t)f.cnt[c] + ob;
-    end = (uint64_t)f.cnt[c] + oe;
-}
-
-__device__ __forceinline__ uint32_t fm_bwt(const FmiD &f, uint64_t i)
-{
-    return ((uint32_t)f.bwt[i >> 2] >> (2 * (uint32_t)(i & 3))) & 3u;
-}
-
 // ---- the interleaved rank blocks: one lane per 64 rows, from the on-disk arrays ------------------------------------
 __global__ __launch_bounds__(FM_THREADS) void k_fm_blocks(FmiD f, uint64_t nblocks, uint4 *__restrict__ blk)
 {
@@ -167,17 +98,6 @@ __global__ __launch_bounds__(FM_THREADS) void k_fm_blocks(FmiD f, uint64_t nbloc
     w.w = bwt_word(f, o2 + 3);
     blk[2 * j] = c;
     blk[2 * j + 1] = w;
-}
-// compute_b_occ, fm_index.hpp:189-208.  SA_INTV = 1 keeps no bit-vector (b == nullptr): every row is sampled and its
-// rank is the row itself, so the walk below emits sa_[beg, end) at depth 0 -- get_offsets' span (:455-456)
-__device__ __forceinline__ uint32_t fm_b_occ(const FmiD &f, uint64_t i)
-{
-    if (!f.b) return (uint32_t)i;
-    const uint64_t w = i >> 6;
-    const uint32_t r = (uint32_t)(i & 63);
-    uint32_t c = f.b_occ[w];
-    if (r) c += (uint32_t)__popcll(f.b[w] & ((1ull << r) - 1ull));
-    return c;
 }
 
 // ---- backward search: one lane per pattern -------------------------------------------------------
@@ -799,47 +719,15 @@ __global__ __launch_bounds__(FM_THREADS) void k_fm_rebase(uint32_t *a, uint64_t 
     a[i] -= j == 0 ? b0 : (j == 1 ? b1 : (j == 2 ? b2 : b3));
 }
 
-struct DevBuf {
-    void *p = nullptr;
-    bool pooled = false;
-    ~DevBuf()
-    {
-        if (p && !pooled) (void)hipFree(p);
-    }
-    int alloc(kiss_hip_ctx *ctx, uint64_t bytes)
-    {
-        hipError_t e = hipMalloc(&p, bytes ? bytes : 1);
-        if (e != hipSuccess) {
-            ctx->last_hip_error = (int)e;
-            p = nullptr;
-            return KISS_HIP_E_NOMEM;
-        }
-        return KISS_HIP_OK;
-    }
-    // scratch of the batched query: kept in the ctx between calls (slot = fixed role), regrown when too small --
-    // nine hipMalloc / hipFree pairs per batch cost as much as the kernels
-    int take(kiss_hip_ctx *ctx, int slot, uint64_t bytes)
-    {
-        pooled = true;
-        if (ctx->fm_pool_cap[slot] < bytes) {
-            if (ctx->fm_pool[slot]) (void)hipFree(ctx->fm_pool[slot]);
-            ctx->fm_pool[slot] = nullptr;
-            ctx->fm_pool_cap[slot] = 0;
-            const uint64_t want = bytes + bytes / 8 + 256;
-            hipError_t e = hipMalloc(&ctx->fm_pool[slot], want);
-            if (e != hipSuccess) {
-                ctx->last_hip_error = (int)e;
-                ctx->fm_pool[slot] = nullptr;
-                return KISS_HIP_E_NOMEM;
-            }
-            ctx->fm_pool_cap[slot] = want;
-        }
-        p = ctx->fm_pool[slot];
-        return KISS_HIP_OK;
-    }
-};
-
 } // namespace
+
+int kiss_fm_make_blocks(kiss_hip_ctx *ctx, const FmiD &f, uint64_t nblocks, uint4 *blk)
+{
+    KTimer t(ctx, KISS_HIP_K_FM_BUILD, nblocks);
+    hipLaunchKernelGGL(k_fm_blocks, dim3((unsigned)div_up(nblocks, FM_THREADS)), dim3(FM_THREADS), 0, ctx->stream, f, nblocks, blk);
+    KCHECK(hipGetLastError());
+    return KISS_HIP_OK;
+}
 
 namespace {
 

@@ -7,6 +7,9 @@
 //   fmindex_query  [-q STR] [-n NUM(=10)] [-b patterns.bin]                                  (command/fmindex_query.hpp)
 //   (opt-in: fmindex_build --sa-intv N --lookup-len L, fmindex_query --sa-intv N: FMIndex<N>{.LOOKUP_LEN = L}; the
 //    defaults 4 and 0 are the reference CLI's; the query reads L from the file, which does not record N)
+//   (opt-in: fmindex_query --mismatches E, E in 0..3: every position within Hamming distance E of the query, ascending,
+//    each with its mismatch count (kiss_hip_fmi_query_mm_host); the positions need an index of the EXACT suffix array:
+//    fmindex_build --exact, same .fmi layout)
 // and its log fields ("n = …, k = …, suffix sorting elapsed …", "query = … found N times", "searching time",
 // "number of matched locations", "location checksum").  Extras (opt-in): --output-sa FILE (raw u32 LE, n+1
 // entries; the reference never writes the SA), --output-lcp FILE (the LCP array of an exact suffix array, same format), --device N, and for suffix_sort --gpus N / --devices LIST (the LMS sort
@@ -52,12 +55,16 @@ void usage()
               << "./kiss fmindex_build [--option ...] <FASTA filename/Text filename>\n"
               << "  -k [ --kordered ] NUM (=256)   accepted and ignored (the index is built with k = 32)\n"
               << "  --sa-intv NUM (=4)             SA sampling interval, 1..32 (1: the whole SA)\n"
-              << "  --lookup-len NUM (=0)          k-mer lookup table of 4^NUM ranges, 0..14\n\n"
+              << "  --lookup-len NUM (=0)          k-mer lookup table of 4^NUM ranges, 0..14\n"
+              << "  --exact                        build from the exact suffix array (k = -1) instead of k = 32: what the\n"
+              << "                                 positions of fmindex_query --mismatches need; same .fmi layout\n\n"
               << "./kiss fmindex_query [--option ...] <FASTA filename/Text filename>\n"
               << "  -q [ --query ] STR             content of the query string\n"
               << "  -n [ --headn ] NUM (=10)       output the first n locations in single query mode\n"
               << "  -b [ --batch ] patterns.bin    batch query mode (u32 len, u32 count, then count x len bytes)\n"
-              << "  --sa-intv NUM (=4)             the SA sampling interval the index was built with\n";
+              << "  --sa-intv NUM (=4)             the SA sampling interval the index was built with\n"
+              << "  --mismatches NUM               also report the locations with up to NUM (0..3) substitutions; the\n"
+              << "                                 positions need an index built with fmindex_build --exact\n";
 }
 
 inline uint8_t to_code(unsigned char c)
@@ -129,7 +136,8 @@ struct Args {
     uint32_t sa_intv = 4, lookup_len = 0; // FMIndex<SA_INTV>{.LOOKUP_LEN}: the reference CLI's (fmindex_build.hpp:27-29)
     int device = 0, gpus = 1;
     std::vector<int> devices; // --devices; empty: device, device + 1, ... (gpus of them)
-    bool verbose = false, generic = false;
+    bool verbose = false, generic = false, exact = false;
+    int mismatches = -1; // fmindex_query --mismatches (-1: the exact query of the reference)
 };
 
 Args parse(int argc, char **argv)
@@ -158,6 +166,8 @@ Args parse(int argc, char **argv)
         else if (s == "--sa-intv") a.sa_intv = (uint32_t)std::stoul(next("--sa-intv"));
         else if (s == "--lookup-len") a.lookup_len = (uint32_t)std::stoul(next("--lookup-len"));
         else if (s == "--gpus") a.gpus = std::stoi(next("--gpus"));
+        else if (s == "--exact") a.exact = true;
+        else if (s == "--mismatches") a.mismatches = std::stoi(next("--mismatches"));
         else if (s == "--devices") {
             const std::string list = next("--devices");
             size_t at = 0;
@@ -177,6 +187,7 @@ Args parse(int argc, char **argv)
     if (a.gpus < 1) throw std::runtime_error("--gpus must be >= 1");
     if (a.sa_intv < 1 || a.sa_intv > KISS_HIP_FMI_MAX_SA_INTV) throw std::runtime_error("--sa-intv must be in 1..32");
     if (a.lookup_len > KISS_HIP_FMI_MAX_LOOKUP_LEN) throw std::runtime_error("--lookup-len must be in 0..14");
+    if (a.mismatches < -1 || a.mismatches > (int)KISS_HIP_FMI_MAX_MISMATCHES) throw std::runtime_error("--mismatches must be in 0..3");
     if (a.devices.empty())
         for (int g = 0; g < a.gpus; g++) a.devices.push_back(a.device + g);
     else
@@ -492,12 +503,19 @@ int fmindex_build_main(const Args &a)
     if (S.empty()) throw std::runtime_error("empty sequence");
     Fmi f(a.sa_intv, a.lookup_len);
     f.alloc(S.size());
+    std::vector<uint32_t> SA; // --exact: the exact suffix array instead of the build's own k = 32 sort
+    if (a.exact) {
+        SA.resize(S.size() + 1);
+        check(kiss_hip_suffix_sort_dna_u32(S.data(), S.size(), 0xFFFFFFFFu, KISS_HIP_ALGO_PARALLEL_SORTING, SA.data(), a.device),
+              "kiss_hip_suffix_sort_dna_u32");
+    }
+    const uint32_t *sa_or_null = a.exact ? SA.data() : nullptr;
     if (f.classic())
-        check(kiss_hip_fmi_build_host(S.data(), S.size(), nullptr, f.bwt.data(), f.occ1.data(), f.occ2.data(), f.sa.data(),
+        check(kiss_hip_fmi_build_host(S.data(), S.size(), sa_or_null, f.bwt.data(), f.occ1.data(), f.occ2.data(), f.sa.data(),
                                       f.b.data(), f.b_occ.data(), f.cnt, &f.pri, a.device),
               "kiss_hip_fmi_build_host");
     else
-        check(kiss_hip_fmi_build_ex_host(S.data(), S.size(), nullptr, f.sa_intv, f.lookup_len, f.bwt.data(), f.occ1.data(),
+        check(kiss_hip_fmi_build_ex_host(S.data(), S.size(), sa_or_null, f.sa_intv, f.lookup_len, f.bwt.data(), f.occ1.data(),
                                          f.occ2.data(), f.sa.data(), f.b.data(), f.b_occ.data(), f.lookup.data(), f.cnt,
                                          &f.pri, a.device),
               "kiss_hip_fmi_build_ex_host");
@@ -515,6 +533,35 @@ const char *ending(size_t x)
     return "th";
 }
 
+// fmindex_query --mismatches: counts first (they size the output), then the hits of every pattern in ascending position
+struct MmHits {
+    std::vector<uint32_t> counts, positions;
+    std::vector<uint8_t> mismatches;
+    std::vector<uint64_t> index;
+    kiss_hip_fmi_mm_report rep{};
+    uint64_t total = 0;
+};
+MmHits mm_query(const Fmi &f, const uint8_t *pat, uint32_t L, uint64_t Q, uint32_t e, int device)
+{
+    MmHits h;
+    const kiss_hip_fmi_view v = f.view();
+    h.counts.resize((size_t)Q * (e + 1) + 1);
+    check(kiss_hip_fmi_query_mm_host(&v, pat, L, Q, e, h.counts.data(), nullptr, nullptr, nullptr, 0, &h.rep, device),
+          "kiss_hip_fmi_query_mm_host");
+    for (int j = 0; j < 4; j++) h.total += h.rep.hits[j];
+    h.positions.resize(h.total + 1);
+    h.mismatches.resize(h.total + 1);
+    h.index.resize(Q + 1);
+    const int rc = kiss_hip_fmi_query_mm_host(&v, pat, L, Q, e, h.counts.data(), h.positions.data(), h.mismatches.data(),
+                                              h.index.data(), h.total, &h.rep, device);
+    if (rc == KISS_HIP_E_INVALID && h.rep.walk_failures)
+        throw std::runtime_error("fmindex_query --mismatches: " + std::to_string(h.rep.walk_failures) +
+                                 " rows of the index reached no sampled row: the positions need an index built with "
+                                 "fmindex_build --exact");
+    check(rc, "kiss_hip_fmi_query_mm_host");
+    return h;
+}
+
 int fmindex_query_main(const Args &a)
 {
     std::vector<uint8_t> S;
@@ -524,7 +571,22 @@ int fmindex_query_main(const Args &a)
     }
     Fmi f(a.sa_intv, 0);
     f.load(a.fasta + ".fmi");
-    if (!a.query.empty()) {
+    if (!a.query.empty() && a.mismatches >= 0) {
+        std::vector<uint8_t> q;
+        for (unsigned char c : a.query) q.push_back(to_code(c));
+        const MmHits h = mm_query(f, q.data(), (uint32_t)q.size(), 1, (uint32_t)a.mismatches, a.device);
+        std::string qs, classes;
+        for (auto c : q) qs.push_back("ACGT"[c]);
+        for (int j = 0; j <= a.mismatches; j++)
+            classes += (j ? ", " : "") + std::to_string(h.counts[j]) + (j == 0 ? " exact" : j == 1 ? " with 1 mismatch" : " with " + std::to_string(j) + " mismatches");
+        std::fprintf(stderr, "[info] query = %s found %llu times (%s)\n", qs.c_str(), (unsigned long long)h.total, classes.c_str());
+        for (size_t i = 0; i < std::min<size_t>(a.headn, h.total); i++) {
+            std::string sub;
+            for (size_t j = 0; j < q.size() && h.positions[i] + j < S.size(); j++) sub.push_back("ACGT"[S[h.positions[i] + j]]);
+            std::fprintf(stderr, "[info] The %zu-%s position is %u, %u mismatches, content of substring is %s\n", i + 1,
+                         ending(i + 1), h.positions[i], (unsigned)h.mismatches[i], sub.c_str());
+        }
+    } else if (!a.query.empty()) {
         std::vector<uint8_t> q;
         for (unsigned char c : a.query) q.push_back(to_code(c));
         uint32_t beg = 0, end = 0;
@@ -558,7 +620,15 @@ int fmindex_query_main(const Args &a)
         std::vector<uint32_t> beg(Q), end(Q);
         uint64_t hits = 0, chk = 0;
         const auto t0 = std::chrono::steady_clock::now();
-        f.query(pat.data(), L, Q, beg.data(), end.data(), &hits, &chk, nullptr, nullptr, 0, a.device);
+        if (a.mismatches >= 0) {
+            const MmHits h = mm_query(f, pat.data(), L, Q, (uint32_t)a.mismatches, a.device);
+            hits = h.total;
+            chk = h.rep.checksum;
+            for (int j = 0; j <= a.mismatches; j++)
+                std::fprintf(stderr, "[info] matched locations with %d mismatches: %llu\n", j, (unsigned long long)h.rep.hits[j]);
+        } else {
+            f.query(pat.data(), L, Q, beg.data(), end.data(), &hits, &chk, nullptr, nullptr, 0, a.device);
+        }
         std::fprintf(stderr, "[info] searching time: %.6f seconds\n", seconds_since(t0));
         std::fprintf(stderr, "[info] number of matched locations: %llu\n", (unsigned long long)hits);
         std::fprintf(stderr, "[info] location checksum: %llu\n", (unsigned long long)chk);

@@ -17,10 +17,11 @@ import struct
 import numpy as np
 
 from . import _lib
-from .sorter import Context, _check
+from .sorter import Context, K_UNBOUNDED, _check
 
 SA_INTV = 4          # fmindex_build.hpp:27
 MAX_SA_INTV, MAX_LOOKUP_LEN = 32, 14  # KISS_HIP_FMI_MAX_SA_INTV / KISS_HIP_FMI_MAX_LOOKUP_LEN
+MAX_MISMATCHES = 3   # KISS_HIP_FMI_MAX_MISMATCHES
 SORT_LEN = 32        # FMIndex::build sorts with k = 32 whatever the CLI flags say (fm_index.hpp:384-386)
 OCC1_INTV, OCC2_INTV, B_OCC_INTV = 256, 16, 64
 
@@ -40,9 +41,12 @@ def _check_params(sa_intv, lookup_len):
 
 
 class FMIndex:
-    def __init__(self, device=0, sa_intv=SA_INTV, lookup_len=0):
+    def __init__(self, device=0, sa_intv=SA_INTV, lookup_len=0, hooks=None):
+        """hooks (here, on load and on from_bytes) is for the tests and the measuring tools only: True serves this index
+        from libkiss_hip_hooks.so, the build with the A-B switches; None, the default, from the library of the process."""
         _check_params(int(sa_intv), int(lookup_len))
         self.device = int(device)
+        self._hooks = hooks  # which build of the library serves this index (_lib.load): None = the process default
         self.sa_intv = int(sa_intv)
         self.lookup_len = int(lookup_len)
         self.N = 0
@@ -51,6 +55,8 @@ class FMIndex:
         # torch tensors on the GPU; b / b_occ stay None when sa_intv == 1 (the reference keeps no bit-vector)
         self.bwt = self.occ1 = self.occ2 = self.sa = self.b = self.b_occ = self.lookup = None
         self._ctx = None
+        # the index was built from the EXACT suffix array: what query_mismatch needs for positions
+        self.exact_sa = False
 
     @property
     def _classic(self):
@@ -90,13 +96,17 @@ class FMIndex:
         if self._ctx is None or self._ctx.max_n < max_n:
             if self._ctx is not None:
                 self._ctx.close()
-            self._ctx = Context(max_n=max(max_n, 1 << 20), device=self.device)
+            self._ctx = Context(max_n=max(max_n, 1 << 20), device=self.device, hooks=self._hooks)
         return self._ctx
 
     # ---- build (fm_index.hpp:379-451) ------------------------------------------------------------------
-    def build(self, ref, sa=None):
-        """ref: uint8 array with values 0..3.  Sorts with k = 32 (like the reference) unless `sa` is given.
+    def build(self, ref, sa=None, exact=False, exact_sa=False):
+        """ref: uint8 array with values 0..3.  Sorts with k = 32 (like the reference) unless `sa` is given;
+        exact=True sorts in exact order instead (K_UNBOUNDED: what the positions of query_mismatch need; same .fmi
+        layout).  exact_sa: the caller's word that a given `sa` is the exact suffix array.
         ref / sa may also be device tensors of this device (uint8 / int32 holding the u32 values): used in place."""
+        if exact and sa is not None:
+            raise ValueError("exact=True sorts the text itself; with sa= say exact_sa=True instead")
         torch = _torch()
         dev = torch.device("cuda", self.device)
         if isinstance(ref, torch.Tensor) and ref.device == dev:
@@ -107,7 +117,7 @@ class FMIndex:
         ctx = self._context(n)
         if sa is None:
             d_SA = torch.empty(n + 1, dtype=torch.int32, device=dev)
-            ctx.suffix_sort_dev(d_S.data_ptr(), n, d_SA.data_ptr(), k=SORT_LEN)
+            ctx.suffix_sort_dev(d_S.data_ptr(), n, d_SA.data_ptr(), k=K_UNBOUNDED if exact else SORT_LEN)
         elif isinstance(sa, torch.Tensor) and sa.device == dev:
             d_SA = sa.contiguous()
             if d_SA.numel() != n + 1 or d_SA.element_size() != 4:
@@ -118,7 +128,7 @@ class FMIndex:
         self._alloc(n + 1)
         cnt = (ctypes.c_uint32 * 4)()
         pri = ctypes.c_uint32()
-        lib = _lib.load()
+        lib = _lib.load(self._hooks)
         ptr = lambda t: ctypes.c_void_p(t.data_ptr() if t is not None else None)  # noqa: E731
         if self._classic:
             _check(lib.kiss_hip_fmi_build_dev(ctx._ctx, ctypes.c_void_p(d_S.data_ptr()), n,
@@ -136,6 +146,7 @@ class FMIndex:
                    "kiss_hip_fmi_build_ex_dev", ctx._ctx)
         self.cnt = np.array(list(cnt), dtype=np.uint32)
         self.pri = int(pri.value)
+        self.exact_sa = bool(exact or (sa is not None and exact_sa))
         return self
 
     # ---- .fmi serialisation (fm_index.hpp:591-646; Serializer: u64 count + raw bytes, nothing when empty) -----
@@ -165,9 +176,10 @@ class FMIndex:
             f.write(self.to_bytes())
 
     @classmethod
-    def from_bytes(cls, buf, device=0, sa_intv=SA_INTV):
+    def from_bytes(cls, buf, device=0, sa_intv=SA_INTV, exact_sa=False, hooks=None):
         """the file does not record SA_INTV: the caller names it, and a file whose vector counts do not fit it is
-        rejected; LOOKUP_LEN is read from the lookup_ count (4^L + 1)"""
+        rejected; LOOKUP_LEN is read from the lookup_ count (4^L + 1).  Nor does it record the order of the suffix array it
+        was built from: exact_sa is the caller's word that it was the exact one."""
         torch = _torch()
         _check_params(int(sa_intv), 0)
         mv = memoryview(buf)
@@ -208,7 +220,8 @@ class FMIndex:
                 raise ValueError("b_ / b_occ_ sizes of the .fmi do not fit N = %d" % N)
         if off != len(mv):
             raise ValueError("trailing bytes in .fmi (the reference asserts EOF, fm_index.hpp:642)")
-        self = cls(device, sa_intv=sa_intv, lookup_len=lookup_len)
+        self = cls(device, sa_intv=sa_intv, lookup_len=lookup_len, hooks=hooks)
+        self.exact_sa = bool(exact_sa)
         self.cnt = cnt
         self.pri = pri
         self._alloc(N)
@@ -230,9 +243,9 @@ class FMIndex:
         return self
 
     @classmethod
-    def load(cls, path, device=0, sa_intv=SA_INTV):
+    def load(cls, path, device=0, sa_intv=SA_INTV, exact_sa=False, hooks=None):
         with open(path, "rb") as f:
-            return cls.from_bytes(f.read(), device, sa_intv)
+            return cls.from_bytes(f.read(), device, sa_intv, exact_sa, hooks)
 
     # ---- queries -------------------------------------------------------------------------------------------
     def _view(self):
@@ -271,7 +284,7 @@ class FMIndex:
         offs = torch.empty(Q, dtype=torch.int32, device=dev) if want_offs else None
         tot = ctypes.c_uint64()
         chk = ctypes.c_uint64()
-        lib = _lib.load()
+        lib = _lib.load(self._hooks)
         view = self._view()
         if self._classic and stop_cnt == 0 and not want_offs:
             def call(offsets, index, cap):
@@ -328,6 +341,118 @@ class FMIndex:
         """hit positions of one pattern in the reference's get_offsets order (fm_index.hpp:453-501)."""
         r = self.query_batch(np.asarray(seed, dtype=np.uint8)[None, :], want_offsets=True)
         return r["offsets"]
+
+    # ---- search with mismatches (kiss_hip_fmi_query_mm_dev; no reference counterpart) --------------------------------
+    def query_mismatch(self, patterns, max_mismatches, want_positions=True, d_patterns=None):
+        """Every text position whose Hamming distance to a pattern is at most max_mismatches (0..3; substitutions only).
+        patterns: (Q, L) uint8, used & 3 (host), or a device tensor via d_patterns.  Returns dict(counts (Q, e + 1):
+        hits by number of mismatches, hits_by_mismatch, total_hits, checksum, report) and, with want_positions,
+        positions / mismatches / index in CSR layout (index: Q + 1 u64), ascending position inside a pattern.
+        Counts are defined for L <= the order of the build (32 by default, any L after build(exact=True)); positions
+        only on an index built from the exact suffix array.  With positions the batch is searched twice, as the C
+        interface has it: once for the counts, which size the output and say where to cut a batch that has more hits
+        than one call sorts, then part by part; `report` sums the calls of the second kind (`calls` of them) and gives the
+        first one's time as `ms_counts`."""
+        torch = _torch()
+        dev = torch.device("cuda", self.device)
+        e = int(max_mismatches)
+        if not 0 <= e <= MAX_MISMATCHES:
+            raise ValueError("max_mismatches must be in 0..%d, got %d" % (MAX_MISMATCHES, e))
+        if want_positions and not self.exact_sa:
+            raise ValueError("positions of a search with mismatches need an index built from the exact suffix array: "
+                             "build(ref, exact=True), or exact_sa=True on build(sa=...) / load / from_bytes")
+        if d_patterns is None:
+            d_patterns = torch.from_numpy(np.ascontiguousarray(patterns, dtype=np.uint8)).to(dev)
+        d_patterns = d_patterns.contiguous()
+        Q, L = int(d_patterns.shape[0]), int(d_patterns.shape[1])
+        if L == 0:
+            raise ValueError("patterns of length 0")
+        lib = _lib.load(self._hooks)
+        view = self._view()
+        counts = torch.zeros((Q, e + 1), dtype=torch.int32, device=dev)
+        hits = [0, 0, 0, 0]
+        acc = {"ranges": 0, "lf_pairs": 0, "walk_failures": 0, "checksum": 0, "ms_total": 0.0, "ms_search": 0.0,
+               "ms_locate": 0.0, "ms_sort": 0.0, "calls": 0, "ms_counts": 0.0}
+        pos_parts, mm_parts, sizes = [], [], []
+
+        def add(rep):
+            for k in acc:
+                if k not in ("calls", "ms_counts"):
+                    acc[k] += getattr(rep, k)
+            acc["calls"] += 1
+            for j in range(4):
+                hits[j] += int(rep.hits[j])
+
+        def locate(lo, hi, total):
+            """positions of the patterns [lo, hi), which have `total` hits -> the status of the call"""
+            q = hi - lo
+            ctx = self._ctx
+            positions = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
+            mism = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+            index = torch.empty(q + 1, dtype=torch.int64, device=dev)
+            rep = _lib.FmiMmReport()
+            rc = lib.kiss_hip_fmi_query_mm_dev(ctx._ctx, ctypes.byref(view), ctypes.c_void_p(d_patterns.data_ptr() + lo * L), L, q,
+                                               e, ctypes.c_void_p(counts.data_ptr() + lo * (e + 1) * 4),
+                                               ctypes.c_void_p(positions.data_ptr()), ctypes.c_void_p(mism.data_ptr()),
+                                               ctypes.c_void_p(index.data_ptr()), total, ctypes.byref(rep), None)
+            if rc == _lib.KISS_HIP_E_UNSUPPORTED:
+                return rc
+            if rc == _lib.KISS_HIP_E_INVALID and rep.walk_failures:
+                raise _lib.KissHipError(rc, "kiss_hip_fmi_query_mm_dev",
+                                        "%d rows reached no sampled row: the index was not built from an exact suffix array "
+                                        "(build with exact=True)" % rep.walk_failures)
+            _check(rc, "kiss_hip_fmi_query_mm_dev", ctx._ctx)
+            add(rep)
+            pos_parts.append(positions[:total].cpu().numpy().view(np.uint32))
+            mm_parts.append(mism[:total].cpu().numpy())
+            sizes.append(np.diff(index.cpu().numpy().view(np.uint64)))
+            return rc
+
+        def run():
+            """counts of the whole batch first: they size the output and say where to cut the batch so that every part
+            has no more hits than one call sorts (the context's per-LMS-suffix arrays, 0.32 max_n entries)"""
+            ctx = self._context(max(self.N, 4 * Q))
+            rep = _lib.FmiMmReport()
+            _check(lib.kiss_hip_fmi_query_mm_dev(ctx._ctx, ctypes.byref(view), ctypes.c_void_p(d_patterns.data_ptr()), L, Q, e,
+                                                 ctypes.c_void_p(counts.data_ptr()), None, None, None, 0, ctypes.byref(rep), None),
+                   "kiss_hip_fmi_query_mm_dev", ctx._ctx)
+            if not want_positions:
+                add(rep)
+                return
+            acc["ms_counts"] = float(rep.ms_total)  # (the rest of the report: the calls that return the positions)
+            ends = counts.to(torch.int64).sum(dim=1).cumsum(0).cpu().numpy()  # hits of the patterns [0, q]
+            cap = int(0.32 * ctx.max_n)
+            parts, lo = [], 0
+            while lo < Q:
+                before = int(ends[lo - 1]) if lo else 0
+                hi = max(int(np.searchsorted(ends, before + cap, side="right")), lo + 1)
+                parts.append((lo, hi))
+                lo = hi
+            while parts:
+                lo, hi = parts.pop(0)
+                total = int(ends[hi - 1]) - (int(ends[lo - 1]) if lo else 0)
+                if locate(lo, hi, total) != _lib.KISS_HIP_E_UNSUPPORTED:
+                    continue
+                if hi - lo > 1:  # (the context sorts fewer than reckoned with: halve)
+                    parts[:0] = [(lo, lo + (hi - lo) // 2), (lo + (hi - lo) // 2, hi)]
+                    continue
+                self._context(min(_lib.MAX_N, 4 * total + (1 << 20)))  # one pattern with that many hits: a larger context
+                _check(locate(lo, hi, total), "kiss_hip_fmi_query_mm_dev", self._ctx._ctx)
+
+        if Q:
+            run()
+        rep = dict(acc)
+        rep.update(Q=Q, L=L, max_mismatches=e, hits=list(hits))
+        res = {"counts": counts.cpu().numpy().view(np.uint32), "hits_by_mismatch": hits[:e + 1], "total_hits": sum(hits),
+               "checksum": int(acc["checksum"]), "report": rep}
+        if want_positions:
+            res["positions"] = np.concatenate(pos_parts) if pos_parts else np.zeros(0, np.uint32)
+            res["mismatches"] = np.concatenate(mm_parts) if mm_parts else np.zeros(0, np.uint8)
+            index = np.zeros(Q + 1, np.uint64)
+            if sizes:
+                np.cumsum(np.concatenate(sizes), out=index[1:])
+            res["index"] = index
+        return res
 
     def close(self):
         if self._ctx is not None:
