@@ -546,6 +546,82 @@ int kiss_hip_alloc_dev(void **d_out, uint64_t bytes);
 int kiss_hip_copy_to_host(void *dst, const void *d_src, uint64_t bytes);
 int kiss_hip_free_dev(void *p);
 
+/* ---- FM-index over a byte text (values 0..255; no reference counterpart: its -g commands are a TODO) ---------------------
+ * Built from a text S of n bytes and its EXACT suffix array (kiss_hip_suffix_sort_u8: N = n + 1 entries, SA[0] = n).  A hit of
+ * a pattern P of length L >= 1 is a position p in [0, n - L] with S[p .. p + L) == P; bytes compare as unsigned values and
+ * overlapping hits all count.  Every result is a function of (S, patterns) alone, whatever sa_intv.
+ * Arrays, with nblk = N / 256 + 1 and nsb = N / 65536 + 1:
+ *   C     : 257 u32, C[c] = 1 + #{bytes of S smaller than c}
+ *   map   : 256 bytes, the dense code (0 .. sigma - 1, in value order) of a byte value that occurs in S, 0xFF otherwise
+ *           (a value v is absent iff C[v + 1] == C[v]: at sigma = 256 the code 255 is a code like the others)
+ *   bwt   : nblk * 256 bytes, 16-byte aligned; row i holds S[SA[i] - 1], the primary row (SA[i] == 0) and the rows >= N hold 0
+ *   occ1  : sigma x nsb u32, symbol-major: occurrences of code c in bwt[0, 65536 j), the primary row left out
+ *   occ2  : sigma x nblk u16, symbol-major: occurrences of code c in bwt[65536 (j / 256), 256 j)
+ *   sa / b / b_occ : as in kiss_hip_fmi_view_ex (sa_intv == 1: the whole SA, b = b_occ = NULL)
+ * For the *_dev calls every pointer of the view is a device pointer, for the *_host calls a host pointer. */
+typedef struct kiss_hip_fmi8_view {
+    uint64_t n_sa;        /* N = n + 1 */
+    uint32_t pri;         /* row i with SA[i] == 0 */
+    uint32_t sa_intv;     /* 1..KISS_HIP_FMI_MAX_SA_INTV */
+    uint32_t sigma;       /* distinct byte values of S (0 for n = 0) */
+    uint32_t reserved_;
+    const uint32_t *C;
+    const uint8_t *map;
+    const uint8_t *bwt;
+    const uint32_t *occ1;
+    const uint16_t *occ2;
+    const uint32_t *sa;
+    const uint64_t *b;
+    const uint32_t *b_occ;
+} kiss_hip_fmi8_view;
+typedef struct kiss_hip_fmi8_sizes {
+    uint64_t n_sa, bwt_bytes, occ1_entries, occ2_entries, sa_entries, b_words, b_occ_entries;
+} kiss_hip_fmi8_sizes;
+/* host-only arithmetic.  sa_intv outside 1..32: KISS_HIP_E_UNSUPPORTED; sigma > 256 or n > KISS_HIP_MAX_N: KISS_HIP_E_INVALID */
+int kiss_hip_fmi8_sizes_for(uint64_t n, uint32_t sa_intv, uint32_t sigma, kiss_hip_fmi8_sizes *out);
+typedef struct kiss_hip_fmi8_report {
+    uint64_t Q;
+    uint64_t hits;           /* sum of end - beg */
+    uint64_t lf_pairs;       /* (range, byte) pairs the search evaluated: the denominator of its rate */
+    uint64_t walk_failures;  /* rows that reached no sampled row within sa_intv - 1 steps (index not from an exact SA) */
+    uint64_t checksum;       /* sum of all hit positions (0 without positions) */
+    float ms_total, ms_search, ms_locate, ms_sort;
+} kiss_hip_fmi8_report;
+/* Build from a device text and its exact suffix array.  The arrays depend on sigma, which only the text knows, so the call has
+ * two forms: d_bwt == NULL is the census -- it writes *sigma_out (and d_C / d_map when given) and nothing else; otherwise the
+ * arrays are sized by kiss_hip_fmi8_sizes_for(n, sa_intv, sigma_capacity), sigma_capacity >= the text's sigma (smaller:
+ * KISS_HIP_E_INVALID with *sigma_out set), and occ1 / occ2 are laid out for *sigma_out rows.  d_b / d_b_occ may be NULL when
+ * sa_intv == 1.  n = 0 builds the index of one row.  Device times under KISS_HIP_K_FM_BUILD. */
+int kiss_hip_fmi8_build_dev(kiss_hip_ctx *ctx, const uint8_t *d_S, uint64_t n, const uint32_t *d_SA, uint32_t sa_intv,
+                            uint32_t sigma_capacity, uint32_t *d_C, uint8_t *d_map, uint8_t *d_bwt, uint32_t *d_occ1,
+                            uint16_t *d_occ2, uint32_t *d_sa, uint64_t *d_b, uint32_t *d_b_occ, uint32_t *sigma_out,
+                            uint32_t *pri_out, void *stream);
+/* host pointers (creates a ctx on `device`, uploads, runs, downloads); SA_or_null == NULL sorts with kiss_hip_suffix_sort_u8's
+ * kernels first; bwt == NULL: the census, as above */
+int kiss_hip_fmi8_build_host(const uint8_t *S, uint64_t n, const uint32_t *SA_or_null, uint32_t sa_intv, uint32_t sigma_capacity,
+                             uint32_t *C, uint8_t *map, uint8_t *bwt, uint32_t *occ1, uint16_t *occ2, uint32_t *sa, uint64_t *b,
+                             uint32_t *b_occ, uint32_t *sigma_out, uint32_t *pri_out, int device);
+/* Batched backward search + locate over a RAGGED batch: Q patterns concatenated in `patterns`, pattern q =
+ * patterns[pat_index[q], pat_index[q + 1]) (pat_index: Q + 1 u64, strictly increasing: every pattern has L >= 1).
+ *   beg, end   : Q u32 each, the SA range; count = end - beg; no hits: beg == end
+ *   hit_count_total, checksum : host pointers (may be NULL): sum of the counts, sum of all positions (0 without positions)
+ *   positions / index : optional (both or none; none: capacity = 0).  index has Q + 1 u64 (exclusive prefix of the counts);
+ *                the hits of pattern q are positions[index[q] .. index[q + 1]) in ASCENDING position.
+ *   capacity   : entries available in positions.  Smaller than the total: KISS_HIP_E_INVALID with the total in
+ *                *hit_count_total and report->hits (call again with room).
+ * A zero-length pattern, a pat_index that decreases, a required pointer NULL or a bwt that is not 16-byte aligned:
+ * KISS_HIP_E_INVALID.  L > n or Q == 0: KISS_HIP_OK, no hits.  sa_intv outside 1..32: KISS_HIP_E_UNSUPPORTED.  The hits of a
+ * call are sorted in the ctx's LMS work arrays (their contents are lost): more hits than those hold is
+ * KISS_HIP_E_UNSUPPORTED with the totals reported -- split the batch.  A row that reaches no sampled row (an index that was not
+ * built from an exact suffix array) is counted in walk_failures and the call returns KISS_HIP_E_INVALID.
+ * Device times: report->ms_* (report may be NULL); the kernels also count under KISS_HIP_K_FM_QUERY when that class is profiled. */
+int kiss_hip_fmi8_query_dev(kiss_hip_ctx *ctx, const kiss_hip_fmi8_view *fmi, const uint8_t *patterns, const uint64_t *pat_index,
+                            uint64_t Q, uint32_t *beg, uint32_t *end, uint64_t *hit_count_total, uint64_t *checksum,
+                            uint32_t *positions, uint64_t *index, uint64_t capacity, kiss_hip_fmi8_report *report, void *stream);
+int kiss_hip_fmi8_query_host(const kiss_hip_fmi8_view *fmi, const uint8_t *patterns, const uint64_t *pat_index, uint64_t Q,
+                             uint32_t *beg, uint32_t *end, uint64_t *hit_count_total, uint64_t *checksum, uint32_t *positions,
+                             uint64_t *index, uint64_t capacity, kiss_hip_fmi8_report *report, int device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,3 +6,4 @@ host-side mirror of the reference's sorter facade.
 from ._lib import ALGO_PARALLEL_SORTING, ALGO_PREFIX_DOUBLING, KissHipError, LIB_PATH, load  # noqa: F401
 from .sorter import (K_UNBOUNDED, Context, KISS1Sorter, KISS2Sorter, MultiContext, lcp_array, lcp_array_bytes,  # noqa: F401
                      suffix_array_bytes)
+from .fm_index_bytes import FMIndexBytes  # noqa: F401,E402

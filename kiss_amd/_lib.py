@@ -130,6 +130,37 @@ class FmiMmReport(ctypes.Structure):
         return d
 
 
+class Fmi8View(ctypes.Structure):
+    """kiss_hip_fmi8_view"""
+    _fields_ = [
+        ("n_sa", ctypes.c_uint64), ("pri", ctypes.c_uint32), ("sa_intv", ctypes.c_uint32), ("sigma", ctypes.c_uint32),
+        ("reserved_", ctypes.c_uint32), ("C", ctypes.c_void_p), ("map", ctypes.c_void_p), ("bwt", ctypes.c_void_p),
+        ("occ1", ctypes.c_void_p), ("occ2", ctypes.c_void_p), ("sa", ctypes.c_void_p), ("b", ctypes.c_void_p),
+        ("b_occ", ctypes.c_void_p),
+    ]
+
+
+class Fmi8Sizes(ctypes.Structure):
+    """kiss_hip_fmi8_sizes"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("n_sa", "bwt_bytes", "occ1_entries", "occ2_entries", "sa_entries", "b_words",
+                                               "b_occ_entries")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class Fmi8Report(ctypes.Structure):
+    """kiss_hip_fmi8_report"""
+    _fields_ = [
+        ("Q", ctypes.c_uint64), ("hits", ctypes.c_uint64), ("lf_pairs", ctypes.c_uint64), ("walk_failures", ctypes.c_uint64),
+        ("checksum", ctypes.c_uint64), ("ms_total", ctypes.c_float), ("ms_search", ctypes.c_float),
+        ("ms_locate", ctypes.c_float), ("ms_sort", ctypes.c_float),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class KissHipError(RuntimeError):
     def __init__(self, status, where, detail=""):
         self.status = status
@@ -238,6 +269,17 @@ def load(hooks=None):
     lib.kiss_hip_fmi_query_mm_host.argtypes = [ctypes.POINTER(FmiView), vp, u32, u64, u32, vp, vp, vp, vp, u64,
                                                ctypes.POINTER(FmiMmReport), ctypes.c_int]
     lib.kiss_hip_fmi_query_mm_dev.restype = lib.kiss_hip_fmi_query_mm_host.restype = ctypes.c_int
+    lib.kiss_hip_fmi8_sizes_for.argtypes = [u64, u32, u32, ctypes.POINTER(Fmi8Sizes)]
+    lib.kiss_hip_fmi8_build_dev.argtypes = [vp, vp, u64, vp, u32, u32] + [vp] * 8 + [ctypes.POINTER(u32), ctypes.POINTER(u32), vp]
+    lib.kiss_hip_fmi8_build_host.argtypes = [vp, u64, vp, u32, u32] + [vp] * 8 + [ctypes.POINTER(u32), ctypes.POINTER(u32),
+                                                                                  ctypes.c_int]
+    lib.kiss_hip_fmi8_query_dev.argtypes = [vp, ctypes.POINTER(Fmi8View), vp, vp, u64, vp, vp, ctypes.POINTER(u64),
+                                            ctypes.POINTER(u64), vp, vp, u64, ctypes.POINTER(Fmi8Report), vp]
+    lib.kiss_hip_fmi8_query_host.argtypes = [ctypes.POINTER(Fmi8View), vp, vp, u64, vp, vp, ctypes.POINTER(u64),
+                                             ctypes.POINTER(u64), vp, vp, u64, ctypes.POINTER(Fmi8Report), ctypes.c_int]
+    for name in ("kiss_hip_fmi8_sizes_for", "kiss_hip_fmi8_build_dev", "kiss_hip_fmi8_build_host", "kiss_hip_fmi8_query_dev",
+                 "kiss_hip_fmi8_query_host"):
+        getattr(lib, name).restype = ctypes.c_int
     lib.kiss_hip_file_size.argtypes = [ctypes.c_char_p, ctypes.POINTER(u64)]
     lib.kiss_hip_ctx_parse_text_dev.argtypes = [vp, vp, u64, vp, ctypes.POINTER(u64), vp]
     lib.kiss_hip_ctx_load_text_file.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(vp), ctypes.POINTER(u64)]
@@ -300,4 +342,6 @@ EXPORTED_SYMBOLS = [
     "kiss_hip_fmi_sizes_ex_for", "kiss_hip_fmi_build_ex_dev", "kiss_hip_fmi_query_ex_dev", "kiss_hip_fmi_build_ex_host",
     "kiss_hip_fmi_query_ex_host", "kiss_hip_ctx_lcp_dna_u32_dev", "kiss_hip_ctx_lcp_u8_dev", "kiss_hip_lcp_dna_u32",
     "kiss_hip_lcp_u8", "kiss_hip_fmi_query_mm_dev", "kiss_hip_fmi_query_mm_host",
+    "kiss_hip_fmi8_sizes_for", "kiss_hip_fmi8_build_dev", "kiss_hip_fmi8_build_host", "kiss_hip_fmi8_query_dev",
+    "kiss_hip_fmi8_query_host",
 ]

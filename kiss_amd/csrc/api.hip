@@ -90,6 +90,7 @@ void kiss_opts_refresh(kiss_hip_ctx *ctx)
     o.fm_light = (uint32_t)env_u64("KISS_HIP_FM_LIGHT", 0);
     o.fm_mm_wave = env_on("KISS_HIP_FM_MM_WAVE");
     o.fm_mm_budget = env_u64("KISS_HIP_FM_MM_BUDGET", 0);
+    o.fm8_group = env_on("KISS_HIP_FM8_GROUP");
     o.isa_direct_max = env_u64("KISS_HIP_ISA_DIRECT_MAX", 0);
     o.lx_sync_points = (unsigned)env_u64("KISS_HIP_LX_SYNC_POINTS", 0);
     o.tie_trace = (unsigned)env_u64("KISS_HIP_TIE_TRACE", 0);

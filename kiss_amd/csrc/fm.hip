@@ -721,6 +721,29 @@ __global__ __launch_bounds__(FM_THREADS) void k_fm_rebase(uint32_t *a, uint64_t 
 
 } // namespace
 
+int kiss_fm_sample_sa(kiss_hip_ctx *ctx, const uint32_t *d_SA, uint64_t N, uint32_t sa_intv, uint32_t *d_sa, uint64_t *d_b,
+                      uint32_t *d_b_occ)
+{
+    if (sa_intv == 1) { // build_sa, fm_index.hpp:331-335: sa_ = the whole SA, no b_ / b_occ_
+        KCHECK(hipMemcpyAsync(d_sa, d_SA, N * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+        return KISS_HIP_OK;
+    }
+    // sampling bit-vector, its rank directory and the sampled SA
+    const uint64_t words = (N + 63) / 64, nbocc = N / 64 + 1;
+    if (nbocc / 4096 + 16 > ctx->scan_tmp_cap) return KISS_HIP_E_UNSUPPORTED;
+    DevBuf wcnt;
+    KTRY(wcnt.alloc(ctx, nbocc * 4));
+    hipLaunchKernelGGL(k_fm_bits, dim3((unsigned)div_up(nbocc, FM_THREADS)), dim3(FM_THREADS), 0, ctx->stream, d_SA, N, words,
+                       nbocc, sa_intv, d_b, (uint32_t *)wcnt.p);
+    KCHECK(hipGetLastError());
+    KTRY(kiss_scan_u32(ctx, (const uint32_t *)wcnt.p, d_b_occ, nbocc));
+    hipLaunchKernelGGL(k_fm_sample, dim3((unsigned)div_up(words, FM_THREADS)), dim3(FM_THREADS), 0, ctx->stream, d_SA, N, words,
+                       d_b, d_b_occ, d_sa);
+    KCHECK(hipGetLastError());
+    KCHECK(hipStreamSynchronize(ctx->stream)); // (wcnt is freed on return)
+    return KISS_HIP_OK;
+}
+
 int kiss_fm_make_blocks(kiss_hip_ctx *ctx, const FmiD &f, uint64_t nblocks, uint4 *blk)
 {
     KTimer t(ctx, KISS_HIP_K_FM_BUILD, nblocks);
@@ -930,13 +953,12 @@ int fmi_build(kiss_hip_ctx *ctx, const uint8_t *d_S, uint64_t n, const uint32_t 
     KTRY(kiss_workspace_ready(ctx));
     const uint64_t N = n + 1;
     const uint64_t chunks = N / 16 + 1, blocks = N / 256 + 1;
-    const uint64_t words = (N + 63) / 64, nbocc = N / 64 + 1;
+    const uint64_t nbocc = N / 64 + 1;
     const uint64_t bwt_bytes = (N + 3) / 4;
     if (blocks / 4096 + 16 > ctx->scan_tmp_cap || nbocc / 4096 + 16 > ctx->scan_tmp_cap) return KISS_HIP_E_UNSUPPORTED;
-    DevBuf chunk_cnt, blk_tot, wcnt, pri;
+    DevBuf chunk_cnt, blk_tot, pri;
     KTRY(chunk_cnt.alloc(ctx, chunks * 4));
     KTRY(blk_tot.alloc(ctx, (4 * blocks + 1) * 4));
-    KTRY(wcnt.alloc(ctx, nbocc * 4));
     KTRY(pri.alloc(ctx, 4));
     KTimer t(ctx, KISS_HIP_K_FM_BUILD, N);
     hipLaunchKernelGGL(k_fm_bwt, dim3((unsigned)div_up(chunks, FM_THREADS)), dim3(FM_THREADS), 0, ctx->stream, d_S, d_SA,
@@ -959,17 +981,7 @@ int fmi_build(kiss_hip_ctx *ctx, const uint8_t *d_S, uint64_t n, const uint32_t 
                        (uint32_t *)blk_tot.p, blocks, base[0], base[1], base[2], base[3]);
     hipLaunchKernelGGL(k_fm_occ1, dim3((unsigned)div_up(blocks, FM_THREADS)), dim3(FM_THREADS), 0, ctx->stream,
                        (const uint32_t *)blk_tot.p, blocks, d_occ1);
-    if (sa_intv == 1) { // build_sa, fm_index.hpp:331-335: sa_ = the whole SA, no b_ / b_occ_
-        KCHECK(hipMemcpyAsync(d_sa_sampled, d_SA, N * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
-    } else { // sampling bit-vector, its rank directory and the sampled SA
-        hipLaunchKernelGGL(k_fm_bits, dim3((unsigned)div_up(nbocc, FM_THREADS)), dim3(FM_THREADS), 0, ctx->stream, d_SA, N,
-                           words, nbocc, sa_intv, d_b, (uint32_t *)wcnt.p);
-        KCHECK(hipGetLastError());
-        KTRY(kiss_scan_u32(ctx, (const uint32_t *)wcnt.p, d_b_occ, nbocc));
-        hipLaunchKernelGGL(k_fm_sample, dim3((unsigned)div_up(words, FM_THREADS)), dim3(FM_THREADS), 0, ctx->stream, d_SA, N,
-                           words, d_b, d_b_occ, d_sa_sampled);
-        KCHECK(hipGetLastError());
-    }
+    KTRY(kiss_fm_sample_sa(ctx, d_SA, N, sa_intv, d_sa_sampled, d_b, d_b_occ));
     uint32_t h_pri = 0;
     KCHECK(hipMemcpyAsync(&h_pri, pri.p, 4, hipMemcpyDeviceToHost, ctx->stream));
     KCHECK(hipStreamSynchronize(ctx->stream));

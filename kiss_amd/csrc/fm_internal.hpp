@@ -75,15 +75,17 @@ __device__ __forceinline__ uint32_t fm_bwt(const FmiD &f, uint64_t i)
 
 // compute_b_occ, fm_index.hpp:189-208.  SA_INTV = 1 keeps no bit-vector (b == nullptr): every row is sampled and its
 // rank is the row itself, so the walk below emits sa_[beg, end) at depth 0 -- get_offsets' span (:455-456)
-__device__ __forceinline__ uint32_t fm_b_occ(const FmiD &f, uint64_t i)
+// (the arrays alone: fm8.hip keeps the same bit-vector beside another kind of index)
+__device__ __forceinline__ uint32_t fm_b_rank(const uint64_t *__restrict__ b, const uint32_t *__restrict__ b_occ, uint64_t i)
 {
-    if (!f.b) return (uint32_t)i;
+    if (!b) return (uint32_t)i;
     const uint64_t w = i >> 6;
     const uint32_t r = (uint32_t)(i & 63);
-    uint32_t c = f.b_occ[w];
-    if (r) c += (uint32_t)__popcll(f.b[w] & ((1ull << r) - 1ull));
+    uint32_t c = b_occ[w];
+    if (r) c += (uint32_t)__popcll(b[w] & ((1ull << r) - 1ull));
     return c;
 }
+__device__ __forceinline__ uint32_t fm_b_occ(const FmiD &f, uint64_t i) { return fm_b_rank(f.b, f.b_occ, i); }
 
 struct DevBuf {
     void *p = nullptr;
@@ -127,3 +129,8 @@ struct DevBuf {
 
 // fm.hip: fills blk (nblocks = f.N / 64 + 1 blocks of 32 bytes) from the on-disk arrays of f on the ctx stream (k_fm_blocks)
 int kiss_fm_make_blocks(kiss_hip_ctx *ctx, const FmiD &f, uint64_t nblocks, uint4 *blk);
+// fm.hip: the part of a build that depends on the suffix array only (k_fm_bits / k_fm_sample), queued on the ctx stream.
+// sa_intv == 1: d_sa = the whole SA (N entries), d_b / d_b_occ untouched; else the sampling bit-vector (ceil(N / 64) words),
+// its rank directory (N / 64 + 1) and the SA values with SA[i] % sa_intv == 0 in row order.
+int kiss_fm_sample_sa(kiss_hip_ctx *ctx, const uint32_t *d_SA, uint64_t N, uint32_t sa_intv, uint32_t *d_sa, uint64_t *d_b,
+                      uint32_t *d_b_occ);

@@ -10,6 +10,11 @@
 //   (opt-in: fmindex_query --mismatches E, E in 0..3: every position within Hamming distance E of the query, ascending,
 //    each with its mismatch count (kiss_hip_fmi_query_mm_host); the positions need an index of the EXACT suffix array:
 //    fmindex_build --exact, same .fmi layout)
+//   (-g / --generic: the file is a text over the byte alphabet, taken byte for byte -- no FASTA rule, no newline stripping,
+//    no % 4.  suffix_sort gives the exact suffix array (kiss_hip_suffix_sort_u8; -k and -s are ignored) and, with
+//    --output-lcp, its LCP array; fmindex_build writes <file>.fmi8 (kiss_hip_fmi8_build_host);
+//    fmindex_query reads it: -q STR is the bytes of STR, -b patterns.bin holds raw bytes.  One device, no lookup table, no
+//    mismatches.  The reference rejects -g in all three commands: command/*.hpp:15-18.)
 // and its log fields ("n = …, k = …, suffix sorting elapsed …", "query = … found N times", "searching time",
 // "number of matched locations", "location checksum").  Extras (opt-in): --output-sa FILE (raw u32 LE, n+1
 // entries; the reference never writes the SA), --output-lcp FILE (the LCP array of an exact suffix array, same format), --device N, and for suffix_sort --gpus N / --devices LIST (the LMS sort
@@ -41,7 +46,8 @@ void usage()
               << "Generic options:\n"
               << "  -h [ --help ]            produce help message\n"
               << "  -v [ --version ]         print version string\n"
-              << "  -g [ --generic ]         (not supported) generic alphabet\n"
+              << "  -g [ --generic ]         the file is a text over the byte alphabet, byte for byte: exact suffix array\n"
+              << "                           (-k, -s ignored), FILE.fmi8 index; not with --gpus, --lookup-len, --exact, --mismatches\n"
               << "  -t [ --num_threads ] NUM accepted for compatibility; no result depends on it\n"
               << "  --verbose                print per-stage device times\n"
               << "  --device NUM             HIP device index (default 0)\n\n"
@@ -137,6 +143,7 @@ struct Args {
     int device = 0, gpus = 1;
     std::vector<int> devices; // --devices; empty: device, device + 1, ... (gpus of them)
     bool verbose = false, generic = false, exact = false;
+    std::vector<std::string> seen; // the long names of the options given (what -g refuses is named)
     int mismatches = -1; // fmindex_query --mismatches (-1: the exact query of the reference)
 };
 
@@ -150,6 +157,10 @@ Args parse(int argc, char **argv)
             if (i + 1 >= argc) throw std::runtime_error(std::string("the required argument for option '") + name + "' is missing");
             return argv[++i];
         };
+        if (s == "--gpus" || s == "--devices" || s == "--lookup-len" || s == "--exact" || s == "--mismatches" || s == "--sa-intv")
+            a.seen.push_back(s);
+        if (s == "-k" || s == "--kordered") a.seen.push_back("--kordered");
+        if (s == "-s" || s == "--sorting-algorithm") a.seen.push_back("--sorting-algorithm");
         if (s == "-h" || s == "--help") { usage(); std::exit(1); }
         else if (s == "-v" || s == "--version") { std::cerr << VERSION << std::endl; std::exit(1); }
         else if (s == "-g" || s == "--generic") a.generic = true;
@@ -636,14 +647,271 @@ int fmindex_query_main(const Args &a)
     return 0;
 }
 
+// ---- -g / --generic: texts over the byte alphabet ---------------------------------------------------------------------
+bool given(const Args &a, const char *name) { return std::find(a.seen.begin(), a.seen.end(), name) != a.seen.end(); }
+
+void check_generic_options(const Args &a)
+{
+    if (a.devices.size() > 1)
+        throw std::runtime_error(std::string("--generic: one device only (not with ") + (given(a, "--devices") ? "--devices" : "--gpus") +
+                                 " above 1)");
+    for (const char *o : {"--lookup-len", "--exact", "--mismatches"})
+        if (given(a, o)) throw std::runtime_error(std::string("--generic: ") + o + " is not supported for byte texts");
+}
+
+std::vector<uint8_t> read_bytes(const std::string &path)
+{
+    std::ifstream in(path, std::ios::binary);
+    if (!in) throw std::runtime_error("cannot open " + path);
+    in.seekg(0, std::ios::end);
+    const std::streamoff size = in.tellg();
+    in.seekg(0, std::ios::beg);
+    std::vector<uint8_t> S((size_t)(size > 0 ? size : 0));
+    if (!S.empty()) in.read(reinterpret_cast<char *>(S.data()), (std::streamsize)S.size());
+    if (!in) throw std::runtime_error("cannot read " + path);
+    return S;
+}
+
+void write_u32(const std::string &path, const std::vector<uint32_t> &v)
+{
+    std::ofstream o(path, std::ios::binary);
+    if (!o) throw std::runtime_error("cannot write " + path);
+    o.write(reinterpret_cast<const char *>(v.data()), (std::streamsize)(v.size() * sizeof(uint32_t)));
+}
+
+// printable ASCII as it is, every other byte (and the backslash) as \xHH
+std::string escaped(const uint8_t *p, size_t len)
+{
+    std::string s;
+    char buf[8];
+    for (size_t i = 0; i < len; i++) {
+        if (p[i] >= 0x20 && p[i] < 0x7F && p[i] != '\\') {
+            s.push_back((char)p[i]);
+        } else {
+            std::snprintf(buf, sizeof buf, "\\x%02X", (unsigned)p[i]);
+            s += buf;
+        }
+    }
+    return s;
+}
+
+int generic_suffix_sort_main(const Args &a)
+{
+    const std::vector<uint8_t> S = read_bytes(a.fasta);
+    if (given(a, "--kordered") || given(a, "--sorting-algorithm"))
+        std::fprintf(stderr, "[info] --generic: -k and -s are ignored, the suffix array of a byte text is always exact\n");
+    std::vector<uint32_t> SA(S.size() + 1), LCP;
+    const auto t0 = std::chrono::steady_clock::now();
+    check(kiss_hip_suffix_sort_u8(S.data(), S.size(), SA.data(), a.device), "kiss_hip_suffix_sort_u8");
+    std::fprintf(stderr, "[info] n = %llu, k = %llu, suffix sorting elapsed %.6f\n", (unsigned long long)S.size(), ~0ull,
+                 seconds_since(t0));
+    if (!a.output_sa.empty()) write_u32(a.output_sa, SA);
+    if (!a.output_lcp.empty()) {
+        LCP.resize(S.size() + 1);
+        const auto tl = std::chrono::steady_clock::now();
+        check(kiss_hip_lcp_u8(S.data(), S.size(), SA.data(), nullptr, LCP.data(), a.device), "kiss_hip_lcp_u8");
+        std::fprintf(stderr, "[info] LCP array elapsed %.6f\n", seconds_since(tl));
+        write_u32(a.output_lcp, LCP);
+    }
+    return 0;
+}
+
+// FILE.fmi8: "KISSFMI8", u32 version, u32 sa_intv, u64 N, u32 pri, u32 sigma, then C, map, bwt, occ1, occ2, sa,
+// b, b_occ, each as a u64 count of entries + little-endian entries (b / b_occ: count 0 when sa_intv == 1)
+struct Fmi8 {
+    static constexpr uint32_t FORMAT_VERSION = 1;
+    kiss_hip_fmi8_sizes z{};
+    uint32_t sa_intv = 4, pri = 0, sigma = 0;
+    std::vector<uint32_t> C, occ1, sa, b_occ;
+    std::vector<uint8_t> map, bwt;
+    std::vector<uint16_t> occ2;
+    std::vector<uint64_t> b;
+    void alloc(uint64_t n)
+    {
+        check(kiss_hip_fmi8_sizes_for(n, sa_intv, sigma, &z), "kiss_hip_fmi8_sizes_for");
+        C.assign(257, 0);
+        map.assign(256, 0);
+        bwt.assign(z.bwt_bytes, 0);
+        occ1.assign(z.occ1_entries, 0);
+        occ2.assign(z.occ2_entries, 0);
+        sa.assign(z.sa_entries, 0);
+        b.assign(z.b_words, 0);
+        b_occ.assign(z.b_occ_entries, 0);
+    }
+    template <typename T> static void put(std::ofstream &o, const std::vector<T> &v)
+    {
+        const uint64_t count = v.size();
+        o.write(reinterpret_cast<const char *>(&count), 8);
+        o.write(reinterpret_cast<const char *>(v.data()), (std::streamsize)(v.size() * sizeof(T)));
+    }
+    template <typename T> static void get(std::ifstream &in, std::vector<T> &v, const char *name)
+    {
+        uint64_t count = 0;
+        in.read(reinterpret_cast<char *>(&count), 8);
+        if (!in) throw std::runtime_error("truncated .fmi8");
+        if (count != v.size()) throw std::runtime_error(std::string("bad ") + name + " size in .fmi8");
+        in.read(reinterpret_cast<char *>(v.data()), (std::streamsize)(v.size() * sizeof(T)));
+        if (!in) throw std::runtime_error("truncated .fmi8");
+    }
+    void save(const std::string &path) const
+    {
+        std::ofstream o(path, std::ios::binary);
+        if (!o) throw std::runtime_error("cannot write " + path);
+        const uint32_t version = FORMAT_VERSION;
+        o.write("KISSFMI8", 8);
+        o.write(reinterpret_cast<const char *>(&version), 4);
+        o.write(reinterpret_cast<const char *>(&sa_intv), 4);
+        o.write(reinterpret_cast<const char *>(&z.n_sa), 8);
+        o.write(reinterpret_cast<const char *>(&pri), 4);
+        o.write(reinterpret_cast<const char *>(&sigma), 4);
+        put(o, C);
+        put(o, map);
+        put(o, bwt);
+        put(o, occ1);
+        put(o, occ2);
+        put(o, sa);
+        put(o, b);
+        put(o, b_occ);
+        if (!o) throw std::runtime_error("cannot write " + path);
+    }
+    void load(const std::string &path)
+    {
+        std::ifstream in(path, std::ios::binary);
+        if (!in) throw std::runtime_error("cannot open " + path + " (run -g fmindex_build first)");
+        char magic[8];
+        uint32_t version = 0;
+        uint64_t N = 0;
+        in.read(magic, 8);
+        if (!in) throw std::runtime_error("truncated .fmi8");
+        if (std::memcmp(magic, "KISSFMI8", 8) != 0) throw std::runtime_error("not a .fmi8 file (bad magic)");
+        in.read(reinterpret_cast<char *>(&version), 4);
+        in.read(reinterpret_cast<char *>(&sa_intv), 4);
+        in.read(reinterpret_cast<char *>(&N), 8);
+        in.read(reinterpret_cast<char *>(&pri), 4);
+        in.read(reinterpret_cast<char *>(&sigma), 4);
+        if (!in) throw std::runtime_error("truncated .fmi8");
+        if (version != FORMAT_VERSION) throw std::runtime_error(".fmi8 format version " + std::to_string(version) + " is not supported");
+        if (N == 0 || pri >= N || sigma > 256 || sa_intv < 1 || sa_intv > KISS_HIP_FMI_MAX_SA_INTV) throw std::runtime_error("bad .fmi8 header");
+        alloc(N - 1);
+        get(in, C, "C");
+        get(in, map, "map");
+        get(in, bwt, "bwt");
+        get(in, occ1, "occ1");
+        get(in, occ2, "occ2");
+        get(in, sa, "sa");
+        get(in, b, "b");
+        get(in, b_occ, "b_occ");
+        if (in.peek() != EOF) throw std::runtime_error("trailing bytes in .fmi8");
+    }
+    kiss_hip_fmi8_view view() const
+    {
+        kiss_hip_fmi8_view v{};
+        v.n_sa = z.n_sa;
+        v.pri = pri;
+        v.sa_intv = sa_intv;
+        v.sigma = sigma;
+        v.C = C.data();
+        v.map = map.data();
+        v.bwt = bwt.data();
+        v.occ1 = occ1.data();
+        v.occ2 = occ2.data();
+        v.sa = sa.data();
+        v.b = sa_intv == 1 ? nullptr : b.data();
+        v.b_occ = sa_intv == 1 ? nullptr : b_occ.data();
+        return v;
+    }
+};
+
+int generic_fmindex_build_main(const Args &a)
+{
+    const std::vector<uint8_t> S = read_bytes(a.fasta);
+    if (given(a, "--kordered")) std::fprintf(stderr, "[info] --generic: -k is ignored, the index is built from the exact suffix array\n");
+    Fmi8 f;
+    f.sa_intv = a.sa_intv;
+    // the census first: the arrays are sized by the number of distinct byte values
+    check(kiss_hip_fmi8_build_host(S.data(), S.size(), nullptr, f.sa_intv, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                   nullptr, nullptr, &f.sigma, &f.pri, a.device),
+          "kiss_hip_fmi8_build_host");
+    f.alloc(S.size());
+    check(kiss_hip_fmi8_build_host(S.data(), S.size(), nullptr, f.sa_intv, f.sigma, f.C.data(), f.map.data(), f.bwt.data(),
+                                   f.occ1.data(), f.occ2.data(), f.sa.data(), f.b.data(), f.b_occ.data(), &f.sigma, &f.pri, a.device),
+          "kiss_hip_fmi8_build_host");
+    f.save(a.fasta + ".fmi8");
+    return 0;
+}
+
+int generic_fmindex_query_main(const Args &a)
+{
+    const std::vector<uint8_t> S = read_bytes(a.fasta);
+    Fmi8 f;
+    f.load(a.fasta + ".fmi8");
+    const kiss_hip_fmi8_view v = f.view();
+    // counts first (they size the output), then the positions of every pattern in ascending order
+    auto run = [&](const uint8_t *pat, const std::vector<uint64_t> &pidx, std::vector<uint32_t> &pos, std::vector<uint64_t> &idx,
+                   uint64_t &hits, uint64_t &chk) {
+        const uint64_t Q = pidx.size() - 1;
+        std::vector<uint32_t> beg(Q + 1), end(Q + 1);
+        check(kiss_hip_fmi8_query_host(&v, pat, pidx.data(), Q, beg.data(), end.data(), &hits, &chk, nullptr, nullptr, 0, nullptr,
+                                       a.device),
+              "kiss_hip_fmi8_query_host");
+        pos.assign(hits + 1, 0);
+        idx.assign(Q + 1, 0);
+        check(kiss_hip_fmi8_query_host(&v, pat, pidx.data(), Q, beg.data(), end.data(), &hits, &chk, pos.data(), idx.data(), hits,
+                                       nullptr, a.device),
+              "kiss_hip_fmi8_query_host");
+    };
+    if (!a.query.empty()) {
+        const uint8_t *q = reinterpret_cast<const uint8_t *>(a.query.data());
+        std::vector<uint32_t> pos;
+        std::vector<uint64_t> idx;
+        uint64_t hits = 0, chk = 0;
+        run(q, {0, a.query.size()}, pos, idx, hits, chk);
+        std::fprintf(stderr, "[info] query = %s found %llu times\n", escaped(q, a.query.size()).c_str(), (unsigned long long)hits);
+        for (size_t i = 0; i < std::min<size_t>(a.headn, hits); i++) {
+            const size_t len = std::min<size_t>(a.query.size(), S.size() - std::min<size_t>(S.size(), pos[i]));
+            std::fprintf(stderr, "[info] The %zu-%s position is %u, content of substring is %s\n", i + 1, ending(i + 1), pos[i],
+                         escaped(S.data() + pos[i], len).c_str());
+        }
+    }
+    if (!a.batch.empty()) {
+        std::ifstream p(a.batch, std::ios::binary);
+        if (!p) throw std::runtime_error("cannot open " + a.batch);
+        uint32_t L = 0, Q = 0;
+        p.read(reinterpret_cast<char *>(&L), 4);
+        p.read(reinterpret_cast<char *>(&Q), 4);
+        std::fprintf(stderr, "[info] query_len: %u, num_query: %u\n", L, Q);
+        if (!p || (L == 0 && Q != 0)) throw std::runtime_error("bad pattern file");
+        std::vector<uint8_t> pat((size_t)L * Q);
+        p.read(reinterpret_cast<char *>(pat.data()), (std::streamsize)pat.size());
+        if (!p) throw std::runtime_error("truncated pattern file");
+        std::vector<uint64_t> pidx((size_t)Q + 1);
+        for (uint64_t q = 0; q <= Q; q++) pidx[q] = q * L;
+        std::vector<uint32_t> pos;
+        std::vector<uint64_t> idx;
+        uint64_t hits = 0, chk = 0;
+        const auto t0 = std::chrono::steady_clock::now();
+        run(pat.data(), pidx, pos, idx, hits, chk);
+        std::fprintf(stderr, "[info] searching time: %.6f seconds\n", seconds_since(t0));
+        std::fprintf(stderr, "[info] number of matched locations: %llu\n", (unsigned long long)hits);
+        std::fprintf(stderr, "[info] location checksum: %llu\n", (unsigned long long)chk);
+    }
+    return 0;
+}
+
 } // namespace
 
 int main(int argc, char **argv)
 {
     try {
         Args a = parse(argc, argv);
-        // TODO of the reference kept as is: generic alphabets are rejected (suffix_sort.hpp:26-28)
-        if (a.generic) throw std::invalid_argument("Generic sorting and indexing are currently not supported.");
+        if (a.generic) { // the reference's TODO (suffix_sort.hpp:26-28): texts over the byte alphabet
+            check_generic_options(a);
+            if (a.command == "suffix_sort") return generic_suffix_sort_main(a);
+            if (a.command == "fmindex_build") return generic_fmindex_build_main(a);
+            if (a.command == "fmindex_query") return generic_fmindex_query_main(a);
+            usage();
+            throw std::runtime_error("invalid command '" + a.command + "'");
+        }
         if (a.command == "suffix_sort") return suffix_sort_main(a);
         if (a.command == "fmindex_build") return fmindex_build_main(a);
         if (a.command == "fmindex_query") return fmindex_query_main(a);

@@ -51,6 +51,7 @@ struct KissOpts {
     uint64_t collapse_n = 0;       // KISS_HIP_COLLAPSE_N (0 = default)
     uint32_t fm_heavy = 0, fm_light = 0; // KISS_HIP_FM_HEAVY / KISS_HIP_FM_LIGHT (0 = default)
     bool fm_mm_wave = false;       // KISS_HIP_FM_MM_WAVE: the mismatch search with one wave per pattern whatever the batch size (fm_mm.hip)
+    bool fm8_group = false;        // KISS_HIP_FM8_GROUP: the byte index's search with 16 lanes per pattern instead of one (fm8.hip)
     uint64_t fm_mm_budget = 0;     // KISS_HIP_FM_MM_BUDGET: lanes first whatever the batch size; pairs a lane evaluates before a wave takes its pattern over (0 = default)
     uint64_t isa_direct_max = 0;   // KISS_HIP_ISA_DIRECT_MAX (0 = default)
     unsigned lx_sync_points = 0;   // KISS_HIP_LX_SYNC_POINTS
@@ -192,11 +193,11 @@ struct kiss_hip_ctx {
     // PREFIX_DOUBLING: (position, index) pairs of the binned inverse-suffix-array build (isa.hip), allocated on first use
     uint64_t *pairs1 = nullptr, *pairs2 = nullptr;
     uint64_t pairs_cap = 0;
-    // scratch of kiss_hip_fmi_query_batch_dev (slots 0..12, fm.hip) and of kiss_hip_fmi_query_mm_dev (slots 13..,
-    // fm_mm.hip), kept between calls
-    void *fm_pool[20] = {};
-    uint64_t fm_pool_cap[20] = {};
-    hipEvent_t fm_mm_ev[6] = {}; // fm_mm.hip: the times of kiss_hip_fmi_mm_report (created by the first call that wants one)
+    // scratch of kiss_hip_fmi_query_batch_dev (slots 0..12, fm.hip), of kiss_hip_fmi_query_mm_dev (slots 13..19,
+    // fm_mm.hip) and of kiss_hip_fmi8_query_dev (slots 20.., fm8.hip), kept between calls
+    void *fm_pool[24] = {};
+    uint64_t fm_pool_cap[24] = {};
+    hipEvent_t fm_mm_ev[6] = {}; // fm_mm.hip / fm8.hip: the times of their reports (created by the first call that wants one)
     // near-end
     uint32_t *near_idx = nullptr, *near_fin = nullptr, *near_pos = nullptr, *near_tmp = nullptr, *near_tmp2 = nullptr; // place.hip: near_reserve
     uint64_t near_cap = 0;
