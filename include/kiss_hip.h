@@ -622,6 +622,60 @@ int kiss_hip_fmi8_query_host(const kiss_hip_fmi8_view *fmi, const uint8_t *patte
                              uint32_t *beg, uint32_t *end, uint64_t *hit_count_total, uint64_t *checksum, uint32_t *positions,
                              uint64_t *index, uint64_t capacity, kiss_hip_fmi8_report *report, int device);
 
+/* ---- FM-index: maximal exact match seeds of a batch of reads (no reference counterpart) -------------------------------
+ * Every other query of this header takes whole patterns.  This one takes reads that need not occur in the text anywhere in
+ * full and reports which stretches of them do, and where: what a read mapper chains and extends.
+ * Text S: n bases as indexed.  A read R has L >= 1 bytes; the values 0..3 are bases, ANY OTHER VALUE IS "NO BASE": no match
+ * contains it (this is how N is carried -- on purpose NOT the `& 3` of the pattern calls above).  The complement of a
+ * no-base is itself.  The batch is ragged, as with kiss_hip_fmi8_query_dev: read q = reads[read_index[q], read_index[q + 1]).
+ * Virtual reads: without both_strands V = Q and virtual read v is read v; with it V = 2 Q, virtual read 2 q is read q and
+ * 2 q + 1 its reverse complement R'[j] = 3 - R[L - 1 - j].  All coordinates of a virtual read are in that virtual read.
+ * Matching statistics: for an end e in 1..L, ms[e] is the largest l <= min(e, max_len or e) such that R[e - l, e) occurs in
+ * S (0 if R[e - 1] does not occur); start[e] = e - ms[e], non-decreasing in e.
+ * Seeds: e ends a seed iff ms[e] >= min_len and (e == L or start[e + 1] > start[e]); the seed is (start[e], ms[e]).  These
+ * are the substrings of R of at most max_len bases that occur in S and are contained in no other such substring, of length
+ * >= min_len; with max_len == 0 (no cap) the super-maximal exact matches.  The seeds of a virtual read come out in ascending
+ * e, which is strictly ascending start.
+ *   min_len >= 1; max_len: 0 = no cap; max_occ: 0 = no limit.
+ *   ms         : optional, `bases` u32 (bases = sum of the virtual read lengths): ms of end e of virtual read v at
+ *                vbase[v] + e - 1, vbase = the exclusive prefix sum of the virtual read lengths.
+ *   seeds / seed_index : seed_index has V + 1 u64; the seeds of virtual read v are seeds[seed_index[v] .. seed_index[v + 1]).
+ *                sa_beg / sa_end: the backward-search range of the seed string, count = sa_end - sa_beg.
+ *   seed_capacity : entries available in seeds; `bases` always suffices.
+ *   positions / pos_index : optional (both or none; none: pos_capacity = 0).  pos_index has seeds + 1 u64; the occurrences of
+ *                seed s -- every p with S[p, p + len) == the seed -- are positions[pos_index[s] .. pos_index[s + 1]) in
+ *                ASCENDING order.  Only seeds with count <= max_occ are located (all when max_occ == 0); a seed over the
+ *                limit has an empty segment and still reports its range.
+ * A capacity smaller than the total: KISS_HIP_E_INVALID with the totals in the report (seeds, positions; call again with
+ * room).  Other KISS_HIP_E_INVALID: a required pointer NULL, min_len == 0, a zero-length read or a read_index that
+ * decreases.  Q == 0: KISS_HIP_OK, seed_index[0] = 0.
+ * Domain (that of kiss_hip_fmi_query_mm_dev).  RANGES and ms are defined when max_len is at most the order of the suffix
+ * array the index was built from: max_len in 1..32 on the default build, any max_len including 0 on an index built from the
+ * exact suffix array.  POSITIONS are defined only on an index built from the EXACT suffix array; the locate walk is bounded
+ * as there, walk_failures > 0 gives KISS_HIP_E_INVALID, and walk_failures == 0 proves nothing.
+ * Limits (KISS_HIP_E_UNSUPPORTED): sa_intv outside 1..32; a read of 2^31 bytes or more; more ends in one call than the ctx
+ * scans -- bases must be below 2^31 and below about 0.32 x the ctx's max_n; more located positions than the ctx's LMS work
+ * arrays hold (about 0.32 x max_n entries; their contents are lost), with the totals in the report -- split the batch.
+ * A kiss_hip_fmi_view_ex is taken so that any SA_INTV works; lookup may be NULL (the search does not use it: the ends have
+ * no common length).  Device times: report->ms_* (report may be NULL); the kernels also count under KISS_HIP_K_FM_QUERY. */
+typedef struct kiss_hip_fmi_seed { uint32_t start, len, sa_beg, sa_end; } kiss_hip_fmi_seed;
+typedef struct kiss_hip_fmi_seed_report {
+    uint64_t Q, V, bases;      /* bases = ends searched (sum of virtual read lengths) */
+    uint64_t seeds, located_seeds, positions, lf_pairs, walk_failures, checksum;
+    uint32_t max_ms, reserved_;
+    float ms_total, ms_search, ms_compact, ms_locate, ms_sort;
+} kiss_hip_fmi_seed_report;
+/* every pointer except fmi and report is a device pointer (the arrays of the view too) */
+int kiss_hip_fmi_seeds_dev(kiss_hip_ctx *ctx, const kiss_hip_fmi_view_ex *fmi, const uint8_t *reads, const uint64_t *read_index,
+                           uint64_t Q, uint32_t min_len, uint32_t max_len, uint32_t max_occ, int both_strands, uint32_t *ms,
+                           kiss_hip_fmi_seed *seeds, uint64_t *seed_index, uint64_t seed_capacity, uint32_t *positions,
+                           uint64_t *pos_index, uint64_t pos_capacity, kiss_hip_fmi_seed_report *report, void *stream);
+/* the same with host pointers, as kiss_hip_fmi_query_mm_host (creates a ctx on `device`, uploads, runs, downloads) */
+int kiss_hip_fmi_seeds_host(const kiss_hip_fmi_view_ex *fmi, const uint8_t *reads, const uint64_t *read_index, uint64_t Q,
+                            uint32_t min_len, uint32_t max_len, uint32_t max_occ, int both_strands, uint32_t *ms,
+                            kiss_hip_fmi_seed *seeds, uint64_t *seed_index, uint64_t seed_capacity, uint32_t *positions,
+                            uint64_t *pos_index, uint64_t pos_capacity, kiss_hip_fmi_seed_report *report, int device);
+
 #ifdef __cplusplus
 }
 #endif

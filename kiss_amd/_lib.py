@@ -130,6 +130,25 @@ class FmiMmReport(ctypes.Structure):
         return d
 
 
+class FmiSeed(ctypes.Structure):
+    """kiss_hip_fmi_seed"""
+    _fields_ = [("start", ctypes.c_uint32), ("len", ctypes.c_uint32), ("sa_beg", ctypes.c_uint32), ("sa_end", ctypes.c_uint32)]
+
+
+class FmiSeedReport(ctypes.Structure):
+    """kiss_hip_fmi_seed_report"""
+    _fields_ = [
+        ("Q", ctypes.c_uint64), ("V", ctypes.c_uint64), ("bases", ctypes.c_uint64), ("seeds", ctypes.c_uint64),
+        ("located_seeds", ctypes.c_uint64), ("positions", ctypes.c_uint64), ("lf_pairs", ctypes.c_uint64),
+        ("walk_failures", ctypes.c_uint64), ("checksum", ctypes.c_uint64), ("max_ms", ctypes.c_uint32),
+        ("reserved_", ctypes.c_uint32), ("ms_total", ctypes.c_float), ("ms_search", ctypes.c_float),
+        ("ms_compact", ctypes.c_float), ("ms_locate", ctypes.c_float), ("ms_sort", ctypes.c_float),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved_"}
+
+
 class Fmi8View(ctypes.Structure):
     """kiss_hip_fmi8_view"""
     _fields_ = [
@@ -269,6 +288,11 @@ def load(hooks=None):
     lib.kiss_hip_fmi_query_mm_host.argtypes = [ctypes.POINTER(FmiView), vp, u32, u64, u32, vp, vp, vp, vp, u64,
                                                ctypes.POINTER(FmiMmReport), ctypes.c_int]
     lib.kiss_hip_fmi_query_mm_dev.restype = lib.kiss_hip_fmi_query_mm_host.restype = ctypes.c_int
+    lib.kiss_hip_fmi_seeds_dev.argtypes = [vp, ctypes.POINTER(FmiViewEx), vp, vp, u64, u32, u32, u32, ctypes.c_int, vp, vp, vp, u64,
+                                           vp, vp, u64, ctypes.POINTER(FmiSeedReport), vp]
+    lib.kiss_hip_fmi_seeds_host.argtypes = [ctypes.POINTER(FmiViewEx), vp, vp, u64, u32, u32, u32, ctypes.c_int, vp, vp, vp, u64,
+                                            vp, vp, u64, ctypes.POINTER(FmiSeedReport), ctypes.c_int]
+    lib.kiss_hip_fmi_seeds_dev.restype = lib.kiss_hip_fmi_seeds_host.restype = ctypes.c_int
     lib.kiss_hip_fmi8_sizes_for.argtypes = [u64, u32, u32, ctypes.POINTER(Fmi8Sizes)]
     lib.kiss_hip_fmi8_build_dev.argtypes = [vp, vp, u64, vp, u32, u32] + [vp] * 8 + [ctypes.POINTER(u32), ctypes.POINTER(u32), vp]
     lib.kiss_hip_fmi8_build_host.argtypes = [vp, u64, vp, u32, u32] + [vp] * 8 + [ctypes.POINTER(u32), ctypes.POINTER(u32),
@@ -343,5 +367,5 @@ EXPORTED_SYMBOLS = [
     "kiss_hip_fmi_query_ex_host", "kiss_hip_ctx_lcp_dna_u32_dev", "kiss_hip_ctx_lcp_u8_dev", "kiss_hip_lcp_dna_u32",
     "kiss_hip_lcp_u8", "kiss_hip_fmi_query_mm_dev", "kiss_hip_fmi_query_mm_host",
     "kiss_hip_fmi8_sizes_for", "kiss_hip_fmi8_build_dev", "kiss_hip_fmi8_build_host", "kiss_hip_fmi8_query_dev",
-    "kiss_hip_fmi8_query_host",
+    "kiss_hip_fmi8_query_host", "kiss_hip_fmi_seeds_dev", "kiss_hip_fmi_seeds_host",
 ]

@@ -1,6 +1,7 @@
 // fm_internal.hpp -- what the FM-index translation units share (fm.hip: exact queries + construction; fm_mm.hip: the
-// search with mismatches): the device view of an index, the one-sector rank blocks and the LF arithmetic on them, the
-// rank of the sampling bit-vector, and the pooled scratch buffers of a batch.
+// search with mismatches; fm_seed.hip: maximal exact match seeds): the device view of an index, the one-sector rank blocks
+// and the LF arithmetic on them, the rank of the sampling bit-vector, the bounded locate walk of one row, the pooled
+// scratch buffers of a batch and the events behind a report's times.
 #pragma once
 #include "kiss_internal.hpp"
 
@@ -87,6 +88,45 @@ __device__ __forceinline__ uint32_t fm_b_rank(const uint64_t *__restrict__ b, co
 }
 __device__ __forceinline__ uint32_t fm_b_occ(const FmiD &f, uint64_t i) { return fm_b_rank(f.b, f.b_occ, i); }
 
+// The locate walk of one SA row: LF to a sampled row -- at most sa_intv - 1 steps and never from the primary row (its BWT
+// symbol is a placeholder), so the walk is bounded whatever arrays it is handed.  false: no sampled row inside the bound (an
+// index that was not built from an exact suffix array); position is then 0xFFFFFFFF.
+__device__ __forceinline__ bool fm_locate_row(const FmiD &f, uint32_t sa_intv, uint64_t sa_entries, uint64_t row,
+                                              uint32_t &position)
+{
+    position = 0xFFFFFFFFu;
+    for (uint32_t step = 0; step < sa_intv && row < f.N; step++) {
+        const bool sampled = !f.b || ((f.b[row >> 6] >> (row & 63u)) & 1ull);
+        if (sampled) {
+            const uint64_t r = fm_b_occ(f, row);
+            if (r >= sa_entries) return false;
+            position = f.sa[r] + step;
+            return true;
+        }
+        if (row == f.pri || step + 1 == sa_intv) break;
+        row = fm_lf(f, fm_bwt(f, row), row);
+    }
+    return false;
+}
+
+// the device view of the arrays of a kiss_hip_fmi_view (blk is filled in by the caller: kiss_fm_make_blocks)
+static inline FmiD fm_view_of(const kiss_hip_fmi_view *fmi)
+{
+    FmiD f;
+    f.N = fmi->n_sa;
+    for (int c = 0; c < 4; c++) f.cnt[c] = fmi->cnt[c];
+    f.pri = fmi->pri;
+    f.bwt_bytes = (fmi->n_sa + 3) / 4;
+    f.bwt = fmi->bwt;
+    f.occ1 = fmi->occ1;
+    f.occ2 = fmi->occ2;
+    f.sa = fmi->sa;
+    f.b = fmi->sa_intv == 1 ? nullptr : fmi->b;
+    f.b_occ = fmi->b_occ;
+    f.blk = nullptr;
+    return f;
+}
+
 struct DevBuf {
     void *p = nullptr;
     bool pooled = false;
@@ -124,6 +164,32 @@ struct DevBuf {
         }
         p = ctx->fm_pool[slot];
         return KISS_HIP_OK;
+    }
+};
+
+// the times of a report: six events kept in the ctx (one call at a time per ctx), recorded only for a caller that wants a
+// report
+struct FmEvents {
+    kiss_hip_ctx *ctx;
+    bool ok;
+    int last = -1; // the last event recorded
+    FmEvents(kiss_hip_ctx *c, bool wanted) : ctx(c), ok(wanted)
+    {
+        for (auto &x : ctx->fm_mm_ev)
+            if (ok && !x && hipEventCreate(&x) != hipSuccess) {
+                x = nullptr;
+                ok = false;
+            }
+    }
+    void mark(int i)
+    {
+        if (ok && hipEventRecord(ctx->fm_mm_ev[i], ctx->stream) == hipSuccess) last = i;
+    }
+    float ms(int a, int b)
+    {
+        float v = 0.f;
+        if (!ok || hipEventElapsedTime(&v, ctx->fm_mm_ev[a], ctx->fm_mm_ev[b]) != hipSuccess) return 0.f;
+        return v;
     }
 };
 

@@ -356,9 +356,9 @@ __global__ __launch_bounds__(MM_LOC_THREADS) void k_fm_mm_leaf_sizes(const uint4
     sizes[i] = s; // [nleaves] = 0: the scan turns it into the total
 }
 
-// one lane per hit row: its leaf by binary search in the scanned sizes, then LF to a sampled row -- at most sa_intv - 1
-// steps and never from the primary row (its BWT symbol is a placeholder).  A row that finds no sampled row inside the bound
-// (an index that was not built from an exact suffix array) is counted and gets position 0xFFFFFFFF.
+// one lane per hit row: its leaf by binary search in the scanned sizes, then the bounded walk to a sampled row
+// (fm_locate_row).  A row that finds no sampled row inside the bound (an index that was not built from an exact suffix
+// array) is counted and gets position 0xFFFFFFFF.
 __global__ __launch_bounds__(MM_LOC_THREADS) void k_fm_mm_locate(FmiD f, uint32_t sa_intv, uint64_t sa_entries,
                                                                 const uint4 *__restrict__ leaves, uint64_t nleaves,
                                                                 const uint64_t *__restrict__ leaf_index, uint64_t total,
@@ -377,22 +377,9 @@ __global__ __launch_bounds__(MM_LOC_THREADS) void k_fm_mm_locate(FmiD f, uint32_
             else hi = mid;
         }
         const uint4 lv = leaves[lo];
-        uint64_t row = (uint64_t)lv.y + (h - leaf_index[lo]);
-        uint32_t position = 0xFFFFFFFFu;
-        fail = true;
-        for (uint32_t step = 0; step < sa_intv && row < f.N; step++) {
-            const bool sampled = !f.b || ((f.b[row >> 6] >> (row & 63u)) & 1ull);
-            if (sampled) {
-                const uint64_t r = fm_b_occ(f, row);
-                if (r < sa_entries) {
-                    position = f.sa[r] + step;
-                    fail = false;
-                }
-                break;
-            }
-            if (row == f.pri || step + 1 == sa_intv) break;
-            row = fm_lf(f, fm_bwt(f, row), row);
-        }
+        const uint64_t row = (uint64_t)lv.y + (h - leaf_index[lo]);
+        uint32_t position;
+        fail = !fm_locate_row(f, sa_intv, sa_entries, row, position);
         keys[h] = (((uint64_t)lv.x << 32) | position) << key_shift;
         vals[h] = lv.w & 0xFFu;
         if (!fail) sum = position;
@@ -453,30 +440,7 @@ void mm_launch_search(kiss_hip_ctx *ctx, uint32_t e, const FmiD &f, const uint8_
 #undef MM_GO
 }
 
-// the report's times: six events kept in the ctx, recorded only for a caller that wants a report
-struct MmEvents {
-    kiss_hip_ctx *ctx;
-    bool ok;
-    int last = -1; // the last event recorded
-    MmEvents(kiss_hip_ctx *c, bool wanted) : ctx(c), ok(wanted)
-    {
-        for (auto &x : ctx->fm_mm_ev)
-            if (ok && !x && hipEventCreate(&x) != hipSuccess) {
-                x = nullptr;
-                ok = false;
-            }
-    }
-    void mark(int i)
-    {
-        if (ok && hipEventRecord(ctx->fm_mm_ev[i], ctx->stream) == hipSuccess) last = i;
-    }
-    float ms(int a, int b)
-    {
-        float v = 0.f;
-        if (!ok || hipEventElapsedTime(&v, ctx->fm_mm_ev[a], ctx->fm_mm_ev[b]) != hipSuccess) return 0.f;
-        return v;
-    }
-};
+using MmEvents = FmEvents; // (fm_internal.hpp)
 
 int mm_query_steps(kiss_hip_ctx *ctx, const kiss_hip_fmi_view *fmi, const uint8_t *patterns, uint32_t L, uint64_t Q,
                    uint32_t e, uint32_t *counts, uint32_t *positions, uint8_t *mismatches, uint64_t *index,
@@ -486,17 +450,7 @@ int mm_query_steps(kiss_hip_ctx *ctx, const kiss_hip_fmi_view *fmi, const uint8_
     if (Q > 0x7FFFFFFFull || Q / 4096 + 16 > ctx->scan_tmp_cap) return KISS_HIP_E_UNSUPPORTED; // more than the ctx can scan
     kiss_opts_refresh(ctx);
     const uint32_t sa_intv = fmi->sa_intv;
-    FmiD f;
-    f.N = fmi->n_sa;
-    for (int c = 0; c < 4; c++) f.cnt[c] = fmi->cnt[c];
-    f.pri = fmi->pri;
-    f.bwt_bytes = (fmi->n_sa + 3) / 4;
-    f.bwt = fmi->bwt;
-    f.occ1 = fmi->occ1;
-    f.occ2 = fmi->occ2;
-    f.sa = fmi->sa;
-    f.b = sa_intv == 1 ? nullptr : fmi->b;
-    f.b_occ = fmi->b_occ;
+    FmiD f = fm_view_of(fmi);
     const uint64_t sa_entries = (f.N + sa_intv - 1) / sa_intv;
 
     DevBuf blocks, ctl, leaves, qtot, lsize, lidx, heavy, hflag;

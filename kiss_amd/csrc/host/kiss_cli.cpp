@@ -10,6 +10,10 @@
 //   (opt-in: fmindex_query --mismatches E, E in 0..3: every position within Hamming distance E of the query, ascending,
 //    each with its mismatch count (kiss_hip_fmi_query_mm_host); the positions need an index of the EXACT suffix array:
 //    fmindex_build --exact, same .fmi layout)
+//   (opt-in: fmindex_query --seeds READS [--min-seed-len N] [--max-seed-len M] [--max-occ N] [--both-strands]: the maximal
+//    exact match seeds of every read of READS (one read per line, ACGTacgt, any other letter is no base; lines starting
+//    with '>' and empty lines are skipped), one line per seed on stdout: read strand start len count pos...; also needs
+//    fmindex_build --exact)
 //   (-g / --generic: the file is a text over the byte alphabet, taken byte for byte -- no FASTA rule, no newline stripping,
 //    no % 4.  suffix_sort gives the exact suffix array (kiss_hip_suffix_sort_u8; -k and -s are ignored) and, with
 //    --output-lcp, its LCP array; fmindex_build writes <file>.fmi8 (kiss_hip_fmi8_build_host);
@@ -70,7 +74,15 @@ void usage()
               << "  -b [ --batch ] patterns.bin    batch query mode (u32 len, u32 count, then count x len bytes)\n"
               << "  --sa-intv NUM (=4)             the SA sampling interval the index was built with\n"
               << "  --mismatches NUM               also report the locations with up to NUM (0..3) substitutions; the\n"
-              << "                                 positions need an index built with fmindex_build --exact\n";
+              << "                                 positions need an index built with fmindex_build --exact\n"
+              << "  --seeds READS                  the maximal exact match seeds of the reads of READS (one per line, ACGT,\n"
+              << "                                 any other letter is no base; '>' lines are skipped) on stdout, one line\n"
+              << "                                 per seed: read strand(+/-) start len count pos...; the positions need an\n"
+              << "                                 index built with fmindex_build --exact; not with -g, -q, -b, --mismatches\n"
+              << "  --min-seed-len NUM (=19)       shortest seed reported\n"
+              << "  --max-seed-len NUM (=0)        longest match followed (0: no cap)\n"
+              << "  --max-occ NUM (=500)           seeds with more occurrences get no positions (0: no limit)\n"
+              << "  --both-strands                 also the reverse complement of every read (strand -)\n";
 }
 
 inline uint8_t to_code(unsigned char c)
@@ -145,6 +157,9 @@ struct Args {
     bool verbose = false, generic = false, exact = false;
     std::vector<std::string> seen; // the long names of the options given (what -g refuses is named)
     int mismatches = -1; // fmindex_query --mismatches (-1: the exact query of the reference)
+    std::string seeds;   // fmindex_query --seeds READS
+    uint32_t min_seed_len = 19, max_seed_len = 0, max_occ = 500;
+    bool both_strands = false;
 };
 
 Args parse(int argc, char **argv)
@@ -157,7 +172,8 @@ Args parse(int argc, char **argv)
             if (i + 1 >= argc) throw std::runtime_error(std::string("the required argument for option '") + name + "' is missing");
             return argv[++i];
         };
-        if (s == "--gpus" || s == "--devices" || s == "--lookup-len" || s == "--exact" || s == "--mismatches" || s == "--sa-intv")
+        if (s == "--gpus" || s == "--devices" || s == "--lookup-len" || s == "--exact" || s == "--mismatches" || s == "--sa-intv" ||
+            s == "--seeds" || s == "--min-seed-len" || s == "--max-seed-len" || s == "--max-occ" || s == "--both-strands")
             a.seen.push_back(s);
         if (s == "-k" || s == "--kordered") a.seen.push_back("--kordered");
         if (s == "-s" || s == "--sorting-algorithm") a.seen.push_back("--sorting-algorithm");
@@ -179,6 +195,11 @@ Args parse(int argc, char **argv)
         else if (s == "--gpus") a.gpus = std::stoi(next("--gpus"));
         else if (s == "--exact") a.exact = true;
         else if (s == "--mismatches") a.mismatches = std::stoi(next("--mismatches"));
+        else if (s == "--seeds") a.seeds = next("--seeds");
+        else if (s == "--min-seed-len") a.min_seed_len = (uint32_t)std::stoul(next("--min-seed-len"));
+        else if (s == "--max-seed-len") a.max_seed_len = (uint32_t)std::stoul(next("--max-seed-len"));
+        else if (s == "--max-occ") a.max_occ = (uint32_t)std::stoul(next("--max-occ"));
+        else if (s == "--both-strands") a.both_strands = true;
         else if (s == "--devices") {
             const std::string list = next("--devices");
             size_t at = 0;
@@ -199,11 +220,23 @@ Args parse(int argc, char **argv)
     if (a.sa_intv < 1 || a.sa_intv > KISS_HIP_FMI_MAX_SA_INTV) throw std::runtime_error("--sa-intv must be in 1..32");
     if (a.lookup_len > KISS_HIP_FMI_MAX_LOOKUP_LEN) throw std::runtime_error("--lookup-len must be in 0..14");
     if (a.mismatches < -1 || a.mismatches > (int)KISS_HIP_FMI_MAX_MISMATCHES) throw std::runtime_error("--mismatches must be in 0..3");
+    {
+        const auto given_here = [&](const char *o) { return std::find(a.seen.begin(), a.seen.end(), o) != a.seen.end(); };
+        for (const char *o : {"--min-seed-len", "--max-seed-len", "--max-occ", "--both-strands"})
+            if (given_here(o) && !given_here("--seeds")) throw std::runtime_error(std::string(o) + " goes with --seeds");
+        if (given_here("--seeds")) {
+            if (a.generic) throw std::runtime_error("--seeds is not supported for byte texts (--generic)");
+            if (!a.query.empty() || !a.batch.empty() || a.mismatches >= 0)
+                throw std::runtime_error("--seeds cannot be combined with -q, -b or --mismatches");
+            if (a.min_seed_len < 1) throw std::runtime_error("--min-seed-len must be at least 1");
+        }
+    }
     if (a.devices.empty())
         for (int g = 0; g < a.gpus; g++) a.devices.push_back(a.device + g);
     else
         a.device = a.devices[0]; // the text is loaded, and the induction runs, on the first device of the list
     a.command = pos[0];
+    if (!a.seeds.empty() && a.command != "fmindex_query") throw std::runtime_error("--seeds is an option of fmindex_query");
     if (pos.size() < 2) throw std::runtime_error("the option '--fasta' is required but missing");
     a.fasta = pos[1];
     std::transform(a.algo.begin(), a.algo.end(), a.algo.begin(), [](unsigned char c) { return (char)std::toupper(c); });
@@ -573,8 +606,80 @@ MmHits mm_query(const Fmi &f, const uint8_t *pat, uint32_t L, uint64_t Q, uint32
     return h;
 }
 
+// fmindex_query --seeds: one line per seed on stdout, `read strand start len count pos...`
+int seeds_main(const Args &a, const Fmi &f)
+{
+    std::ifstream in(a.seeds);
+    if (!in) throw std::runtime_error("cannot open " + a.seeds);
+    std::vector<uint8_t> reads;
+    std::vector<uint64_t> ridx{0};
+    std::string line;
+    while (std::getline(in, line)) {
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.empty() || line[0] == '>') continue;
+        for (unsigned char c : line) {
+            uint8_t code = 4; // no base
+            switch (c) {
+            case 'A': case 'a': code = 0; break;
+            case 'C': case 'c': code = 1; break;
+            case 'G': case 'g': code = 2; break;
+            case 'T': case 't': code = 3; break;
+            default: break;
+            }
+            reads.push_back(code);
+        }
+        ridx.push_back(reads.size());
+    }
+    const uint64_t Q = ridx.size() - 1, bases = (a.both_strands ? 2 : 1) * (uint64_t)reads.size();
+    const uint64_t V = a.both_strands ? 2 * Q : Q;
+    const kiss_hip_fmi_view_ex v = f.view_ex();
+    std::vector<kiss_hip_fmi_seed> seeds(bases + 1);
+    std::vector<uint64_t> sidx(V + 1, 0), pidx;
+    std::vector<uint32_t> pos;
+    kiss_hip_fmi_seed_report rep{};
+    // the first call sizes the output
+    check(kiss_hip_fmi_seeds_host(&v, reads.data(), ridx.data(), Q, a.min_seed_len, a.max_seed_len, a.max_occ, a.both_strands,
+                                  nullptr, seeds.data(), sidx.data(), bases, nullptr, nullptr, 0, &rep, a.device),
+          "kiss_hip_fmi_seeds_host");
+    pos.resize(rep.positions + 1);
+    pidx.resize(rep.seeds + 1);
+    const int rc = kiss_hip_fmi_seeds_host(&v, reads.data(), ridx.data(), Q, a.min_seed_len, a.max_seed_len, a.max_occ,
+                                           a.both_strands, nullptr, seeds.data(), sidx.data(), bases, pos.data(), pidx.data(),
+                                           rep.positions, &rep, a.device);
+    if (rc == KISS_HIP_E_INVALID && rep.walk_failures)
+        throw std::runtime_error("fmindex_query --seeds: " + std::to_string(rep.walk_failures) +
+                                 " rows of the index reached no sampled row: the positions need an index built with "
+                                 "fmindex_build --exact");
+    check(rc, "kiss_hip_fmi_seeds_host");
+    std::string out;
+    for (uint64_t vr = 0; vr < V; vr++) {
+        const uint64_t q = a.both_strands ? vr / 2 : vr;
+        const char strand = a.both_strands && (vr & 1) ? '-' : '+';
+        for (uint64_t s = sidx[vr]; s < sidx[vr + 1]; s++) {
+            out += std::to_string(q) + ' ' + strand + ' ' + std::to_string(seeds[s].start) + ' ' + std::to_string(seeds[s].len) + ' ' +
+                   std::to_string(seeds[s].sa_end - seeds[s].sa_beg);
+            for (uint64_t i = pidx[s]; i < pidx[s + 1]; i++) out += ' ' + std::to_string(pos[i]);
+            out += '\n';
+        }
+        if (out.size() > (1u << 20)) {
+            std::fwrite(out.data(), 1, out.size(), stdout);
+            out.clear();
+        }
+    }
+    std::fwrite(out.data(), 1, out.size(), stdout);
+    std::fflush(stdout);
+    std::fprintf(stderr, "[info] reads: %llu, seeds: %llu, located seeds: %llu, positions: %llu\n", (unsigned long long)Q,
+                 (unsigned long long)rep.seeds, (unsigned long long)rep.located_seeds, (unsigned long long)rep.positions);
+    return 0;
+}
+
 int fmindex_query_main(const Args &a)
 {
+    if (!a.seeds.empty()) { // (the text itself is not needed)
+        Fmi f(a.sa_intv, 0);
+        f.load(a.fasta + ".fmi");
+        return seeds_main(a, f);
+    }
     std::vector<uint8_t> S;
     {
         DeviceText T(a.fasta, a.device);

@@ -454,6 +454,102 @@ class FMIndex:
             res["index"] = index
         return res
 
+    # ---- maximal exact match seeds (kiss_hip_fmi_seeds_dev; no reference counterpart) -------------------------------
+    def seeds(self, reads, min_len=19, max_len=0, max_occ=500, both_strands=False, want_positions=True, want_ms=False):
+        """The maximal exact match seeds of a batch of reads (include/kiss_hip.h has the definition).
+        reads: a list of uint8 arrays, or (concatenated, index) with read q = concatenated[index[q]:index[q + 1]].  The
+        values 0..3 are bases, any other value is no base (N): no seed contains it.  both_strands: virtual read 2 q is read
+        q, 2 q + 1 its reverse complement; otherwise virtual read q is read q.
+        Returns dict(seeds: structured array (start, len, sa_beg, sa_end), seed_index (V + 1: the seeds of virtual read v
+        are seeds[seed_index[v]:seed_index[v + 1]], ascending start), count (sa_end - sa_beg), report) and, with
+        want_positions, positions / pos_index in CSR layout over the seeds (ascending inside a seed; seeds with more than
+        max_occ occurrences -- 0: no limit -- have an empty segment), with want_ms the matching statistics `ms` (one per
+        end, virtual read after virtual read).
+        max_len: 0 = no cap.  Seeds are defined for max_len <= the order of the build: 1..32 by default, any value after
+        build(exact=True); positions only on an index built from the exact suffix array.  With positions the batch is
+        searched twice, as the C interface has it: the first call sizes the output."""
+        torch = _torch()
+        dev = torch.device("cuda", self.device)
+        min_len, max_len, max_occ = int(min_len), int(max_len), int(max_occ)
+        if min_len < 1:
+            raise ValueError("min_len must be at least 1")
+        if max_len < 0 or max_occ < 0 or max(min_len, max_len, max_occ) > 0xFFFFFFFF:
+            raise ValueError("min_len, max_len and max_occ are u32 (0: no cap / no limit)")
+        if not self.exact_sa:
+            if want_positions:
+                raise ValueError("positions of seeds need an index built from the exact suffix array: "
+                                 "build(ref, exact=True), or exact_sa=True on build(sa=...) / load / from_bytes")
+            if max_len == 0 or max_len > SORT_LEN:
+                raise ValueError("an index of a suffix array of order %d defines seeds for max_len in 1..%d only "
+                                 "(build with exact=True for longer ones)" % (SORT_LEN, SORT_LEN))
+        if isinstance(reads, tuple):
+            cat = np.ascontiguousarray(reads[0], dtype=np.uint8)
+            index = np.ascontiguousarray(reads[1], dtype=np.uint64)
+        else:
+            arrs = [np.ascontiguousarray(r, dtype=np.uint8).ravel() for r in reads]
+            cat = np.concatenate(arrs) if arrs else np.zeros(0, np.uint8)
+            index = np.zeros(len(arrs) + 1, np.uint64)
+            np.cumsum([a.size for a in arrs], out=index[1:])
+        if index.ndim != 1 or index.size < 1:
+            raise ValueError("the read index has Q + 1 entries")
+        Q = int(index.size) - 1
+        if Q and (np.any(index[1:] <= index[:-1]) or int(index[-1]) > cat.size):
+            raise ValueError("reads of length 0, or a read index that decreases or points past the reads")
+        V = 2 * Q if both_strands else Q
+        bases = (int(index[-1]) - int(index[0])) * (2 if both_strands else 1) if Q else 0
+        lib = _lib.load(self._hooks)
+        vex = _lib.FmiViewEx()
+        vex.base = self._view()
+        vex.lookup_len = self.lookup_len
+        vex.lookup = self.lookup.data_ptr() if self.lookup is not None else None
+        vp = ctypes.c_void_p
+        d_reads = torch.from_numpy(cat).to(dev) if cat.size else torch.zeros(1, dtype=torch.uint8, device=dev)
+        d_index = torch.from_numpy(index.view(np.int64)).to(dev)
+        d_ms = torch.zeros(max(bases, 1), dtype=torch.int32, device=dev) if want_ms else None
+        d_seeds = torch.zeros((max(bases, 1), 4), dtype=torch.int32, device=dev)
+        d_sidx = torch.zeros(V + 1, dtype=torch.int64, device=dev)
+        rep = _lib.FmiSeedReport()
+
+        def call(ctx, d_pos, d_pidx, cap):
+            return lib.kiss_hip_fmi_seeds_dev(ctx._ctx, ctypes.byref(vex), vp(d_reads.data_ptr()), vp(d_index.data_ptr()), Q,
+                                              min_len, max_len, max_occ, 1 if both_strands else 0,
+                                              vp(d_ms.data_ptr() if d_ms is not None else None), vp(d_seeds.data_ptr()),
+                                              vp(d_sidx.data_ptr()), bases, d_pos, d_pidx, cap, ctypes.byref(rep), None)
+
+        # the ends of a call are scanned in the context's scratch (0.32 max_n entries)
+        ctx = self._context(min(_lib.MAX_N, max(self.N, 4 * (bases + 1))))
+        _check(call(ctx, None, None, 0), "kiss_hip_fmi_seeds_dev", ctx._ctx)
+        res = {}
+        if want_positions:
+            total, nseeds = int(rep.positions), int(rep.seeds)
+            if total > 0.3 * ctx.max_n:  # one call sorts its positions in the context's LMS arrays: a context sized for them
+                ctx = self._context(min(_lib.MAX_N, int(3.3 * total) + (1 << 20)))
+            d_pos = torch.zeros(max(total, 1), dtype=torch.int32, device=dev)
+            d_pidx = torch.zeros(nseeds + 1, dtype=torch.int64, device=dev)
+            rc = call(ctx, vp(d_pos.data_ptr()), vp(d_pidx.data_ptr()), total)
+            if rc == _lib.KISS_HIP_E_INVALID and rep.walk_failures:
+                raise _lib.KissHipError(rc, "kiss_hip_fmi_seeds_dev",
+                                        "%d rows reached no sampled row: the index was not built from an exact suffix array "
+                                        "(build with exact=True)" % rep.walk_failures)
+            if rc == _lib.KISS_HIP_E_UNSUPPORTED:
+                raise _lib.KissHipError(rc, "kiss_hip_fmi_seeds_dev",
+                                        "%d positions are more than one call sorts: split the batch" % total)
+            _check(rc, "kiss_hip_fmi_seeds_dev", ctx._ctx)
+            res["positions"] = d_pos[:total].cpu().numpy().view(np.uint32)
+            res["pos_index"] = d_pidx.cpu().numpy().view(np.uint64)
+        nseeds = int(rep.seeds)
+        raw = d_seeds[:nseeds].cpu().numpy().view(np.uint32).reshape(nseeds, 4)
+        seeds = np.zeros(nseeds, dtype=[("start", np.uint32), ("len", np.uint32), ("sa_beg", np.uint32), ("sa_end", np.uint32)])
+        for j, name in enumerate(("start", "len", "sa_beg", "sa_end")):
+            seeds[name] = raw[:, j]
+        res["seeds"] = seeds
+        res["seed_index"] = d_sidx.cpu().numpy().view(np.uint64)
+        res["count"] = (seeds["sa_end"] - seeds["sa_beg"]).astype(np.uint32)
+        if want_ms:
+            res["ms"] = d_ms[:bases].cpu().numpy().view(np.uint32)
+        res["report"] = rep.as_dict()
+        return res
+
     def close(self):
         if self._ctx is not None:
             self._ctx.close()
