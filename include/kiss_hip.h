@@ -106,7 +106,9 @@ typedef struct kiss_hip_stats {
     /* appended in 0.1.3 (fields are only ever appended from here on) */
     uint32_t tie_run_retries; /* near-end placement: searches of the tie runs that failed their verification and were
                                * repeated (0 on an undisturbed device; see DESIGN.md 4.2 when it is not) */
-    uint32_t reserved_tail_;
+    uint32_t pair_records;    /* LMS sort: tied segments of two members that round 0 wrote as pair records and one lane each
+                               * decided; their members count in sort_item_rounds like every other tied item.  (Takes the
+                               * place of the reserved word at the tail: the struct keeps its size; always 0 before.) */
 } kiss_hip_stats;
 
 /* kernel classes for ms_kernel[] / launches_kernel[] */

@@ -42,7 +42,7 @@ class Stats(ctypes.Structure):
         ("refine_items", ctypes.c_uint64), ("refine_depth", ctypes.c_uint32), ("doubling_rounds", ctypes.c_uint32),
         ("ms_refine", ctypes.c_float), ("ms_h2d", ctypes.c_float), ("ms_d2h", ctypes.c_float),
         ("refine_form", ctypes.c_uint32), ("ms_fm_range", ctypes.c_float), ("ms_fm_locate", ctypes.c_float),
-        ("tie_run_retries", ctypes.c_uint32), ("reserved_tail_", ctypes.c_uint32),
+        ("tie_run_retries", ctypes.c_uint32), ("pair_records", ctypes.c_uint32),
     ]
 
     def as_dict(self):

@@ -67,6 +67,7 @@ void kiss_opts_refresh(kiss_hip_ctx *ctx)
     o.pivot_from_round2 = env_on("KISS_HIP_PIVOT_FROM_ROUND2");
     o.pair_keys = env_on("KISS_HIP_PAIR_KEYS");
     o.no_fc0_onepass = env_on("KISS_HIP_NO_FC0_ONEPASS");
+    o.no_pair_records = env_on("KISS_HIP_NO_PAIR_RECORDS");
     o.no_class_bytes = env_on("KISS_HIP_NO_CLASS_BYTES");
     o.no_pivot_ctx = env_on("KISS_HIP_NO_PIVOT_CTX");
     o.no_taint = env_on("KISS_HIP_NO_TAINT");
@@ -475,7 +476,7 @@ int kiss_lms_reserve(kiss_hip_ctx *ctx, uint64_t m_cap, uint64_t t_cap_wanted)
         ctx->rx_tiles_cap = m_cap / 16384 + 2;
         ALLOC(rx_desc, 256 * ctx->rx_tiles_cap);
         ALLOC(rx_ghist, 256 * 12);
-        ctx->fc_desc_cap = m_cap / 8192 + 4;
+        ctx->fc_desc_cap = 2 * (m_cap / 8192 + 4); // two words per tile: (survivors, heads) and pairs
         ALLOC(fc_desc, ctx->fc_desc_cap);
 #undef ALLOC
         // descriptors carry the epoch of the pass that wrote them: cleared once, never again (the epoch keeps counting)

@@ -27,6 +27,7 @@ struct KissOpts {
     bool pivot_from_round2 = false;// KISS_HIP_PIVOT_FROM_ROUND2
     bool pair_keys = false;        // KISS_HIP_PAIR_KEYS: gather the round's key for pairs as well
     bool no_fc0_onepass = false;   // KISS_HIP_NO_FC0_ONEPASS: count + scan + compact after round 0
+    bool no_pair_records = false;  // KISS_HIP_NO_PAIR_RECORDS: tied pairs stay in the survivor stream (k_seg_finish decides them)
     bool no_class_bytes = false;   // KISS_HIP_NO_CLASS_BYTES: the induction's count pass reads the context words (rounds 1-3)
     bool no_pivot_ctx = false;     // KISS_HIP_NO_PIVOT_CTX
     bool no_taint = false;         // KISS_HIP_NO_TAINT: the suffix-array form compares every neighbour pair
@@ -167,7 +168,7 @@ struct kiss_hip_ctx {
     uint32_t *rx_ghist = nullptr, *rx_ctl = nullptr;
     uint64_t rx_ghist_count = 0; // != 0: rx_ghist already holds the round-0 digit counts of that many keys (classify.hip)
     uint64_t rx_tiles_cap = 0, rx_epoch = 0;
-    uint64_t *fc_desc = nullptr;  // round 0 flag + compact in one pass: one descriptor per 8192-item tile (+ ticket)
+    uint64_t *fc_desc = nullptr;  // round 0 flag + compact in one pass: two descriptor words per 8192-item tile (+ ticket)
     uint64_t fc_desc_cap = 0;
     uint32_t rx_ticket_base = 0;
     uint64_t *scan_tmp = nullptr;  // block sums for scans

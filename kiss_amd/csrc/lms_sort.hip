@@ -8,6 +8,8 @@
 // GPU formulation: MSD refinement.
 //   round 0 : stable LSD radix sort of all suffixes on their first 20 bases (5 passes of 8 bits);
 //             suffixes that share those 20 bases form a segment, singletons retire to their final slot.
+//             A segment of exactly two -- more than half of what is tied -- leaves the stream there and then as one
+//             pair record, decided by one lane's walk to the full depth D (k_fc0_onepass<true>, k_pair_finish).
 //   round r : every still-tied suffix fetches its next 32 bases (one u64 key).
 //             - a segment of <= SMALL_SEG suffixes is FINISHED on the spot: one lane per suffix ranks it
 //               against the others of its segment, first on the fetched key and, for pairs that tie on it,
@@ -244,6 +246,35 @@ __global__ __launch_bounds__(LS_THREADS) void k_seg_finish(const uint64_t *__res
     }
     (void)nbig; // the number of big-segment items comes out of the flag scan (one address hit by every wave's
                 // atomicAdd cost more than the rest of this kernel)
+}
+
+// the pairs that k_fc0_onepass took out of the survivor stream, one lane per record: what the pair path of k_seg_finish
+// does, without the seg -> segstart -> pos[mate] -> slot chain.  The list still holds the two members in position order
+// (out[slot] = p0, out[slot + 1] = p1) and octx their context words, so only what changes is stored: a pair that swaps,
+// a taint bit.
+__global__ __launch_bounds__(LS_THREADS) void k_pair_finish(const uint64_t *__restrict__ pk, uint64_t n,
+                                                           const uint32_t *__restrict__ rpos0,
+                                                           const uint32_t *__restrict__ rpos1,
+                                                           const uint32_t *__restrict__ rslot, uint64_t npairs,
+                                                           uint64_t off, uint64_t depth, uint32_t *__restrict__ out,
+                                                           uint32_t *__restrict__ octx, uint8_t *__restrict__ hfar)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * LS_THREADS + threadIdx.x;
+    if (i >= npairs) return;
+    const uint32_t p0 = rpos0[i], p1 = rpos1[i], s = rslot[i];
+    bool taint = false;
+    // the first member's walk in k_seg_finish: is the second member smaller?  (tied through the depth: no, position order)
+    const bool swap = deep_less(pk, n, p1, p0, off - 32, depth, false, &taint);
+    if (!swap && !taint) return;
+    const uint32_t c0 = octx[s], c1 = octx[s + 1];
+    const uint32_t t = taint ? KISS_CTX_TAINT : 0u;
+    if (swap) {
+        out[s] = p1;
+        out[s + 1] = p0;
+    }
+    octx[s] = (swap ? c1 : c0) | t;
+    octx[s + 1] = (swap ? c0 : c1) | t;
+    if (hfar && taint) hfar[s + 1] = 0; // the member in the second slot is tied with the one before it
 }
 
 // ---- big segments: three-way split around a pivot key before any radix pass ---------------------------------
@@ -854,6 +885,17 @@ __device__ __forceinline__ uint64_t lane_value_u64(uint64_t v, int src_lane) // 
     return ((uint64_t)hi << 32) | lo;
 }
 
+// PAIRS: a tied segment of exactly two items (head at i, none at i + 1, head at i + 2 or the end of the list) does not
+// survive.  The lane that holds its first member writes ONE record -- (position of the first member, position of the
+// second, list index of the first = its slot; the second's slot is the next one), three columns of rcol words in rec --
+// at index (pairs in front of it), and k_pair_finish decides the pair with one lane and no index chasing.  Both members
+// keep their context words in octx instead of the zero of a tied item, so a record needs none.
+// A third running count goes through the look-back in a second descriptor word per tile, [status:2 | pairs:62], next to
+// the first (desc[2 t], desc[2 t + 1]); the two are written one after the other, so a reader that finds them in different
+// states reads them again.  The second member is the lane's own second item, the first item of the lane above or (lane 63)
+// the first item of the next chunk; a pair whose first member is the LAST item of a wave's 512-item stretch would need
+// the key two items past the stretch: it stays in the survivor stream, where k_seg_finish decides it as before.
+template <bool PAIRS>
 __global__ __launch_bounds__(FC1_THREADS, KISS_FC1_MIN_WAVES) void k_fc0_onepass(const uint64_t *__restrict__ key,
                                                             const uint32_t *__restrict__ pos, uint64_t count,
                                                             int cmp_shift, uint64_t tiles, uint64_t *__restrict__ desc,
@@ -861,11 +903,13 @@ __global__ __launch_bounds__(FC1_THREADS, KISS_FC1_MIN_WAVES) void k_fc0_onepass
                                                             uint32_t *__restrict__ npos, uint32_t *__restrict__ nslot,
                                                             uint32_t *__restrict__ nseg, uint32_t *__restrict__ nsegstart,
                                                             uint32_t *__restrict__ octx, uint32_t *__restrict__ nctx,
-                                                            uint64_t cap, uint64_t *__restrict__ total)
+                                                            uint64_t cap, uint64_t *__restrict__ total,
+                                                            uint32_t *__restrict__ rec, uint32_t rcol)
 {
-    __shared__ uint32_t ws[FC1_THREADS / 64][2];
+    constexpr int DS = PAIRS ? 2 : 1; // descriptor words per tile
+    __shared__ uint32_t ws[FC1_THREADS / 64][3];
     __shared__ uint32_t s_tile;
-    __shared__ uint32_t s_excl[2];
+    __shared__ uint32_t s_excl[3];
 #ifdef FC_PROF
     unsigned long long t_prev_ = wall_clock64();
 #endif
@@ -917,7 +961,6 @@ __global__ __launch_bounds__(FC1_THREADS, KISS_FC1_MIN_WAVES) void k_fc0_onepass
     FC_MARK(1); // keys, neighbours and positions have arrived
 #endif
     // head(i) = item i starts a segment (differs from item i - 1; items past the end count as heads)
-    uint64_t H0[FC1_CHUNKS]; // ballot of head(first item of the lane), per chunk
     uint32_t h01 = 0;        // my own head bits: bit 2j = first item, bit 2j + 1 = second item of chunk j
 #pragma unroll
     for (int j = 0; j < FC1_CHUNKS; j++) {
@@ -927,62 +970,103 @@ __global__ __launch_bounds__(FC1_THREADS, KISS_FC1_MIN_WAVES) void k_fc0_onepass
         if (lane == 0) up = before;
         const bool h0 = a == 0 || a >= count || up != k0[j];
         const bool h1 = a + 1 >= count || k0[j] != k1[j];
-        H0[j] = __ballot(h0);
         h01 |= (h0 ? 1u : 0u) << (2 * j) | (h1 ? 1u : 0u) << (2 * j + 1);
     }
+    // the head bits of the lane above, and of lane 0: the item after lane 63's second one is lane 0's first of the next chunk
+    const uint32_t h01_up = __shfl_down(h01, 1, 64);
+    const uint32_t h01_l0 = (uint32_t)__builtin_amdgcn_readlane((int)h01, 0);
     const bool next_head = !has_next || lane_value_u64(k1[FC1_CHUNKS - 1], 63) != knext; // head(first item after my wave)
     // survivors (tied with a neighbour) and the heads among them; ranks inside the wave
     uint32_t fl = 0;                              // bits 4j .. 4j+3: surv0, surv1, headsurv0, headsurv1
-    uint32_t rs[FC1_CHUNKS], gs[FC1_CHUNKS];      // survivors / surviving heads of my wave in front of my first item of chunk j
-    uint32_t run_s = 0, run_h = 0;                // (wave-uniform running totals)
+                                                  // (PAIRS) bits 16+2j, 17+2j: my first / second item is the first member of a pair
+    // survivors / surviving heads / (PAIRS) pairs of my wave in front of my first item of chunk j: each below FC1_WAVE_ITEMS,
+    // 10 bits a piece in one word (a word each costs eight registers more, which the kernel with PAIRS does not have)
+    uint32_t rk[FC1_CHUNKS];
+    static_assert(FC1_WAVE_ITEMS < 1024, "rank fields of 10 bits");
+    uint32_t run_s = 0, run_h = 0, run_p = 0;     // (wave-uniform running totals)
+    uint32_t pair_carry = 0; // (PAIRS, wave-uniform) lane 63's second item of the chunk before is the first member of a pair
     const uint64_t below = (1ull << lane) - 1ull;
 #pragma unroll
     for (int j = 0; j < FC1_CHUNKS; j++) {
-        const uint64_t a = wbase + (uint64_t)j * 128 + 2 * lane;
-        const bool h0 = (h01 >> (2 * j)) & 1u, h1 = (h01 >> (2 * j + 1)) & 1u;
-        const uint64_t nxt = j + 1 < FC1_CHUNKS ? H0[j + 1 < FC1_CHUNKS ? j + 1 : j] : (next_head ? 1ull : 0ull);
-        const bool hn = lane < 63u ? ((H0[j] >> (lane + 1u)) & 1ull) != 0 : (nxt & 1ull) != 0; // head(item after my second)
-        const bool s0 = a < count && !(h0 && h1), s1 = a + 1 < count && !(h1 && hn);
-        const bool m0 = s0 && h0, m1 = s1 && h1;
-        const uint64_t S0 = __ballot(s0), S1 = __ballot(s1), M0 = __ballot(m0), M1 = __ballot(m1);
-        rs[j] = run_s + (uint32_t)__popcll(S0 & below) + (uint32_t)__popcll(S1 & below);
-        gs[j] = run_h + (uint32_t)__popcll(M0 & below) + (uint32_t)__popcll(M1 & below);
+        // (flags as 0 / 1 words, not bools: a bool of a lane is a 64-bit wave mask in scalar registers, and four chunks'
+        //  worth of them at once do not fit the scalar file)
+        const uint32_t h0 = (h01 >> (2 * j)) & 1u, h1 = (h01 >> (2 * j + 1)) & 1u;
+        // bit 0: head(item after my second), bit 1: head(the one after that; 0 past my wave's stretch)
+        const uint32_t nb = lane < 63u ? h01_up >> (2 * j) : (j + 1 < FC1_CHUNKS ? h01_l0 >> (2 * j + 2) : (next_head ? 1u : 0u));
+        const uint32_t hn = nb & 1u;
+        // (items past the end are heads and so is everything after them: they are no survivors without a look at `count`)
+        uint32_t s0 = (h0 & h1) ^ 1u, s1 = (h1 & hn) ^ 1u;
+        if (PAIRS) {
+            const uint32_t hnn = (nb >> 1) & 1u;
+            const uint32_t pf0 = h0 & (h1 ^ 1u) & hn;          // my two items are a pair
+            const uint32_t pf1 = h1 & (hn ^ 1u) & hnn;         // my second item and the one after it (never the last of the stretch)
+            uint32_t ps0 = __shfl_up(pf1, 1, 64);              // my first item is the second member of the lane below's pair
+            if (lane == 0u) ps0 = pair_carry;
+            pair_carry = (uint32_t)__builtin_amdgcn_readlane((int)pf1, 63);
+            s0 &= (pf0 | ps0) ^ 1u;
+            s1 &= (pf1 | pf0) ^ 1u;
+            const uint64_t PF = __ballot((pf0 | pf1) != 0u); // (pf0 and pf1 of one lane exclude each other)
+            rk[j] = (run_p + (uint32_t)__popcll(PF & below)) << 20;
+            run_p += (uint32_t)__popcll(PF);
+            fl |= (pf0 | (pf1 << 1)) << (16 + 2 * j);
+        }
+        const uint32_t m0 = s0 & h0, m1 = s1 & h1;
+        const uint64_t S0 = __ballot(s0 != 0u), S1 = __ballot(s1 != 0u), M0 = __ballot(m0 != 0u), M1 = __ballot(m1 != 0u);
+        if (!PAIRS) rk[j] = 0;
+        rk[j] |= run_s + (uint32_t)__popcll(S0 & below) + (uint32_t)__popcll(S1 & below);
+        rk[j] |= (run_h + (uint32_t)__popcll(M0 & below) + (uint32_t)__popcll(M1 & below)) << 10;
         run_s += (uint32_t)__popcll(S0) + (uint32_t)__popcll(S1);
         run_h += (uint32_t)__popcll(M0) + (uint32_t)__popcll(M1);
-        fl |= ((s0 ? 1u : 0u) | (s1 ? 2u : 0u) | (m0 ? 4u : 0u) | (m1 ? 8u : 0u)) << (4 * j);
+        fl |= (s0 | (s1 << 1) | (m0 << 2) | (m1 << 3)) << (4 * j);
     }
     if (lane == 0) {
         ws[wave][0] = run_s;
         ws[wave][1] = run_h;
+        ws[wave][2] = run_p;
     }
     FC_MARK(2); // flags and ranks of my wave
     __syncthreads();
     FC_MARK(3); // ... of the slowest wave
-    uint32_t ts = 0, th = 0, ws0 = 0, wh0 = 0; // tile totals; totals of the waves before mine
+    uint32_t ts = 0, th = 0, tp = 0, ws0 = 0, wh0 = 0, wp0 = 0; // tile totals; totals of the waves before mine
 #pragma unroll
     for (int w = 0; w < FC1_THREADS / 64; w++) {
         if (w < wave) {
             ws0 += ws[w][0];
             wh0 += ws[w][1];
+            if (PAIRS) wp0 += ws[w][2];
         }
         ts += ws[w][0];
         th += ws[w][1];
+        if (PAIRS) tp += ws[w][2];
     }
     if (wave == 0) {
         constexpr uint64_t M31 = 0x7FFFFFFFull;
         const uint64_t mine = ((uint64_t)ts << 31) | (uint64_t)th;
-        uint64_t es = 0, eh = 0; // survivors / heads in all earlier tiles
+        constexpr uint64_t M62 = (1ull << 62) - 1ull;
+        uint64_t es = 0, eh = 0, ep = 0; // survivors / heads / pairs in all earlier tiles
         if (tile == 0) {
-            if (lane == 0) __hip_atomic_store(&desc[0], (2ull << 62) | mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (lane == 0) {
+                __hip_atomic_store(&desc[0], (2ull << 62) | mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (PAIRS) __hip_atomic_store(&desc[1], (2ull << 62) | (uint64_t)tp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
         } else {
-            if (lane == 0) __hip_atomic_store(&desc[tile], (1ull << 62) | mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (lane == 0) {
+                __hip_atomic_store(&desc[DS * tile], (1ull << 62) | mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (PAIRS)
+                    __hip_atomic_store(&desc[DS * tile + 1], (1ull << 62) | (uint64_t)tp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
             int64_t base = (int64_t)tile;
             uint32_t spins = 0;
             for (;;) {
                 const int64_t t = base - 1 - (int64_t)lane;
-                const uint64_t v = t >= 0 ? __hip_atomic_load(&desc[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                const uint64_t v = t >= 0 ? __hip_atomic_load(&desc[DS * t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
                                           : (2ull << 62); // in front of tile 0: nothing
-                const uint32_t st = (uint32_t)(v >> 62);
+                uint32_t st = (uint32_t)(v >> 62);
+                uint64_t v2 = 0;
+                if (PAIRS) {
+                    v2 = t >= 0 ? __hip_atomic_load(&desc[DS * t + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : (2ull << 62);
+                    if ((uint32_t)(v2 >> 62) != st) st = 0; // caught between its two stores: not ready, read again
+                }
                 const uint64_t incl = __ballot(st == 2u), ready = __ballot(st != 0u);
                 const uint32_t first = incl ? (uint32_t)__builtin_ctzll(incl) : 64u;      // nearest running total
                 const uint64_t need = first >= 63u ? ~0ull : ((2ull << first) - 1ull); // lanes 0 .. first
@@ -995,37 +1079,51 @@ __global__ __launch_bounds__(FC1_THREADS, KISS_FC1_MIN_WAVES) void k_fc0_onepass
                     continue;
                 }
                 uint64_t a = lane <= first ? (v >> 31) & M31 : 0ull, b = lane <= first ? v & M31 : 0ull;
+                uint64_t c = lane <= first ? v2 & M62 : 0ull;
 #pragma unroll
                 for (int d = 32; d >= 1; d >>= 1) {
                     a += __shfl_xor(a, d, 64);
                     b += __shfl_xor(b, d, 64);
+                    if (PAIRS) c += __shfl_xor(c, d, 64);
                 }
                 es += a;
                 eh += b;
+                ep += c;
                 if (first < 64u) break;
                 base -= 64;
             }
-            if (lane == 0)
-                __hip_atomic_store(&desc[tile], (2ull << 62) | ((es + ts) << 31) | (eh + th), __ATOMIC_RELAXED,
+            if (lane == 0) {
+                __hip_atomic_store(&desc[DS * tile], (2ull << 62) | ((es + ts) << 31) | (eh + th), __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_AGENT);
+                if (PAIRS)
+                    __hip_atomic_store(&desc[DS * tile + 1], (2ull << 62) | (ep + tp), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
         }
         if (lane == 0) {
             s_excl[0] = (uint32_t)es;
             s_excl[1] = (uint32_t)eh;
-            if (tile + 1 == tiles) total[0] = ((es + ts) << 32) | (eh + th);
+            s_excl[2] = (uint32_t)ep;
+            if (tile + 1 == tiles) {
+                total[0] = ((es + ts) << 32) | (eh + th);
+                total[1] = ep + tp; // (0 without PAIRS)
+            }
         }
     }
     FC_MARK(4); // look-back (wave 0)
     __syncthreads();
     FC_MARK(5);
     if (wbase >= count) return;
-    const uint32_t bs = s_excl[0] + ws0, bh = s_excl[1] + wh0;
+    const uint32_t bs = s_excl[0] + ws0, bh = s_excl[1] + wh0, bp = s_excl[2] + wp0;
+    // the store phase works its addresses and bounds out anew: computed ahead of the look-back and kept across it, they
+    // are what pushes the kernel past its registers
+    uint32_t lane_st = lane;
+    asm volatile("" : "+v"(lane_st));
 #pragma unroll KISS_FC1_STORE_UNROLL
     for (int j = 0; j < FC1_CHUNKS; j++) {
-        const uint64_t a = wbase + (uint64_t)j * 128 + 2 * lane;
+        const uint64_t a = wbase + (uint64_t)j * 128 + 2 * lane_st;
         const uint32_t f = (fl >> (4 * j)) & 15u;
-        const uint32_t ni0 = bs + rs[j], ni1 = ni0 + (f & 1u);
-        const uint32_t sid0 = bh + gs[j] + ((f >> 2) & 1u) - 1u;   // heads up to and including the item's own, minus one
+        const uint32_t ni0 = bs + (rk[j] & 1023u), ni1 = ni0 + (f & 1u);
+        const uint32_t sid0 = bh + ((rk[j] >> 10) & 1023u) + ((f >> 2) & 1u) - 1u;   // heads up to and including the item's own, minus one
         const uint32_t sid1 = sid0 + ((f >> 3) & 1u);
         if (f & 1u) {
             if (ni0 < cap) {
@@ -1051,6 +1149,25 @@ __global__ __launch_bounds__(FC1_THREADS, KISS_FC1_MIN_WAVES) void k_fc0_onepass
         else {
             if (a < count) octx[a] = c0[j];
             if (a + 1 < count) octx[a + 1] = c1[j];
+        }
+    }
+    if (PAIRS) {
+#pragma unroll
+        for (int j = 0; j < FC1_CHUNKS; j++) {
+            const uint32_t a32 = (uint32_t)wbase + (uint32_t)j * 128u + 2u * lane_st; // (a slot: the list has fewer than 2^32 items)
+            const uint32_t pf = (fl >> (16 + 2 * j)) & 3u;
+            // the item after my second one: the first item of the lane above, of lane 0 of the next chunk for lane 63
+            uint32_t pn = __shfl_down(p0[j], 1, 64);
+            if (j + 1 < FC1_CHUNKS) {
+                const uint32_t w0 = (uint32_t)__builtin_amdgcn_readlane((int)p0[j + 1 < FC1_CHUNKS ? j + 1 : j], 0);
+                if (lane == 63u) pn = w0;
+            }
+            if (pf) { // records in list order: a wave's stores of one chunk go to consecutive records
+                const uint32_t ri = bp + (rk[j] >> 20);
+                rec[ri] = (pf & 1u) ? p0[j] : p1[j];
+                rec[rcol + ri] = (pf & 1u) ? p1[j] : pn;
+                rec[2u * rcol + ri] = a32 + (pf >> 1);
+            }
         }
     }
     FC_MARK(6); // stores issued
@@ -1385,6 +1502,7 @@ int kiss_lms_sort(kiss_hip_ctx *ctx, uint64_t n, uint32_t k, uint64_t depth)
     const uint64_t m_far = ctx->m_far;
     ctx->stats.lms_rounds = 0;
     ctx->stats.sort_item_rounds = 0;
+    ctx->stats.pair_records = 0;
     if (m_far == 0) return KISS_HIP_OK;
     if (m_far == 1) {
         KCHECK(hipMemcpyAsync(ctx->lms_sorted_far, ctx->lms_pos, sizeof(uint32_t), hipMemcpyDeviceToDevice,
@@ -1431,21 +1549,34 @@ int kiss_lms_sort(kiss_hip_ctx *ctx, uint64_t n, uint32_t k, uint64_t depth)
     const bool no_onepass = ctx->opts.no_fc0_onepass;
     const uint64_t tiles1 = div_up(count, FC1_TILE);
     // (the result of the five passes is in buffer 1 = the output list itself, so there are no positions to copy)
-    const bool onepass = !no_onepass && ctx->fc_desc && tiles1 >= 8 && tiles1 + 1 <= ctx->fc_desc_cap &&
+    const bool onepass = !no_onepass && ctx->fc_desc && tiles1 >= 8 && 2 * tiles1 + 1 <= ctx->fc_desc_cap &&
                          rb.pos[res] == ctx->lms_sorted_far;
+    // pair records: in keyA, which is dead between the fifth pass (its result is in keyB) and k_gather_keys (K1).  Three
+    // columns of count / 2 words at most (a pair is two items) in its 2 count words.
+    const bool pair_records = onepass && !ctx->opts.no_pair_records && rb.key[res] == ctx->keyB;
+    const uint64_t rcol = (count / 2 + 4) & ~3ull;
+    uint32_t *const rpos0 = reinterpret_cast<uint32_t *>(ctx->keyA), *const rpos1 = rpos0 + rcol, *const rslot = rpos1 + rcol;
+    uint64_t npairs = 0;
     if (onepass) {
         uint64_t *desc = ctx->fc_desc;
-        uint32_t *ticket = reinterpret_cast<uint32_t *>(desc + tiles1);
+        uint32_t *ticket = reinterpret_cast<uint32_t *>(desc + 2 * tiles1);
         for (int attempt = 0; attempt < 2; attempt++) {
-            KTRY(kiss_zero_u32(ctx, desc, 2 * tiles1 + 2));
+            KTRY(kiss_zero_u32(ctx, desc, 4 * tiles1 + 2));
             {
                 KTimer t(ctx, KISS_HIP_K_FLAG_COMPACT, count);
-                hipLaunchKernelGGL(k_fc0_onepass, dim3((unsigned)tiles1), dim3(FC1_THREADS), 0, ctx->stream, rb.key[res], rb.pos[res],
-                                   count, r0_shift, tiles1, desc, ticket, ctx->rx_ctl + 1, Pc, ctx->slotA, ctx->segA, ctx->segstartA,
-                                   ctx->lms_ctx_far, ctx->bslot, ctx->t_cap, d_total);
+                if (pair_records)
+                    hipLaunchKernelGGL(k_fc0_onepass<true>, dim3((unsigned)tiles1), dim3(FC1_THREADS), 0, ctx->stream, rb.key[res],
+                                       rb.pos[res], count, r0_shift, tiles1, desc, ticket, ctx->rx_ctl + 1, Pc, ctx->slotA, ctx->segA,
+                                       ctx->segstartA, ctx->lms_ctx_far, ctx->bslot, ctx->t_cap, d_total, rpos0, (uint32_t)rcol);
+                else
+                    hipLaunchKernelGGL(k_fc0_onepass<false>, dim3((unsigned)tiles1), dim3(FC1_THREADS), 0, ctx->stream, rb.key[res],
+                                       rb.pos[res], count, r0_shift, tiles1, desc, ticket, ctx->rx_ctl + 1, Pc, ctx->slotA, ctx->segA,
+                                       ctx->segstartA, ctx->lms_ctx_far, ctx->bslot, ctx->t_cap, d_total, (uint32_t *)nullptr, 0u);
                 KCHECK(hipGetLastError());
             }
-            KTRY(fc_read_total(ctx, d_total, &tot));
+            KTRY(kiss_readback(ctx, d_total, 4)); // (survivors << 32 | heads), pairs
+            std::memcpy(&tot, ctx->h_pinned, sizeof(uint64_t));
+            std::memcpy(&npairs, ctx->h_pinned + 2, sizeof(uint64_t));
 #ifdef FC_PROF
             {
                 unsigned long long h[12], z[12] = {0};
@@ -1465,6 +1596,14 @@ int kiss_lms_sort(kiss_hip_ctx *ctx, uint64_t n, uint32_t k, uint64_t depth)
             KTRY(kiss_tied_reserve(ctx, surv + surv / 8 + 1024));
         }
         have_tctx = true;
+        if (npairs) { // (after the retry: the list and the context words it patches are written by the pass itself)
+            if (npairs > count / 2) return KINTERNAL();
+            KTimer t(ctx, KISS_HIP_K_SEGRANK, 2 * npairs);
+            hipLaunchKernelGGL(k_pair_finish, dim3((unsigned)div_up(npairs, T)), dim3(T), 0, ctx->stream, ctx->pk, n, rpos0, rpos1,
+                               rslot, npairs, (uint64_t)ROUND0_BASES, depth, ctx->lms_sorted_far, ctx->lms_ctx_far, ctx->hfar);
+            KCHECK(hipGetLastError());
+            ctx->stats.pair_records = (uint32_t)npairs;
+        }
     } else {
         KTRY((fc_count<FC_KEY>(ctx, rb.key[res], nullptr, count, r0_shift, 0, d_total)));
         KTRY(fc_read_total(ctx, d_total, &tot));
@@ -1489,6 +1628,10 @@ int kiss_lms_sort(kiss_hip_ctx *ctx, uint64_t n, uint32_t k, uint64_t depth)
 
     // ------------------------------ rounds >= 1 ---------------------------------------------
     uint64_t off = ROUND0_BASES;
+    if (npairs) { // the pairs are the first refinement round's items like the survivors: the counts keep their meaning
+        ctx->stats.sort_item_rounds += 2 * npairs;
+        if (count == 0) ctx->stats.lms_rounds++; // (nothing but pairs was tied: the loop below does not run)
+    }
     bool first_refine = true; // the tied items' context words (in bslot) are only good for the first pass over them
     for (;; first_refine = false) {
         if (count == 0) break;
