@@ -678,6 +678,63 @@ int kiss_hip_fmi_seeds_host(const kiss_hip_fmi_view_ex *fmi, const uint8_t *read
                             kiss_hip_fmi_seed *seeds, uint64_t *seed_index, uint64_t seed_capacity, uint32_t *positions,
                             uint64_t *pos_index, uint64_t pos_capacity, kiss_hip_fmi_seed_report *report, int device);
 
+/* ---- FM-index: the seeds of a read chained into candidate loci (no reference counterpart) -----------------------------
+ * The seeds call ends where a mapper begins: it says where every seed occurs, not which occurrences belong together.  This
+ * call groups them.  The result is a function of the input arrays and the parameters alone; it needs no index and no text.
+ * Input: the output of kiss_hip_fmi_seeds_dev -- seeds with seed_index (V + 1 u64), positions with pos_index (seeds + 1
+ * u64).  The ANCHORS of virtual read v are the triples (r, t, l) = (start, position, len), one for every position of every
+ * seed of v; a seed with an empty position segment (over max_occ) contributes none.  An anchor's SLOT is its index in
+ * `positions`; the anchors of one v are contiguous in slots.
+ * Order: the anchors of v are numbered 0 .. A - 1 in ascending (t, slot).
+ * Parameters (kiss_hip_chain_params, all u32; in parentheses the defaults of Python and the command line): max_gap (5000),
+ * band (500), gap_cost (2), max_lookback (64; 0 = no bound), min_score (40).  max_gap and band are at most 2^31 - 1,
+ * gap_cost at most 65535; anything else is KISS_HIP_E_INVALID.
+ * Predecessors: anchor j may precede anchor i when all of these hold: j < i; if max_lookback != 0, i - j <= max_lookback;
+ * with dt = t_i - t_j and dr = r_i - r_j (signed), dt > 0 and dr > 0; dt <= max_gap and dr <= max_gap;
+ * g = |dt - dr| <= band.  The score through j is f(j) + min(l_i, dr, dt) - floor(g * gap_cost / 8), in signed 64-bit
+ * arithmetic that cannot wrap.
+ * Score: take the maximum, in lexicographic order, of the pair (l_i, 0) and the pairs (score through j, j + 1) over all
+ * allowed j.  f(i) is its first component; pred(i) its second minus 1, none if that is 0.  So on equal scores the nearest
+ * predecessor in the order wins, and a predecessor that only ties with starting afresh still wins.  root(i) = i if pred(i)
+ * is none, else root(pred(i)); depth(i) = 0 if pred(i) is none, else depth(pred(i)) + 1.
+ * Chains: the pred pointers form a forest, and every tree yields at most one chain.  Its end is the anchor of the tree with
+ * the largest f, the smallest i on ties; the chain is the path from the root to that end; it is reported iff
+ * f(end) >= min_score.  The chains of v come in ascending root number, that is ascending (tbeg, slot).  The record has
+ * score = f(end), anchors = depth(end) + 1, (rbeg, tbeg) from the root, rend = r_end + l_end, tend = t_end + l_end.
+ * KNOWN PROPERTY: one chain per tree means that two loci closer together than max_gap, and inside the band, come out as ONE
+ * chain; there are no secondary chains inside a tree.
+ * Outputs: chains with chain_index (V + 1 u64: the chains of v are chains[chain_index[v] .. chain_index[v + 1])); optionally
+ * (both or neither) chain_anchors with anchor_index (chains + 1 u64): the anchors of each chain from root to end.
+ * A capacity smaller than the total: KISS_HIP_E_INVALID with the totals in the report (chains, chain_anchors; call again
+ * with room) -- the seeds call's convention.  Other KISS_HIP_E_INVALID: a required pointer NULL, a seed_index or pos_index
+ * that decreases, a located seed with len == 0 (checked on the device while the anchors are expanded).  V == 0: KISS_HIP_OK,
+ * chain_index[0] = 0.
+ * The u32 fields of a record hold the low 32 bits of their values.  Nothing is lost on the output of the seeds call, where
+ * r + l is at most a read length (below 2^31), so every score is below 2^32; t + l must not pass 2^32 - 1.
+ * Limits (KISS_HIP_E_UNSUPPORTED): V of 2^31 or more; more anchors in one call than the ctx's LMS work arrays hold (about
+ * 0.32 x max_n entries; their contents are lost) or than it scans, with the total in the report -- split the batch.
+ * seed_index[0] and pos_index[seed_index[0]] need not be 0: seeds and positions are indexed as the indexes say.
+ * Device times: report->ms_* (report may be NULL); the kernels also count under KISS_HIP_K_FM_QUERY. */
+typedef struct kiss_hip_chain_params { uint32_t max_gap, band, gap_cost, max_lookback, min_score; } kiss_hip_chain_params;
+typedef struct kiss_hip_chain { uint32_t score, anchors, rbeg, rend, tbeg, tend; } kiss_hip_chain;
+typedef struct kiss_hip_chain_anchor { uint32_t rstart, tpos, len; } kiss_hip_chain_anchor;
+typedef struct kiss_hip_chain_report {
+    uint64_t V, anchors, chains, chain_anchors;
+    uint64_t dp_pairs;         /* the (i, j) candidates with j inside the lookback: sum over i of min(i, max_lookback) */
+    uint32_t max_anchors, best_score; /* the largest A of a virtual read; the largest score of a reported chain */
+    float ms_total, ms_sort, ms_dp, ms_emit; /* sort: expand, order, gather; emit: tree ends, scan, totals, records */
+} kiss_hip_chain_report;
+/* every pointer except params and report is a device pointer */
+int kiss_hip_fmi_chain_dev(kiss_hip_ctx *ctx, const kiss_hip_fmi_seed *seeds, const uint64_t *seed_index, uint64_t V,
+                           const uint32_t *positions, const uint64_t *pos_index, const kiss_hip_chain_params *params,
+                           kiss_hip_chain *chains, uint64_t *chain_index, uint64_t chain_capacity, kiss_hip_chain_anchor *chain_anchors,
+                           uint64_t *anchor_index, uint64_t anchor_capacity, kiss_hip_chain_report *report, void *stream);
+/* the same with host pointers (the device's cached one-shot context, as kiss_hip_lcp_dna_u32: uploads, runs, downloads) */
+int kiss_hip_fmi_chain_host(const kiss_hip_fmi_seed *seeds, const uint64_t *seed_index, uint64_t V, const uint32_t *positions,
+                            const uint64_t *pos_index, const kiss_hip_chain_params *params, kiss_hip_chain *chains,
+                            uint64_t *chain_index, uint64_t chain_capacity, kiss_hip_chain_anchor *chain_anchors, uint64_t *anchor_index,
+                            uint64_t anchor_capacity, kiss_hip_chain_report *report, int device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,3 +7,4 @@ from ._lib import ALGO_PARALLEL_SORTING, ALGO_PREFIX_DOUBLING, KissHipError, LIB
 from .sorter import (K_UNBOUNDED, Context, KISS1Sorter, KISS2Sorter, MultiContext, lcp_array, lcp_array_bytes,  # noqa: F401
                      suffix_array_bytes)
 from .fm_index_bytes import FMIndexBytes  # noqa: F401,E402
+from .fm_chain import chain_seeds  # noqa: F401,E402

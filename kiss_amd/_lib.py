@@ -149,6 +149,33 @@ class FmiSeedReport(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved_"}
 
 
+class ChainParams(ctypes.Structure):
+    """kiss_hip_chain_params"""
+    _fields_ = [(k, ctypes.c_uint32) for k in ("max_gap", "band", "gap_cost", "max_lookback", "min_score")]
+
+
+class Chain(ctypes.Structure):
+    """kiss_hip_chain"""
+    _fields_ = [(k, ctypes.c_uint32) for k in ("score", "anchors", "rbeg", "rend", "tbeg", "tend")]
+
+
+class ChainAnchor(ctypes.Structure):
+    """kiss_hip_chain_anchor"""
+    _fields_ = [(k, ctypes.c_uint32) for k in ("rstart", "tpos", "len")]
+
+
+class ChainReport(ctypes.Structure):
+    """kiss_hip_chain_report"""
+    _fields_ = [
+        ("V", ctypes.c_uint64), ("anchors", ctypes.c_uint64), ("chains", ctypes.c_uint64), ("chain_anchors", ctypes.c_uint64),
+        ("dp_pairs", ctypes.c_uint64), ("max_anchors", ctypes.c_uint32), ("best_score", ctypes.c_uint32),
+        ("ms_total", ctypes.c_float), ("ms_sort", ctypes.c_float), ("ms_dp", ctypes.c_float), ("ms_emit", ctypes.c_float),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class Fmi8View(ctypes.Structure):
     """kiss_hip_fmi8_view"""
     _fields_ = [
@@ -293,6 +320,11 @@ def load(hooks=None):
     lib.kiss_hip_fmi_seeds_host.argtypes = [ctypes.POINTER(FmiViewEx), vp, vp, u64, u32, u32, u32, ctypes.c_int, vp, vp, vp, u64,
                                             vp, vp, u64, ctypes.POINTER(FmiSeedReport), ctypes.c_int]
     lib.kiss_hip_fmi_seeds_dev.restype = lib.kiss_hip_fmi_seeds_host.restype = ctypes.c_int
+    lib.kiss_hip_fmi_chain_dev.argtypes = [vp, vp, vp, u64, vp, vp, ctypes.POINTER(ChainParams), vp, vp, u64, vp, vp, u64,
+                                           ctypes.POINTER(ChainReport), vp]
+    lib.kiss_hip_fmi_chain_host.argtypes = [vp, vp, u64, vp, vp, ctypes.POINTER(ChainParams), vp, vp, u64, vp, vp, u64,
+                                            ctypes.POINTER(ChainReport), ctypes.c_int]
+    lib.kiss_hip_fmi_chain_dev.restype = lib.kiss_hip_fmi_chain_host.restype = ctypes.c_int
     lib.kiss_hip_fmi8_sizes_for.argtypes = [u64, u32, u32, ctypes.POINTER(Fmi8Sizes)]
     lib.kiss_hip_fmi8_build_dev.argtypes = [vp, vp, u64, vp, u32, u32] + [vp] * 8 + [ctypes.POINTER(u32), ctypes.POINTER(u32), vp]
     lib.kiss_hip_fmi8_build_host.argtypes = [vp, u64, vp, u32, u32] + [vp] * 8 + [ctypes.POINTER(u32), ctypes.POINTER(u32),
@@ -368,4 +400,5 @@ EXPORTED_SYMBOLS = [
     "kiss_hip_lcp_u8", "kiss_hip_fmi_query_mm_dev", "kiss_hip_fmi_query_mm_host",
     "kiss_hip_fmi8_sizes_for", "kiss_hip_fmi8_build_dev", "kiss_hip_fmi8_build_host", "kiss_hip_fmi8_query_dev",
     "kiss_hip_fmi8_query_host", "kiss_hip_fmi_seeds_dev", "kiss_hip_fmi_seeds_host",
+    "kiss_hip_fmi_chain_dev", "kiss_hip_fmi_chain_host",
 ]

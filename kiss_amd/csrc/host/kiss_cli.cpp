@@ -13,7 +13,9 @@
 //   (opt-in: fmindex_query --seeds READS [--min-seed-len N] [--max-seed-len M] [--max-occ N] [--both-strands]: the maximal
 //    exact match seeds of every read of READS (one read per line, ACGTacgt, any other letter is no base; lines starting
 //    with '>' and empty lines are skipped), one line per seed on stdout: read strand start len count pos...; also needs
-//    fmindex_build --exact)
+//    fmindex_build --exact; with --chain [--max-gap N] [--band N] [--gap-cost N] [--max-lookback N] [--min-chain-score N] the
+//    positions of the seeds of a read are chained into candidate loci (kiss_hip_fmi_chain_host) and the output is one line
+//    per chain instead: read strand score anchors rbeg rend tbeg tend)
 //   (-g / --generic: the file is a text over the byte alphabet, taken byte for byte -- no FASTA rule, no newline stripping,
 //    no % 4.  suffix_sort gives the exact suffix array (kiss_hip_suffix_sort_u8; -k and -s are ignored) and, with
 //    --output-lcp, its LCP array; fmindex_build writes <file>.fmi8 (kiss_hip_fmi8_build_host);
@@ -82,7 +84,15 @@ void usage()
               << "  --min-seed-len NUM (=19)       shortest seed reported\n"
               << "  --max-seed-len NUM (=0)        longest match followed (0: no cap)\n"
               << "  --max-occ NUM (=500)           seeds with more occurrences get no positions (0: no limit)\n"
-              << "  --both-strands                 also the reverse complement of every read (strand -)\n";
+              << "  --both-strands                 also the reverse complement of every read (strand -)\n"
+              << "  --chain                        with --seeds: chain the seed positions of every read into candidate loci\n"
+              << "                                 and print one line per chain instead: read strand score anchors rbeg rend\n"
+              << "                                 tbeg tend\n"
+              << "  --max-gap NUM (=5000)          largest step between two anchors of a chain, in the read and in the text\n"
+              << "  --band NUM (=500)              largest difference between the two steps\n"
+              << "  --gap-cost NUM (=2)            eighths of a point taken off per base of that difference\n"
+              << "  --max-lookback NUM (=64)       predecessors tried per anchor (0: no bound)\n"
+              << "  --min-chain-score NUM (=40)    lowest score of a chain reported\n";
 }
 
 inline uint8_t to_code(unsigned char c)
@@ -160,6 +170,8 @@ struct Args {
     std::string seeds;   // fmindex_query --seeds READS
     uint32_t min_seed_len = 19, max_seed_len = 0, max_occ = 500;
     bool both_strands = false;
+    bool chain = false; // fmindex_query --seeds READS --chain
+    kiss_hip_chain_params chain_params{5000, 500, 2, 64, 40};
 };
 
 Args parse(int argc, char **argv)
@@ -173,7 +185,8 @@ Args parse(int argc, char **argv)
             return argv[++i];
         };
         if (s == "--gpus" || s == "--devices" || s == "--lookup-len" || s == "--exact" || s == "--mismatches" || s == "--sa-intv" ||
-            s == "--seeds" || s == "--min-seed-len" || s == "--max-seed-len" || s == "--max-occ" || s == "--both-strands")
+            s == "--seeds" || s == "--min-seed-len" || s == "--max-seed-len" || s == "--max-occ" || s == "--both-strands" || s == "--chain" ||
+            s == "--max-gap" || s == "--band" || s == "--gap-cost" || s == "--max-lookback" || s == "--min-chain-score")
             a.seen.push_back(s);
         if (s == "-k" || s == "--kordered") a.seen.push_back("--kordered");
         if (s == "-s" || s == "--sorting-algorithm") a.seen.push_back("--sorting-algorithm");
@@ -200,6 +213,12 @@ Args parse(int argc, char **argv)
         else if (s == "--max-seed-len") a.max_seed_len = (uint32_t)std::stoul(next("--max-seed-len"));
         else if (s == "--max-occ") a.max_occ = (uint32_t)std::stoul(next("--max-occ"));
         else if (s == "--both-strands") a.both_strands = true;
+        else if (s == "--chain") a.chain = true;
+        else if (s == "--max-gap") a.chain_params.max_gap = (uint32_t)std::stoul(next("--max-gap"));
+        else if (s == "--band") a.chain_params.band = (uint32_t)std::stoul(next("--band"));
+        else if (s == "--gap-cost") a.chain_params.gap_cost = (uint32_t)std::stoul(next("--gap-cost"));
+        else if (s == "--max-lookback") a.chain_params.max_lookback = (uint32_t)std::stoul(next("--max-lookback"));
+        else if (s == "--min-chain-score") a.chain_params.min_score = (uint32_t)std::stoul(next("--min-chain-score"));
         else if (s == "--devices") {
             const std::string list = next("--devices");
             size_t at = 0;
@@ -224,6 +243,11 @@ Args parse(int argc, char **argv)
         const auto given_here = [&](const char *o) { return std::find(a.seen.begin(), a.seen.end(), o) != a.seen.end(); };
         for (const char *o : {"--min-seed-len", "--max-seed-len", "--max-occ", "--both-strands"})
             if (given_here(o) && !given_here("--seeds")) throw std::runtime_error(std::string(o) + " goes with --seeds");
+        for (const char *o : {"--max-gap", "--band", "--gap-cost", "--max-lookback", "--min-chain-score"})
+            if (given_here(o) && !given_here("--chain")) throw std::runtime_error(std::string(o) + " goes with --chain");
+        if (given_here("--chain") && !given_here("--seeds")) throw std::runtime_error("--chain goes with --seeds");
+        if (a.chain_params.max_gap > 0x7FFFFFFFu || a.chain_params.band > 0x7FFFFFFFu || a.chain_params.gap_cost > 65535u)
+            throw std::runtime_error("--max-gap and --band are at most 2147483647, --gap-cost at most 65535");
         if (given_here("--seeds")) {
             if (a.generic) throw std::runtime_error("--seeds is not supported for byte texts (--generic)");
             if (!a.query.empty() || !a.batch.empty() || a.mismatches >= 0)
@@ -606,6 +630,44 @@ MmHits mm_query(const Fmi &f, const uint8_t *pat, uint32_t L, uint64_t Q, uint32
     return h;
 }
 
+// fmindex_query --seeds READS --chain: one line per chain on stdout, `read strand score anchors rbeg rend tbeg tend`
+int chains_main(const Args &a, uint64_t V, const std::vector<kiss_hip_fmi_seed> &seeds, const std::vector<uint64_t> &sidx,
+                const std::vector<uint32_t> &pos, const std::vector<uint64_t> &pidx)
+{
+    std::vector<kiss_hip_chain> chains(1);
+    std::vector<uint64_t> cidx(V + 1, 0);
+    kiss_hip_chain_report rep{};
+    // the first call sizes the output
+    int rc = kiss_hip_fmi_chain_host(seeds.data(), sidx.data(), V, pos.data(), pidx.data(), &a.chain_params, chains.data(),
+                                     cidx.data(), 0, nullptr, nullptr, 0, &rep, a.device);
+    if (rc == KISS_HIP_E_INVALID && rep.chains) {
+        chains.resize(rep.chains);
+        rc = kiss_hip_fmi_chain_host(seeds.data(), sidx.data(), V, pos.data(), pidx.data(), &a.chain_params, chains.data(),
+                                     cidx.data(), rep.chains, nullptr, nullptr, 0, &rep, a.device);
+    }
+    check(rc, "kiss_hip_fmi_chain_host");
+    std::string out;
+    for (uint64_t vr = 0; vr < V; vr++) {
+        const uint64_t q = a.both_strands ? vr / 2 : vr;
+        const char strand = a.both_strands && (vr & 1) ? '-' : '+';
+        for (uint64_t c = cidx[vr]; c < cidx[vr + 1]; c++) {
+            const kiss_hip_chain &k = chains[c];
+            out += std::to_string(q) + ' ' + strand + ' ' + std::to_string(k.score) + ' ' + std::to_string(k.anchors) + ' ' +
+                   std::to_string(k.rbeg) + ' ' + std::to_string(k.rend) + ' ' + std::to_string(k.tbeg) + ' ' +
+                   std::to_string(k.tend) + '\n';
+        }
+        if (out.size() > (1u << 20)) {
+            std::fwrite(out.data(), 1, out.size(), stdout);
+            out.clear();
+        }
+    }
+    std::fwrite(out.data(), 1, out.size(), stdout);
+    std::fflush(stdout);
+    std::fprintf(stderr, "[info] virtual reads: %llu, anchors: %llu, chains: %llu, best score: %u\n", (unsigned long long)V,
+                 (unsigned long long)rep.anchors, (unsigned long long)rep.chains, rep.best_score);
+    return 0;
+}
+
 // fmindex_query --seeds: one line per seed on stdout, `read strand start len count pos...`
 int seeds_main(const Args &a, const Fmi &f)
 {
@@ -651,6 +713,7 @@ int seeds_main(const Args &a, const Fmi &f)
                                  " rows of the index reached no sampled row: the positions need an index built with "
                                  "fmindex_build --exact");
     check(rc, "kiss_hip_fmi_seeds_host");
+    if (a.chain) return chains_main(a, V, seeds, sidx, pos, pidx);
     std::string out;
     for (uint64_t vr = 0; vr < V; vr++) {
         const uint64_t q = a.both_strands ? vr / 2 : vr;

@@ -468,6 +468,26 @@ class FMIndex:
         max_len: 0 = no cap.  Seeds are defined for max_len <= the order of the build: 1..32 by default, any value after
         build(exact=True); positions only on an index built from the exact suffix array.  With positions the batch is
         searched twice, as the C interface has it: the first call sizes the output."""
+        d = self._seeds_dev(reads, min_len, max_len, max_occ, both_strands, want_positions, want_ms)
+        rep, nseeds = d["rep"], d["nseeds"]
+        res = {}
+        if want_positions:
+            res["positions"] = d["d_pos"][:d["total"]].cpu().numpy().view(np.uint32)
+            res["pos_index"] = d["d_pidx"].cpu().numpy().view(np.uint64)
+        raw = d["d_seeds"][:nseeds].cpu().numpy().view(np.uint32).reshape(nseeds, 4)
+        seeds = np.zeros(nseeds, dtype=[("start", np.uint32), ("len", np.uint32), ("sa_beg", np.uint32), ("sa_end", np.uint32)])
+        for j, name in enumerate(("start", "len", "sa_beg", "sa_end")):
+            seeds[name] = raw[:, j]
+        res["seeds"] = seeds
+        res["seed_index"] = d["d_sidx"].cpu().numpy().view(np.uint64)
+        res["count"] = (seeds["sa_end"] - seeds["sa_beg"]).astype(np.uint32)
+        if want_ms:
+            res["ms"] = d["d_ms"][:d["bases"]].cpu().numpy().view(np.uint32)
+        res["report"] = rep.as_dict()
+        return res
+
+    def _seeds_dev(self, reads, min_len, max_len, max_occ, both_strands, want_positions, want_ms):
+        """the device half of seeds(): checks, upload and the call(s); the outputs stay on the device (torch tensors)"""
         torch = _torch()
         dev = torch.device("cuda", self.device)
         min_len, max_len, max_occ = int(min_len), int(max_len), int(max_occ)
@@ -519,7 +539,7 @@ class FMIndex:
         # the ends of a call are scanned in the context's scratch (0.32 max_n entries)
         ctx = self._context(min(_lib.MAX_N, max(self.N, 4 * (bases + 1))))
         _check(call(ctx, None, None, 0), "kiss_hip_fmi_seeds_dev", ctx._ctx)
-        res = {}
+        out = {"d_seeds": d_seeds, "d_sidx": d_sidx, "d_ms": d_ms, "rep": rep, "V": V, "bases": bases, "total": 0}
         if want_positions:
             total, nseeds = int(rep.positions), int(rep.seeds)
             if total > 0.3 * ctx.max_n:  # one call sorts its positions in the context's LMS arrays: a context sized for them
@@ -535,19 +555,30 @@ class FMIndex:
                 raise _lib.KissHipError(rc, "kiss_hip_fmi_seeds_dev",
                                         "%d positions are more than one call sorts: split the batch" % total)
             _check(rc, "kiss_hip_fmi_seeds_dev", ctx._ctx)
-            res["positions"] = d_pos[:total].cpu().numpy().view(np.uint32)
-            res["pos_index"] = d_pidx.cpu().numpy().view(np.uint64)
-        nseeds = int(rep.seeds)
-        raw = d_seeds[:nseeds].cpu().numpy().view(np.uint32).reshape(nseeds, 4)
-        seeds = np.zeros(nseeds, dtype=[("start", np.uint32), ("len", np.uint32), ("sa_beg", np.uint32), ("sa_end", np.uint32)])
-        for j, name in enumerate(("start", "len", "sa_beg", "sa_end")):
-            seeds[name] = raw[:, j]
-        res["seeds"] = seeds
-        res["seed_index"] = d_sidx.cpu().numpy().view(np.uint64)
-        res["count"] = (seeds["sa_end"] - seeds["sa_beg"]).astype(np.uint32)
-        if want_ms:
-            res["ms"] = d_ms[:bases].cpu().numpy().view(np.uint32)
-        res["report"] = rep.as_dict()
+            out.update(d_pos=d_pos, d_pidx=d_pidx, total=total)
+        out["nseeds"] = int(rep.seeds)
+        out["ctx"] = ctx
+        return out
+
+    # ---- the seeds chained into candidate loci (kiss_hip_fmi_chain_dev; no reference counterpart) --------------------
+    def chains(self, reads, min_len=19, max_len=0, max_occ=500, both_strands=False, want_anchors=False, **params):
+        """The seeds of every read chained into candidate loci (include/kiss_hip.h has the definition): the seeds call and
+        the chain call, with the seeds and their positions staying on the device.  reads and the seed parameters as in
+        seeds(); params: max_gap (5000), band (500), gap_cost (2), max_lookback (64; 0: no bound), min_score (40).
+        Returns dict(chains: structured array (score, anchors, rbeg, rend, tbeg, tend), chain_index (V + 1: the chains of
+        virtual read v are chains[chain_index[v]:chain_index[v + 1]], ascending tbeg), report, seed_report) and, with
+        want_anchors, anchors (rstart, tpos, len) / anchor_index in CSR layout over the chains, root to end.
+        Needs an index built from the exact suffix array, as seeds(want_positions=True) does."""
+        from .fm_chain import chain_params, chain_dev, chain_arrays
+        p = chain_params(**params)
+        d = self._seeds_dev(reads, min_len, max_len, max_occ, both_strands, True, False)
+        ctx = d["ctx"]
+        if d["total"] > 0.3 * ctx.max_n:  # (the anchors are sorted where the positions were)
+            ctx = self._context(min(_lib.MAX_N, int(3.3 * d["total"]) + (1 << 20)))
+        out = chain_dev(_lib.load(self._hooks), ctx, self.device, d["d_seeds"], d["d_sidx"], d["V"], d["d_pos"], d["d_pidx"], p,
+                        want_anchors)
+        res = chain_arrays(out, want_anchors)
+        res["seed_report"] = d["rep"].as_dict()
         return res
 
     def close(self):
