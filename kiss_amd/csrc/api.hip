@@ -68,6 +68,7 @@ void kiss_opts_refresh(kiss_hip_ctx *ctx)
     o.pair_keys = env_on("KISS_HIP_PAIR_KEYS");
     o.no_fc0_onepass = env_on("KISS_HIP_NO_FC0_ONEPASS");
     o.no_pair_records = env_on("KISS_HIP_NO_PAIR_RECORDS");
+    o.no_small_fused = env_on("KISS_HIP_NO_SMALL_FUSED");
     o.no_class_bytes = env_on("KISS_HIP_NO_CLASS_BYTES");
     o.no_pivot_ctx = env_on("KISS_HIP_NO_PIVOT_CTX");
     o.no_taint = env_on("KISS_HIP_NO_TAINT");

@@ -28,6 +28,7 @@ struct KissOpts {
     bool pair_keys = false;        // KISS_HIP_PAIR_KEYS: gather the round's key for pairs as well
     bool no_fc0_onepass = false;   // KISS_HIP_NO_FC0_ONEPASS: count + scan + compact after round 0
     bool no_pair_records = false;  // KISS_HIP_NO_PAIR_RECORDS: tied pairs stay in the survivor stream (k_seg_finish decides them)
+    bool no_small_fused = false;   // KISS_HIP_NO_SMALL_FUSED: small tied segments by k_gather_keys + k_seg_adjacent + k_seg_finish
     bool no_class_bytes = false;   // KISS_HIP_NO_CLASS_BYTES: the induction's count pass reads the context words (rounds 1-3)
     bool no_pivot_ctx = false;     // KISS_HIP_NO_PIVOT_CTX
     bool no_taint = false;         // KISS_HIP_NO_TAINT: the suffix-array form compares every neighbour pair

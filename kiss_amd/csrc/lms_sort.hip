@@ -11,9 +11,10 @@
 //             A segment of exactly two -- more than half of what is tied -- leaves the stream there and then as one
 //             pair record, decided by one lane's walk to the full depth D (k_fc0_onepass<true>, k_pair_finish).
 //   round r : every still-tied suffix fetches its next 32 bases (one u64 key).
-//             - a segment of <= SMALL_SEG suffixes is FINISHED on the spot: one lane per suffix ranks it
-//               against the others of its segment, first on the fetched key and, for pairs that tie on it,
-//               by walking both suffixes to the full depth D (then position).  All of them retire.
+//             - a segment of <= SMALL_SEG suffixes is FINISHED on the spot: every suffix is ranked against the
+//               others of its segment, first on the fetched key and, for pairs that tie on it, by walking both
+//               suffixes to the full depth D (then position).  All of them retire.  (k_small_finish: one launch,
+//               the keys stay in LDS, every tied pair is walked once.)
 //             - larger segments are compacted and sorted on (segment id, key): from the second refinement round on
 //               by a stable three-way split around the key of the segment's middle item (what is left then is
 //               mostly long tandem arrays, whose members carry one key per round) followed by a radix sort of the
@@ -124,6 +125,9 @@ __device__ __forceinline__ bool deep_less(const uint64_t *__restrict__ pk, uint6
     }
 }
 
+// (k_seg_adjacent and k_seg_finish: the three-kernel form of the small-segment finish, behind k_gather_keys.  The sort
+//  runs k_small_finish below instead; the hooks build keeps this form as its A-B arm, KISS_HIP_NO_SMALL_FUSED, and for
+//  other thresholds than LMS_SMALL_SEG.)
 // phase A for small segments of >= 3 members: is my successor in the segment not smaller than me?
 // (a segment whose adjacent pairs are all in order is already sorted: the common case for periodic repeats,
 //  where all-pairs ranking would walk s^2 pairs to the full depth)
@@ -246,6 +250,202 @@ __global__ __launch_bounds__(LS_THREADS) void k_seg_finish(const uint64_t *__res
     }
     (void)nbig; // the number of big-segment items comes out of the flag scan (one address hit by every wave's
                 // atomicAdd cost more than the rest of this kernel)
+}
+
+// ---- k_gather_keys (small segments) + k_seg_adjacent + k_seg_finish in one kernel -----------------------------------
+// A workgroup owns SF_THREADS consecutive stream items and also loads the SF_HALO items on either side, so every segment of
+// <= LMS_SMALL_SEG members that has a member in the block lies in LDS as a whole (a segment that crosses the block's edge
+// is done by both blocks, each storing its own members).  Per window item LDS holds the position, the round's key (never
+// written to memory), the segment bounds and what the walks found:
+//     inorder[w]    the pair (w, w + 1), as k_seg_adjacent: 0 successor smaller, 1 in order, 2 in order by the tie rule
+//     before[w]     bit d: w sorts before its mate w + d        tiedm[w]  bit d: ... and the two are tied through the depth
+// The key-tied pairs are put on a list in LDS and the block's lanes walk them list entry by list entry -- every unordered
+// pair ONCE (k_seg_finish walked it from both sides, and k_seg_adjacent a third time if it was adjacent) and without the
+// idle lanes of one-lane-per-item: first the adjacent pairs; only a segment that these do not show to be in order lists
+// its other tied pairs.  A rank then is a count over the mates' bits.  A segment of two (no key: it is walked from the
+// segment's depth) is an adjacent pair like the others.  Every thread reaches every barrier.
+constexpr int SF_THREADS = LS_THREADS;
+constexpr int SF_HALO = (int)LMS_SMALL_SEG - 1;
+constexpr int SF_WINDOW = SF_THREADS + 2 * SF_HALO;
+constexpr int SF_PAIRS_CAP = SF_WINDOW * ((int)LMS_SMALL_SEG - 2); // an item lists its pairs with the mates >= 2 places on
+static_assert(LMS_SMALL_SEG <= 32 && SF_WINDOW <= 512 && 2 * SF_HALO <= SF_THREADS, "bit masks per item, 9 + 5 bit list entries");
+
+// the window items a lane loads: its own item of the block, and (the first 2 * SF_HALO lanes) one item of the halo
+__device__ __forceinline__ int sf_window_item(int tid, int t)
+{
+    if (t == 0) return tid + SF_HALO;
+    return tid < SF_HALO ? tid : (tid < 2 * SF_HALO ? tid + SF_THREADS : -1);
+}
+
+__global__ __launch_bounds__(SF_THREADS) void k_small_finish(const uint64_t *__restrict__ pk, uint64_t n,
+                                                            const uint32_t *__restrict__ pos,
+                                                            const uint32_t *__restrict__ slot,
+                                                            const uint32_t *__restrict__ seg,
+                                                            const uint32_t *__restrict__ segstart, uint32_t count,
+                                                            uint64_t off, uint64_t depth, uint64_t mask,
+                                                            uint32_t *__restrict__ out, uint8_t *__restrict__ big,
+                                                            const uint32_t *__restrict__ tctx, // first round only: the
+                                                            uint32_t *__restrict__ octx,       // items' context words
+                                                            uint8_t *__restrict__ hfar)        // as k_seg_finish
+{
+    __shared__ uint64_t s_key[SF_WINDOW];
+    __shared__ uint32_t s_pos[SF_WINDOW];
+    __shared__ int32_t s_a[SF_WINDOW], s_b[SF_WINDOW]; // segment bounds as window indices; s_b = 0: not an item of a small
+                                                       // segment that this block finishes
+    __shared__ uint32_t s_before[SF_WINDOW], s_tiedm[SF_WINDOW];
+    __shared__ uint8_t s_inorder[SF_WINDOW], s_unsorted[SF_WINDOW];
+    __shared__ uint16_t s_adj[SF_WINDOW];     // list of adjacent pairs to walk: w
+    __shared__ uint16_t s_far[SF_PAIRS_CAP];  // list of the other pairs to walk: w | d << 9
+    __shared__ uint32_t s_nadj, s_nfar;
+
+    const int tid = (int)threadIdx.x;
+    const int64_t g0 = (int64_t)blockIdx.x * SF_THREADS - SF_HALO; // stream index of window item 0
+    if (tid == 0) s_nadj = s_nfar = 0;
+    // ---- the window: positions, segment bounds, keys
+    uint32_t my_a = 0, my_len = 0; // of this lane's own item (window index tid + SF_HALO); my_len = 0: past the end
+    // (the first 2 * SF_HALO lanes load a second item: both chains seg -> segstart -> key are issued together)
+    bool valid[2];
+    uint32_t sgv[2] = {0, 0}, pv[2] = {0, 0}, av[2] = {0, 0}, bv[2] = {0, 0};
+#pragma unroll
+    for (int t = 0; t < 2; t++) {
+        const int w = sf_window_item(tid, t);
+        const int64_t g = g0 + w;
+        valid[t] = w >= 0 && g >= 0 && g < (int64_t)count;
+        if (valid[t]) {
+            sgv[t] = seg[g];
+            pv[t] = pos[g];
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < 2; t++)
+        if (valid[t]) {
+            av[t] = segstart[sgv[t]];
+            bv[t] = segstart[sgv[t] + 1];
+        }
+#pragma unroll
+    for (int t = 0; t < 2; t++) {
+        const int w = sf_window_item(tid, t);
+        if (w < 0) continue;
+        const bool own = t == 0;
+        int32_t wa = 0, wb = 0;
+        uint32_t p = 0;
+        uint64_t key = 0;
+        if (valid[t]) {
+            const uint32_t a = av[t], b = bv[t], len = b - a;
+            if (own) {
+                my_a = a;
+                my_len = len;
+            }
+            // (a halo item counts only as a mate of an item of the block)
+            if (len <= LMS_SMALL_SEG && (int64_t)b > g0 + SF_HALO && (int64_t)a < g0 + SF_HALO + SF_THREADS) {
+                wa = (int32_t)((int64_t)a - g0);
+                wb = (int32_t)((int64_t)b - g0);
+                p = pv[t];
+                if (len >= 3) { // as k_gather_keys
+                    const uint64_t q = (uint64_t)p + off;
+                    key = (q < n ? kiss_key32(pk, q) : 0ull) & mask;
+                }
+            }
+        }
+        s_a[w] = wa;
+        s_b[w] = wb;
+        s_pos[w] = p;
+        s_key[w] = key;
+        s_before[w] = 0;
+        s_tiedm[w] = 0;
+        s_inorder[w] = 1;
+        s_unsorted[w] = 0;
+    }
+    __syncthreads();
+    // ---- adjacent pairs: decided by the key, or listed for a walk
+    for (int w = tid; w < SF_WINDOW; w += SF_THREADS) {
+        if (w + 1 < s_b[w]) {
+            const uint64_t ki = s_key[w], kn = s_key[w + 1];
+            if (kn != ki) s_inorder[w] = kn > ki ? 1 : 0;
+            else s_adj[atomicAdd(&s_nadj, 1u)] = (uint16_t)w;
+        }
+    }
+    __syncthreads();
+    const int nadj = (int)s_nadj;
+    for (int e = tid; e < nadj; e += SF_THREADS) {
+        const int w = s_adj[e];
+        const bool pair = s_b[w] - s_a[w] == 2; // no key was compared: the walk starts at the segment's depth
+        bool tied = false;
+        const bool ok = !deep_less(pk, n, s_pos[w + 1], s_pos[w], pair ? off - 32 : off, depth, false, &tied);
+        s_inorder[w] = tied ? 2 : (ok ? 1 : 0);
+    }
+    __syncthreads();
+    // ---- a segment with an adjacent pair out of order: every pair of it counts.  Item w decides its pairs with the mates
+    // behind it: by the key, from the adjacent walk, or it lists them for a walk
+    for (int w = tid; w < SF_WINDOW; w += SF_THREADS) {
+        const int wa = s_a[w], wb = s_b[w];
+        bool sorted = true;
+        for (int j = wa; j + 1 < wb; j++) sorted = sorted && s_inorder[j] != 0;
+        if (sorted) continue;
+        s_unsorted[w] = 1;
+        const bool own = w >= SF_HALO && w < SF_HALO + SF_THREADS;
+        const uint64_t ki = s_key[w];
+        uint32_t before = 0, walk = 0;
+        for (int j = w + 1; j < wb; j++) {
+            const uint64_t kj = s_key[j];
+            const uint32_t bit = 1u << (j - w);
+            if (kj != ki) before |= ki < kj ? bit : 0u;
+            else if (j == w + 1) before |= s_inorder[w] ? bit : 0u;
+            else if (own || (j >= SF_HALO && j < SF_HALO + SF_THREADS)) walk |= bit; // (two halo items: nobody asks)
+        }
+        s_before[w] = before;
+        if (s_inorder[w] == 2) s_tiedm[w] = 2u;
+        if (walk) {
+            uint32_t at = atomicAdd(&s_nfar, (uint32_t)__popc(walk));
+            while (walk) {
+                const int d = __ffs(walk) - 1;
+                walk &= walk - 1;
+                s_far[at++] = (uint16_t)(w | (d << 9));
+            }
+        }
+    }
+    __syncthreads();
+    const int nfar = (int)s_nfar;
+    for (int e = tid; e < nfar; e += SF_THREADS) {
+        const int w = s_far[e] & 511, d = s_far[e] >> 9;
+        bool tied = false;
+        const bool first = deep_less(pk, n, s_pos[w], s_pos[w + d], off, depth, true, &tied);
+        if (first) atomicOr(&s_before[w], 1u << d);
+        if (tied) atomicOr(&s_tiedm[w], 1u << d);
+    }
+    __syncthreads();
+    // ---- ranks and stores, one lane per item of the block
+    const int w = tid + SF_HALO;
+    const uint32_t i = (uint32_t)(g0 + w);
+    if (my_len == 0) return; // past the end of the stream (after the last barrier)
+    if (my_len > LMS_SMALL_SEG) {
+        big[i] = i == my_a ? (uint8_t)3 : (uint8_t)1;
+        return;
+    }
+    const int wa = s_a[w], wb = s_b[w];
+    uint32_t r;
+    bool taint, tied_before;
+    if (!s_unsorted[w]) {
+        r = (uint32_t)(w - wa);
+        tied_before = w > wa && s_inorder[w - 1] == 2;
+        taint = tied_before || (w + 1 < wb && s_inorder[w] == 2);
+    } else {
+        const uint32_t behind = (2u << (wb - 1 - w)) - 2u; // bits 1 .. wb - 1 - w: my mates behind me
+        r = (uint32_t)__popc(~s_before[w] & behind);
+        taint = s_tiedm[w] != 0;
+        tied_before = false;
+        for (int j = wa; j < w; j++) {
+            r += (s_before[j] >> (w - j)) & 1u;
+            tied_before = tied_before || ((s_tiedm[j] >> (w - j)) & 1u);
+        }
+        taint = taint || tied_before;
+    }
+    const uint32_t dst = slot[my_a + r];
+    out[dst] = s_pos[w];
+    if (hfar && tied_before) hfar[dst] = 0;
+    if (tctx) octx[dst] = tctx[i] | (taint ? KISS_CTX_TAINT : 0u);
+    else if (taint) octx[dst] = KISS_CTX_TAINT;
+    big[i] = 0;
 }
 
 // the pairs that k_fc0_onepass took out of the survivor stream, one lane per record: what the pair path of k_seg_finish
@@ -1523,6 +1723,8 @@ int kiss_lms_sort(kiss_hip_ctx *ctx, uint64_t n, uint32_t k, uint64_t depth)
     const int pivot_slots = ctx->opts.pivot_slots >= 1 && ctx->opts.pivot_slots <= 8 ? ctx->opts.pivot_slots : 3;
     const bool no_pair_keys = !ctx->opts.pair_keys;
     const uint32_t small_seg = ctx->opts.small_seg >= 2 && ctx->opts.small_seg <= 4096 ? ctx->opts.small_seg : LMS_SMALL_SEG;
+    // k_small_finish is compiled for LMS_SMALL_SEG (its halo and its bit masks)
+    const bool small_fused = !ctx->opts.no_small_fused && small_seg == LMS_SMALL_SEG;
 
     // ------------------------------ round 0 ------------------------------------------------
     uint64_t count = m_far;
@@ -1644,12 +1846,20 @@ int kiss_lms_sort(kiss_hip_ctx *ctx, uint64_t n, uint32_t k, uint64_t depth)
         const unsigned grid = (unsigned)div_up(count, T);
         // big segments need the round's key only where they are radix sorted on it (no pivot round ahead)
         const bool pivot_ahead = depth && (off > ROUND0_BASES || pivot_r1) && pivot_on;
-        {
+        if (!small_fused) {
             KTimer t(ctx, KISS_HIP_K_KEYGATHER, count);
             // (segstart's end entry is needed by the pair test: set it first)
             hipLaunchKernelGGL(k_set_u32, dim3(1), dim3(64), 0, ctx->stream, SSc + nseg, (uint32_t)count, (uint32_t *)nullptr);
             hipLaunchKernelGGL(k_gather_keys, dim3(grid), dim3(T), 0, ctx->stream, ctx->pk, n, Pc, count, off, mask,
                                K1, no_pair_keys ? Gc : (const uint32_t *)nullptr, SSc, 3u, pivot_ahead ? small_seg : 0xFFFFFFFFu);
+            KCHECK(hipGetLastError());
+        } else if (!pivot_ahead) {
+            // k_small_finish gathers the keys of the small segments itself and keeps them in LDS; the big segments are
+            // radix sorted on theirs (k_bigb_compact reads them from K1)
+            KTimer t(ctx, KISS_HIP_K_KEYGATHER, count);
+            hipLaunchKernelGGL(k_set_u32, dim3(1), dim3(64), 0, ctx->stream, SSc + nseg, (uint32_t)count, (uint32_t *)nullptr);
+            hipLaunchKernelGGL(k_gather_keys, dim3(grid), dim3(T), 0, ctx->stream, ctx->pk, n, Pc, count, off, mask,
+                               K1, Gc, SSc, small_seg + 1u, 0xFFFFFFFFu);
             KCHECK(hipGetLastError());
         }
         uint8_t *bigb = nullptr;
@@ -1663,12 +1873,19 @@ int kiss_lms_sort(kiss_hip_ctx *ctx, uint64_t n, uint32_t k, uint64_t depth)
             KTimer t(ctx, KISS_HIP_K_SEGRANK, count);
             hipLaunchKernelGGL(k_set_u32, dim3(1), dim3(64), 0, ctx->stream, SSc + nseg, (uint32_t)count, d_nbig);
             uint8_t *inorder = reinterpret_cast<uint8_t *>(F2); // F2 is free until the pivot / big-segment steps below
-            bigb = inorder + ((count + 15) & ~15ull);           // the big-segment flags of k_seg_finish, behind them
-            hipLaunchKernelGGL(k_seg_adjacent, dim3(grid), dim3(T), 0, ctx->stream, ctx->pk, n, K1, Pc, Gc, SSc, count, off,
-                               depth, small_seg, inorder);
-            hipLaunchKernelGGL(k_seg_finish, dim3(grid), dim3(T), 0, ctx->stream, ctx->pk, n, K1, Pc, Sc, Gc, SSc,
-                               count, off, depth, small_seg, inorder, ctx->lms_sorted_far, bigb, d_nbig,
-                               (have_tctx && first_refine) ? ctx->bslot : (const uint32_t *)nullptr, ctx->lms_ctx_far, ctx->hfar);
+            bigb = inorder + ((count + 15) & ~15ull);           // the big-segment flags, behind them
+            const uint32_t *tctx = (have_tctx && first_refine) ? ctx->bslot : (const uint32_t *)nullptr;
+            if (small_fused) {
+                hipLaunchKernelGGL(k_small_finish, dim3(grid), dim3(SF_THREADS), 0, ctx->stream, ctx->pk, n, Pc, Sc, Gc, SSc,
+                                   (uint32_t)count, off, depth, mask, ctx->lms_sorted_far, bigb, tctx, ctx->lms_ctx_far,
+                                   ctx->hfar);
+            } else { // the three-kernel form (hooks build: KISS_HIP_NO_SMALL_FUSED, or another KISS_HIP_SMALL_SEG)
+                hipLaunchKernelGGL(k_seg_adjacent, dim3(grid), dim3(T), 0, ctx->stream, ctx->pk, n, K1, Pc, Gc, SSc, count, off,
+                                   depth, small_seg, inorder);
+                hipLaunchKernelGGL(k_seg_finish, dim3(grid), dim3(T), 0, ctx->stream, ctx->pk, n, K1, Pc, Sc, Gc, SSc,
+                                   count, off, depth, small_seg, inorder, ctx->lms_sorted_far, bigb, d_nbig, tctx,
+                                   ctx->lms_ctx_far, ctx->hfar);
+            }
             KCHECK(hipGetLastError());
         }
         ctx->stats.lms_rounds++;
