@@ -735,6 +735,78 @@ int kiss_hip_fmi_chain_host(const kiss_hip_fmi_seed *seeds, const uint64_t *seed
                             uint64_t *chain_index, uint64_t chain_capacity, kiss_hip_chain_anchor *chain_anchors, uint64_t *anchor_index,
                             uint64_t anchor_capacity, kiss_hip_chain_report *report, int device);
 
+/* ---- FM-index: the chains of a read aligned to the text, banded (no reference counterpart) ---------------------------
+ * A chain is a guess: "read bases [rbeg, rend) lie near text bases [tbeg, tend)".  This call turns every chain into a
+ * base-level, banded, affine-gap LOCAL alignment: score, ends, counts and optionally the operations.  One definition in
+ * integers; tests/fm_align_model.py restates it.
+ * Input: the text S -- n bytes of 0..3, the array the index was built from (the index does not keep it); reads /
+ * read_index / Q / both_strands exactly as in kiss_hip_fmi_seeds_dev (virtual read 2 q + 1 is the reverse complement, read
+ * in place; a no-base is its own complement); chains with chain_index (V + 1 u64) as kiss_hip_fmi_chain_dev wrote them.
+ * C = chain_index[V] - chain_index[0]; alignment a (0 <= a < C) belongs to chains[chain_index[0] + a], whose virtual read
+ * is the v with chain_index[v] <= chain_index[0] + a < chain_index[v + 1] (chain_index[0] need not be 0).
+ * Parameters (kiss_hip_align_params, all u32; in parentheses the defaults of Python and the command line): match (1),
+ * mismatch (4), gap_open (6), gap_extend (1), band (32).  A gap of g bases costs gap_open + g * gap_extend.  match >= 1, the
+ * four scores <= 65535, band <= 2^31 - 1; anything else is KISS_HIP_E_INVALID.
+ * Band: for a chain of virtual read v (read R of L bases), in signed 64-bit: d0 = tbeg - rbeg, d1 = tend - rend,
+ * dlo = min(d0, d1) - band, dhi = max(d0, d1) + band, B = dhi - dlo + 1.  Only these four fields of the chain record are
+ * used; no other field is validated and any values are defined.  Cell (i, j), 1 <= i <= L, 1 <= j <= n, compares R[i - 1]
+ * with S[j - 1]; it EXISTS iff dlo <= j - i <= dhi.  B > KISS_HIP_ALIGN_MAX_BAND: the chain is not aligned, flags =
+ * KISS_HIP_ALN_BAND_TOO_WIDE, every other field 0 except band.
+ * Recurrence (o = gap_open, e = gap_extend): s(x, y) = match if x == y <= 3; -1 if x is a no-base (it never matches);
+ * -mismatch otherwise.
+ *   E(i, j) = max(H(i, j - 1) - o - e, E(i, j - 1) - e) if cell (i, j - 1) exists, else -inf   (consumes text: a deletion)
+ *   F(i, j) = max(H(i - 1, j) - o - e, F(i - 1, j) - e) if cell (i - 1, j) exists, else -inf   (consumes read: an insertion)
+ *   H(i, j) = max(0, Hd + s(R[i - 1], S[j - 1]), E(i, j), F(i, j)), Hd = H(i - 1, j - 1) if that cell exists, else 0 (it is
+ *   on the same diagonal, so it is missing only at i = 1 or j = 1).
+ * Equivalently: the best H is the largest score over all lattice paths of M / I / D steps all of whose points lie on the
+ * diagonals dlo..dhi inside [0, L] x [0, n].
+ * Best cell: the largest H; ties: the smallest i, then the smallest j.  Largest H = 0: not aligned, all fields 0 except
+ * band, flags = 0.
+ * Traceback, a function of the final H / E / F values only.  In state H at (i, j): stop if i = 0, j = 0 or H = 0; otherwise
+ * take the diagonal if H = Hd + s, else go to state E if H = E, else to state F.  In state E: emit D; go back to state H if
+ * E(i, j) = H(i, j - 1) - o - e (opening is preferred over extending), else stay in E; then j -= 1.  State F mirrors E with I
+ * and i -= 1.
+ * Record (kiss_hip_aln, 12 u32): score, flags, rbeg, rend, tbeg, tend (half-open, 0-based, in the virtual read and the
+ * text), matches, mismatches (no-base columns count here), ins, del (bases), gaps (maximal runs of I or D), band (= B,
+ * saturated to u32).  So rend - rbeg = matches + mismatches + ins and tend - tbeg = matches + mismatches + del.
+ * CIGAR, optional (cigar with cigar_index, both or neither): u32 ops len << 4 | op, op 0 = M (match or mismatch), 1 = I,
+ * 2 = D; maximal runs in read order, CSR over the alignments (cigar_index has C + 1 u64).  No clip ops: the clips are rbeg
+ * and L - rend.
+ * KNOWN PROPERTY: the alignment is local within the band; it is NOT forced through the chain's anchors.  A chain that wanders
+ * outside [min(d0, d1) - band, max(d0, d1) + band] between its ends is aligned inside the band only.
+ * aln_capacity < C or cigar_capacity < the total of ops: KISS_HIP_E_INVALID with the totals in the report (chains,
+ * cigar_ops), nothing written; call again with room.  Other KISS_HIP_E_INVALID: a required pointer NULL, a chain_index or
+ * read_index that decreases, a zero-length read.  V == 0 or C == 0: KISS_HIP_OK, cigar_index[0] = 0.
+ * Limits (KISS_HIP_E_UNSUPPORTED): n above KISS_HIP_MAX_N; V of 2^31 or more; a read of the batch with L * match >= 2^30;
+ * more DP cells -- `cells`, the sum of L * B over the chains that are not too wide -- than the traceback store of the call
+ * holds.  That store, one byte per cell, comes out of the ctx's pooled scratch, and its limit is
+ * KISS_HIP_ALIGN_CELLS_PER_N x the ctx's max_n cells; the total is in the report -- split the batch.
+ * All score arithmetic is signed 32-bit and cannot wrap under these limits.
+ * Device times: report->ms_* (report may be NULL); the kernels also count under KISS_HIP_K_FM_QUERY. */
+#define KISS_HIP_ALIGN_MAX_BAND 1024u
+#define KISS_HIP_ALIGN_CELLS_PER_N 16u
+#define KISS_HIP_ALN_BAND_TOO_WIDE 1u
+typedef struct kiss_hip_align_params { uint32_t match, mismatch, gap_open, gap_extend, band; } kiss_hip_align_params;
+typedef struct kiss_hip_aln {
+    uint32_t score, flags, rbeg, rend, tbeg, tend, matches, mismatches, ins, del, gaps, band;
+} kiss_hip_aln;
+typedef struct kiss_hip_align_report {
+    uint64_t V, chains, aligned, too_wide; /* aligned = chains - too_wide: the chains whose band was filled */
+    uint64_t cells, cigar_ops;
+    uint32_t best_score, max_band;         /* the largest score; the largest B of a chain that was not too wide */
+    float ms_total, ms_dp, ms_trace, ms_emit; /* trace: the walk back and the op counts; emit: scan, totals, records, ops */
+} kiss_hip_align_report;
+/* every pointer except params and report is a device pointer */
+int kiss_hip_fmi_align_dev(kiss_hip_ctx *ctx, const uint8_t *text, uint64_t n, const uint8_t *reads, const uint64_t *read_index,
+                           uint64_t Q, int both_strands, const kiss_hip_chain *chains, const uint64_t *chain_index,
+                           const kiss_hip_align_params *params, kiss_hip_aln *alns, uint64_t aln_capacity, uint32_t *cigar,
+                           uint64_t *cigar_index, uint64_t cigar_capacity, kiss_hip_align_report *report, void *stream);
+/* the same with host pointers (the device's cached one-shot context, as kiss_hip_fmi_chain_host) */
+int kiss_hip_fmi_align_host(const uint8_t *text, uint64_t n, const uint8_t *reads, const uint64_t *read_index, uint64_t Q,
+                            int both_strands, const kiss_hip_chain *chains, const uint64_t *chain_index,
+                            const kiss_hip_align_params *params, kiss_hip_aln *alns, uint64_t aln_capacity, uint32_t *cigar,
+                            uint64_t *cigar_index, uint64_t cigar_capacity, kiss_hip_align_report *report, int device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,3 +8,4 @@ from .sorter import (K_UNBOUNDED, Context, KISS1Sorter, KISS2Sorter, MultiContex
                      suffix_array_bytes)
 from .fm_index_bytes import FMIndexBytes  # noqa: F401,E402
 from .fm_chain import chain_seeds  # noqa: F401,E402
+from .fm_align import ALIGN_DEFAULTS, align_chains, align_params  # noqa: F401,E402

@@ -176,6 +176,29 @@ class ChainReport(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class AlignParams(ctypes.Structure):
+    """kiss_hip_align_params"""
+    _fields_ = [(k, ctypes.c_uint32) for k in ("match", "mismatch", "gap_open", "gap_extend", "band")]
+
+
+class Aln(ctypes.Structure):
+    """kiss_hip_aln"""
+    _fields_ = [(k, ctypes.c_uint32) for k in ("score", "flags", "rbeg", "rend", "tbeg", "tend", "matches", "mismatches", "ins",
+                                               "del", "gaps", "band")]
+
+
+class AlignReport(ctypes.Structure):
+    """kiss_hip_align_report"""
+    _fields_ = [
+        ("V", ctypes.c_uint64), ("chains", ctypes.c_uint64), ("aligned", ctypes.c_uint64), ("too_wide", ctypes.c_uint64),
+        ("cells", ctypes.c_uint64), ("cigar_ops", ctypes.c_uint64), ("best_score", ctypes.c_uint32), ("max_band", ctypes.c_uint32),
+        ("ms_total", ctypes.c_float), ("ms_dp", ctypes.c_float), ("ms_trace", ctypes.c_float), ("ms_emit", ctypes.c_float),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class Fmi8View(ctypes.Structure):
     """kiss_hip_fmi8_view"""
     _fields_ = [
@@ -325,6 +348,11 @@ def load(hooks=None):
     lib.kiss_hip_fmi_chain_host.argtypes = [vp, vp, u64, vp, vp, ctypes.POINTER(ChainParams), vp, vp, u64, vp, vp, u64,
                                             ctypes.POINTER(ChainReport), ctypes.c_int]
     lib.kiss_hip_fmi_chain_dev.restype = lib.kiss_hip_fmi_chain_host.restype = ctypes.c_int
+    lib.kiss_hip_fmi_align_dev.argtypes = [vp, vp, u64, vp, vp, u64, ctypes.c_int, vp, vp, ctypes.POINTER(AlignParams), vp, u64, vp,
+                                           vp, u64, ctypes.POINTER(AlignReport), vp]
+    lib.kiss_hip_fmi_align_host.argtypes = [vp, u64, vp, vp, u64, ctypes.c_int, vp, vp, ctypes.POINTER(AlignParams), vp, u64, vp, vp,
+                                            u64, ctypes.POINTER(AlignReport), ctypes.c_int]
+    lib.kiss_hip_fmi_align_dev.restype = lib.kiss_hip_fmi_align_host.restype = ctypes.c_int
     lib.kiss_hip_fmi8_sizes_for.argtypes = [u64, u32, u32, ctypes.POINTER(Fmi8Sizes)]
     lib.kiss_hip_fmi8_build_dev.argtypes = [vp, vp, u64, vp, u32, u32] + [vp] * 8 + [ctypes.POINTER(u32), ctypes.POINTER(u32), vp]
     lib.kiss_hip_fmi8_build_host.argtypes = [vp, u64, vp, u32, u32] + [vp] * 8 + [ctypes.POINTER(u32), ctypes.POINTER(u32),
@@ -400,5 +428,5 @@ EXPORTED_SYMBOLS = [
     "kiss_hip_lcp_u8", "kiss_hip_fmi_query_mm_dev", "kiss_hip_fmi_query_mm_host",
     "kiss_hip_fmi8_sizes_for", "kiss_hip_fmi8_build_dev", "kiss_hip_fmi8_build_host", "kiss_hip_fmi8_query_dev",
     "kiss_hip_fmi8_query_host", "kiss_hip_fmi_seeds_dev", "kiss_hip_fmi_seeds_host",
-    "kiss_hip_fmi_chain_dev", "kiss_hip_fmi_chain_host",
+    "kiss_hip_fmi_chain_dev", "kiss_hip_fmi_chain_host", "kiss_hip_fmi_align_dev", "kiss_hip_fmi_align_host",
 ]

@@ -15,7 +15,9 @@
 //    with '>' and empty lines are skipped), one line per seed on stdout: read strand start len count pos...; also needs
 //    fmindex_build --exact; with --chain [--max-gap N] [--band N] [--gap-cost N] [--max-lookback N] [--min-chain-score N] the
 //    positions of the seeds of a read are chained into candidate loci (kiss_hip_fmi_chain_host) and the output is one line
-//    per chain instead: read strand score anchors rbeg rend tbeg tend)
+//    per chain instead: read strand score anchors rbeg rend tbeg tend; with --align on top [--match N] [--mismatch N]
+//    [--gap-open N] [--gap-extend N] [--align-band N] every chain is aligned to the text (kiss_hip_fmi_align_host: banded,
+//    affine gaps, local) and the line of a chain is: read strand score rbeg rend tbeg tend nm cigar)
 //   (-g / --generic: the file is a text over the byte alphabet, taken byte for byte -- no FASTA rule, no newline stripping,
 //    no % 4.  suffix_sort gives the exact suffix array (kiss_hip_suffix_sort_u8; -k and -s are ignored) and, with
 //    --output-lcp, its LCP array; fmindex_build writes <file>.fmi8 (kiss_hip_fmi8_build_host);
@@ -92,7 +94,15 @@ void usage()
               << "  --band NUM (=500)              largest difference between the two steps\n"
               << "  --gap-cost NUM (=2)            eighths of a point taken off per base of that difference\n"
               << "  --max-lookback NUM (=64)       predecessors tried per anchor (0: no bound)\n"
-              << "  --min-chain-score NUM (=40)    lowest score of a chain reported\n";
+              << "  --min-chain-score NUM (=40)    lowest score of a chain reported\n"
+              << "  --align                        with --chain: align every chain to the text (banded, affine gaps, local) and\n"
+              << "                                 print per chain: read strand score rbeg rend tbeg tend nm cigar (SAM style\n"
+              << "                                 with S clips; * when nothing aligns)\n"
+              << "  --match NUM (=1)               score of a matching column\n"
+              << "  --mismatch NUM (=4)            penalty of a mismatching column\n"
+              << "  --gap-open NUM (=6)            a gap of g bases costs gap-open + g * gap-extend\n"
+              << "  --gap-extend NUM (=1)\n"
+              << "  --align-band NUM (=32)         diagonals aligned on either side of the chain's own\n";
 }
 
 inline uint8_t to_code(unsigned char c)
@@ -172,6 +182,8 @@ struct Args {
     bool both_strands = false;
     bool chain = false; // fmindex_query --seeds READS --chain
     kiss_hip_chain_params chain_params{5000, 500, 2, 64, 40};
+    bool align = false; // fmindex_query --seeds READS --chain --align
+    kiss_hip_align_params align_params{1, 4, 6, 1, 32};
 };
 
 Args parse(int argc, char **argv)
@@ -186,7 +198,8 @@ Args parse(int argc, char **argv)
         };
         if (s == "--gpus" || s == "--devices" || s == "--lookup-len" || s == "--exact" || s == "--mismatches" || s == "--sa-intv" ||
             s == "--seeds" || s == "--min-seed-len" || s == "--max-seed-len" || s == "--max-occ" || s == "--both-strands" || s == "--chain" ||
-            s == "--max-gap" || s == "--band" || s == "--gap-cost" || s == "--max-lookback" || s == "--min-chain-score")
+            s == "--max-gap" || s == "--band" || s == "--gap-cost" || s == "--max-lookback" || s == "--min-chain-score" ||
+            s == "--align" || s == "--match" || s == "--mismatch" || s == "--gap-open" || s == "--gap-extend" || s == "--align-band")
             a.seen.push_back(s);
         if (s == "-k" || s == "--kordered") a.seen.push_back("--kordered");
         if (s == "-s" || s == "--sorting-algorithm") a.seen.push_back("--sorting-algorithm");
@@ -219,6 +232,12 @@ Args parse(int argc, char **argv)
         else if (s == "--gap-cost") a.chain_params.gap_cost = (uint32_t)std::stoul(next("--gap-cost"));
         else if (s == "--max-lookback") a.chain_params.max_lookback = (uint32_t)std::stoul(next("--max-lookback"));
         else if (s == "--min-chain-score") a.chain_params.min_score = (uint32_t)std::stoul(next("--min-chain-score"));
+        else if (s == "--align") a.align = true;
+        else if (s == "--match") a.align_params.match = (uint32_t)std::stoul(next("--match"));
+        else if (s == "--mismatch") a.align_params.mismatch = (uint32_t)std::stoul(next("--mismatch"));
+        else if (s == "--gap-open") a.align_params.gap_open = (uint32_t)std::stoul(next("--gap-open"));
+        else if (s == "--gap-extend") a.align_params.gap_extend = (uint32_t)std::stoul(next("--gap-extend"));
+        else if (s == "--align-band") a.align_params.band = (uint32_t)std::stoul(next("--align-band"));
         else if (s == "--devices") {
             const std::string list = next("--devices");
             size_t at = 0;
@@ -245,7 +264,15 @@ Args parse(int argc, char **argv)
             if (given_here(o) && !given_here("--seeds")) throw std::runtime_error(std::string(o) + " goes with --seeds");
         for (const char *o : {"--max-gap", "--band", "--gap-cost", "--max-lookback", "--min-chain-score"})
             if (given_here(o) && !given_here("--chain")) throw std::runtime_error(std::string(o) + " goes with --chain");
+        for (const char *o : {"--align", "--match", "--mismatch", "--gap-open", "--gap-extend", "--align-band"})
+            if (given_here(o) && !given_here("--chain")) throw std::runtime_error(std::string(o) + " goes with --chain");
+        for (const char *o : {"--match", "--mismatch", "--gap-open", "--gap-extend", "--align-band"})
+            if (given_here(o) && !given_here("--align")) throw std::runtime_error(std::string(o) + " goes with --align");
         if (given_here("--chain") && !given_here("--seeds")) throw std::runtime_error("--chain goes with --seeds");
+        if (a.align_params.match < 1 || a.align_params.match > 65535u || a.align_params.mismatch > 65535u ||
+            a.align_params.gap_open > 65535u || a.align_params.gap_extend > 65535u || a.align_params.band > 0x7FFFFFFFu)
+            throw std::runtime_error("--match is in 1..65535, --mismatch, --gap-open and --gap-extend are at most 65535, "
+                                     "--align-band at most 2147483647");
         if (a.chain_params.max_gap > 0x7FFFFFFFu || a.chain_params.band > 0x7FFFFFFFu || a.chain_params.gap_cost > 65535u)
             throw std::runtime_error("--max-gap and --band are at most 2147483647, --gap-cost at most 65535");
         if (given_here("--seeds")) {
@@ -630,9 +657,69 @@ MmHits mm_query(const Fmi &f, const uint8_t *pat, uint32_t L, uint64_t Q, uint32
     return h;
 }
 
+// fmindex_query --seeds READS --chain --align: one line per chain on stdout, `read strand score rbeg rend tbeg tend nm cigar`
+int align_main(const Args &a, uint64_t V, const std::vector<kiss_hip_chain> &chains, const std::vector<uint64_t> &cidx,
+               const std::vector<uint8_t> &reads, const std::vector<uint64_t> &ridx)
+{
+    std::vector<uint8_t> S;
+    {
+        DeviceText T(a.fasta, a.device);
+        S = T.to_host();
+    }
+    S.reserve(1); // (a pointer that is not NULL)
+    const uint64_t Q = ridx.size() - 1, C = cidx[V], n = S.size();
+    std::vector<kiss_hip_aln> alns(C + 1);
+    std::vector<uint32_t> cigar(1);
+    std::vector<uint64_t> oidx(C + 1, 0);
+    kiss_hip_align_report rep{};
+    // the first call sizes the ops
+    int rc = kiss_hip_fmi_align_host(S.data(), n, reads.data(), ridx.data(), Q, a.both_strands, chains.data(), cidx.data(),
+                                     &a.align_params, alns.data(), C, cigar.data(), oidx.data(), 0, &rep, a.device);
+    if (rc == KISS_HIP_E_INVALID && rep.cigar_ops) {
+        cigar.resize(rep.cigar_ops);
+        rc = kiss_hip_fmi_align_host(S.data(), n, reads.data(), ridx.data(), Q, a.both_strands, chains.data(), cidx.data(),
+                                     &a.align_params, alns.data(), C, cigar.data(), oidx.data(), rep.cigar_ops, &rep, a.device);
+    }
+    if (rc == KISS_HIP_E_UNSUPPORTED && rep.cells)
+        throw std::runtime_error("fmindex_query --align: " + std::to_string(rep.cells) +
+                                 " DP cells are more than one call holds: split the reads");
+    check(rc, "kiss_hip_fmi_align_host");
+    std::string out;
+    for (uint64_t vr = 0; vr < V; vr++) {
+        const uint64_t q = a.both_strands ? vr / 2 : vr, L = ridx[q + 1] - ridx[q];
+        const char strand = a.both_strands && (vr & 1) ? '-' : '+';
+        for (uint64_t c = cidx[vr]; c < cidx[vr + 1]; c++) {
+            const kiss_hip_aln &k = alns[c];
+            out += std::to_string(q) + ' ' + strand + ' ' + std::to_string(k.score) + ' ' + std::to_string(k.rbeg) + ' ' +
+                   std::to_string(k.rend) + ' ' + std::to_string(k.tbeg) + ' ' + std::to_string(k.tend) + ' ' +
+                   std::to_string(k.mismatches + k.ins + k.del) + ' ';
+            if (oidx[c + 1] == oidx[c]) {
+                out += '*';
+            } else {
+                if (k.rbeg) out += std::to_string(k.rbeg) + 'S';
+                for (uint64_t o = oidx[c]; o < oidx[c + 1]; o++) out += std::to_string(cigar[o] >> 4) + "MID"[cigar[o] & 15u];
+                if (L > k.rend) out += std::to_string(L - k.rend) + 'S';
+            }
+            out += '\n';
+        }
+        if (out.size() > (1u << 20)) {
+            std::fwrite(out.data(), 1, out.size(), stdout);
+            out.clear();
+        }
+    }
+    std::fwrite(out.data(), 1, out.size(), stdout);
+    std::fflush(stdout);
+    std::fprintf(stderr, "[info] virtual reads: %llu, chains: %llu, aligned: %llu, band too wide: %llu, best score: %u\n",
+                 (unsigned long long)V, (unsigned long long)rep.chains, (unsigned long long)rep.aligned,
+                 (unsigned long long)rep.too_wide, rep.best_score);
+    return 0;
+}
+
 // fmindex_query --seeds READS --chain: one line per chain on stdout, `read strand score anchors rbeg rend tbeg tend`
+// (with --align: `read strand score rbeg rend tbeg tend nm cigar`, the fields of the alignment of the chain)
 int chains_main(const Args &a, uint64_t V, const std::vector<kiss_hip_fmi_seed> &seeds, const std::vector<uint64_t> &sidx,
-                const std::vector<uint32_t> &pos, const std::vector<uint64_t> &pidx)
+                const std::vector<uint32_t> &pos, const std::vector<uint64_t> &pidx, const std::vector<uint8_t> &reads,
+                const std::vector<uint64_t> &ridx)
 {
     std::vector<kiss_hip_chain> chains(1);
     std::vector<uint64_t> cidx(V + 1, 0);
@@ -646,6 +733,7 @@ int chains_main(const Args &a, uint64_t V, const std::vector<kiss_hip_fmi_seed> 
                                      cidx.data(), rep.chains, nullptr, nullptr, 0, &rep, a.device);
     }
     check(rc, "kiss_hip_fmi_chain_host");
+    if (a.align) return align_main(a, V, chains, cidx, reads, ridx);
     std::string out;
     for (uint64_t vr = 0; vr < V; vr++) {
         const uint64_t q = a.both_strands ? vr / 2 : vr;
@@ -713,7 +801,7 @@ int seeds_main(const Args &a, const Fmi &f)
                                  " rows of the index reached no sampled row: the positions need an index built with "
                                  "fmindex_build --exact");
     check(rc, "kiss_hip_fmi_seeds_host");
-    if (a.chain) return chains_main(a, V, seeds, sidx, pos, pidx);
+    if (a.chain) return chains_main(a, V, seeds, sidx, pos, pidx, reads, ridx);
     std::string out;
     for (uint64_t vr = 0; vr < V; vr++) {
         const uint64_t q = a.both_strands ? vr / 2 : vr;

@@ -539,7 +539,8 @@ class FMIndex:
         # the ends of a call are scanned in the context's scratch (0.32 max_n entries)
         ctx = self._context(min(_lib.MAX_N, max(self.N, 4 * (bases + 1))))
         _check(call(ctx, None, None, 0), "kiss_hip_fmi_seeds_dev", ctx._ctx)
-        out = {"d_seeds": d_seeds, "d_sidx": d_sidx, "d_ms": d_ms, "rep": rep, "V": V, "bases": bases, "total": 0}
+        out = {"d_seeds": d_seeds, "d_sidx": d_sidx, "d_ms": d_ms, "rep": rep, "V": V, "bases": bases, "total": 0,
+               "d_reads": d_reads, "d_ridx": d_index, "Q": Q}
         if want_positions:
             total, nseeds = int(rep.positions), int(rep.seeds)
             if total > 0.3 * ctx.max_n:  # one call sorts its positions in the context's LMS arrays: a context sized for them
@@ -579,6 +580,56 @@ class FMIndex:
                         want_anchors)
         res = chain_arrays(out, want_anchors)
         res["seed_report"] = d["rep"].as_dict()
+        return res
+
+    # ---- the chains aligned to the text (kiss_hip_fmi_align_dev; no reference counterpart) ----------------------------
+    def align(self, reads, text, min_len=19, max_len=0, max_occ=500, both_strands=False, chain_params=None, want_cigar=True,
+              **params):
+        """Seeds, chains and the banded affine-gap local alignment of every chain to the text (include/kiss_hip.h has the
+        definition), with the reads, the seeds and the chains staying on the device.  text: the bases the index was built
+        from (the index does not keep them), a uint8 array or a device tensor; reads and the seed parameters as in seeds();
+        chain_params: a dict of the parameters of chains(); params: match (1), mismatch (4), gap_open (6), gap_extend (1),
+        band (32).  Returns what chains() returns plus alignments (structured array: score, flags, rbeg, rend, tbeg, tend,
+        matches, mismatches, ins, del, gaps, band; alignment c belongs to chain c), align_report and, with want_cigar,
+        cigar (u32 ops len << 4 | op, op 0 M, 1 I, 2 D) / cigar_index in CSR layout over the chains."""
+        from .fm_align import ALIGN_CELLS_PER_N, ALIGN_MAX_BAND, align_arrays, align_dev, align_params
+        from .fm_chain import chain_params as make_chain_params, chain_dev, chain_arrays
+        torch = _torch()
+        p = align_params(**params)
+        cp = make_chain_params(**(chain_params or {}))
+        dev = torch.device("cuda", self.device)
+        if isinstance(text, torch.Tensor):
+            d_text = text.to(device=dev, dtype=torch.uint8).contiguous().reshape(-1)
+        else:
+            arr = np.ascontiguousarray(text, dtype=np.uint8).ravel()
+            d_text = torch.from_numpy(arr).to(dev) if arr.size else torch.zeros(0, dtype=torch.uint8, device=dev)
+        n = int(d_text.numel())
+        if n == 0:
+            d_text = torch.zeros(1, dtype=torch.uint8, device=dev)
+        d = self._seeds_dev(reads, min_len, max_len, max_occ, both_strands, True, False)
+        ctx = d["ctx"]
+        if d["total"] > 0.3 * ctx.max_n:  # (the anchors are sorted where the positions were)
+            ctx = self._context(min(_lib.MAX_N, int(3.3 * d["total"]) + (1 << 20)))
+        lib = _lib.load(self._hooks)
+        out = chain_dev(lib, ctx, self.device, d["d_seeds"], d["d_sidx"], d["V"], d["d_pos"], d["d_pidx"], cp, False)
+        res = chain_arrays(out, False)
+        res["seed_report"] = d["rep"].as_dict()
+        C = int(out["rep"].chains)
+        # the traceback store holds ALIGN_CELLS_PER_N cells per base of the context: a context sized for this batch
+        ridx = d["d_ridx"].cpu().numpy().view(np.uint64)
+        lens = (ridx[1:] - ridx[:-1]).astype(np.int64)
+        per_v = np.diff(res["chain_index"].astype(np.int64))
+        vlen = np.repeat(lens, 2) if both_strands else lens
+        ch = res["chains"]
+        d0 = ch["tbeg"].astype(np.int64) - ch["rbeg"].astype(np.int64)
+        d1 = ch["tend"].astype(np.int64) - ch["rend"].astype(np.int64)
+        B = np.abs(d0 - d1) + 2 * int(p.band) + 1
+        cells = int((np.repeat(vlen, per_v) * np.where(B > ALIGN_MAX_BAND, 0, B)).sum()) if C else 0
+        if cells > ALIGN_CELLS_PER_N * ctx.max_n:
+            ctx = self._context(min(_lib.MAX_N, cells // ALIGN_CELLS_PER_N + (1 << 20)))
+        al = align_dev(lib, ctx, self.device, d_text, n, d["d_reads"], d["d_ridx"], d["Q"], both_strands, out["d_chains"],
+                       out["d_cidx"], C, p, want_cigar)
+        res.update(align_arrays(al, want_cigar))
         return res
 
     def close(self):
