@@ -807,6 +807,79 @@ int kiss_hip_fmi_align_host(const uint8_t *text, uint64_t n, const uint8_t *read
                             const kiss_hip_align_params *params, kiss_hip_aln *alns, uint64_t aln_capacity, uint32_t *cigar,
                             uint64_t *cigar_index, uint64_t cigar_capacity, kiss_hip_align_report *report, int device);
 
+/* ---- FM-index: the alignments of a read turned into its mappings: primary, secondary, MAPQ (no reference counterpart) ---
+ * The align call writes one record per CHAIN.  Two neighbouring chains routinely give the same alignment (see the two KNOWN
+ * PROPERTY notes above), both strands may reach one locus, a repeat gives many.  This call says which alignment is the
+ * mapping, which are the same locus twice, which are repeats and how far the best can be trusted, and which reads did not
+ * map.  One definition in integers; tests/fm_select_model.py restates it.  The result is a function of the input arrays and
+ * the parameters alone; it needs no index, no text and no reads.
+ * Input: alns with chain_index (V + 1 u64) exactly as kiss_hip_fmi_align_dev wrote and read them: C = chain_index[V] -
+ * chain_index[0], and alignment a (0 <= a < C, alns[a]) belongs to the virtual read v that contains chain_index[0] + a.
+ * read_index (Q + 1 u64): only the lengths L_q = read_index[q + 1] - read_index[q] are used.  Q and both_strands: V = 2 Q or
+ * Q; read q owns the virtual reads 2 q and 2 q + 1, or just q, so its alignments are one contiguous stretch of alns.
+ * bounds, optional: R + 1 u64, bounds[0] = 0, strictly ascending -- the starts of the R records of the text, bounds[R] = n.
+ * NULL (R is then ignored): one record and no boundary rule.
+ * Parameters (kiss_hip_select_params, all u32; in parentheses the defaults of Python and the command line): min_score (30),
+ * overlap (128, in 256ths; at most 256), mapq_coef (120; at most 65535), mapq_max (60; at most 255), max_hits (0 = all).
+ * Strand and frames: alignment a of virtual read v is on the reverse strand iff both_strands and v is odd.  Its text interval
+ * is [tbeg, tend).  Its read interval in the frame of the ORIGINAL read is [rbeg, rend) on the forward strand and
+ * [L - rend, L - rbeg) on the reverse strand.  All interval arithmetic is signed 64-bit; the length |X| of an interval is
+ * max(0, x1 - x0), so a record with tend < tbeg overlaps nothing.
+ * Candidates: alignment a of read q is a candidate iff flags == 0, score >= max(min_score, 1) and, if bounds is given, its
+ * record rho (the largest rho with bounds[rho] <= tbeg) has rho < R and tend <= bounds[rho + 1].  An alignment that fails only
+ * the third condition is SPANNING: counted in the report, not a candidate (a tbeg at or past bounds[R] too).
+ * Order: the candidates of a read in descending score, then ascending a.
+ * Overlap: ov(X, Y) = max(0, min(x1, y1) - max(x0, y0)); X and Y "overlap by more than the share" iff
+ * ov * 256 > overlap * min(|X|, |Y|), in u64.  So overlap = 256 never holds and overlap = 0 holds for any common base.
+ * Walk -- greedy, and the order is part of the definition.  Go through the candidates in order, K = the kept ones so far:
+ *   1. candidate c is REDUNDANT iff some k in K has c's strand and their text intervals overlap by more than the share: c is
+ *      dropped and counted.  Only KEPT alignments make others redundant.
+ *   2. otherwise c is kept as hit number h = |K| of its read.  Let g be the HEAD in K with the smallest hit number whose read
+ *      interval overlaps c's by more than the share.  If g exists, c is SECONDARY, head(c) = g, g.n_sec += 1, g.sub =
+ *      max(g.sub, score(c)).  Otherwise c is a HEAD, head(c) = h; the first head of a read is its PRIMARY, every later head
+ *      is SUPPLEMENTARY.
+ * MAPQ: a secondary has 0.  A head with s = score and s2 = sub (0 when n_sec = 0) has min(mapq_max, floor(mapq_coef *
+ * (s - s2) / s)), in u64: a head whose best secondary ties it has 0, a head with no secondary min(mapq_max, mapq_coef).
+ * Cap: with max_hits != 0 only the hits with number < max_hits are written; sub, n_sec and mapq are computed before the cap;
+ * head points at an earlier hit or at the hit itself, so it stays valid.
+ * Output: hits with hit_index (Q + 1 u64, CSR over the READS, not the virtual reads), in hit-number order.  Record
+ * kiss_hip_hit, 8 u32: aln (a), flags, mapq, score, sub, n_sec, head, ref (rho; 0 without bounds); sub and n_sec of a secondary
+ * are 0.  A read with no candidate has an empty segment.
+ * Report: Q, V, alignments (C), candidates, spanning, redundant, hits (written, that is after the cap), heads (among the
+ * written hits), mapped (reads with at least one hit), max_candidates (the largest candidate count of a read), times.
+ * hit_capacity below the total: KISS_HIP_E_INVALID with the totals in the report, nothing written; call again with room.
+ * A read keeps no more hits than it has alignments, so hit_capacity = C always suffices and no sizing call is needed.
+ * hits and alns need no more than the 4-byte alignment of their fields: records are read and written field by field.
+ * Other KISS_HIP_E_INVALID: a required pointer NULL, a chain_index or read_index that decreases, a zero-length read, bounds
+ * with bounds[0] != 0 or not strictly ascending (or R == 0), a parameter over its limit.  Q == 0 or C == 0: KISS_HIP_OK,
+ * hit_index all zero.
+ * Limits (KISS_HIP_E_UNSUPPORTED): V of 2^31 or more, C of 2^32 or more; more alignments in one call than the ctx's LMS work
+ * arrays hold (about 0.32 x max_n entries; their contents are lost: the alignments are sorted there) -- split the batch.
+ * KNOWN PROPERTY: the walk of a read is sequential in its candidates and parallel over the kept hits, 64 per step: a read with
+ * c candidates of which k are kept costs about c * ceil(k / 64) steps of one wave.  A read with thousands of candidates is
+ * slow, and finite.
+ * Device times: report->ms_* (report may be NULL); the kernels also count under KISS_HIP_K_FM_QUERY. */
+#define KISS_HIP_HIT_REVERSE 1u
+#define KISS_HIP_HIT_SECONDARY 2u
+#define KISS_HIP_HIT_SUPPLEMENTARY 4u
+typedef struct kiss_hip_select_params { uint32_t min_score, overlap, mapq_coef, mapq_max, max_hits; } kiss_hip_select_params;
+typedef struct kiss_hip_hit { uint32_t aln, flags, mapq, score, sub, n_sec, head, ref; } kiss_hip_hit;
+typedef struct kiss_hip_select_report {
+    uint64_t Q, V, alignments, candidates, spanning, redundant, hits, heads, mapped;
+    uint32_t max_candidates, reserved_;
+    float ms_total, ms_sort, ms_walk, ms_emit; /* sort: checks, keys, the radix sort; emit: scan, totals, records */
+} kiss_hip_select_report;
+/* every pointer except params and report is a device pointer */
+int kiss_hip_fmi_select_dev(kiss_hip_ctx *ctx, const kiss_hip_aln *alns, const uint64_t *chain_index, const uint64_t *read_index,
+                            uint64_t Q, int both_strands, const uint64_t *bounds, uint64_t R, const kiss_hip_select_params *params,
+                            kiss_hip_hit *hits, uint64_t *hit_index, uint64_t hit_capacity, kiss_hip_select_report *report,
+                            void *stream);
+/* the same with host pointers (the device's cached one-shot context, as kiss_hip_fmi_chain_host) */
+int kiss_hip_fmi_select_host(const kiss_hip_aln *alns, const uint64_t *chain_index, const uint64_t *read_index, uint64_t Q,
+                             int both_strands, const uint64_t *bounds, uint64_t R, const kiss_hip_select_params *params,
+                             kiss_hip_hit *hits, uint64_t *hit_index, uint64_t hit_capacity, kiss_hip_select_report *report,
+                             int device);
+
 #ifdef __cplusplus
 }
 #endif

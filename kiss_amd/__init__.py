@@ -9,3 +9,4 @@ from .sorter import (K_UNBOUNDED, Context, KISS1Sorter, KISS2Sorter, MultiContex
 from .fm_index_bytes import FMIndexBytes  # noqa: F401,E402
 from .fm_chain import chain_seeds  # noqa: F401,E402
 from .fm_align import ALIGN_DEFAULTS, align_chains, align_params  # noqa: F401,E402
+from .fm_select import SELECT_DEFAULTS, select_alignments, select_params  # noqa: F401,E402

@@ -199,6 +199,28 @@ class AlignReport(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class SelectParams(ctypes.Structure):
+    """kiss_hip_select_params"""
+    _fields_ = [(k, ctypes.c_uint32) for k in ("min_score", "overlap", "mapq_coef", "mapq_max", "max_hits")]
+
+
+class Hit(ctypes.Structure):
+    """kiss_hip_hit"""
+    _fields_ = [(k, ctypes.c_uint32) for k in ("aln", "flags", "mapq", "score", "sub", "n_sec", "head", "ref")]
+
+
+class SelectReport(ctypes.Structure):
+    """kiss_hip_select_report"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("Q", "V", "alignments", "candidates", "spanning", "redundant", "hits", "heads",
+                                               "mapped")] + [
+        ("max_candidates", ctypes.c_uint32), ("reserved_", ctypes.c_uint32), ("ms_total", ctypes.c_float),
+        ("ms_sort", ctypes.c_float), ("ms_walk", ctypes.c_float), ("ms_emit", ctypes.c_float),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved_"}
+
+
 class Fmi8View(ctypes.Structure):
     """kiss_hip_fmi8_view"""
     _fields_ = [
@@ -353,6 +375,11 @@ def load(hooks=None):
     lib.kiss_hip_fmi_align_host.argtypes = [vp, u64, vp, vp, u64, ctypes.c_int, vp, vp, ctypes.POINTER(AlignParams), vp, u64, vp, vp,
                                             u64, ctypes.POINTER(AlignReport), ctypes.c_int]
     lib.kiss_hip_fmi_align_dev.restype = lib.kiss_hip_fmi_align_host.restype = ctypes.c_int
+    lib.kiss_hip_fmi_select_dev.argtypes = [vp, vp, vp, vp, u64, ctypes.c_int, vp, u64, ctypes.POINTER(SelectParams), vp, vp, u64,
+                                            ctypes.POINTER(SelectReport), vp]
+    lib.kiss_hip_fmi_select_host.argtypes = [vp, vp, vp, u64, ctypes.c_int, vp, u64, ctypes.POINTER(SelectParams), vp, vp, u64,
+                                             ctypes.POINTER(SelectReport), ctypes.c_int]
+    lib.kiss_hip_fmi_select_dev.restype = lib.kiss_hip_fmi_select_host.restype = ctypes.c_int
     lib.kiss_hip_fmi8_sizes_for.argtypes = [u64, u32, u32, ctypes.POINTER(Fmi8Sizes)]
     lib.kiss_hip_fmi8_build_dev.argtypes = [vp, vp, u64, vp, u32, u32] + [vp] * 8 + [ctypes.POINTER(u32), ctypes.POINTER(u32), vp]
     lib.kiss_hip_fmi8_build_host.argtypes = [vp, u64, vp, u32, u32] + [vp] * 8 + [ctypes.POINTER(u32), ctypes.POINTER(u32),
@@ -429,4 +456,5 @@ EXPORTED_SYMBOLS = [
     "kiss_hip_fmi8_sizes_for", "kiss_hip_fmi8_build_dev", "kiss_hip_fmi8_build_host", "kiss_hip_fmi8_query_dev",
     "kiss_hip_fmi8_query_host", "kiss_hip_fmi_seeds_dev", "kiss_hip_fmi_seeds_host",
     "kiss_hip_fmi_chain_dev", "kiss_hip_fmi_chain_host", "kiss_hip_fmi_align_dev", "kiss_hip_fmi_align_host",
+    "kiss_hip_fmi_select_dev", "kiss_hip_fmi_select_host",
 ]

@@ -17,6 +17,8 @@
 //    positions of the seeds of a read are chained into candidate loci (kiss_hip_fmi_chain_host) and the output is one line
 //    per chain instead: read strand score anchors rbeg rend tbeg tend; with --align on top [--match N] [--mismatch N]
 //    [--gap-open N] [--gap-extend N] [--align-band N] every chain is aligned to the text (kiss_hip_fmi_align_host: banded,
+//    and with --sam on top [--min-map-score N] [--overlap N] [--mapq-coef N] [--mapq-max N] [--max-hits N] the alignments of
+//    a read are turned into its mappings (kiss_hip_fmi_select_host) and stdout is SAM: one line per hit, one per unmapped read;
 //    affine gaps, local) and the line of a chain is: read strand score rbeg rend tbeg tend nm cigar)
 //   (-g / --generic: the file is a text over the byte alphabet, taken byte for byte -- no FASTA rule, no newline stripping,
 //    no % 4.  suffix_sort gives the exact suffix array (kiss_hip_suffix_sort_u8; -k and -s are ignored) and, with
@@ -102,7 +104,16 @@ void usage()
               << "  --mismatch NUM (=4)            penalty of a mismatching column\n"
               << "  --gap-open NUM (=6)            a gap of g bases costs gap-open + g * gap-extend\n"
               << "  --gap-extend NUM (=1)\n"
-              << "  --align-band NUM (=32)         diagonals aligned on either side of the chain's own\n";
+              << "  --align-band NUM (=32)         diagonals aligned on either side of the chain's own\n"
+              << "  --sam                          with --align: pick the mappings of every read (primary, secondary,\n"
+              << "                                 supplementary, MAPQ) and print SAM instead: a header with one @SQ per record\n"
+              << "                                 of the reference file, one line per hit, one line (FLAG 4) per unmapped read\n"
+              << "  --min-map-score NUM (=30)      lowest alignment score of a mapping\n"
+              << "  --overlap NUM (=128)           share of the shorter interval, in 256ths (0..256), above which two\n"
+              << "                                 alignments are the same locus (in the text) or compete (in the read)\n"
+              << "  --mapq-coef NUM (=120)         MAPQ = min(mapq-max, mapq-coef * (score - best secondary) / score)\n"
+              << "  --mapq-max NUM (=60)\n"
+              << "  --max-hits NUM (=0)            hits written per read (0: all)\n";
 }
 
 inline uint8_t to_code(unsigned char c)
@@ -184,6 +195,8 @@ struct Args {
     kiss_hip_chain_params chain_params{5000, 500, 2, 64, 40};
     bool align = false; // fmindex_query --seeds READS --chain --align
     kiss_hip_align_params align_params{1, 4, 6, 1, 32};
+    bool sam = false; // fmindex_query --seeds READS --chain --align --sam
+    kiss_hip_select_params select_params{30, 128, 120, 60, 0};
 };
 
 Args parse(int argc, char **argv)
@@ -199,7 +212,8 @@ Args parse(int argc, char **argv)
         if (s == "--gpus" || s == "--devices" || s == "--lookup-len" || s == "--exact" || s == "--mismatches" || s == "--sa-intv" ||
             s == "--seeds" || s == "--min-seed-len" || s == "--max-seed-len" || s == "--max-occ" || s == "--both-strands" || s == "--chain" ||
             s == "--max-gap" || s == "--band" || s == "--gap-cost" || s == "--max-lookback" || s == "--min-chain-score" ||
-            s == "--align" || s == "--match" || s == "--mismatch" || s == "--gap-open" || s == "--gap-extend" || s == "--align-band")
+            s == "--align" || s == "--match" || s == "--mismatch" || s == "--gap-open" || s == "--gap-extend" || s == "--align-band" ||
+            s == "--sam" || s == "--min-map-score" || s == "--overlap" || s == "--mapq-coef" || s == "--mapq-max" || s == "--max-hits")
             a.seen.push_back(s);
         if (s == "-k" || s == "--kordered") a.seen.push_back("--kordered");
         if (s == "-s" || s == "--sorting-algorithm") a.seen.push_back("--sorting-algorithm");
@@ -238,6 +252,12 @@ Args parse(int argc, char **argv)
         else if (s == "--gap-open") a.align_params.gap_open = (uint32_t)std::stoul(next("--gap-open"));
         else if (s == "--gap-extend") a.align_params.gap_extend = (uint32_t)std::stoul(next("--gap-extend"));
         else if (s == "--align-band") a.align_params.band = (uint32_t)std::stoul(next("--align-band"));
+        else if (s == "--sam") a.sam = true;
+        else if (s == "--min-map-score") a.select_params.min_score = (uint32_t)std::stoul(next("--min-map-score"));
+        else if (s == "--overlap") a.select_params.overlap = (uint32_t)std::stoul(next("--overlap"));
+        else if (s == "--mapq-coef") a.select_params.mapq_coef = (uint32_t)std::stoul(next("--mapq-coef"));
+        else if (s == "--mapq-max") a.select_params.mapq_max = (uint32_t)std::stoul(next("--mapq-max"));
+        else if (s == "--max-hits") a.select_params.max_hits = (uint32_t)std::stoul(next("--max-hits"));
         else if (s == "--devices") {
             const std::string list = next("--devices");
             size_t at = 0;
@@ -269,6 +289,11 @@ Args parse(int argc, char **argv)
         for (const char *o : {"--match", "--mismatch", "--gap-open", "--gap-extend", "--align-band"})
             if (given_here(o) && !given_here("--align")) throw std::runtime_error(std::string(o) + " goes with --align");
         if (given_here("--chain") && !given_here("--seeds")) throw std::runtime_error("--chain goes with --seeds");
+        if (given_here("--sam") && !given_here("--align")) throw std::runtime_error("--sam goes with --align");
+        for (const char *o : {"--min-map-score", "--overlap", "--mapq-coef", "--mapq-max", "--max-hits"})
+            if (given_here(o) && !given_here("--sam")) throw std::runtime_error(std::string(o) + " goes with --sam");
+        if (a.select_params.overlap > 256u || a.select_params.mapq_coef > 65535u || a.select_params.mapq_max > 255u)
+            throw std::runtime_error("--overlap is at most 256, --mapq-coef at most 65535, --mapq-max at most 255");
         if (a.align_params.match < 1 || a.align_params.match > 65535u || a.align_params.mismatch > 65535u ||
             a.align_params.gap_open > 65535u || a.align_params.gap_extend > 65535u || a.align_params.band > 0x7FFFFFFFu)
             throw std::runtime_error("--match is in 1..65535, --mismatch, --gap-open and --gap-extend are at most 65535, "
@@ -657,9 +682,117 @@ MmHits mm_query(const Fmi &f, const uint8_t *pat, uint32_t L, uint64_t Q, uint32
     return h;
 }
 
+// The records of the reference file, scanned on the host under the parse rules of fasta.hip: the file is FASTA iff its first
+// byte is '>'; a line that begins with '>' is a header unless the line in front of it was one (the line after a header is
+// always sequence); every byte of a sequence line except '\n' is a base.  A plain-text file is one record named after the
+// file.  Records without bases are left out (SAM has no LN:0, and the record starts must ascend strictly).
+struct RefRecords {
+    std::vector<std::string> names;
+    std::vector<uint64_t> bounds{0};
+};
+RefRecords scan_records(const std::string &path)
+{
+    std::ifstream in(path, std::ios::binary);
+    if (!in) throw std::runtime_error("cannot open " + path);
+    RefRecords r;
+    std::string name = path.substr(path.find_last_of('/') == std::string::npos ? 0 : path.find_last_of('/') + 1);
+    uint64_t len = 0;
+    const auto close = [&]() {
+        if (len) {
+            r.names.push_back(name);
+            r.bounds.push_back(r.bounds.back() + len);
+        }
+        len = 0;
+    };
+    const int first = in.peek();
+    const bool fasta = first == '>';
+    bool after_header = false;
+    std::string line;
+    while (std::getline(in, line)) {
+        if (fasta && !after_header && !line.empty() && line[0] == '>') {
+            close();
+            const size_t ws = line.find_first_of(" \t\r", 1);
+            name = line.substr(1, ws == std::string::npos ? std::string::npos : ws - 1);
+            after_header = true;
+            continue;
+        }
+        after_header = false;
+        len += line.size();
+    }
+    close();
+    return r;
+}
+
+// fmindex_query --seeds READS --chain --align --sam: the alignments of every read turned into its mappings, stdout is SAM
+int sam_main(const Args &a, uint64_t C, uint64_t n, const std::vector<kiss_hip_aln> &alns, const std::vector<uint64_t> &cidx,
+             const std::vector<uint32_t> &cigar, const std::vector<uint64_t> &oidx, const std::vector<uint8_t> &reads,
+             const std::vector<uint64_t> &ridx, const std::vector<std::string> &names)
+{
+    const uint64_t Q = ridx.size() - 1;
+    const RefRecords ref = scan_records(a.fasta);
+    if (ref.bounds.back() != n)
+        throw std::runtime_error("fmindex_query --sam: the records of " + a.fasta + " have " + std::to_string(ref.bounds.back()) +
+                                 " bases, the parsed text has " + std::to_string(n));
+    const uint64_t R = ref.names.size();
+    std::vector<kiss_hip_hit> hits(C + 1); // (a read keeps no more hits than it has alignments: one call)
+    std::vector<uint64_t> hidx(Q + 1, 0);
+    kiss_hip_select_report rep{};
+    check(kiss_hip_fmi_select_host(alns.data(), cidx.data(), ridx.data(), Q, a.both_strands, R ? ref.bounds.data() : nullptr, R,
+                                   &a.select_params, hits.data(), hidx.data(), C, &rep, a.device),
+          "kiss_hip_fmi_select_host");
+    std::string out = "@HD\tVN:1.6\tSO:unsorted\n";
+    for (uint64_t r = 0; r < R; r++)
+        out += "@SQ\tSN:" + ref.names[r] + "\tLN:" + std::to_string(ref.bounds[r + 1] - ref.bounds[r]) + '\n';
+    out += std::string("@PG\tID:kiss\tPN:kiss\tVN:") + VERSION + '\n';
+    for (uint64_t q = 0; q < Q; q++) {
+        const uint64_t L = ridx[q + 1] - ridx[q];
+        const auto seq = [&](bool reverse) {
+            std::string s(L, 'N');
+            for (uint64_t j = 0; j < L; j++) {
+                const uint8_t c = reads[ridx[q] + (reverse ? L - 1 - j : j)];
+                if (c <= 3) s[j] = "ACGT"[reverse ? 3 - c : c];
+            }
+            return s;
+        };
+        if (hidx[q + 1] == hidx[q]) {
+            out += names[q] + "\t4\t*\t0\t0\t*\t*\t0\t0\t" + seq(false) + "\t*\n";
+            continue;
+        }
+        for (uint64_t h = hidx[q]; h < hidx[q + 1]; h++) {
+            const kiss_hip_hit &t = hits[h];
+            const uint64_t c = t.aln; // (alignment a: alns[a] and the ops oidx[a] .. oidx[a + 1])
+            const kiss_hip_aln &k = alns[c];
+            const bool reverse = (t.flags & KISS_HIP_HIT_REVERSE) != 0, head = !(t.flags & KISS_HIP_HIT_SECONDARY);
+            const unsigned flag = (reverse ? 16u : 0u) | (t.flags & KISS_HIP_HIT_SECONDARY ? 256u : 0u) |
+                                  (t.flags & KISS_HIP_HIT_SUPPLEMENTARY ? 2048u : 0u);
+            out += names[q] + '\t' + std::to_string(flag) + '\t' + (R ? ref.names[t.ref] : std::string("*")) + '\t' +
+                   std::to_string((uint64_t)k.tbeg - (R ? ref.bounds[t.ref] : 0) + 1) + '\t' + std::to_string(t.mapq) + '\t';
+            if (k.rbeg) out += std::to_string(k.rbeg) + 'S';
+            for (uint64_t o = oidx[c]; o < oidx[c + 1]; o++) out += std::to_string(cigar[o] >> 4) + "MID"[cigar[o] & 15u];
+            if (L > k.rend) out += std::to_string(L - k.rend) + 'S';
+            out += "\t*\t0\t0\t" + seq(reverse) + "\t*\tNM:i:" + std::to_string(k.mismatches + k.ins + k.del) + "\tAS:i:" +
+                   std::to_string(t.score);
+            if (head) out += "\tXS:i:" + std::to_string(t.sub);
+            out += '\n';
+        }
+        if (out.size() > (1u << 20)) {
+            std::fwrite(out.data(), 1, out.size(), stdout);
+            out.clear();
+        }
+    }
+    std::fwrite(out.data(), 1, out.size(), stdout);
+    std::fflush(stdout);
+    std::fprintf(stderr, "[info] reads: %llu, alignments: %llu, candidates: %llu, spanning: %llu, redundant: %llu, hits: %llu, "
+                         "heads: %llu, mapped: %llu, most candidates of a read: %u\n",
+                 (unsigned long long)Q, (unsigned long long)rep.alignments, (unsigned long long)rep.candidates,
+                 (unsigned long long)rep.spanning, (unsigned long long)rep.redundant, (unsigned long long)rep.hits,
+                 (unsigned long long)rep.heads, (unsigned long long)rep.mapped, rep.max_candidates);
+    return 0;
+}
+
 // fmindex_query --seeds READS --chain --align: one line per chain on stdout, `read strand score rbeg rend tbeg tend nm cigar`
 int align_main(const Args &a, uint64_t V, const std::vector<kiss_hip_chain> &chains, const std::vector<uint64_t> &cidx,
-               const std::vector<uint8_t> &reads, const std::vector<uint64_t> &ridx)
+               const std::vector<uint8_t> &reads, const std::vector<uint64_t> &ridx, const std::vector<std::string> &names)
 {
     std::vector<uint8_t> S;
     {
@@ -684,6 +817,7 @@ int align_main(const Args &a, uint64_t V, const std::vector<kiss_hip_chain> &cha
         throw std::runtime_error("fmindex_query --align: " + std::to_string(rep.cells) +
                                  " DP cells are more than one call holds: split the reads");
     check(rc, "kiss_hip_fmi_align_host");
+    if (a.sam) return sam_main(a, C, n, alns, cidx, cigar, oidx, reads, ridx, names);
     std::string out;
     for (uint64_t vr = 0; vr < V; vr++) {
         const uint64_t q = a.both_strands ? vr / 2 : vr, L = ridx[q + 1] - ridx[q];
@@ -719,7 +853,7 @@ int align_main(const Args &a, uint64_t V, const std::vector<kiss_hip_chain> &cha
 // (with --align: `read strand score rbeg rend tbeg tend nm cigar`, the fields of the alignment of the chain)
 int chains_main(const Args &a, uint64_t V, const std::vector<kiss_hip_fmi_seed> &seeds, const std::vector<uint64_t> &sidx,
                 const std::vector<uint32_t> &pos, const std::vector<uint64_t> &pidx, const std::vector<uint8_t> &reads,
-                const std::vector<uint64_t> &ridx)
+                const std::vector<uint64_t> &ridx, const std::vector<std::string> &names)
 {
     std::vector<kiss_hip_chain> chains(1);
     std::vector<uint64_t> cidx(V + 1, 0);
@@ -733,7 +867,7 @@ int chains_main(const Args &a, uint64_t V, const std::vector<kiss_hip_fmi_seed> 
                                      cidx.data(), rep.chains, nullptr, nullptr, 0, &rep, a.device);
     }
     check(rc, "kiss_hip_fmi_chain_host");
-    if (a.align) return align_main(a, V, chains, cidx, reads, ridx);
+    if (a.align) return align_main(a, V, chains, cidx, reads, ridx, names);
     std::string out;
     for (uint64_t vr = 0; vr < V; vr++) {
         const uint64_t q = a.both_strands ? vr / 2 : vr;
@@ -763,10 +897,19 @@ int seeds_main(const Args &a, const Fmi &f)
     if (!in) throw std::runtime_error("cannot open " + a.seeds);
     std::vector<uint8_t> reads;
     std::vector<uint64_t> ridx{0};
-    std::string line;
+    std::vector<std::string> names; // --sam: the word after '>' on the line directly in front of a read, else its number
+    std::string line, pending;
     while (std::getline(in, line)) {
         if (!line.empty() && line.back() == '\r') line.pop_back();
-        if (line.empty() || line[0] == '>') continue;
+        if (line.empty() || line[0] == '>') {
+            if (a.sam) {
+                const size_t ws = line.find_first_of(" \t", 1);
+                pending = line.empty() ? std::string() : line.substr(1, ws == std::string::npos ? std::string::npos : ws - 1);
+            }
+            continue;
+        }
+        if (a.sam) names.push_back(pending.empty() ? std::to_string(ridx.size() - 1) : pending);
+        pending.clear();
         for (unsigned char c : line) {
             uint8_t code = 4; // no base
             switch (c) {
@@ -801,7 +944,7 @@ int seeds_main(const Args &a, const Fmi &f)
                                  " rows of the index reached no sampled row: the positions need an index built with "
                                  "fmindex_build --exact");
     check(rc, "kiss_hip_fmi_seeds_host");
-    if (a.chain) return chains_main(a, V, seeds, sidx, pos, pidx, reads, ridx);
+    if (a.chain) return chains_main(a, V, seeds, sidx, pos, pidx, reads, ridx, names);
     std::string out;
     for (uint64_t vr = 0; vr < V; vr++) {
         const uint64_t q = a.both_strands ? vr / 2 : vr;

@@ -197,7 +197,7 @@ struct kiss_hip_ctx {
     uint64_t pairs_cap = 0;
     // scratch of kiss_hip_fmi_query_batch_dev (slots 0..12, fm.hip), of kiss_hip_fmi_query_mm_dev (slots 13..19,
     // fm_mm.hip), of kiss_hip_fmi8_query_dev (slots 20.., fm8.hip), of the seeds and the chain call (22..30) and of
-    // kiss_hip_fmi_align_dev (31..33, fm_align.hip), kept between calls
+    // kiss_hip_fmi_align_dev (31..33, fm_align.hip) and of kiss_hip_fmi_select_dev (34..35, fm_select.hip), kept between calls
     void *fm_pool[36] = {};
     uint64_t fm_pool_cap[36] = {};
     hipEvent_t fm_mm_ev[6] = {}; // fm_mm.hip / fm8.hip / fm_seed.hip: the times of their reports (created by the first call that wants one)

@@ -592,6 +592,11 @@ class FMIndex:
         band (32).  Returns what chains() returns plus alignments (structured array: score, flags, rbeg, rend, tbeg, tend,
         matches, mismatches, ins, del, gaps, band; alignment c belongs to chain c), align_report and, with want_cigar,
         cigar (u32 ops len << 4 | op, op 0 M, 1 I, 2 D) / cigar_index in CSR layout over the chains."""
+        res, _ = self._align_dev(reads, text, min_len, max_len, max_occ, both_strands, chain_params, want_cigar, params)
+        return res
+
+    def _align_dev(self, reads, text, min_len, max_len, max_occ, both_strands, chain_params, want_cigar, params):
+        """align(): -> (its result, the device tensors a later stage reads: reads, read index, chain index, alignments)"""
         from .fm_align import ALIGN_CELLS_PER_N, ALIGN_MAX_BAND, align_arrays, align_dev, align_params
         from .fm_chain import chain_params as make_chain_params, chain_dev, chain_arrays
         torch = _torch()
@@ -630,6 +635,28 @@ class FMIndex:
         al = align_dev(lib, ctx, self.device, d_text, n, d["d_reads"], d["d_ridx"], d["Q"], both_strands, out["d_chains"],
                        out["d_cidx"], C, p, want_cigar)
         res.update(align_arrays(al, want_cigar))
+        return res, {"lib": lib, "ctx": ctx, "d_ridx": d["d_ridx"], "Q": d["Q"], "d_cidx": out["d_cidx"], "d_alns": al["d_alns"],
+                     "C": C, "keep": (d, out, al)}
+
+    # ---- the mappings of every read (kiss_hip_fmi_select_dev; no reference counterpart) ---------------------------------
+    def map(self, reads, text, min_len=19, max_len=0, max_occ=500, both_strands=False, chain_params=None, align_params=None,
+            bounds=None, want_cigar=True, **select_params):
+        """Seeds, chains, alignments and the selection of every read's mappings (include/kiss_hip.h has the definition),
+        with everything staying on the device between the four calls.  reads, text and the seed parameters as in align();
+        chain_params / align_params: dicts of the parameters of chains() / align(); bounds: the starts of the R records of
+        the text plus n (R + 1 ascending values, the first 0), None: one record; select_params: min_score (30), overlap
+        (128, in 256ths), mapq_coef (120), mapq_max (60), max_hits (0: all).  Returns what align() returns plus hits
+        (structured array: aln, flags, mapq, score, sub, n_sec, head, ref; flags 1 reverse, 2 secondary, 4 supplementary),
+        hit_index (Q + 1: the hits of read q are hits[hit_index[q]:hit_index[q + 1]], the primary first) and select_report."""
+        from .fm_select import select_arrays, select_dev, select_params as make_select_params
+        sp = make_select_params(**select_params)
+        res, t = self._align_dev(reads, text, min_len, max_len, max_occ, both_strands, chain_params, want_cigar,
+                                 align_params or {})
+        ctx = t["ctx"]
+        if t["C"] > 0.3 * ctx.max_n:  # (the alignments of a call are sorted in the context's LMS arrays)
+            ctx = self._context(min(_lib.MAX_N, int(3.3 * t["C"]) + (1 << 20)))
+        sel = select_dev(t["lib"], ctx, self.device, t["d_alns"], t["d_cidx"], t["d_ridx"], t["Q"], t["C"], both_strands, bounds, sp)
+        res.update(select_arrays(sel))
         return res
 
     def close(self):
