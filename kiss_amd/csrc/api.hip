@@ -249,7 +249,7 @@ void free_all(kiss_hip_ctx *ctx)
         if (p) (void)hipFree(p);
     for (void *p : ctx->fm_pool)
         if (p) (void)hipFree(p);
-    for (hipEvent_t e : ctx->fm_mm_ev)
+    for (hipEvent_t e : ctx->fm_ev)
         if (e) (void)hipEventDestroy(e);
 #ifdef KISS_HIP_HOOKS
     if (ctx->tie_dbg) (void)hipFree(ctx->tie_dbg);
@@ -913,12 +913,7 @@ int kiss_hip_debug_radix_sort(kiss_hip_ctx *ctx, uint64_t *keys, uint32_t *pos, 
     ctx->stream = ctx->own_stream;
     KCHECK(hipMemcpy(ctx->keyA, keys, count * 8, hipMemcpyHostToDevice));
     KCHECK(hipMemcpy(ctx->posA, pos, count * 4, hipMemcpyHostToDevice));
-    RadixBufs rb;
-    rb.key[0] = ctx->keyA;
-    rb.key[1] = ctx->keyB;
-    rb.pos[0] = ctx->posA;
-    rb.pos[1] = ctx->posB;
-    rb.seg[0] = rb.seg[1] = nullptr;
+    RadixBufs rb = kiss_ctx_radix_bufs(ctx);
     int res = 0;
     KTRY(kiss_radix_sort(ctx, rb, count, key_lo_bit, 0, &res));
     KTRY(kiss_radix_check(ctx));

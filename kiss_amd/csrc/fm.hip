@@ -763,30 +763,18 @@ int fmi_query(kiss_hip_ctx *ctx, const kiss_hip_fmi_view *fmi, const uint32_t *l
 {
     const int max_depth = (int)fmi->sa_intv;
     const bool deep = max_depth > 4; // levels past 4^3 = 64 ranges: k_fm_locate_group_deep
-    KCHECK(hipSetDevice(ctx->device));
-    ctx->stream = stream ? (hipStream_t)stream : ctx->own_stream;
-    KTRY(kiss_workspace_ready(ctx));
+    KTRY(fm_enter(ctx, stream));
     if (hit_count_total) *hit_count_total = 0;
     if (checksum) *checksum = 0;
     if (Q == 0) return KISS_HIP_OK;
     if (Q / 4096 + 16 > ctx->scan_tmp_cap) return KISS_HIP_E_UNSUPPORTED; // batch larger than the ctx can scan
-    FmiD f;
-    f.N = fmi->n_sa;
-    for (int c = 0; c < 4; c++) f.cnt[c] = fmi->cnt[c];
-    f.pri = fmi->pri;
-    f.bwt_bytes = (fmi->n_sa + 3) / 4;
-    f.bwt = fmi->bwt;
-    f.occ1 = fmi->occ1;
-    f.occ2 = fmi->occ2;
-    f.sa = fmi->sa;
-    f.b = max_depth == 1 ? nullptr : fmi->b; // (SA_INTV = 1: every row sampled, fm_b_occ is the identity)
-    f.b_occ = fmi->b_occ;
+    FmiD f = fm_view_of(fmi); // (SA_INTV = 1: b is null, every row sampled, fm_b_occ is the identity)
 
     DevBuf cap, capidx, fcap, fcapidx, got, gotidx, tot, fr0, fr1, scratch, heavy, medium, blocks;
     // the interleaved rank blocks, derived from the caller's arrays at the start of every batch (never kept: the arrays
     // may have changed between calls)
     const uint64_t nblocks = f.N / 64 + 1;
-    KTRY(blocks.take(ctx, 11, nblocks * 32));
+    KTRY(blocks.take(ctx, FM_SLOT_BLOCKS, nblocks * 32));
     f.blk = (const uint4 *)blocks.p;
     const bool split = ((ctx->profile_mask >> KISS_HIP_K_FM_QUERY) & 1ull) != 0;
     hipEvent_t sev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -812,18 +800,18 @@ int fmi_query(kiss_hip_ctx *ctx, const kiss_hip_fmi_view *fmi, const uint32_t *l
     // (hooks build: the two tier thresholds can be swept, 16 .. 65536 and 1 .. fm_heavy)
     const uint32_t fm_heavy = ctx->opts.fm_heavy >= 16 && ctx->opts.fm_heavy <= 65536 ? ctx->opts.fm_heavy : (uint32_t)FM_HEAVY;
     const uint32_t fm_light = ctx->opts.fm_light >= 1 && ctx->opts.fm_light <= fm_heavy ? ctx->opts.fm_light : fm_heavy;
-    KTRY(heavy.take(ctx, 0, (Q + 2) * 4)); // [0] = count, [1..] = pattern numbers
+    KTRY(heavy.take(ctx, FM_SLOT_HEAVY, (Q + 2) * 4)); // [0] = count, [1..] = pattern numbers
     KTRY(kiss_zero_u32(ctx, heavy.p, 1));
-    KTRY(medium.take(ctx, 12, (Q + 2) * 4));
+    KTRY(medium.take(ctx, FM_SLOT_MEDIUM, (Q + 2) * 4));
     KTRY(kiss_zero_u32(ctx, medium.p, 1));
 
-    KTRY(cap.take(ctx, 1, (Q + 1) * 8));
-    KTRY(capidx.take(ctx, 2, (Q + 1) * 8));
-    KTRY(fcap.take(ctx, 9, (Q + 1) * 8));
-    KTRY(fcapidx.take(ctx, 10, (Q + 1) * 8));
-    KTRY(got.take(ctx, 3, (Q + 1) * 8));
-    KTRY(gotidx.take(ctx, 4, (Q + 1) * 8));
-    KTRY(tot.take(ctx, 5, 64)); // [0] hits, [1] checksum, [2] offset-scratch entries needed, [3] frontier entries, [4] overflow
+    KTRY(cap.take(ctx, FM_SLOT_CAP, (Q + 1) * 8));
+    KTRY(capidx.take(ctx, FM_SLOT_CAP_INDEX, (Q + 1) * 8));
+    KTRY(fcap.take(ctx, FM_SLOT_FCAP, (Q + 1) * 8));
+    KTRY(fcapidx.take(ctx, FM_SLOT_FCAP_INDEX, (Q + 1) * 8));
+    KTRY(got.take(ctx, FM_SLOT_GOT, (Q + 1) * 8));
+    KTRY(gotidx.take(ctx, FM_SLOT_GOT_INDEX, (Q + 1) * 8));
+    KTRY(tot.take(ctx, FM_SLOT_TOTALS, 64)); // [0] hits, [1] checksum, [2] offset-scratch entries needed, [3] frontier entries, [4] overflow
     const unsigned grid = (unsigned)div_up(Q, FM_THREADS);
     {
         KTimer t(ctx, KISS_HIP_K_FM_QUERY, Q);
@@ -849,11 +837,13 @@ int fmi_query(kiss_hip_ctx *ctx, const kiss_hip_fmi_view *fmi, const uint32_t *l
     uint64_t h[5] = {0, 0, 0, 0, 0};
     uint32_t nheavy = 0;
     for (int attempt = 0; attempt < 2; attempt++) {
-        const uint64_t scratch_entries = ctx->fm_pool_cap[8] / sizeof(uint32_t);
-        const uint64_t frontier_entries = (ctx->fm_pool_cap[6] < ctx->fm_pool_cap[7] ? ctx->fm_pool_cap[6] : ctx->fm_pool_cap[7]) / sizeof(uint2);
-        KTRY(fr0.take(ctx, 6, ctx->fm_pool_cap[6]));
-        KTRY(fr1.take(ctx, 7, ctx->fm_pool_cap[7]));
-        KTRY(scratch.take(ctx, 8, ctx->fm_pool_cap[8]));
+        const uint64_t *held = ctx->fm_pool_cap;
+        const uint64_t scratch_entries = held[FM_SLOT_OFFSETS] / sizeof(uint32_t);
+        const uint64_t frontier_entries =
+            (held[FM_SLOT_FRONTIER0] < held[FM_SLOT_FRONTIER1] ? held[FM_SLOT_FRONTIER0] : held[FM_SLOT_FRONTIER1]) / sizeof(uint2);
+        KTRY(fr0.take(ctx, FM_SLOT_FRONTIER0, held[FM_SLOT_FRONTIER0]));
+        KTRY(fr1.take(ctx, FM_SLOT_FRONTIER1, held[FM_SLOT_FRONTIER1]));
+        KTRY(scratch.take(ctx, FM_SLOT_OFFSETS, held[FM_SLOT_OFFSETS]));
         KTRY(kiss_zero_u32(ctx, tot.p, 4));
         hipLaunchKernelGGL(k_fm_check, dim3(1), dim3(64), 0, ctx->stream, (const uint64_t *)capidx.p, (const uint64_t *)fcapidx.p, Q,
                            scratch_entries, frontier_entries, d_need, d_over);
@@ -894,9 +884,9 @@ int fmi_query(kiss_hip_ctx *ctx, const kiss_hip_fmi_view *fmi, const uint32_t *l
         if ((uint32_t)h[4] == 0) break; // the buffers held the batch
         if (attempt) return KINTERNAL();
         // grow the pool to what this batch needs and locate again (the ranges stand)
-        KTRY(fr0.take(ctx, 6, (h[3] + 1) * sizeof(uint2)));
-        KTRY(fr1.take(ctx, 7, (h[3] + 1) * sizeof(uint2)));
-        KTRY(scratch.take(ctx, 8, h[2] * sizeof(uint32_t)));
+        KTRY(fr0.take(ctx, FM_SLOT_FRONTIER0, (h[3] + 1) * sizeof(uint2)));
+        KTRY(fr1.take(ctx, FM_SLOT_FRONTIER1, (h[3] + 1) * sizeof(uint2)));
+        KTRY(scratch.take(ctx, FM_SLOT_OFFSETS, h[2] * sizeof(uint32_t)));
     }
     const uint64_t total_cap = h[2];
     (void)nheavy;
@@ -948,9 +938,7 @@ int fmi_build(kiss_hip_ctx *ctx, const uint8_t *d_S, uint64_t n, const uint32_t 
               uint32_t cnt_out[4], uint32_t *pri_out, void *stream)
 {
     if (n > KISS_HIP_MAX_N) return KISS_HIP_E_INVALID;
-    KCHECK(hipSetDevice(ctx->device));
-    ctx->stream = stream ? (hipStream_t)stream : ctx->own_stream;
-    KTRY(kiss_workspace_ready(ctx));
+    KTRY(fm_enter(ctx, stream));
     const uint64_t N = n + 1;
     const uint64_t chunks = N / 16 + 1, blocks = N / 256 + 1;
     const uint64_t nbocc = N / 64 + 1;
@@ -1034,7 +1022,7 @@ int fmi_lookup(kiss_hip_ctx *ctx, uint64_t N, const uint32_t cnt[4], uint32_t pr
 
 bool fm_params_ok(uint32_t sa_intv, uint32_t lookup_len)
 {
-    return sa_intv >= 1 && sa_intv <= KISS_HIP_FMI_MAX_SA_INTV && lookup_len <= KISS_HIP_FMI_MAX_LOOKUP_LEN;
+    return fm_sa_intv_ok(sa_intv) && lookup_len <= KISS_HIP_FMI_MAX_LOOKUP_LEN;
 }
 
 } // namespace
@@ -1098,46 +1086,100 @@ int kiss_hip_fmi_sizes_for(uint64_t n, kiss_hip_fmi_sizes *out)
     return KISS_HIP_OK;
 }
 
+// both host forms of the build (z: the sizes of the arrays).  lookup == nullptr: the classic entry, kiss_hip_fmi_build_dev
+static int fmi_build_host(const uint8_t *S, uint64_t n, const uint32_t *SA_or_null, uint32_t sa_intv, uint32_t lookup_len,
+                          const kiss_hip_fmi_sizes_ex &z, uint8_t *bwt, uint32_t *occ1, uint8_t *occ2, uint32_t *sa, uint64_t *b,
+                          uint32_t *b_occ, uint32_t *lookup, uint32_t cnt_out[4], uint32_t *pri_out, int device)
+{
+    kiss_hip_ctx *ctx = nullptr;
+    int rc = kiss_hip_ctx_create(&ctx, device, n);
+    if (rc) return rc;
+    DevBuf dS, dSA, dbwt, docc1, docc2, dsa, db, dbocc, dlookup;
+    do {
+        if ((rc = dS.alloc(ctx, n)) || (rc = dSA.alloc(ctx, (n + 1) * 4)) || (rc = dbwt.alloc(ctx, z.base.bwt_bytes + 8)) ||
+            (rc = docc1.alloc(ctx, z.base.occ1_entries * 4)) || (rc = docc2.alloc(ctx, z.base.occ2_bytes)) ||
+            (rc = dsa.alloc(ctx, z.base.sa_entries * 4)) || (rc = db.alloc(ctx, z.base.b_words * 8 + 8)) ||
+            (rc = dbocc.alloc(ctx, z.base.b_occ_entries * 4)) || (lookup && (rc = dlookup.alloc(ctx, z.lookup_entries * 4))))
+            break;
+        if ((rc = fm_h2d(ctx, dS.p, S, n))) break;
+        // FMIndex::build sorts with k = 32 whatever the caller's flags say (fm_index.hpp:384-386)
+        if ((rc = SA_or_null ? fm_h2d(ctx, dSA.p, SA_or_null, (n + 1) * 4)
+                             : kiss_hip_ctx_suffix_sort_dna_u32_dev(ctx, (const uint8_t *)dS.p, n, 32u, KISS_HIP_ALGO_PARALLEL_SORTING,
+                                                                    (uint32_t *)dSA.p, nullptr)))
+            break;
+        if ((rc = lookup ? kiss_hip_fmi_build_ex_dev(ctx, (const uint8_t *)dS.p, n, (const uint32_t *)dSA.p, sa_intv, lookup_len,
+                                                     (uint8_t *)dbwt.p, (uint32_t *)docc1.p, (uint8_t *)docc2.p, (uint32_t *)dsa.p,
+                                                     (uint64_t *)db.p, (uint32_t *)dbocc.p, (uint32_t *)dlookup.p, cnt_out, pri_out,
+                                                     nullptr)
+                         : kiss_hip_fmi_build_dev(ctx, (const uint8_t *)dS.p, n, (const uint32_t *)dSA.p, sa_intv, (uint8_t *)dbwt.p,
+                                                  (uint32_t *)docc1.p, (uint8_t *)docc2.p, (uint32_t *)dsa.p, (uint64_t *)db.p,
+                                                  (uint32_t *)dbocc.p, cnt_out, pri_out, nullptr)))
+            break;
+        // (sa_intv == 1: no b / b_occ, their sizes are 0)
+        if ((rc = fm_d2h(ctx, bwt, dbwt.p, z.base.bwt_bytes)) || (rc = fm_d2h(ctx, occ1, docc1.p, z.base.occ1_entries * 4)) ||
+            (rc = fm_d2h(ctx, occ2, docc2.p, z.base.occ2_bytes)) || (rc = fm_d2h(ctx, sa, dsa.p, z.base.sa_entries * 4)) ||
+            (lookup && (rc = fm_d2h(ctx, lookup, dlookup.p, z.lookup_entries * 4))) || (rc = fm_d2h(ctx, b, db.p, z.base.b_words * 8)))
+            break;
+        rc = fm_d2h(ctx, b_occ, dbocc.p, z.base.b_occ_entries * 4);
+    } while (0);
+    kiss_hip_ctx_destroy(ctx);
+    return rc;
+}
+
+// both host forms of the query (z: the sizes of the index's arrays).  ex == nullptr: the classic entry,
+// kiss_hip_fmi_query_batch_dev
+static int fmi_query_host(const kiss_hip_fmi_view &base, const kiss_hip_fmi_view_ex *ex, const kiss_hip_fmi_sizes_ex &z,
+                          const uint8_t *patterns, uint32_t L, uint64_t Q, uint32_t stop_cnt, uint32_t *beg, uint32_t *end, uint32_t *offs,
+                          uint64_t *hit_count_total, uint64_t *checksum, uint32_t *offsets, uint64_t *offsets_index,
+                          uint64_t offsets_capacity, int device)
+{
+    kiss_hip_ctx *ctx = nullptr;
+    uint64_t max_n = base.n_sa > 4 * Q ? base.n_sa : 4 * Q;
+    if (max_n < (1u << 20)) max_n = 1u << 20;
+    int rc = kiss_hip_ctx_create(&ctx, device, max_n);
+    if (rc) return rc;
+    FmIndexOnDevice idx;
+    DevBuf dlookup, dpat, dbeg, dend, doffs, doff, didx;
+    do {
+        if ((rc = idx.upload(ctx, base, z.base)) || (ex && (rc = dlookup.alloc(ctx, z.lookup_entries * 4))) ||
+            (rc = dpat.alloc(ctx, Q * L)) || (rc = dbeg.alloc(ctx, Q * 4)) || (rc = dend.alloc(ctx, Q * 4)) ||
+            (offs && (rc = doffs.alloc(ctx, Q * 4))) || (ex && (rc = fm_h2d(ctx, dlookup.p, ex->lookup, z.lookup_entries * 4))) ||
+            (rc = fm_h2d(ctx, dpat.p, patterns, Q * L)))
+            break;
+        const bool want = offsets && offsets_index && offsets_capacity;
+        if (want && ((rc = doff.alloc(ctx, offsets_capacity * 4)) || (rc = didx.alloc(ctx, (Q + 1) * 8)))) break;
+        uint32_t *d_offsets = want ? (uint32_t *)doff.p : nullptr;
+        uint64_t *d_index = want ? (uint64_t *)didx.p : nullptr;
+        const uint64_t cap = want ? offsets_capacity : 0;
+        if (ex) {
+            kiss_hip_fmi_view_ex v = *ex;
+            v.base = idx.view;
+            v.lookup = (const uint32_t *)dlookup.p;
+            rc = kiss_hip_fmi_query_ex_dev(ctx, &v, (const uint8_t *)dpat.p, L, Q, stop_cnt, (uint32_t *)dbeg.p, (uint32_t *)dend.p,
+                                           offs ? (uint32_t *)doffs.p : nullptr, hit_count_total, checksum, d_offsets, d_index, cap,
+                                           nullptr);
+        } else {
+            rc = kiss_hip_fmi_query_batch_dev(ctx, &idx.view, (const uint8_t *)dpat.p, L, Q, (uint32_t *)dbeg.p, (uint32_t *)dend.p,
+                                              hit_count_total, checksum, d_offsets, d_index, cap, nullptr);
+        }
+        if (!rc) rc = fm_d2h(ctx, beg, dbeg.p, Q * 4);
+        if (!rc) rc = fm_d2h(ctx, end, dend.p, Q * 4);
+        if (!rc && offs) rc = fm_d2h(ctx, offs, doffs.p, Q * 4);
+        if (!rc && want) rc = fm_d2h(ctx, offsets_index, didx.p, (Q + 1) * 8);
+        if (!rc && want) rc = fm_d2h(ctx, offsets, doff.p, offsets_capacity * 4);
+    } while (0);
+    kiss_hip_ctx_destroy(ctx);
+    return rc;
+}
+
 int kiss_hip_fmi_build_host(const uint8_t *S, uint64_t n, const uint32_t *SA_or_null, uint8_t *bwt, uint32_t *occ1,
                             uint8_t *occ2, uint32_t *sa, uint64_t *b, uint32_t *b_occ, uint32_t cnt_out[4],
                             uint32_t *pri_out, int device)
 {
     if (!S || !bwt || !occ1 || !occ2 || !sa || !b || !b_occ || !cnt_out || !pri_out || n == 0) return KISS_HIP_E_INVALID;
-    kiss_hip_fmi_sizes z;
-    KTRY(kiss_hip_fmi_sizes_for(n, &z));
-    kiss_hip_ctx *ctx = nullptr;
-    int rc = kiss_hip_ctx_create(&ctx, device, n);
-    if (rc) return rc;
-    DevBuf dS, dSA, dbwt, docc1, docc2, dsa, db, dbocc;
-    do {
-        if ((rc = dS.alloc(ctx, n)) || (rc = dSA.alloc(ctx, (n + 1) * 4)) || (rc = dbwt.alloc(ctx, z.bwt_bytes + 8)) ||
-            (rc = docc1.alloc(ctx, z.occ1_entries * 4)) || (rc = docc2.alloc(ctx, z.occ2_bytes)) ||
-            (rc = dsa.alloc(ctx, z.sa_entries * 4)) || (rc = db.alloc(ctx, z.b_words * 8 + 8)) ||
-            (rc = dbocc.alloc(ctx, z.b_occ_entries * 4)))
-            break;
-        if (hipMemcpy(dS.p, S, n, hipMemcpyHostToDevice) != hipSuccess) { rc = KISS_HIP_E_HIP; break; }
-        if (SA_or_null) {
-            if (hipMemcpy(dSA.p, SA_or_null, (n + 1) * 4, hipMemcpyHostToDevice) != hipSuccess) { rc = KISS_HIP_E_HIP; break; }
-        } else {
-            // FMIndex::build sorts with k = 32 whatever the caller's flags say (fm_index.hpp:384-386)
-            if ((rc = kiss_hip_ctx_suffix_sort_dna_u32_dev(ctx, (const uint8_t *)dS.p, n, 32u, KISS_HIP_ALGO_PARALLEL_SORTING,
-                                                           (uint32_t *)dSA.p, nullptr)))
-                break;
-        }
-        if ((rc = kiss_hip_fmi_build_dev(ctx, (const uint8_t *)dS.p, n, (const uint32_t *)dSA.p, 4, (uint8_t *)dbwt.p,
-                                         (uint32_t *)docc1.p, (uint8_t *)docc2.p, (uint32_t *)dsa.p, (uint64_t *)db.p,
-                                         (uint32_t *)dbocc.p, cnt_out, pri_out, nullptr)))
-            break;
-        hipError_t e = hipMemcpy(bwt, dbwt.p, z.bwt_bytes, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(occ1, docc1.p, z.occ1_entries * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(occ2, docc2.p, z.occ2_bytes, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(sa, dsa.p, z.sa_entries * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(b, db.p, z.b_words * 8, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(b_occ, dbocc.p, z.b_occ_entries * 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = KISS_HIP_E_HIP;
-    } while (0);
-    kiss_hip_ctx_destroy(ctx);
-    return rc;
+    kiss_hip_fmi_sizes_ex z{};
+    KTRY(kiss_hip_fmi_sizes_for(n, &z.base));
+    return fmi_build_host(S, n, SA_or_null, 4, 0, z, bwt, occ1, occ2, sa, b, b_occ, nullptr, cnt_out, pri_out, device);
 }
 
 int kiss_hip_fmi_query_batch_host(const kiss_hip_fmi_view *fmi, const uint8_t *patterns, uint32_t L, uint64_t Q,
@@ -1145,50 +1187,12 @@ int kiss_hip_fmi_query_batch_host(const kiss_hip_fmi_view *fmi, const uint8_t *p
                                   uint32_t *offsets, uint64_t *offsets_index, uint64_t offsets_capacity, int device)
 {
     if (!fmi || !beg || !end || (Q && !patterns) || fmi->n_sa == 0) return KISS_HIP_E_INVALID;
-    kiss_hip_fmi_sizes z;
-    KTRY(kiss_hip_fmi_sizes_for(fmi->n_sa - 1, &z));
-    kiss_hip_ctx *ctx = nullptr;
-    uint64_t max_n = fmi->n_sa > 4 * Q ? fmi->n_sa : 4 * Q;
-    if (max_n < (1u << 20)) max_n = 1u << 20;
-    int rc = kiss_hip_ctx_create(&ctx, device, max_n);
-    if (rc) return rc;
-    DevBuf dbwt, docc1, docc2, dsa, db, dbocc, dpat, dbeg, dend, doff, didx;
-    do {
-        if ((rc = dbwt.alloc(ctx, z.bwt_bytes + 8)) || (rc = docc1.alloc(ctx, z.occ1_entries * 4)) ||
-            (rc = docc2.alloc(ctx, z.occ2_bytes)) || (rc = dsa.alloc(ctx, z.sa_entries * 4)) ||
-            (rc = db.alloc(ctx, z.b_words * 8 + 8)) || (rc = dbocc.alloc(ctx, z.b_occ_entries * 4)) ||
-            (rc = dpat.alloc(ctx, Q * L)) || (rc = dbeg.alloc(ctx, Q * 4)) || (rc = dend.alloc(ctx, Q * 4)))
-            break;
-        hipError_t e = hipMemcpy(dbwt.p, fmi->bwt, z.bwt_bytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(docc1.p, fmi->occ1, z.occ1_entries * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(docc2.p, fmi->occ2, z.occ2_bytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(dsa.p, fmi->sa, z.sa_entries * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(db.p, fmi->b, z.b_words * 8, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(dbocc.p, fmi->b_occ, z.b_occ_entries * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess && Q) e = hipMemcpy(dpat.p, patterns, Q * L, hipMemcpyHostToDevice);
-        if (e != hipSuccess) { rc = KISS_HIP_E_HIP; break; }
-        kiss_hip_fmi_view v = *fmi;
-        v.bwt = (const uint8_t *)dbwt.p;
-        v.occ1 = (const uint32_t *)docc1.p;
-        v.occ2 = (const uint8_t *)docc2.p;
-        v.sa = (const uint32_t *)dsa.p;
-        v.b = (const uint64_t *)db.p;
-        v.b_occ = (const uint32_t *)dbocc.p;
-        const bool want = offsets && offsets_index && offsets_capacity;
-        if (want && ((rc = doff.alloc(ctx, offsets_capacity * 4)) || (rc = didx.alloc(ctx, (Q + 1) * 8)))) break;
-        if ((rc = kiss_hip_fmi_query_batch_dev(ctx, &v, (const uint8_t *)dpat.p, L, Q, (uint32_t *)dbeg.p, (uint32_t *)dend.p,
-                                               hit_count_total, checksum, want ? (uint32_t *)doff.p : nullptr,
-                                               want ? (uint64_t *)didx.p : nullptr, want ? offsets_capacity : 0, nullptr)))
-            break;
-        e = hipMemcpy(beg, dbeg.p, Q * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(end, dend.p, Q * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && want) e = hipMemcpy(offsets_index, didx.p, (Q + 1) * 8, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && want) e = hipMemcpy(offsets, doff.p, offsets_capacity * 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = KISS_HIP_E_HIP;
-    } while (0);
-    kiss_hip_ctx_destroy(ctx);
-    return rc;
+    kiss_hip_fmi_sizes_ex z{};
+    KTRY(kiss_hip_fmi_sizes_for(fmi->n_sa - 1, &z.base));
+    return fmi_query_host(*fmi, nullptr, z, patterns, L, Q, 0, beg, end, nullptr, hit_count_total, checksum, offsets, offsets_index,
+                          offsets_capacity, device);
 }
+
 int kiss_hip_fmi_sizes_ex_for(uint64_t n, uint32_t sa_intv, uint32_t lookup_len, kiss_hip_fmi_sizes_ex *out)
 {
     if (!fm_params_ok(sa_intv, lookup_len)) return KISS_HIP_E_UNSUPPORTED;
@@ -1210,39 +1214,7 @@ int kiss_hip_fmi_build_ex_host(const uint8_t *S, uint64_t n, const uint32_t *SA_
         return KISS_HIP_E_INVALID;
     kiss_hip_fmi_sizes_ex z;
     KTRY(kiss_hip_fmi_sizes_ex_for(n, sa_intv, lookup_len, &z));
-    kiss_hip_ctx *ctx = nullptr;
-    int rc = kiss_hip_ctx_create(&ctx, device, n);
-    if (rc) return rc;
-    DevBuf dS, dSA, dbwt, docc1, docc2, dsa, db, dbocc, dlookup;
-    do {
-        if ((rc = dS.alloc(ctx, n)) || (rc = dSA.alloc(ctx, (n + 1) * 4)) || (rc = dbwt.alloc(ctx, z.base.bwt_bytes + 8)) ||
-            (rc = docc1.alloc(ctx, z.base.occ1_entries * 4)) || (rc = docc2.alloc(ctx, z.base.occ2_bytes)) ||
-            (rc = dsa.alloc(ctx, z.base.sa_entries * 4)) || (rc = db.alloc(ctx, z.base.b_words * 8 + 8)) ||
-            (rc = dbocc.alloc(ctx, z.base.b_occ_entries * 4)) || (rc = dlookup.alloc(ctx, z.lookup_entries * 4)))
-            break;
-        if (hipMemcpy(dS.p, S, n, hipMemcpyHostToDevice) != hipSuccess) { rc = KISS_HIP_E_HIP; break; }
-        if (SA_or_null) {
-            if (hipMemcpy(dSA.p, SA_or_null, (n + 1) * 4, hipMemcpyHostToDevice) != hipSuccess) { rc = KISS_HIP_E_HIP; break; }
-        } else if ((rc = kiss_hip_ctx_suffix_sort_dna_u32_dev(ctx, (const uint8_t *)dS.p, n, 32u, KISS_HIP_ALGO_PARALLEL_SORTING,
-                                                              (uint32_t *)dSA.p, nullptr))) {
-            break;
-        }
-        if ((rc = kiss_hip_fmi_build_ex_dev(ctx, (const uint8_t *)dS.p, n, (const uint32_t *)dSA.p, sa_intv, lookup_len,
-                                            (uint8_t *)dbwt.p, (uint32_t *)docc1.p, (uint8_t *)docc2.p, (uint32_t *)dsa.p,
-                                            (uint64_t *)db.p, (uint32_t *)dbocc.p, (uint32_t *)dlookup.p, cnt_out, pri_out,
-                                            nullptr)))
-            break;
-        hipError_t e = hipMemcpy(bwt, dbwt.p, z.base.bwt_bytes, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(occ1, docc1.p, z.base.occ1_entries * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(occ2, docc2.p, z.base.occ2_bytes, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(sa, dsa.p, z.base.sa_entries * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(lookup, dlookup.p, z.lookup_entries * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && sa_intv != 1) e = hipMemcpy(b, db.p, z.base.b_words * 8, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && sa_intv != 1) e = hipMemcpy(b_occ, dbocc.p, z.base.b_occ_entries * 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = KISS_HIP_E_HIP;
-    } while (0);
-    kiss_hip_ctx_destroy(ctx);
-    return rc;
+    return fmi_build_host(S, n, SA_or_null, sa_intv, lookup_len, z, bwt, occ1, occ2, sa, b, b_occ, lookup, cnt_out, pri_out, device);
 }
 
 int kiss_hip_fmi_query_ex_host(const kiss_hip_fmi_view_ex *fmi, const uint8_t *patterns, uint32_t L, uint64_t Q,
@@ -1258,51 +1230,7 @@ int kiss_hip_fmi_query_ex_host(const kiss_hip_fmi_view_ex *fmi, const uint8_t *p
         return KISS_HIP_E_INVALID;
     kiss_hip_fmi_sizes_ex z;
     KTRY(kiss_hip_fmi_sizes_ex_for(fmi->base.n_sa - 1, sa_intv, fmi->lookup_len, &z));
-    kiss_hip_ctx *ctx = nullptr;
-    uint64_t max_n = fmi->base.n_sa > 4 * Q ? fmi->base.n_sa : 4 * Q;
-    if (max_n < (1u << 20)) max_n = 1u << 20;
-    int rc = kiss_hip_ctx_create(&ctx, device, max_n);
-    if (rc) return rc;
-    DevBuf dbwt, docc1, docc2, dsa, db, dbocc, dlookup, dpat, dbeg, dend, doffs, doff, didx;
-    do {
-        if ((rc = dbwt.alloc(ctx, z.base.bwt_bytes + 8)) || (rc = docc1.alloc(ctx, z.base.occ1_entries * 4)) ||
-            (rc = docc2.alloc(ctx, z.base.occ2_bytes)) || (rc = dsa.alloc(ctx, z.base.sa_entries * 4)) ||
-            (rc = db.alloc(ctx, z.base.b_words * 8 + 8)) || (rc = dbocc.alloc(ctx, z.base.b_occ_entries * 4)) ||
-            (rc = dlookup.alloc(ctx, z.lookup_entries * 4)) || (rc = dpat.alloc(ctx, Q * L)) ||
-            (rc = dbeg.alloc(ctx, Q * 4)) || (rc = dend.alloc(ctx, Q * 4)) || (offs && (rc = doffs.alloc(ctx, Q * 4))))
-            break;
-        hipError_t e = hipMemcpy(dbwt.p, fmi->base.bwt, z.base.bwt_bytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(docc1.p, fmi->base.occ1, z.base.occ1_entries * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(docc2.p, fmi->base.occ2, z.base.occ2_bytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(dsa.p, fmi->base.sa, z.base.sa_entries * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(dlookup.p, fmi->lookup, z.lookup_entries * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess && sa_intv != 1) e = hipMemcpy(db.p, fmi->base.b, z.base.b_words * 8, hipMemcpyHostToDevice);
-        if (e == hipSuccess && sa_intv != 1) e = hipMemcpy(dbocc.p, fmi->base.b_occ, z.base.b_occ_entries * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess && Q) e = hipMemcpy(dpat.p, patterns, Q * L, hipMemcpyHostToDevice);
-        if (e != hipSuccess) { rc = KISS_HIP_E_HIP; break; }
-        kiss_hip_fmi_view_ex v = *fmi;
-        v.base.bwt = (const uint8_t *)dbwt.p;
-        v.base.occ1 = (const uint32_t *)docc1.p;
-        v.base.occ2 = (const uint8_t *)docc2.p;
-        v.base.sa = (const uint32_t *)dsa.p;
-        v.base.b = sa_intv == 1 ? nullptr : (const uint64_t *)db.p;
-        v.base.b_occ = sa_intv == 1 ? nullptr : (const uint32_t *)dbocc.p;
-        v.lookup = (const uint32_t *)dlookup.p;
-        const bool want = offsets && offsets_index && offsets_capacity;
-        if (want && ((rc = doff.alloc(ctx, offsets_capacity * 4)) || (rc = didx.alloc(ctx, (Q + 1) * 8)))) break;
-        if ((rc = kiss_hip_fmi_query_ex_dev(ctx, &v, (const uint8_t *)dpat.p, L, Q, stop_cnt, (uint32_t *)dbeg.p,
-                                            (uint32_t *)dend.p, offs ? (uint32_t *)doffs.p : nullptr, hit_count_total, checksum,
-                                            want ? (uint32_t *)doff.p : nullptr, want ? (uint64_t *)didx.p : nullptr,
-                                            want ? offsets_capacity : 0, nullptr)))
-            break;
-        e = hipMemcpy(beg, dbeg.p, Q * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(end, dend.p, Q * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && offs) e = hipMemcpy(offs, doffs.p, Q * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && want) e = hipMemcpy(offsets_index, didx.p, (Q + 1) * 8, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && want) e = hipMemcpy(offsets, doff.p, offsets_capacity * 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = KISS_HIP_E_HIP;
-    } while (0);
-    kiss_hip_ctx_destroy(ctx);
-    return rc;
+    return fmi_query_host(fmi->base, fmi, z, patterns, L, Q, stop_cnt, beg, end, offs, hit_count_total, checksum, offsets, offsets_index,
+                          offsets_capacity, device);
 }
 }

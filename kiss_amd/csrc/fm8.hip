@@ -333,8 +333,6 @@ __global__ __launch_bounds__(F8_THREADS) void k_fm8_occ1(const uint32_t *__restr
     if (i < entries) occ1[i] = scanned[i] - scanned[(i / nsb) * nsb];
 }
 
-bool f8_sa_intv_ok(uint32_t sa_intv) { return sa_intv >= 1 && sa_intv <= KISS_HIP_FMI_MAX_SA_INTV; }
-
 // the census: C, map and sigma of a device text (synchronises)
 int f8_census(kiss_hip_ctx *ctx, const uint8_t *d_S, uint64_t n, uint32_t C[257], uint8_t map[256], uint32_t *sigma)
 {
@@ -365,9 +363,7 @@ int f8_build(kiss_hip_ctx *ctx, const uint8_t *d_S, uint64_t n, const uint32_t *
              uint32_t *d_C, uint8_t *d_map, uint8_t *d_bwt, uint32_t *d_occ1, uint16_t *d_occ2, uint32_t *d_sa, uint64_t *d_b,
              uint32_t *d_b_occ, uint32_t *sigma_out, uint32_t *pri_out, void *stream)
 {
-    KCHECK(hipSetDevice(ctx->device));
-    ctx->stream = stream ? (hipStream_t)stream : ctx->own_stream;
-    KTRY(kiss_workspace_ready(ctx));
+    KTRY(fm_enter(ctx, stream));
     KTimer t(ctx, KISS_HIP_K_FM_BUILD, n + 1);
     uint32_t C[257], sigma = 0;
     uint8_t map[256];
@@ -402,35 +398,9 @@ int f8_build(kiss_hip_ctx *ctx, const uint8_t *d_S, uint64_t n, const uint32_t *
     return KISS_HIP_OK;
 }
 
-// the report's times: events kept in the ctx (shared with fm_mm.hip: one call at a time per ctx), recorded only for a caller
-// that wants a report
-struct F8Events {
-    kiss_hip_ctx *ctx;
-    bool ok;
-    int last = -1;
-    F8Events(kiss_hip_ctx *c, bool wanted) : ctx(c), ok(wanted)
-    {
-        for (auto &x : ctx->fm_mm_ev)
-            if (ok && !x && hipEventCreate(&x) != hipSuccess) {
-                x = nullptr;
-                ok = false;
-            }
-    }
-    void mark(int i)
-    {
-        if (ok && hipEventRecord(ctx->fm_mm_ev[i], ctx->stream) == hipSuccess) last = i;
-    }
-    float ms(int a, int b)
-    {
-        float v = 0.f;
-        if (!ok || hipEventElapsedTime(&v, ctx->fm_mm_ev[a], ctx->fm_mm_ev[b]) != hipSuccess) return 0.f;
-        return v;
-    }
-};
-
 int f8_query_steps(kiss_hip_ctx *ctx, const kiss_hip_fmi8_view *fmi, const uint8_t *patterns, const uint64_t *pat_index, uint64_t Q,
                    uint32_t *beg, uint32_t *end, uint64_t *hit_count_total, uint64_t *checksum, uint32_t *positions,
-                   uint64_t *index, uint64_t capacity, kiss_hip_fmi8_report *rep, F8Events &ev)
+                   uint64_t *index, uint64_t capacity, kiss_hip_fmi8_report *rep, FmEvents &ev)
 {
     const bool want = positions != nullptr;
     if (Q > 0x7FFFFFFFull || Q / 4096 + 16 > ctx->scan_tmp_cap) return KISS_HIP_E_UNSUPPORTED; // more than the ctx can scan
@@ -450,25 +420,25 @@ int f8_query_steps(kiss_hip_ctx *ctx, const kiss_hip_fmi8_view *fmi, const uint8
     f.b = fmi->sa_intv == 1 ? nullptr : fmi->b;
     f.b_occ = fmi->b_occ;
     const uint64_t sa_entries = (f.N + fmi->sa_intv - 1) / fmi->sa_intv;
-    DevBuf ctl, counts;
-    KTRY(ctl.take(ctx, 20, F8_CTL_WORDS * 8));
-    if (want) KTRY(counts.take(ctx, 21, (Q + 1) * 8));
-    KTRY(kiss_zero_u32(ctx, ctl.p, F8_CTL_WORDS * 2));
+    DevBuf counts;
+    FmCtl<F8_CTL_WORDS> ctl;
+    unsigned long long *const h = ctl.h;
+    KTRY(ctl.take(ctx, FM_SLOT_FM8_CTL));
+    if (want) KTRY(counts.take(ctx, FM_SLOT_FM8_COUNTS, (Q + 1) * 8));
+    KTRY(ctl.zero());
     ev.mark(0);
     {
         KTimer t(ctx, KISS_HIP_K_FM_QUERY, Q);
         if (ctx->opts.fm8_group)
             hipLaunchKernelGGL((k_fm8_search<true>), dim3((unsigned)div_up(Q * F8_GROUP, F8_THREADS)), dim3(F8_THREADS), 0, ctx->stream,
-                               f, patterns, pat_index, Q, beg, end, (uint64_t *)counts.p, (unsigned long long *)ctl.p);
+                               f, patterns, pat_index, Q, beg, end, (uint64_t *)counts.p, ctl.d);
         else
             hipLaunchKernelGGL((k_fm8_search<false>), dim3((unsigned)div_up(Q, F8_THREADS)), dim3(F8_THREADS), 0, ctx->stream, f,
-                               patterns, pat_index, Q, beg, end, (uint64_t *)counts.p, (unsigned long long *)ctl.p);
+                               patterns, pat_index, Q, beg, end, (uint64_t *)counts.p, ctl.d);
         KCHECK(hipGetLastError());
         ev.mark(1);
     }
-    unsigned long long h[F8_CTL_WORDS] = {0};
-    KCHECK(hipMemcpyAsync(h, ctl.p, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
-    KCHECK(hipStreamSynchronize(ctx->stream));
+    KTRY(ctl.fetch_sync());
     if (h[F8_BAD]) return KISS_HIP_E_INVALID; // a pattern of length zero, or pat_index decreases
     const uint64_t total = h[F8_HITS];
     if (hit_count_total) *hit_count_total = total;
@@ -486,24 +456,17 @@ int f8_query_steps(kiss_hip_ctx *ctx, const kiss_hip_fmi8_view *fmi, const uint8
         KCHECK(hipStreamSynchronize(ctx->stream));
         return KISS_HIP_OK;
     }
-    int qbits = 0;
-    while (qbits < 32 && (1ull << qbits) < Q) qbits++;
-    const int key_shift = (32 - qbits) & ~7; // the sort takes whole bytes from the top of the key
+    const int key_shift = (32 - fm_bits(Q, 32, 0)) & ~7; // the sort takes whole bytes from the top of the key
     {
         KTimer t(ctx, KISS_HIP_K_FM_QUERY, total);
         ev.mark(2);
         hipLaunchKernelGGL(k_fm8_locate, dim3((unsigned)div_up(total, F8_THREADS)), dim3(F8_THREADS), 0, ctx->stream, f,
                            fmi->sa_intv, sa_entries, (const uint32_t *)beg, (const uint64_t *)index, Q, total, key_shift, ctx->keyA,
-                           (unsigned long long *)ctl.p);
+                           ctl.d);
         KCHECK(hipGetLastError());
         ev.mark(3);
     }
-    RadixBufs rb;
-    rb.key[0] = ctx->keyA;
-    rb.key[1] = ctx->keyB;
-    rb.seg[0] = rb.seg[1] = nullptr;
-    rb.pos[0] = ctx->posA; // (a payload nobody reads)
-    rb.pos[1] = ctx->posB;
+    RadixBufs rb = kiss_ctx_radix_bufs(ctx); // (a payload nobody reads)
     int res = 0;
     KTRY(kiss_radix_sort(ctx, rb, total, key_shift, 0, &res));
     {
@@ -513,7 +476,7 @@ int f8_query_steps(kiss_hip_ctx *ctx, const kiss_hip_fmi8_view *fmi, const uint8
         KCHECK(hipGetLastError());
     }
     ev.mark(4);
-    KCHECK(hipMemcpyAsync(h, ctl.p, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+    KTRY(ctl.fetch());
     KTRY(kiss_radix_check(ctx)); // (synchronises)
     if (checksum) *checksum = h[F8_CHECKSUM];
     if (rep) {
@@ -528,7 +491,7 @@ int f8_query_steps(kiss_hip_ctx *ctx, const kiss_hip_fmi8_view *fmi, const uint8
 int f8_view_check(const kiss_hip_fmi8_view *v, bool want)
 {
     if (!v) return KISS_HIP_E_INVALID;
-    if (!f8_sa_intv_ok(v->sa_intv)) return KISS_HIP_E_UNSUPPORTED;
+    if (!fm_sa_intv_ok(v->sa_intv)) return KISS_HIP_E_UNSUPPORTED;
     if (v->n_sa == 0 || v->n_sa > KISS_HIP_MAX_N + 1 || v->sigma > 256 || !v->C || !v->map || !v->bwt ||
         (v->sigma && (!v->occ1 || !v->occ2)))
         return KISS_HIP_E_INVALID;
@@ -542,7 +505,7 @@ extern "C" {
 
 int kiss_hip_fmi8_sizes_for(uint64_t n, uint32_t sa_intv, uint32_t sigma, kiss_hip_fmi8_sizes *out)
 {
-    if (!f8_sa_intv_ok(sa_intv)) return KISS_HIP_E_UNSUPPORTED;
+    if (!fm_sa_intv_ok(sa_intv)) return KISS_HIP_E_UNSUPPORTED;
     if (!out || n > KISS_HIP_MAX_N || sigma > 256) return KISS_HIP_E_INVALID;
     const uint64_t N = n + 1;
     out->n_sa = N;
@@ -560,7 +523,7 @@ int kiss_hip_fmi8_build_dev(kiss_hip_ctx *ctx, const uint8_t *d_S, uint64_t n, c
                             uint16_t *d_occ2, uint32_t *d_sa, uint64_t *d_b, uint32_t *d_b_occ, uint32_t *sigma_out,
                             uint32_t *pri_out, void *stream)
 {
-    if (!f8_sa_intv_ok(sa_intv)) return KISS_HIP_E_UNSUPPORTED;
+    if (!fm_sa_intv_ok(sa_intv)) return KISS_HIP_E_UNSUPPORTED;
     if (!ctx || (n && !d_S) || n > KISS_HIP_MAX_N || !sigma_out) return KISS_HIP_E_INVALID;
     if (d_bwt && (!d_SA || !d_C || !d_map || !d_sa || !pri_out || ((uintptr_t)d_bwt & 15) || (n && (!d_occ1 || !d_occ2)) ||
                   (sa_intv != 1 && (!d_b || !d_b_occ))))
@@ -586,9 +549,7 @@ int kiss_hip_fmi8_query_dev(kiss_hip_ctx *ctx, const kiss_hip_fmi8_view *fmi, co
     KTRY(f8_view_check(fmi, all));
     if (!ctx || (Q && (!patterns || !pat_index || !beg || !end)) || any != all || (!any && capacity) || ((uintptr_t)fmi->bwt & 15))
         return KISS_HIP_E_INVALID;
-    KCHECK(hipSetDevice(ctx->device));
-    ctx->stream = stream ? (hipStream_t)stream : ctx->own_stream;
-    KTRY(kiss_workspace_ready(ctx));
+    KTRY(fm_enter(ctx, stream));
     if (Q == 0) {
         if (all) { // index[0] = 0
             KTRY(kiss_zero_u32(ctx, index, 2));
@@ -596,13 +557,10 @@ int kiss_hip_fmi8_query_dev(kiss_hip_ctx *ctx, const kiss_hip_fmi8_view *fmi, co
         }
         return KISS_HIP_OK;
     }
-    F8Events ev(ctx, report != nullptr);
+    FmEvents ev(ctx, report != nullptr);
     const int rc = f8_query_steps(ctx, fmi, patterns, pat_index, Q, beg, end, hit_count_total, checksum, positions, index, capacity,
                                   report, ev);
-    if (rc != KISS_HIP_OK) (void)hipStreamSynchronize(ctx->stream);
-    if (report && ev.last > 0) report->ms_total = ev.ms(0, ev.last);
-    ktimer_collect(ctx);
-    return rc;
+    return fm_leave(ctx, ev, rc, report ? &report->ms_total : nullptr);
 }
 
 int kiss_hip_fmi8_build_host(const uint8_t *S, uint64_t n, const uint32_t *SA_or_null, uint32_t sa_intv, uint32_t sigma_capacity,
@@ -619,8 +577,7 @@ int kiss_hip_fmi8_build_host(const uint8_t *S, uint64_t n, const uint32_t *SA_or
     DevBuf dS, dSA, dC, dmap, dbwt, docc1, docc2, dsa, db, dbocc;
     do {
         if ((rc = dS.alloc(ctx, n)) || (rc = dC.alloc(ctx, 257 * 4)) || (rc = dmap.alloc(ctx, 256))) break;
-        hipError_t e = n ? hipMemcpy(dS.p, S, n, hipMemcpyHostToDevice) : hipSuccess;
-        if (e != hipSuccess) { rc = KISS_HIP_E_HIP; break; }
+        if ((rc = fm_h2d(ctx, dS.p, S, n))) break;
         if (!bwt) { // the census
             rc = kiss_hip_fmi8_build_dev(ctx, (const uint8_t *)dS.p, n, nullptr, sa_intv, 0, (uint32_t *)dC.p, (uint8_t *)dmap.p, nullptr,
                                          nullptr, nullptr, nullptr, nullptr, nullptr, sigma_out, nullptr, nullptr);
@@ -630,7 +587,7 @@ int kiss_hip_fmi8_build_host(const uint8_t *S, uint64_t n, const uint32_t *SA_or
                 (rc = db.alloc(ctx, z.b_words * 8 + 8)) || (rc = dbocc.alloc(ctx, z.b_occ_entries * 4)))
                 break;
             if (SA_or_null) {
-                if (hipMemcpy(dSA.p, SA_or_null, (n + 1) * 4, hipMemcpyHostToDevice) != hipSuccess) { rc = KISS_HIP_E_HIP; break; }
+                if ((rc = fm_h2d(ctx, dSA.p, SA_or_null, (n + 1) * 4))) break;
             } else if ((rc = kiss_hip_ctx_suffix_sort_u8_dev(ctx, (const uint8_t *)dS.p, n, (uint32_t *)dSA.p, nullptr))) {
                 break;
             }
@@ -639,19 +596,17 @@ int kiss_hip_fmi8_build_host(const uint8_t *S, uint64_t n, const uint32_t *SA_or
                                          (uint64_t *)db.p, (uint32_t *)dbocc.p, sigma_out, pri_out, nullptr);
         }
         if (rc) break;
-        if (C) e = hipMemcpy(C, dC.p, 257 * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && map) e = hipMemcpy(map, dmap.p, 256, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && bwt) {
+        if (C) rc = fm_d2h(ctx, C, dC.p, 257 * 4);
+        if (!rc && map) rc = fm_d2h(ctx, map, dmap.p, 256);
+        if (!rc && bwt) {
             kiss_hip_fmi8_sizes zs; // occ1 / occ2 are laid out for the text's own sigma
             (void)kiss_hip_fmi8_sizes_for(n, sa_intv, *sigma_out, &zs);
-            e = hipMemcpy(bwt, dbwt.p, zs.bwt_bytes, hipMemcpyDeviceToHost);
-            if (e == hipSuccess && zs.occ1_entries) e = hipMemcpy(occ1, docc1.p, zs.occ1_entries * 4, hipMemcpyDeviceToHost);
-            if (e == hipSuccess && zs.occ2_entries) e = hipMemcpy(occ2, docc2.p, zs.occ2_entries * 2, hipMemcpyDeviceToHost);
-            if (e == hipSuccess) e = hipMemcpy(sa, dsa.p, zs.sa_entries * 4, hipMemcpyDeviceToHost);
-            if (e == hipSuccess && zs.b_words) e = hipMemcpy(b, db.p, zs.b_words * 8, hipMemcpyDeviceToHost);
-            if (e == hipSuccess && zs.b_occ_entries) e = hipMemcpy(b_occ, dbocc.p, zs.b_occ_entries * 4, hipMemcpyDeviceToHost);
+            if ((rc = fm_d2h(ctx, bwt, dbwt.p, zs.bwt_bytes)) || (rc = fm_d2h(ctx, occ1, docc1.p, zs.occ1_entries * 4)) ||
+                (rc = fm_d2h(ctx, occ2, docc2.p, zs.occ2_entries * 2)) || (rc = fm_d2h(ctx, sa, dsa.p, zs.sa_entries * 4)) ||
+                (rc = fm_d2h(ctx, b, db.p, zs.b_words * 8)))
+                break;
+            rc = fm_d2h(ctx, b_occ, dbocc.p, zs.b_occ_entries * 4);
         }
-        if (e != hipSuccess) rc = KISS_HIP_E_HIP;
     } while (0);
     kiss_hip_ctx_destroy(ctx);
     return rc;
@@ -670,17 +625,13 @@ int kiss_hip_fmi8_query_host(const kiss_hip_fmi8_view *fmi, const uint8_t *patte
     const bool any = positions || index, all = positions && index;
     KTRY(f8_view_check(fmi, true));
     if ((Q && (!patterns || !pat_index || !beg || !end)) || any != all || (!any && capacity)) return KISS_HIP_E_INVALID;
-    for (uint64_t q = 0; q < Q; q++)
-        if (pat_index[q + 1] <= pat_index[q]) return KISS_HIP_E_INVALID;
+    if (!fm_index_ascending(pat_index, Q, true)) return KISS_HIP_E_INVALID;
     kiss_hip_fmi8_sizes z;
     KTRY(kiss_hip_fmi8_sizes_for(fmi->n_sa - 1, fmi->sa_intv, fmi->sigma, &z));
     const uint64_t pat_bytes = Q ? pat_index[Q] : 0;
     kiss_hip_ctx *ctx = nullptr;
-    uint64_t max_n = fmi->n_sa > 4 * Q ? fmi->n_sa : 4 * Q;
-    if (max_n < 4 * capacity) max_n = 4 * capacity; // the hits of a call are sorted in the ctx's LMS arrays (0.32 max_n entries)
-    if (max_n < (1u << 20)) max_n = 1u << 20;
-    if (max_n > KISS_HIP_MAX_N) max_n = KISS_HIP_MAX_N;
-    int rc = kiss_hip_ctx_create(&ctx, device, max_n);
+    // (the hits of a call are sorted in the ctx's LMS arrays)
+    int rc = kiss_hip_ctx_create(&ctx, device, fm_host_max_n(fmi->n_sa, Q, capacity));
     if (rc) return rc;
     DevBuf dC, dmap, dbwt, docc1, docc2, dsa, db, dbocc, dpat, dpidx, dbeg, dend, dpos, didx;
     do {
@@ -690,17 +641,13 @@ int kiss_hip_fmi8_query_host(const kiss_hip_fmi8_view *fmi, const uint8_t *patte
             (rc = dbocc.alloc(ctx, z.b_occ_entries * 4)) || (rc = dpat.alloc(ctx, pat_bytes)) || (rc = dpidx.alloc(ctx, (Q + 1) * 8)) ||
             (rc = dbeg.alloc(ctx, Q * 4)) || (rc = dend.alloc(ctx, Q * 4)))
             break;
-        hipError_t e = hipMemcpy(dC.p, fmi->C, 257 * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(dmap.p, fmi->map, 256, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(dbwt.p, fmi->bwt, z.bwt_bytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess && z.occ1_entries) e = hipMemcpy(docc1.p, fmi->occ1, z.occ1_entries * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess && z.occ2_entries) e = hipMemcpy(docc2.p, fmi->occ2, z.occ2_entries * 2, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(dsa.p, fmi->sa, z.sa_entries * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess && z.b_words) e = hipMemcpy(db.p, fmi->b, z.b_words * 8, hipMemcpyHostToDevice);
-        if (e == hipSuccess && z.b_occ_entries) e = hipMemcpy(dbocc.p, fmi->b_occ, z.b_occ_entries * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess && pat_bytes) e = hipMemcpy(dpat.p, patterns, pat_bytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess && Q) e = hipMemcpy(dpidx.p, pat_index, (Q + 1) * 8, hipMemcpyHostToDevice);
-        if (e != hipSuccess) { rc = KISS_HIP_E_HIP; break; }
+        // (another kind of view than FmIndexOnDevice uploads: C, map, 16-bit occ2; sa_intv == 1: the sizes of b / b_occ are 0)
+        if ((rc = fm_h2d(ctx, dC.p, fmi->C, 257 * 4)) || (rc = fm_h2d(ctx, dmap.p, fmi->map, 256)) ||
+            (rc = fm_h2d(ctx, dbwt.p, fmi->bwt, z.bwt_bytes)) || (rc = fm_h2d(ctx, docc1.p, fmi->occ1, z.occ1_entries * 4)) ||
+            (rc = fm_h2d(ctx, docc2.p, fmi->occ2, z.occ2_entries * 2)) || (rc = fm_h2d(ctx, dsa.p, fmi->sa, z.sa_entries * 4)) ||
+            (rc = fm_h2d(ctx, db.p, fmi->b, z.b_words * 8)) || (rc = fm_h2d(ctx, dbocc.p, fmi->b_occ, z.b_occ_entries * 4)) ||
+            (rc = fm_h2d(ctx, dpat.p, patterns, pat_bytes)) || (Q && (rc = fm_h2d(ctx, dpidx.p, pat_index, (Q + 1) * 8))))
+            break;
         kiss_hip_fmi8_view v = *fmi;
         v.C = (const uint32_t *)dC.p;
         v.map = (const uint8_t *)dmap.p;
@@ -717,11 +664,10 @@ int kiss_hip_fmi8_query_host(const kiss_hip_fmi8_view *fmi, const uint8_t *patte
                                      all ? (uint64_t *)didx.p : nullptr, all ? capacity : 0, report, nullptr);
         if (hit_count_total) *hit_count_total = total;
         if (rc) break;
-        if (Q) e = hipMemcpy(beg, dbeg.p, Q * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && Q) e = hipMemcpy(end, dend.p, Q * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && all) e = hipMemcpy(index, didx.p, (Q + 1) * 8, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && all && total) e = hipMemcpy(positions, dpos.p, total * 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = KISS_HIP_E_HIP;
+        rc = fm_d2h(ctx, beg, dbeg.p, Q * 4);
+        if (!rc) rc = fm_d2h(ctx, end, dend.p, Q * 4);
+        if (!rc && all) rc = fm_d2h(ctx, index, didx.p, (Q + 1) * 8);
+        if (!rc && all) rc = fm_d2h(ctx, positions, dpos.p, total * 4);
     } while (0);
     kiss_hip_ctx_destroy(ctx);
     return rc;

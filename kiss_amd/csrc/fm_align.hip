@@ -376,9 +376,6 @@ __global__ __launch_bounds__(AL_THREADS) void k_align_emit(const kiss_hip_chain 
     });
 }
 
-inline unsigned al_grid(uint64_t items) { return (unsigned)div_up(items, AL_THREADS); }
-inline uint64_t al_up(uint64_t bytes) { return (bytes + 255) & ~255ull; }
-
 int align_steps(kiss_hip_ctx *ctx, const uint8_t *text, uint64_t n, const uint8_t *reads, const uint64_t *read_index, uint64_t Q,
                 int both, uint64_t V, const kiss_hip_chain *chains, const uint64_t *chain_index, const AlignP &P, kiss_hip_aln *alns,
                 uint64_t aln_capacity, uint32_t *cigar, uint64_t *cigar_index, uint64_t cigar_capacity, kiss_hip_align_report *rep,
@@ -386,16 +383,15 @@ int align_steps(kiss_hip_ctx *ctx, const uint8_t *text, uint64_t n, const uint8_
 {
     if (n > KISS_HIP_MAX_N || V > 0x7FFFFFFFull) return KISS_HIP_E_UNSUPPORTED;
     kiss_opts_refresh(ctx);
-    DevBuf ctl, slab, st;
-    KTRY(ctl.take(ctx, 31, AL_CTL_WORDS * 8));
-    unsigned long long *d_ctl = (unsigned long long *)ctl.p;
-    unsigned long long h[AL_CTL_WORDS] = {0};
+    DevBuf slab, st;
+    FmCtl<AL_CTL_WORDS> ctl;
+    KTRY(ctl.take(ctx, FM_SLOT_ALIGN_CTL));
+    unsigned long long *const d_ctl = ctl.d, *const h = ctl.h;
     ev.mark(0);
-    KTRY(kiss_zero_u32(ctx, ctl.p, AL_CTL_WORDS * 2));
-    hipLaunchKernelGGL(k_align_head, dim3(al_grid(V + 1)), dim3(AL_THREADS), 0, ctx->stream, chain_index, V, read_index, Q, d_ctl);
+    KTRY(ctl.zero());
+    hipLaunchKernelGGL(k_align_head, dim3(fm_grid(V + 1, AL_THREADS)), dim3(AL_THREADS), 0, ctx->stream, chain_index, V, read_index, Q, d_ctl);
     KCHECK(hipGetLastError());
-    KCHECK(hipMemcpyAsync(h, ctl.p, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
-    KCHECK(hipStreamSynchronize(ctx->stream));
+    KTRY(ctl.fetch_sync());
     if (h[AL_BAD]) return KISS_HIP_E_INVALID; // chain_index or read_index decreases, or a read of length 0
     const uint64_t c0 = h[AL_C0], C = h[AL_C1] - c0;
     if (rep) rep->chains = C;
@@ -408,28 +404,23 @@ int align_steps(kiss_hip_ctx *ctx, const uint8_t *text, uint64_t n, const uint8_
         return KISS_HIP_OK;
     }
     // the per-chain arrays of the call, one slab
-    uint64_t off = 0;
-    const auto carve = [&](uint64_t bytes) {
-        const uint64_t at = off;
-        off += al_up(bytes);
-        return at;
-    };
-    const uint64_t o_cells = carve((C + 1) * 8), o_nops = carve((C + 1) * 8), o_recs = carve(C * sizeof(kiss_hip_aln)),
-                   o_best = carve(C * 12), o_vof = carve(C * 4);
-    KTRY(slab.take(ctx, 32, off));
+    FmSlab lay;
+    const uint64_t o_cells = lay.carve((C + 1) * 8), o_nops = lay.carve((C + 1) * 8), o_recs = lay.carve(C * sizeof(kiss_hip_aln)),
+                   o_best = lay.carve(C * 12), o_vof = lay.carve(C * 4);
+    KTRY(slab.take(ctx, FM_SLOT_ALIGN_SLAB, lay.size));
     char *sb = (char *)slab.p;
     uint64_t *cells = (uint64_t *)(sb + o_cells), *nops = (uint64_t *)(sb + o_nops);
     kiss_hip_aln *recs = (kiss_hip_aln *)(sb + o_recs);
     uint32_t *best = (uint32_t *)(sb + o_best), *vof = (uint32_t *)(sb + o_vof);
     {
         KTimer t(ctx, KISS_HIP_K_FM_QUERY, C);
-        hipLaunchKernelGGL(k_align_prep, dim3(al_grid(C + 1)), dim3(AL_THREADS), 0, ctx->stream, chains, chain_index, V, c0, C,
+        hipLaunchKernelGGL(k_align_prep, dim3(fm_grid(C + 1, AL_THREADS)), dim3(AL_THREADS), 0, ctx->stream, chains, chain_index, V, c0, C,
                            read_index, both, P.band, vof, cells, d_ctl);
         KCHECK(hipGetLastError());
     }
     KTRY(kiss_scan_u64(ctx, cells, cells, C + 1));
     uint64_t total_cells = 0;
-    KCHECK(hipMemcpyAsync(h, ctl.p, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+    KTRY(ctl.fetch());
     KCHECK(hipMemcpyAsync(&total_cells, cells + C, 8, hipMemcpyDeviceToHost, ctx->stream));
     KCHECK(hipStreamSynchronize(ctx->stream));
     if (rep) {
@@ -440,7 +431,7 @@ int align_steps(kiss_hip_ctx *ctx, const uint8_t *text, uint64_t n, const uint8_
     }
     // (the total is in the report: split the batch)
     if (total_cells > (uint64_t)KISS_HIP_ALIGN_CELLS_PER_N * ctx->max_n) return KISS_HIP_E_UNSUPPORTED;
-    KTRY(st.take(ctx, 33, total_cells));
+    KTRY(st.take(ctx, FM_SLOT_ALIGN_TRACE, total_cells));
     uint8_t *store = (uint8_t *)st.p;
     ev.mark(1);
     {
@@ -452,14 +443,14 @@ int align_steps(kiss_hip_ctx *ctx, const uint8_t *text, uint64_t n, const uint8_
     ev.mark(2);
     {
         KTimer t(ctx, KISS_HIP_K_FM_QUERY, C);
-        hipLaunchKernelGGL(k_align_trace, dim3(al_grid(C + 1)), dim3(AL_THREADS), 0, ctx->stream, chains, c0, C, (const uint64_t *)cells,
+        hipLaunchKernelGGL(k_align_trace, dim3(fm_grid(C + 1, AL_THREADS)), dim3(AL_THREADS), 0, ctx->stream, chains, c0, C, (const uint64_t *)cells,
                            P.band, (const uint8_t *)store, (const uint32_t *)best, recs, nops, d_ctl);
         KCHECK(hipGetLastError());
     }
     ev.mark(3);
     KTRY(kiss_scan_u64(ctx, nops, nops, C + 1));
     uint64_t total_ops = 0;
-    KCHECK(hipMemcpyAsync(h, ctl.p, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+    KTRY(ctl.fetch());
     KCHECK(hipMemcpyAsync(&total_ops, nops + C, 8, hipMemcpyDeviceToHost, ctx->stream));
     KCHECK(hipStreamSynchronize(ctx->stream));
     if (rep) {
@@ -472,7 +463,7 @@ int align_steps(kiss_hip_ctx *ctx, const uint8_t *text, uint64_t n, const uint8_
     if (aln_capacity < C || (cigar && cigar_capacity < total_ops)) return KISS_HIP_E_INVALID;
     {
         KTimer t(ctx, KISS_HIP_K_FM_QUERY, C);
-        hipLaunchKernelGGL(k_align_emit, dim3(al_grid(C + 1)), dim3(AL_THREADS), 0, ctx->stream, chains, c0, C, (const uint64_t *)cells,
+        hipLaunchKernelGGL(k_align_emit, dim3(fm_grid(C + 1, AL_THREADS)), dim3(AL_THREADS), 0, ctx->stream, chains, c0, C, (const uint64_t *)cells,
                            P.band, (const uint8_t *)store, (const uint32_t *)best, (const kiss_hip_aln *)recs, (const uint64_t *)nops,
                            alns, cigar, cigar_index);
         KCHECK(hipGetLastError());
@@ -528,30 +519,21 @@ int align_one_shot(kiss_hip_ctx *ctx, void *arg)
         (rc = dalns.alloc(ctx, acap * sizeof(kiss_hip_aln))) ||
         (all && ((rc = dcig.alloc(ctx, ocap * 4)) || (rc = doidx.alloc(ctx, (C + 1) * 8)))))
         return rc;
-    hipError_t e = hipMemcpy(dridx.p, a.read_index, (a.Q + 1) * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dcidx.p, a.chain_index, (a.V + 1) * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess && a.n) e = hipMemcpy(dtext.p, a.text, a.n, hipMemcpyHostToDevice);
-    if (e == hipSuccess && a.nbases) e = hipMemcpy(dreads.p, a.reads, a.nbases, hipMemcpyHostToDevice);
-    if (e == hipSuccess && a.nchains) e = hipMemcpy(dchains.p, a.chains, a.nchains * sizeof(kiss_hip_chain), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        ctx->last_hip_error = (int)e;
-        return KISS_HIP_E_HIP;
-    }
+    KTRY(fm_h2d(ctx, dridx.p, a.read_index, (a.Q + 1) * 8));
+    KTRY(fm_h2d(ctx, dcidx.p, a.chain_index, (a.V + 1) * 8));
+    KTRY(fm_h2d(ctx, dtext.p, a.text, a.n));
+    KTRY(fm_h2d(ctx, dreads.p, a.reads, a.nbases));
+    KTRY(fm_h2d(ctx, dchains.p, a.chains, a.nchains * sizeof(kiss_hip_chain)));
     kiss_hip_align_report r{};
     rc = kiss_hip_fmi_align_dev(ctx, (const uint8_t *)dtext.p, a.n, (const uint8_t *)dreads.p, (const uint64_t *)dridx.p, a.Q, a.both,
                                 (const kiss_hip_chain *)dchains.p, (const uint64_t *)dcidx.p, a.params, (kiss_hip_aln *)dalns.p, acap,
                                 all ? (uint32_t *)dcig.p : nullptr, all ? (uint64_t *)doidx.p : nullptr, all ? ocap : 0, &r, nullptr);
     if (a.report) *a.report = r;
     if (rc) return rc;
-    e = hipSuccess;
-    if (C) e = hipMemcpy(a.alns, dalns.p, C * sizeof(kiss_hip_aln), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && all) e = hipMemcpy(a.cigar_index, doidx.p, (C + 1) * 8, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && all && r.cigar_ops) e = hipMemcpy(a.cigar, dcig.p, r.cigar_ops * 4, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) {
-        ctx->last_hip_error = (int)e;
-        return KISS_HIP_E_HIP;
-    }
-    return KISS_HIP_OK;
+    KTRY(fm_d2h(ctx, a.alns, dalns.p, C * sizeof(kiss_hip_aln)));
+    if (!all) return KISS_HIP_OK;
+    KTRY(fm_d2h(ctx, a.cigar_index, doidx.p, (C + 1) * 8));
+    return fm_d2h(ctx, a.cigar, dcig.p, r.cigar_ops * 4);
 }
 
 } // namespace
@@ -570,9 +552,7 @@ int kiss_hip_fmi_align_dev(kiss_hip_ctx *ctx, const uint8_t *text, uint64_t n, c
     }
     KTRY(align_args_check(text, reads, read_index, chains, chain_index, params, alns, cigar, cigar_index, cigar_capacity));
     if (!ctx) return KISS_HIP_E_INVALID;
-    KCHECK(hipSetDevice(ctx->device));
-    ctx->stream = stream ? (hipStream_t)stream : ctx->own_stream;
-    KTRY(kiss_workspace_ready(ctx));
+    KTRY(fm_enter(ctx, stream));
     if (V == 0) { // cigar_index[0] = 0
         if (cigar_index) KTRY(kiss_zero_u32(ctx, cigar_index, 2));
         KCHECK(hipStreamSynchronize(ctx->stream));
@@ -587,11 +567,7 @@ int kiss_hip_fmi_align_dev(kiss_hip_ctx *ctx, const uint8_t *text, uint64_t n, c
     FmEvents ev(ctx, report != nullptr);
     const int rc = align_steps(ctx, text, n, reads, read_index, Q, both_strands ? 1 : 0, V, chains, chain_index, P, alns, aln_capacity,
                                cigar, cigar_index, cigar_capacity, report, ev);
-    // whichever way the steps ended: the time up to the last step that was queued, and no timer left open in the ctx
-    if (rc != KISS_HIP_OK) (void)hipStreamSynchronize(ctx->stream);
-    if (report && ev.last > 0) report->ms_total = ev.ms(0, ev.last);
-    ktimer_collect(ctx);
-    return rc;
+    return fm_leave(ctx, ev, rc, report ? &report->ms_total : nullptr);
 }
 
 int kiss_hip_fmi_align_host(const uint8_t *text, uint64_t n, const uint8_t *reads, const uint64_t *read_index, uint64_t Q,
@@ -605,10 +581,7 @@ int kiss_hip_fmi_align_host(const uint8_t *text, uint64_t n, const uint8_t *read
         report->V = V;
     }
     KTRY(align_args_check(text, reads, read_index, chains, chain_index, params, alns, cigar, cigar_index, cigar_capacity));
-    for (uint64_t q = 0; q < Q; q++)
-        if (read_index[q + 1] <= read_index[q]) return KISS_HIP_E_INVALID;
-    for (uint64_t v = 0; v < V; v++)
-        if (chain_index[v + 1] < chain_index[v]) return KISS_HIP_E_INVALID;
+    if (!fm_index_ascending(read_index, Q, true) || !fm_index_ascending(chain_index, V, false)) return KISS_HIP_E_INVALID;
     AlignHostArgs a{text, n, reads, read_index, Q, both_strands ? 1 : 0, chains, chain_index, params, alns, aln_capacity, cigar,
                     cigar_index, cigar_capacity, report, V, 0, 0, 0};
     a.nchains = chain_index[V]; // (the arrays are uploaded from their first entry)
@@ -626,13 +599,8 @@ int kiss_hip_fmi_align_host(const uint8_t *text, uint64_t n, const uint8_t *read
             }
         }
     }
-    uint64_t max_n = cells / KISS_HIP_ALIGN_CELLS_PER_N + 1;
     const uint64_t C = a.nchains - chain_index[0];
-    if (max_n < 4 * (C + 1)) max_n = 4 * (C + 1);
-    if (max_n < 4 * (V + 1)) max_n = 4 * (V + 1);
-    if (max_n < (1u << 20)) max_n = 1u << 20;
-    if (max_n > KISS_HIP_MAX_N) max_n = KISS_HIP_MAX_N;
-    return kiss_cached_ctx_run(device, max_n, align_one_shot, &a);
+    return kiss_cached_ctx_run(device, fm_host_max_n(cells / KISS_HIP_ALIGN_CELLS_PER_N + 1, C + 1, V + 1), align_one_shot, &a);
 }
 
 } // extern "C"

@@ -355,15 +355,6 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain_emit(const uint4 *__restri
     }
 }
 
-inline unsigned ch_grid(uint64_t items) { return (unsigned)div_up(items, CH_THREADS); }
-inline uint64_t ch_up(uint64_t bytes) { return (bytes + 255) & ~255ull; }
-inline int ch_bits(uint64_t count) // bits that hold 0 .. count - 1, at least 1
-{
-    int b = 1;
-    while (b < 63 && (1ull << b) < count) b++;
-    return b;
-}
-
 int chain_steps(kiss_hip_ctx *ctx, const kiss_hip_fmi_seed *seeds, const uint64_t *seed_index, uint64_t V, const uint32_t *positions,
                 const uint64_t *pos_index, const ChainP &P, kiss_hip_chain *chains, uint64_t *chain_index, uint64_t chain_capacity,
                 kiss_hip_chain_anchor *chain_anchors, uint64_t *anchor_index, uint64_t anchor_capacity, kiss_hip_chain_report *rep,
@@ -371,24 +362,22 @@ int chain_steps(kiss_hip_ctx *ctx, const kiss_hip_fmi_seed *seeds, const uint64_
 {
     if (V > 0x7FFFFFFFull || (V + 1) / 4096 + 16 > ctx->scan_tmp_cap) return KISS_HIP_E_UNSUPPORTED;
     kiss_opts_refresh(ctx);
-    DevBuf ctl, slab, vs;
-    KTRY(ctl.take(ctx, 28, CH_CTL_WORDS * 8));
-    unsigned long long *d_ctl = (unsigned long long *)ctl.p;
-    unsigned long long h[CH_CTL_WORDS] = {0};
+    DevBuf slab, vs;
+    FmCtl<CH_CTL_WORDS> ctl;
+    KTRY(ctl.take(ctx, FM_SLOT_CHAIN_CTL));
+    unsigned long long *const d_ctl = ctl.d, *const h = ctl.h;
     ev.mark(0);
-    KTRY(kiss_zero_u32(ctx, ctl.p, CH_CTL_WORDS * 2));
-    hipLaunchKernelGGL(k_chain_head, dim3(ch_grid(V)), dim3(CH_THREADS), 0, ctx->stream, seed_index, V, d_ctl);
+    KTRY(ctl.zero());
+    hipLaunchKernelGGL(k_chain_head, dim3(fm_grid(V, CH_THREADS)), dim3(CH_THREADS), 0, ctx->stream, seed_index, V, d_ctl);
     KCHECK(hipGetLastError());
-    KCHECK(hipMemcpyAsync(h, ctl.p, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
-    KCHECK(hipStreamSynchronize(ctx->stream));
+    KTRY(ctl.fetch_sync());
     if (h[CH_BAD]) return KISS_HIP_E_INVALID; // seed_index decreases
     const uint64_t s0 = h[CH_S0], s1 = h[CH_S1], nseeds = s1 - s0;
     if (nseeds > 0xFFFFFFFFull) return KISS_HIP_E_UNSUPPORTED;
     hipLaunchKernelGGL(k_chain_input, dim3(nseeds > (1u << 18) ? 1024u : 64u), dim3(CH_THREADS), 0, ctx->stream, pos_index, s0, s1,
                        positions, d_ctl);
     KCHECK(hipGetLastError());
-    KCHECK(hipMemcpyAsync(h, ctl.p, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
-    KCHECK(hipStreamSynchronize(ctx->stream));
+    KTRY(ctl.fetch_sync());
     if (h[CH_BAD]) return KISS_HIP_E_INVALID; // pos_index decreases
     const uint64_t p0 = h[CH_P0], total = h[CH_P1] - p0;
     if (rep) rep->anchors = total;
@@ -401,21 +390,16 @@ int chain_steps(kiss_hip_ctx *ctx, const kiss_hip_fmi_seed *seeds, const uint64_
         KCHECK(hipStreamSynchronize(ctx->stream));
         return KISS_HIP_OK;
     }
-    const int vbits = ch_bits(V), tbits = ch_bits(h[CH_MAXT] + 1);
+    const int vbits = fm_bits(V), tbits = fm_bits(h[CH_MAXT] + 1);
     const int key_shift = (64 - vbits - tbits) & ~7; // the sort takes whole bytes from the top of the key
 
     // the per-anchor arrays of the call, one slab
-    uint64_t off = 0;
-    const auto carve = [&](uint64_t bytes) {
-        const uint64_t at = off;
-        off += ch_up(bytes);
-        return at;
-    };
-    const uint64_t o_anc = carve(total * 16), o_f = carve(total * 8), o_bestf = carve(total * 8), o_packed = carve((total + 1) * 8),
-                   o_seedof = carve(total * 4), o_pred = carve(total * 4), o_root = carve(total * 4), o_depth = carve(total * 4),
-                   o_bestend = carve(total * 4);
-    KTRY(slab.take(ctx, 29, off));
-    KTRY(vs.take(ctx, 30, (V + 1) * 4));
+    FmSlab lay;
+    const uint64_t o_anc = lay.carve(total * 16), o_f = lay.carve(total * 8), o_bestf = lay.carve(total * 8),
+                   o_packed = lay.carve((total + 1) * 8), o_seedof = lay.carve(total * 4), o_pred = lay.carve(total * 4),
+                   o_root = lay.carve(total * 4), o_depth = lay.carve(total * 4), o_bestend = lay.carve(total * 4);
+    KTRY(slab.take(ctx, FM_SLOT_CHAIN_SLAB, lay.size));
+    KTRY(vs.take(ctx, FM_SLOT_CHAIN_VSTART, (V + 1) * 4));
     char *sb = (char *)slab.p;
     uint4 *anc = (uint4 *)(sb + o_anc);
     long long *f = (long long *)(sb + o_f);
@@ -427,22 +411,17 @@ int chain_steps(kiss_hip_ctx *ctx, const kiss_hip_fmi_seed *seeds, const uint64_
     ev.mark(1);
     {
         KTimer t(ctx, KISS_HIP_K_FM_QUERY, total);
-        hipLaunchKernelGGL(k_chain_vstart, dim3(ch_grid(V + 1)), dim3(CH_THREADS), 0, ctx->stream, seed_index, V, pos_index, p0, vstart);
-        hipLaunchKernelGGL(k_chain_expand, dim3(ch_grid(total)), dim3(CH_THREADS), 0, ctx->stream, seeds, seed_index, V, s0, s1,
+        hipLaunchKernelGGL(k_chain_vstart, dim3(fm_grid(V + 1, CH_THREADS)), dim3(CH_THREADS), 0, ctx->stream, seed_index, V, pos_index, p0, vstart);
+        hipLaunchKernelGGL(k_chain_expand, dim3(fm_grid(total, CH_THREADS)), dim3(CH_THREADS), 0, ctx->stream, seeds, seed_index, V, s0, s1,
                            positions, pos_index, p0, total, tbits, key_shift, ctx->keyA, ctx->posA, seed_of, d_ctl);
         KCHECK(hipGetLastError());
     }
-    RadixBufs rb;
-    rb.key[0] = ctx->keyA;
-    rb.key[1] = ctx->keyB;
-    rb.seg[0] = rb.seg[1] = nullptr;
-    rb.pos[0] = ctx->posA; // the slots
-    rb.pos[1] = ctx->posB;
+    RadixBufs rb = kiss_ctx_radix_bufs(ctx); // (the positions: the slots)
     int res = 0;
     KTRY(kiss_radix_sort(ctx, rb, total, key_shift, 0, &res));
     {
         KTimer t(ctx, KISS_HIP_K_FM_QUERY, total);
-        hipLaunchKernelGGL(k_chain_gather, dim3(ch_grid(total)), dim3(CH_THREADS), 0, ctx->stream, (const uint64_t *)rb.key[res],
+        hipLaunchKernelGGL(k_chain_gather, dim3(fm_grid(total, CH_THREADS)), dim3(CH_THREADS), 0, ctx->stream, (const uint64_t *)rb.key[res],
                            (const uint32_t *)rb.pos[res], (const uint32_t *)seed_of, seeds, s0, total, tbits, key_shift, anc);
         KCHECK(hipGetLastError());
     }
@@ -458,16 +437,16 @@ int chain_steps(kiss_hip_ctx *ctx, const kiss_hip_fmi_seed *seeds, const uint64_
     ev.mark(3);
     {
         KTimer t(ctx, KISS_HIP_K_FM_QUERY, total);
-        hipLaunchKernelGGL(k_chain_end, dim3(ch_grid(total)), dim3(CH_THREADS), 0, ctx->stream, (const long long *)f,
+        hipLaunchKernelGGL(k_chain_end, dim3(fm_grid(total, CH_THREADS)), dim3(CH_THREADS), 0, ctx->stream, (const long long *)f,
                            (const uint32_t *)root, (const unsigned long long *)bestf, total, bestend);
-        hipLaunchKernelGGL(k_chain_flag, dim3(ch_grid(total + 1)), dim3(CH_THREADS), 0, ctx->stream, (const uint32_t *)root,
+        hipLaunchKernelGGL(k_chain_flag, dim3(fm_grid(total + 1, CH_THREADS)), dim3(CH_THREADS), 0, ctx->stream, (const uint32_t *)root,
                            (const uint32_t *)depth, (const unsigned long long *)bestf, (const uint32_t *)bestend, total, P.min_score,
                            packed, d_ctl);
         KCHECK(hipGetLastError());
     }
     KTRY(kiss_scan_u64(ctx, packed, packed, total + 1));
     uint64_t totals = 0;
-    KCHECK(hipMemcpyAsync(h, ctl.p, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+    KTRY(ctl.fetch());
     KCHECK(hipMemcpyAsync(&totals, packed + total, 8, hipMemcpyDeviceToHost, ctx->stream));
     KTRY(kiss_radix_check(ctx)); // (synchronises)
     if (h[CH_LEN0]) return KISS_HIP_E_INVALID; // a located seed of length 0
@@ -485,9 +464,9 @@ int chain_steps(kiss_hip_ctx *ctx, const kiss_hip_fmi_seed *seeds, const uint64_
     if (chain_capacity < nchains || (chain_anchors && anchor_capacity < nanchors)) return KISS_HIP_E_INVALID;
     {
         KTimer t(ctx, KISS_HIP_K_FM_QUERY, total);
-        hipLaunchKernelGGL(k_chain_index, dim3(ch_grid(V + 1)), dim3(CH_THREADS), 0, ctx->stream, (const uint32_t *)vstart, V,
+        hipLaunchKernelGGL(k_chain_index, dim3(fm_grid(V + 1, CH_THREADS)), dim3(CH_THREADS), 0, ctx->stream, (const uint32_t *)vstart, V,
                            (const uint64_t *)packed, chain_index);
-        hipLaunchKernelGGL(k_chain_emit, dim3(ch_grid(total + 1)), dim3(CH_THREADS), 0, ctx->stream, (const uint4 *)anc,
+        hipLaunchKernelGGL(k_chain_emit, dim3(fm_grid(total + 1, CH_THREADS)), dim3(CH_THREADS), 0, ctx->stream, (const uint4 *)anc,
                            (const long long *)f, (const uint32_t *)pred1, (const uint32_t *)root, (const uint32_t *)depth,
                            (const unsigned long long *)bestf, (const uint32_t *)bestend, (const uint64_t *)packed, total, P.min_score,
                            chains, chain_anchors, anchor_index);
@@ -541,14 +520,10 @@ int chain_one_shot(kiss_hip_ctx *ctx, void *arg)
         (rc = dcidx.alloc(ctx, (a.V + 1) * 8)) || (all && ((rc = danc.alloc(ctx, acap * sizeof(kiss_hip_chain_anchor))) ||
                                                          (rc = daidx.alloc(ctx, (ccap + 1) * 8)))))
         return rc;
-    hipError_t e = hipMemcpy(dsidx.p, a.seed_index, (a.V + 1) * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dpidx.p, a.pos_index, (a.nseeds + 1) * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess && a.nseeds) e = hipMemcpy(dseeds.p, a.seeds, a.nseeds * 16, hipMemcpyHostToDevice);
-    if (e == hipSuccess && a.npos) e = hipMemcpy(dpos.p, a.positions, a.npos * 4, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        ctx->last_hip_error = (int)e;
-        return KISS_HIP_E_HIP;
-    }
+    KTRY(fm_h2d(ctx, dsidx.p, a.seed_index, (a.V + 1) * 8));
+    KTRY(fm_h2d(ctx, dpidx.p, a.pos_index, (a.nseeds + 1) * 8));
+    KTRY(fm_h2d(ctx, dseeds.p, a.seeds, a.nseeds * 16));
+    KTRY(fm_h2d(ctx, dpos.p, a.positions, a.npos * 4));
     kiss_hip_chain_report r{};
     rc = kiss_hip_fmi_chain_dev(ctx, (const kiss_hip_fmi_seed *)dseeds.p, (const uint64_t *)dsidx.p, a.V, (const uint32_t *)dpos.p,
                                 (const uint64_t *)dpidx.p, a.params, (kiss_hip_chain *)dchains.p, (uint64_t *)dcidx.p, ccap,
@@ -556,16 +531,11 @@ int chain_one_shot(kiss_hip_ctx *ctx, void *arg)
                                 nullptr);
     if (a.report) *a.report = r;
     if (rc) return rc;
-    e = hipMemcpy(a.chain_index, dcidx.p, (a.V + 1) * 8, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && r.chains) e = hipMemcpy(a.chains, dchains.p, r.chains * sizeof(kiss_hip_chain), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && all) e = hipMemcpy(a.anchor_index, daidx.p, (r.chains + 1) * 8, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && all && r.chain_anchors)
-        e = hipMemcpy(a.chain_anchors, danc.p, r.chain_anchors * sizeof(kiss_hip_chain_anchor), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) {
-        ctx->last_hip_error = (int)e;
-        return KISS_HIP_E_HIP;
-    }
-    return KISS_HIP_OK;
+    KTRY(fm_d2h(ctx, a.chain_index, dcidx.p, (a.V + 1) * 8));
+    KTRY(fm_d2h(ctx, a.chains, dchains.p, r.chains * sizeof(kiss_hip_chain)));
+    if (!all) return KISS_HIP_OK;
+    KTRY(fm_d2h(ctx, a.anchor_index, daidx.p, (r.chains + 1) * 8));
+    return fm_d2h(ctx, a.chain_anchors, danc.p, r.chain_anchors * sizeof(kiss_hip_chain_anchor));
 }
 
 } // namespace
@@ -584,9 +554,7 @@ int kiss_hip_fmi_chain_dev(kiss_hip_ctx *ctx, const kiss_hip_fmi_seed *seeds, co
     KTRY(chain_args_check(seeds, seed_index, positions, pos_index, params, chains, chain_index, chain_anchors, anchor_index,
                           anchor_capacity));
     if (!ctx) return KISS_HIP_E_INVALID;
-    KCHECK(hipSetDevice(ctx->device));
-    ctx->stream = stream ? (hipStream_t)stream : ctx->own_stream;
-    KTRY(kiss_workspace_ready(ctx));
+    KTRY(fm_enter(ctx, stream));
     if (V == 0) { // chain_index[0] = anchor_index[0] = 0
         KTRY(kiss_zero_u32(ctx, chain_index, 2));
         if (anchor_index) KTRY(kiss_zero_u32(ctx, anchor_index, 2));
@@ -602,11 +570,7 @@ int kiss_hip_fmi_chain_dev(kiss_hip_ctx *ctx, const kiss_hip_fmi_seed *seeds, co
     FmEvents ev(ctx, report != nullptr);
     const int rc = chain_steps(ctx, seeds, seed_index, V, positions, pos_index, P, chains, chain_index, chain_capacity, chain_anchors,
                                anchor_index, anchor_capacity, report, ev);
-    // whichever way the steps ended: the time up to the last step that was queued, and no timer left open in the ctx
-    if (rc != KISS_HIP_OK) (void)hipStreamSynchronize(ctx->stream);
-    if (report && ev.last > 0) report->ms_total = ev.ms(0, ev.last);
-    ktimer_collect(ctx);
-    return rc;
+    return fm_leave(ctx, ev, rc, report ? &report->ms_total : nullptr);
 }
 
 int kiss_hip_fmi_chain_host(const kiss_hip_fmi_seed *seeds, const uint64_t *seed_index, uint64_t V, const uint32_t *positions,
@@ -620,19 +584,14 @@ int kiss_hip_fmi_chain_host(const kiss_hip_fmi_seed *seeds, const uint64_t *seed
     }
     KTRY(chain_args_check(seeds, seed_index, positions, pos_index, params, chains, chain_index, chain_anchors, anchor_index,
                           anchor_capacity));
-    for (uint64_t v = 0; v < V; v++)
-        if (seed_index[v + 1] < seed_index[v]) return KISS_HIP_E_INVALID;
+    if (!fm_index_ascending(seed_index, V, false)) return KISS_HIP_E_INVALID;
     ChainHostArgs a{seeds, seed_index, V, positions, pos_index, params, chains, chain_index, chain_capacity, chain_anchors, anchor_index,
                     anchor_capacity, report, 0, 0};
     a.nseeds = seed_index[V]; // (the arrays are uploaded from their first entry)
-    for (uint64_t s = 0; s < a.nseeds; s++)
-        if (pos_index[s + 1] < pos_index[s]) return KISS_HIP_E_INVALID;
+    if (!fm_index_ascending(pos_index, a.nseeds, false)) return KISS_HIP_E_INVALID;
     a.npos = pos_index[a.nseeds];
-    // the anchors of a call are sorted in the ctx's LMS arrays (0.32 max_n) and scanned in its scratch
-    uint64_t max_n = 4 * (a.npos + 1) > 4 * (V + 1) ? 4 * (a.npos + 1) : 4 * (V + 1);
-    if (max_n < (1u << 20)) max_n = 1u << 20;
-    if (max_n > KISS_HIP_MAX_N) max_n = KISS_HIP_MAX_N;
-    return kiss_cached_ctx_run(device, max_n, chain_one_shot, &a);
+    // the anchors of a call are sorted in the ctx's LMS arrays and scanned in its scratch
+    return kiss_cached_ctx_run(device, fm_host_max_n(0, a.npos + 1, V + 1), chain_one_shot, &a);
 }
 
 } // extern "C"

@@ -1,7 +1,12 @@
-// fm_internal.hpp -- what the FM-index translation units share (fm.hip: exact queries + construction; fm_mm.hip: the
-// search with mismatches; fm_seed.hip: maximal exact match seeds): the device view of an index, the one-sector rank blocks
-// and the LF arithmetic on them, the rank of the sampling bit-vector, the bounded locate walk of one row, the pooled
-// scratch buffers of a batch and the events behind a report's times.
+// fm_internal.hpp -- what the seven FM-index translation units share (fm.hip: exact queries + construction; fm_mm.hip: the
+// search with mismatches; fm8.hip: the byte alphabet; fm_seed.hip: maximal exact match seeds; fm_chain.hip: chains of seeds;
+// fm_align.hip: banded alignment of the chains; fm_select.hip: the mappings of a read).  Device side: the device view of an
+// index, the one-sector rank blocks and the LF arithmetic on them, the rank of the sampling bit-vector, the bounded locate walk
+// of one row.  Host side, the frame around a batch call: the pooled scratch buffers (DevBuf, slots named by FmSlot in
+// kiss_internal.hpp), the events behind a report's times (FmEvents), the prologue and epilogue of a _dev entry (fm_enter /
+// fm_leave), the control words of a call with their host mirror (FmCtl), the small arithmetic (fm_up256, fm_bits, fm_grid,
+// FmSlab) and what the _host entries need: the checked copies (fm_h2d / fm_d2h), an index uploaded (FmIndexOnDevice), the
+// ascending check of an index array and the size of the one-shot ctx (fm_host_max_n).
 #pragma once
 #include "kiss_internal.hpp"
 
@@ -146,7 +151,7 @@ struct DevBuf {
     }
     // scratch of the batched query: kept in the ctx between calls (slot = fixed role), regrown when too small --
     // nine hipMalloc / hipFree pairs per batch cost as much as the kernels
-    int take(kiss_hip_ctx *ctx, int slot, uint64_t bytes)
+    int take(kiss_hip_ctx *ctx, FmSlot slot, uint64_t bytes)
     {
         pooled = true;
         if (ctx->fm_pool_cap[slot] < bytes) {
@@ -175,7 +180,7 @@ struct FmEvents {
     int last = -1; // the last event recorded
     FmEvents(kiss_hip_ctx *c, bool wanted) : ctx(c), ok(wanted)
     {
-        for (auto &x : ctx->fm_mm_ev)
+        for (auto &x : ctx->fm_ev)
             if (ok && !x && hipEventCreate(&x) != hipSuccess) {
                 x = nullptr;
                 ok = false;
@@ -183,15 +188,149 @@ struct FmEvents {
     }
     void mark(int i)
     {
-        if (ok && hipEventRecord(ctx->fm_mm_ev[i], ctx->stream) == hipSuccess) last = i;
+        if (ok && hipEventRecord(ctx->fm_ev[i], ctx->stream) == hipSuccess) last = i;
     }
     float ms(int a, int b)
     {
         float v = 0.f;
-        if (!ok || hipEventElapsedTime(&v, ctx->fm_mm_ev[a], ctx->fm_mm_ev[b]) != hipSuccess) return 0.f;
+        if (!ok || hipEventElapsedTime(&v, ctx->fm_ev[a], ctx->fm_ev[b]) != hipSuccess) return 0.f;
         return v;
     }
 };
+
+// the frame of a _dev entry.  fm_enter: the device, the stream of the call, the work arrays.  fm_leave, whichever way the
+// steps ended: the time up to the last step that was queued (ms_total: the report's field, or null) and no timer left open
+// in the ctx.
+static inline int fm_enter(kiss_hip_ctx *ctx, void *stream)
+{
+    KCHECK(hipSetDevice(ctx->device));
+    ctx->stream = stream ? (hipStream_t)stream : ctx->own_stream;
+    return kiss_workspace_ready(ctx);
+}
+static inline int fm_leave(kiss_hip_ctx *ctx, FmEvents &ev, int rc, float *ms_total)
+{
+    if (rc != KISS_HIP_OK) (void)hipStreamSynchronize(ctx->stream);
+    if (ms_total && ev.last > 0) *ms_total = ev.ms(0, ev.last);
+    ktimer_collect(ctx);
+    return rc;
+}
+
+// the control words of a call: WORDS 64-bit counters in a pooled buffer (d) and their host mirror (h).  fetch() only queues
+// the copy (the caller queues another one behind it and then synchronises, or lets kiss_radix_check do that);
+// fetch_sync() also waits for it.
+template <int WORDS>
+struct FmCtl {
+    kiss_hip_ctx *ctx = nullptr;
+    DevBuf buf;
+    unsigned long long *d = nullptr;
+    unsigned long long h[WORDS] = {0};
+    int take(kiss_hip_ctx *c, FmSlot slot)
+    {
+        ctx = c;
+        KTRY(buf.take(ctx, slot, WORDS * 8));
+        d = (unsigned long long *)buf.p;
+        return KISS_HIP_OK;
+    }
+    int zero() { return kiss_zero_u32(ctx, d, WORDS * 2); }
+    int fetch()
+    {
+        KCHECK(hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+        return KISS_HIP_OK;
+    }
+    int fetch_sync()
+    {
+        KTRY(fetch());
+        KCHECK(hipStreamSynchronize(ctx->stream));
+        return KISS_HIP_OK;
+    }
+};
+
+static inline bool fm_sa_intv_ok(uint32_t sa_intv) { return sa_intv >= 1 && sa_intv <= KISS_HIP_FMI_MAX_SA_INTV; }
+static inline unsigned fm_grid(uint64_t items, unsigned threads) { return (unsigned)div_up(items, threads); }
+static inline uint64_t fm_up256(uint64_t bytes) { return (bytes + 255) & ~255ull; }
+// bits that hold 0 .. count - 1: at least `least`, at most `cap`
+static inline int fm_bits(uint64_t count, int cap = 63, int least = 1)
+{
+    int b = least;
+    while (b < cap && (1ull << b) < count) b++;
+    return b;
+}
+// the arrays of a call laid out in one pooled buffer: carve() gives the offset of the next one (256-byte aligned), size the
+// bytes to take once all are carved
+struct FmSlab {
+    uint64_t size = 0;
+    uint64_t carve(uint64_t bytes)
+    {
+        const uint64_t at = size;
+        size += fm_up256(bytes);
+        return at;
+    }
+};
+
+// ---- the _host entries ----
+// blocking copies that skip an empty array; a failure is recorded in the ctx
+static inline int fm_copy(kiss_hip_ctx *ctx, void *dst, const void *src, uint64_t bytes, hipMemcpyKind kind)
+{
+    if (!bytes) return KISS_HIP_OK;
+    const hipError_t e = hipMemcpy(dst, src, bytes, kind);
+    if (e == hipSuccess) return KISS_HIP_OK;
+    ctx->last_hip_error = (int)e;
+    return KISS_HIP_E_HIP;
+}
+static inline int fm_h2d(kiss_hip_ctx *ctx, void *dst, const void *src, uint64_t bytes)
+{
+    return fm_copy(ctx, dst, src, bytes, hipMemcpyHostToDevice);
+}
+static inline int fm_d2h(kiss_hip_ctx *ctx, void *dst, const void *src, uint64_t bytes)
+{
+    return fm_copy(ctx, dst, src, bytes, hipMemcpyDeviceToHost);
+}
+
+// a host kiss_hip_fmi_view on the device: its six arrays (z: their sizes; bwt and b with 8 spare bytes behind them) and the
+// view over the copies.  sa_intv == 1 keeps no bit-vector: b / b_occ are allocated, not copied, and null in the view.
+struct FmIndexOnDevice {
+    DevBuf bwt, occ1, occ2, sa, b, b_occ;
+    kiss_hip_fmi_view view;
+    int upload(kiss_hip_ctx *ctx, const kiss_hip_fmi_view &h, const kiss_hip_fmi_sizes &z)
+    {
+        const bool bits = h.sa_intv != 1;
+        int rc;
+        if ((rc = bwt.alloc(ctx, z.bwt_bytes + 8)) || (rc = occ1.alloc(ctx, z.occ1_entries * 4)) || (rc = occ2.alloc(ctx, z.occ2_bytes)) ||
+            (rc = sa.alloc(ctx, z.sa_entries * 4)) || (rc = b.alloc(ctx, z.b_words * 8 + 8)) || (rc = b_occ.alloc(ctx, z.b_occ_entries * 4)))
+            return rc;
+        if ((rc = fm_h2d(ctx, bwt.p, h.bwt, z.bwt_bytes)) || (rc = fm_h2d(ctx, occ1.p, h.occ1, z.occ1_entries * 4)) ||
+            (rc = fm_h2d(ctx, occ2.p, h.occ2, z.occ2_bytes)) || (rc = fm_h2d(ctx, sa.p, h.sa, z.sa_entries * 4)) ||
+            (bits && ((rc = fm_h2d(ctx, b.p, h.b, z.b_words * 8)) || (rc = fm_h2d(ctx, b_occ.p, h.b_occ, z.b_occ_entries * 4)))))
+            return rc;
+        view = h;
+        view.bwt = (const uint8_t *)bwt.p;
+        view.occ1 = (const uint32_t *)occ1.p;
+        view.occ2 = (const uint8_t *)occ2.p;
+        view.sa = (const uint32_t *)sa.p;
+        view.b = bits ? (const uint64_t *)b.p : nullptr;
+        view.b_occ = bits ? (const uint32_t *)b_occ.p : nullptr;
+        return KISS_HIP_OK;
+    }
+};
+
+// idx[0 .. count] never decreases (strict: and no two neighbours are equal)
+static inline bool fm_index_ascending(const uint64_t *idx, uint64_t count, bool strict)
+{
+    for (uint64_t i = 0; i < count; i++)
+        if (idx[i + 1] < idx[i] || (strict && idx[i + 1] == idx[i])) return false;
+    return true;
+}
+// max_n of the ctx of a one-shot call: at least `base` and four times whatever the call sorts in the ctx's LMS arrays or scans
+// in its scratch (they hold about 0.32 max_n entries), inside [2^20, KISS_HIP_MAX_N]
+static inline uint64_t fm_host_max_n(uint64_t base, uint64_t sorted0, uint64_t sorted1 = 0)
+{
+    uint64_t max_n = base;
+    if (max_n < 4 * sorted0) max_n = 4 * sorted0;
+    if (max_n < 4 * sorted1) max_n = 4 * sorted1;
+    if (max_n < (1u << 20)) max_n = 1u << 20;
+    if (max_n > KISS_HIP_MAX_N) max_n = KISS_HIP_MAX_N;
+    return max_n;
+}
 
 // fm.hip: fills blk (nblocks = f.N / 64 + 1 blocks of 32 bytes) from the on-disk arrays of f on the ctx stream (k_fm_blocks)
 int kiss_fm_make_blocks(kiss_hip_ctx *ctx, const FmiD &f, uint64_t nblocks, uint4 *blk);

@@ -440,11 +440,9 @@ void mm_launch_search(kiss_hip_ctx *ctx, uint32_t e, const FmiD &f, const uint8_
 #undef MM_GO
 }
 
-using MmEvents = FmEvents; // (fm_internal.hpp)
-
 int mm_query_steps(kiss_hip_ctx *ctx, const kiss_hip_fmi_view *fmi, const uint8_t *patterns, uint32_t L, uint64_t Q,
                    uint32_t e, uint32_t *counts, uint32_t *positions, uint8_t *mismatches, uint64_t *index,
-                   uint64_t capacity, kiss_hip_fmi_mm_report *rep, MmEvents &ev)
+                   uint64_t capacity, kiss_hip_fmi_mm_report *rep, FmEvents &ev)
 {
     const bool want = positions != nullptr;
     if (Q > 0x7FFFFFFFull || Q / 4096 + 16 > ctx->scan_tmp_cap) return KISS_HIP_E_UNSUPPORTED; // more than the ctx can scan
@@ -453,14 +451,15 @@ int mm_query_steps(kiss_hip_ctx *ctx, const kiss_hip_fmi_view *fmi, const uint8_
     FmiD f = fm_view_of(fmi);
     const uint64_t sa_entries = (f.N + sa_intv - 1) / sa_intv;
 
-    DevBuf blocks, ctl, leaves, qtot, lsize, lidx, heavy, hflag;
+    DevBuf blocks, leaves, qtot, lsize, lidx, heavy, hflag;
+    FmCtl<MM_CTL_WORDS> ctl;
     const uint64_t nblocks = f.N / 64 + 1;
-    KTRY(blocks.take(ctx, 11, nblocks * 32)); // (the slot of the exact query's blocks: the same role)
+    KTRY(blocks.take(ctx, FM_SLOT_BLOCKS, nblocks * 32));
     f.blk = (const uint4 *)blocks.p;
-    KTRY(ctl.take(ctx, 13, MM_CTL_WORDS * 8));
-    if (want) KTRY(qtot.take(ctx, 15, (Q + 1) * 8));
-    KTRY(heavy.take(ctx, 18, (Q + 2) * 4));
-    KTRY(hflag.take(ctx, 19, (Q + 8) & ~3ull));
+    KTRY(ctl.take(ctx, FM_SLOT_MM_CTL));
+    if (want) KTRY(qtot.take(ctx, FM_SLOT_MM_QTOT, (Q + 1) * 8));
+    KTRY(heavy.take(ctx, FM_SLOT_MM_HEAVY, (Q + 2) * 4));
+    KTRY(hflag.take(ctx, FM_SLOT_MM_HFLAG, (Q + 8) & ~3ull));
     ev.mark(0);
     KTRY(kiss_fm_make_blocks(ctx, f, nblocks, (uint4 *)blocks.p));
     // the leaf list (only for positions) is sized by what the pool holds (the previous batch of this ctx); a batch that
@@ -469,16 +468,16 @@ int mm_query_steps(kiss_hip_ctx *ctx, const kiss_hip_fmi_view *fmi, const uint8_
     // (hooks build: every pattern by a wave / a bound of the caller's for the lanes, the A-Bs of DESIGN.md 4.6)
     const bool lane_form = e == 0 || (!ctx->opts.fm_mm_wave && (Q > MM_WAVE_ONLY_Q || ctx->opts.fm_mm_budget));
     const unsigned long long budget = e == 0 ? ~0ull : ctx->opts.fm_mm_budget ? ctx->opts.fm_mm_budget : MM_HEAVY_PAIRS[e];
-    unsigned long long h[MM_CTL_WORDS] = {0};
+    unsigned long long *const h = ctl.h;
     uint64_t leaf_cap = 0;
     for (int attempt = 0;; attempt++) {
         if (want) {
             const uint64_t want_leaves = attempt ? h[MM_NLEAVES] + h[MM_NLEAVES] / 4 + 65536 : (e ? 8 * Q : 2 * Q) + 1024;
-            if (ctx->fm_pool_cap[14] / 16 < want_leaves) KTRY(leaves.take(ctx, 14, want_leaves * 16));
-            else KTRY(leaves.take(ctx, 14, ctx->fm_pool_cap[14]));
-            leaf_cap = ctx->fm_pool_cap[14] / 16;
+            const uint64_t held = ctx->fm_pool_cap[FM_SLOT_MM_LEAVES];
+            KTRY(leaves.take(ctx, FM_SLOT_MM_LEAVES, held / 16 < want_leaves ? want_leaves * 16 : held));
+            leaf_cap = ctx->fm_pool_cap[FM_SLOT_MM_LEAVES] / 16;
         }
-        KTRY(kiss_zero_u32(ctx, ctl.p, MM_CTL_WORDS * 2));
+        KTRY(ctl.zero());
         KTRY(kiss_zero_u32(ctx, heavy.p, 1));
         KTRY(kiss_zero_u32(ctx, hflag.p, (Q + 3) / 4));
         {
@@ -487,19 +486,18 @@ int mm_query_steps(kiss_hip_ctx *ctx, const kiss_hip_fmi_view *fmi, const uint8_
             uint64_t *qt = want ? (uint64_t *)qtot.p : nullptr;
             if (lane_form) {
                 mm_launch_search<false>(ctx, e, f, patterns, L, Q, counts, qt, (uint4 *)leaves.p, leaf_cap,
-                                        (unsigned long long *)ctl.p, budget, (uint32_t *)heavy.p, (uint8_t *)hflag.p, 0);
+                                        ctl.d, budget, (uint32_t *)heavy.p, (uint8_t *)hflag.p, 0);
                 if (e) // the patterns the lanes gave up, a wave each (none: the waves find an empty list)
                     mm_launch_search<true>(ctx, e, f, patterns, L, Q, counts, qt, (uint4 *)leaves.p, leaf_cap,
-                                           (unsigned long long *)ctl.p, 0, (uint32_t *)heavy.p, (uint8_t *)hflag.p, 1);
+                                           ctl.d, 0, (uint32_t *)heavy.p, (uint8_t *)hflag.p, 1);
             } else {
                 mm_launch_search<true>(ctx, e, f, patterns, L, Q, counts, qt, (uint4 *)leaves.p, leaf_cap,
-                                       (unsigned long long *)ctl.p, 0, (uint32_t *)heavy.p, (uint8_t *)hflag.p, 0);
+                                       ctl.d, 0, (uint32_t *)heavy.p, (uint8_t *)hflag.p, 0);
             }
             ev.mark(2);
             KCHECK(hipGetLastError());
         }
-        KCHECK(hipMemcpyAsync(h, ctl.p, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
-        KCHECK(hipStreamSynchronize(ctx->stream));
+        KTRY(ctl.fetch_sync());
         if (h[MM_NLEAVES] <= leaf_cap) break;
         if (attempt) return KINTERNAL();
     }
@@ -520,11 +518,9 @@ int mm_query_steps(kiss_hip_ctx *ctx, const kiss_hip_fmi_view *fmi, const uint8_
         KTRY(kiss_zero_u32(ctx, (uint8_t *)qtot.p + Q * 8, 2));
         KTRY(kiss_scan_u64(ctx, (const uint64_t *)qtot.p, index, Q + 1));
         if (total) {
-            KTRY(lsize.take(ctx, 16, (nleaves + 1) * 8));
-            KTRY(lidx.take(ctx, 17, (nleaves + 1) * 8));
-            int qbits = 0;
-            while (qbits < 32 && (1ull << qbits) < Q) qbits++;
-            const int key_shift = (32 - qbits) & ~7; // the sort takes whole bytes from the top of the key
+            KTRY(lsize.take(ctx, FM_SLOT_MM_LEAF_SIZE, (nleaves + 1) * 8));
+            KTRY(lidx.take(ctx, FM_SLOT_MM_LEAF_INDEX, (nleaves + 1) * 8));
+            const int key_shift = (32 - fm_bits(Q, 32, 0)) & ~7; // the sort takes whole bytes from the top of the key
             {
                 KTimer t(ctx, KISS_HIP_K_FM_QUERY, total);
                 ev.mark(3);
@@ -534,16 +530,11 @@ int mm_query_steps(kiss_hip_ctx *ctx, const kiss_hip_fmi_view *fmi, const uint8_
                 KTRY(kiss_scan_u64(ctx, (const uint64_t *)lsize.p, (uint64_t *)lidx.p, nleaves + 1));
                 hipLaunchKernelGGL(k_fm_mm_locate, dim3((unsigned)div_up(total, MM_LOC_THREADS)), dim3(MM_LOC_THREADS), 0, ctx->stream,
                                    f, sa_intv, sa_entries, (const uint4 *)leaves.p, nleaves, (const uint64_t *)lidx.p, total,
-                                   key_shift, ctx->keyA, ctx->posA, (unsigned long long *)ctl.p);
+                                   key_shift, ctx->keyA, ctx->posA, ctl.d);
                 KCHECK(hipGetLastError());
                 ev.mark(4);
             }
-            RadixBufs rb;
-            rb.key[0] = ctx->keyA;
-            rb.key[1] = ctx->keyB;
-            rb.seg[0] = rb.seg[1] = nullptr;
-            rb.pos[0] = ctx->posA;
-            rb.pos[1] = ctx->posB;
+            RadixBufs rb = kiss_ctx_radix_bufs(ctx);
             int res = 0;
             KTRY(kiss_radix_sort(ctx, rb, total, key_shift, 0, &res));
             {
@@ -553,7 +544,7 @@ int mm_query_steps(kiss_hip_ctx *ctx, const kiss_hip_fmi_view *fmi, const uint8_
                 KCHECK(hipGetLastError());
             }
             ev.mark(5);
-            KCHECK(hipMemcpyAsync(h, ctl.p, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+            KTRY(ctl.fetch());
             KTRY(kiss_radix_check(ctx)); // (synchronises)
             if (rep) {
                 rep->walk_failures = h[MM_WALKFAIL];
@@ -573,20 +564,12 @@ int fmi_query_mm(kiss_hip_ctx *ctx, const kiss_hip_fmi_view *fmi, const uint8_t 
                  uint32_t e, uint32_t *counts, uint32_t *positions, uint8_t *mismatches, uint64_t *index,
                  uint64_t capacity, kiss_hip_fmi_mm_report *rep, void *stream)
 {
-    KCHECK(hipSetDevice(ctx->device));
-    ctx->stream = stream ? (hipStream_t)stream : ctx->own_stream;
-    KTRY(kiss_workspace_ready(ctx));
+    KTRY(fm_enter(ctx, stream));
     if (Q == 0) return KISS_HIP_OK;
-    MmEvents ev(ctx, rep != nullptr);
+    FmEvents ev(ctx, rep != nullptr);
     const int rc = mm_query_steps(ctx, fmi, patterns, L, Q, e, counts, positions, mismatches, index, capacity, rep, ev);
-    // whichever way the steps ended: the time up to the last step that was queued, and no timer left open in the ctx
-    if (rc != KISS_HIP_OK) (void)hipStreamSynchronize(ctx->stream);
-    if (rep && ev.last > 0) rep->ms_total = ev.ms(0, ev.last);
-    ktimer_collect(ctx);
-    return rc;
+    return fm_leave(ctx, ev, rc, rep ? &rep->ms_total : nullptr);
 }
-
-bool mm_sa_intv_ok(uint32_t sa_intv) { return sa_intv >= 1 && sa_intv <= KISS_HIP_FMI_MAX_SA_INTV; }
 
 } // namespace
 
@@ -603,7 +586,7 @@ int kiss_hip_fmi_query_mm_dev(kiss_hip_ctx *ctx, const kiss_hip_fmi_view *fmi, c
         report->max_mismatches = max_mismatches;
     }
     if (!fmi) return KISS_HIP_E_INVALID;
-    if (max_mismatches > KISS_HIP_FMI_MAX_MISMATCHES || !mm_sa_intv_ok(fmi->sa_intv)) return KISS_HIP_E_UNSUPPORTED;
+    if (max_mismatches > KISS_HIP_FMI_MAX_MISMATCHES || !fm_sa_intv_ok(fmi->sa_intv)) return KISS_HIP_E_UNSUPPORTED;
     const bool any = positions || mismatches || index, all = positions && mismatches && index;
     if (!ctx || L == 0 || fmi->n_sa == 0 || (Q && (!patterns || !counts)) || any != all || (!any && capacity) || !fmi->bwt ||
         !fmi->occ1 || !fmi->occ2)
@@ -630,7 +613,7 @@ int kiss_hip_fmi_query_mm_host(const kiss_hip_fmi_view *fmi, const uint8_t *patt
     }
     if (!fmi) return KISS_HIP_E_INVALID;
     const uint32_t sa_intv = fmi->sa_intv;
-    if (max_mismatches > KISS_HIP_FMI_MAX_MISMATCHES || !mm_sa_intv_ok(sa_intv)) return KISS_HIP_E_UNSUPPORTED;
+    if (max_mismatches > KISS_HIP_FMI_MAX_MISMATCHES || !fm_sa_intv_ok(sa_intv)) return KISS_HIP_E_UNSUPPORTED;
     const bool any = positions || mismatches || index, all = positions && mismatches && index;
     if (L == 0 || fmi->n_sa == 0 || (Q && (!patterns || !counts)) || any != all || (!any && capacity) || !fmi->bwt || !fmi->occ1 ||
         !fmi->occ2 || !fmi->sa || (sa_intv != 1 && (!fmi->b || !fmi->b_occ)))
@@ -638,50 +621,30 @@ int kiss_hip_fmi_query_mm_host(const kiss_hip_fmi_view *fmi, const uint8_t *patt
     kiss_hip_fmi_sizes_ex z;
     KTRY(kiss_hip_fmi_sizes_ex_for(fmi->n_sa - 1, sa_intv, 0, &z));
     kiss_hip_ctx *ctx = nullptr;
-    uint64_t max_n = fmi->n_sa > 4 * Q ? fmi->n_sa : 4 * Q;
-    if (max_n < 4 * capacity) max_n = 4 * capacity; // the hits of a call are sorted in the ctx's LMS arrays (0.32 max_n entries)
-    if (max_n < (1u << 20)) max_n = 1u << 20;
-    if (max_n > KISS_HIP_MAX_N) max_n = KISS_HIP_MAX_N;
-    int rc = kiss_hip_ctx_create(&ctx, device, max_n);
+    // (the hits of a call are sorted in the ctx's LMS arrays)
+    int rc = kiss_hip_ctx_create(&ctx, device, fm_host_max_n(fmi->n_sa, Q, capacity));
     if (rc) return rc;
     const uint32_t e1 = max_mismatches + 1;
-    DevBuf dbwt, docc1, docc2, dsa, db, dbocc, dpat, dcnt, dpos, dmm, didx;
+    FmIndexOnDevice idx;
+    DevBuf dpat, dcnt, dpos, dmm, didx;
     do {
-        if ((rc = dbwt.alloc(ctx, z.base.bwt_bytes + 8)) || (rc = docc1.alloc(ctx, z.base.occ1_entries * 4)) ||
-            (rc = docc2.alloc(ctx, z.base.occ2_bytes)) || (rc = dsa.alloc(ctx, z.base.sa_entries * 4)) ||
-            (rc = db.alloc(ctx, z.base.b_words * 8 + 8)) || (rc = dbocc.alloc(ctx, z.base.b_occ_entries * 4)) ||
-            (rc = dpat.alloc(ctx, Q * L)) || (rc = dcnt.alloc(ctx, Q * e1 * 4)))
+        if ((rc = idx.upload(ctx, *fmi, z.base)) || (rc = dpat.alloc(ctx, Q * L)) || (rc = dcnt.alloc(ctx, Q * e1 * 4)) ||
+            (rc = fm_h2d(ctx, dpat.p, patterns, Q * L)))
             break;
-        hipError_t e = hipMemcpy(dbwt.p, fmi->bwt, z.base.bwt_bytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(docc1.p, fmi->occ1, z.base.occ1_entries * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(docc2.p, fmi->occ2, z.base.occ2_bytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(dsa.p, fmi->sa, z.base.sa_entries * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess && sa_intv != 1) e = hipMemcpy(db.p, fmi->b, z.base.b_words * 8, hipMemcpyHostToDevice);
-        if (e == hipSuccess && sa_intv != 1) e = hipMemcpy(dbocc.p, fmi->b_occ, z.base.b_occ_entries * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess && Q) e = hipMemcpy(dpat.p, patterns, Q * L, hipMemcpyHostToDevice);
-        if (e != hipSuccess) { rc = KISS_HIP_E_HIP; break; }
-        kiss_hip_fmi_view v = *fmi;
-        v.bwt = (const uint8_t *)dbwt.p;
-        v.occ1 = (const uint32_t *)docc1.p;
-        v.occ2 = (const uint8_t *)docc2.p;
-        v.sa = (const uint32_t *)dsa.p;
-        v.b = sa_intv == 1 ? nullptr : (const uint64_t *)db.p;
-        v.b_occ = sa_intv == 1 ? nullptr : (const uint32_t *)dbocc.p;
         if (all && ((rc = dpos.alloc(ctx, capacity * 4)) || (rc = dmm.alloc(ctx, capacity)) || (rc = didx.alloc(ctx, (Q + 1) * 8))))
             break;
         kiss_hip_fmi_mm_report r{};
-        rc = kiss_hip_fmi_query_mm_dev(ctx, &v, (const uint8_t *)dpat.p, L, Q, max_mismatches, (uint32_t *)dcnt.p,
+        rc = kiss_hip_fmi_query_mm_dev(ctx, &idx.view, (const uint8_t *)dpat.p, L, Q, max_mismatches, (uint32_t *)dcnt.p,
                                        all ? (uint32_t *)dpos.p : nullptr, all ? (uint8_t *)dmm.p : nullptr,
                                        all ? (uint64_t *)didx.p : nullptr, all ? capacity : 0, &r, nullptr);
         if (report) *report = r;
         if (rc) break;
         uint64_t total = 0;
         for (int j = 0; j < 4; j++) total += r.hits[j];
-        if (Q) e = hipMemcpy(counts, dcnt.p, Q * e1 * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && all) e = hipMemcpy(index, didx.p, (Q + 1) * 8, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && all && total) e = hipMemcpy(positions, dpos.p, total * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && all && total) e = hipMemcpy(mismatches, dmm.p, total, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = KISS_HIP_E_HIP;
+        rc = fm_d2h(ctx, counts, dcnt.p, Q * e1 * 4);
+        if (!rc && all) rc = fm_d2h(ctx, index, didx.p, (Q + 1) * 8);
+        if (!rc && all) rc = fm_d2h(ctx, positions, dpos.p, total * 4);
+        if (!rc && all) rc = fm_d2h(ctx, mismatches, dmm.p, total);
     } while (0);
     kiss_hip_ctx_destroy(ctx);
     return rc;

@@ -251,8 +251,6 @@ __global__ __launch_bounds__(SD_THREADS) void k_fm_seed_unpack(const uint64_t *_
     if (i < total) positions[i] = (uint32_t)(keys[i] >> key_shift);
 }
 
-inline unsigned sd_grid(uint64_t items) { return (unsigned)div_up(items, SD_THREADS); }
-
 int seed_steps(kiss_hip_ctx *ctx, const kiss_hip_fmi_view *fmi, const uint8_t *reads, const uint64_t *read_index, uint64_t Q,
                uint32_t min_len, uint32_t max_len, uint32_t max_occ, int both_strands, uint32_t *ms, kiss_hip_fmi_seed *seeds,
                uint64_t *seed_index, uint64_t seed_capacity, uint32_t *positions, uint64_t *pos_index, uint64_t pos_capacity,
@@ -264,15 +262,14 @@ int seed_steps(kiss_hip_ctx *ctx, const kiss_hip_fmi_view *fmi, const uint8_t *r
     const uint32_t sa_intv = fmi->sa_intv;
     FmiD f = fm_view_of(fmi);
     const uint64_t sa_entries = (f.N + sa_intv - 1) / sa_intv;
-    DevBuf blocks, ctl, msbuf, rng, flags, scanned, psize;
-    KTRY(ctl.take(ctx, 22, SD_CTL_WORDS * 8));
-    unsigned long long *d_ctl = (unsigned long long *)ctl.p;
-    KTRY(kiss_zero_u32(ctx, ctl.p, SD_CTL_WORDS * 2));
-    hipLaunchKernelGGL(k_fm_seed_check, dim3(sd_grid(Q)), dim3(SD_THREADS), 0, ctx->stream, read_index, Q, d_ctl);
+    DevBuf blocks, msbuf, rng, flags, scanned, psize;
+    FmCtl<SD_CTL_WORDS> ctl;
+    KTRY(ctl.take(ctx, FM_SLOT_SEED_CTL));
+    unsigned long long *const d_ctl = ctl.d, *const h = ctl.h;
+    KTRY(ctl.zero());
+    hipLaunchKernelGGL(k_fm_seed_check, dim3(fm_grid(Q, SD_THREADS)), dim3(SD_THREADS), 0, ctx->stream, read_index, Q, d_ctl);
     KCHECK(hipGetLastError());
-    unsigned long long h[SD_CTL_WORDS] = {0};
-    KCHECK(hipMemcpyAsync(h, ctl.p, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
-    KCHECK(hipStreamSynchronize(ctx->stream));
+    KTRY(ctl.fetch_sync());
     if (h[SD_BAD]) return KISS_HIP_E_INVALID; // a read of length zero, or read_index decreases
     SeedBatch B;
     B.reads = reads;
@@ -287,31 +284,31 @@ int seed_steps(kiss_hip_ctx *ctx, const kiss_hip_fmi_view *fmi, const uint8_t *r
     if (bases > 0x7FFFFFFFull || (bases + 1) / 4096 + 16 > ctx->scan_tmp_cap) return KISS_HIP_E_UNSUPPORTED;
 
     const uint64_t nblocks = f.N / 64 + 1;
-    KTRY(blocks.take(ctx, 11, nblocks * 32)); // (the slot of the exact query's blocks: the same role)
+    KTRY(blocks.take(ctx, FM_SLOT_BLOCKS, nblocks * 32));
     f.blk = (const uint4 *)blocks.p;
     if (!ms) {
-        KTRY(msbuf.take(ctx, 23, (bases + 1) * 4));
+        KTRY(msbuf.take(ctx, FM_SLOT_SEED_MS, (bases + 1) * 4));
         ms = (uint32_t *)msbuf.p;
     }
-    KTRY(rng.take(ctx, 24, bases * 8));
-    KTRY(flags.take(ctx, 25, (bases + 1) * 4));
-    KTRY(scanned.take(ctx, 26, (bases + 1) * 4));
+    KTRY(rng.take(ctx, FM_SLOT_SEED_RANGES, bases * 8));
+    KTRY(flags.take(ctx, FM_SLOT_SEED_FLAGS, (bases + 1) * 4));
+    KTRY(scanned.take(ctx, FM_SLOT_SEED_SCANNED, (bases + 1) * 4));
     ev.mark(0);
     KTRY(kiss_fm_make_blocks(ctx, f, nblocks, (uint4 *)blocks.p));
     {
         KTimer t(ctx, KISS_HIP_K_FM_QUERY, bases);
         ev.mark(1);
-        hipLaunchKernelGGL(k_fm_seed_ms, dim3(sd_grid(bases)), dim3(SD_THREADS), 0, ctx->stream, f, B, max_len, ms, (uint2 *)rng.p,
+        hipLaunchKernelGGL(k_fm_seed_ms, dim3(fm_grid(bases, SD_THREADS)), dim3(SD_THREADS), 0, ctx->stream, f, B, max_len, ms, (uint2 *)rng.p,
                            d_ctl);
         KCHECK(hipGetLastError());
         ev.mark(2);
-        hipLaunchKernelGGL(k_fm_seed_flag, dim3(sd_grid(bases + 1)), dim3(SD_THREADS), 0, ctx->stream, B, min_len, max_occ,
+        hipLaunchKernelGGL(k_fm_seed_flag, dim3(fm_grid(bases + 1, SD_THREADS)), dim3(SD_THREADS), 0, ctx->stream, B, min_len, max_occ,
                            (const uint32_t *)ms, (const uint2 *)rng.p, (uint32_t *)flags.p, d_ctl);
         KCHECK(hipGetLastError());
     }
     KTRY(kiss_scan_u32(ctx, (const uint32_t *)flags.p, (uint32_t *)scanned.p, bases + 1));
     uint32_t nseeds32 = 0;
-    KCHECK(hipMemcpyAsync(h, ctl.p, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+    KTRY(ctl.fetch());
     KCHECK(hipMemcpyAsync(&nseeds32, (const uint32_t *)scanned.p + bases, 4, hipMemcpyDeviceToHost, ctx->stream));
     KCHECK(hipStreamSynchronize(ctx->stream));
     const uint64_t nseeds = nseeds32, total = h[SD_POSITIONS];
@@ -326,13 +323,13 @@ int seed_steps(kiss_hip_ctx *ctx, const kiss_hip_fmi_view *fmi, const uint8_t *r
     // (the totals are in the report: the caller's second call)
     if (seed_capacity < nseeds || (want && pos_capacity < total)) return KISS_HIP_E_INVALID;
     if (want && total > ctx->m_cap) return KISS_HIP_E_UNSUPPORTED; // the sort runs in the ctx's LMS key arrays
-    if (want) KTRY(psize.take(ctx, 27, (nseeds + 1) * 8));
+    if (want) KTRY(psize.take(ctx, FM_SLOT_SEED_POS_SIZE, (nseeds + 1) * 8));
     {
         KTimer t(ctx, KISS_HIP_K_FM_QUERY, bases);
-        hipLaunchKernelGGL(k_fm_seed_compact, dim3(sd_grid(bases + 1)), dim3(SD_THREADS), 0, ctx->stream, B, max_occ,
+        hipLaunchKernelGGL(k_fm_seed_compact, dim3(fm_grid(bases + 1, SD_THREADS)), dim3(SD_THREADS), 0, ctx->stream, B, max_occ,
                            (const uint32_t *)ms, (const uint2 *)rng.p, (const uint32_t *)flags.p, (const uint32_t *)scanned.p, seeds,
                            (uint64_t *)psize.p);
-        hipLaunchKernelGGL(k_fm_seed_index, dim3(sd_grid(V + 1)), dim3(SD_THREADS), 0, ctx->stream, B, (const uint32_t *)scanned.p,
+        hipLaunchKernelGGL(k_fm_seed_index, dim3(fm_grid(V + 1, SD_THREADS)), dim3(SD_THREADS), 0, ctx->stream, B, (const uint32_t *)scanned.p,
                            seed_index);
         KCHECK(hipGetLastError());
     }
@@ -341,33 +338,26 @@ int seed_steps(kiss_hip_ctx *ctx, const kiss_hip_fmi_view *fmi, const uint8_t *r
     if (rep) rep->ms_compact = 0.f;
     int rc = KISS_HIP_OK;
     if (want && total) {
-        int sbits = 0;
-        while (sbits < 32 && (1ull << sbits) < nseeds) sbits++;
-        const int key_shift = (32 - sbits) & ~7; // the sort takes whole bytes from the top of the key
+        const int key_shift = (32 - fm_bits(nseeds, 32, 0)) & ~7; // the sort takes whole bytes from the top of the key
         {
             KTimer t(ctx, KISS_HIP_K_FM_QUERY, total);
-            hipLaunchKernelGGL(k_fm_seed_locate, dim3(sd_grid(total)), dim3(SD_THREADS), 0, ctx->stream, f, sa_intv, sa_entries,
+            hipLaunchKernelGGL(k_fm_seed_locate, dim3(fm_grid(total, SD_THREADS)), dim3(SD_THREADS), 0, ctx->stream, f, sa_intv, sa_entries,
                                (const kiss_hip_fmi_seed *)seeds, nseeds, (const uint64_t *)pos_index, total, key_shift, ctx->keyA,
                                d_ctl);
             KCHECK(hipGetLastError());
             ev.mark(4);
         }
-        RadixBufs rb;
-        rb.key[0] = ctx->keyA;
-        rb.key[1] = ctx->keyB;
-        rb.seg[0] = rb.seg[1] = nullptr;
-        rb.pos[0] = ctx->posA; // (a payload nobody reads)
-        rb.pos[1] = ctx->posB;
+        RadixBufs rb = kiss_ctx_radix_bufs(ctx); // (a payload nobody reads)
         int res = 0;
         KTRY(kiss_radix_sort(ctx, rb, total, key_shift, 0, &res));
         {
             KTimer t(ctx, KISS_HIP_K_FM_QUERY, total);
-            hipLaunchKernelGGL(k_fm_seed_unpack, dim3(sd_grid(total)), dim3(SD_THREADS), 0, ctx->stream, rb.key[res], total,
+            hipLaunchKernelGGL(k_fm_seed_unpack, dim3(fm_grid(total, SD_THREADS)), dim3(SD_THREADS), 0, ctx->stream, rb.key[res], total,
                                key_shift, positions);
             KCHECK(hipGetLastError());
         }
         ev.mark(5);
-        KCHECK(hipMemcpyAsync(h, ctl.p, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+        KTRY(ctl.fetch());
         KTRY(kiss_radix_check(ctx)); // (synchronises)
         if (rep) {
             rep->walk_failures = h[SD_WALKFAIL];
@@ -389,7 +379,7 @@ int seed_args_check(const kiss_hip_fmi_view_ex *fmi, bool host, const uint8_t *r
 {
     if (!fmi) return KISS_HIP_E_INVALID;
     const kiss_hip_fmi_view &v = fmi->base;
-    if (v.sa_intv < 1 || v.sa_intv > KISS_HIP_FMI_MAX_SA_INTV) return KISS_HIP_E_UNSUPPORTED;
+    if (!fm_sa_intv_ok(v.sa_intv)) return KISS_HIP_E_UNSUPPORTED;
     const bool any = positions || pos_index, all = positions && pos_index;
     if (min_len == 0 || v.n_sa == 0 || !v.bwt || !v.occ1 || !v.occ2 || !seed_index || (Q && (!reads || !read_index || !seeds)) ||
         any != all || (!any && pos_capacity))
@@ -414,9 +404,7 @@ int kiss_hip_fmi_seeds_dev(kiss_hip_ctx *ctx, const kiss_hip_fmi_view_ex *fmi, c
     }
     KTRY(seed_args_check(fmi, false, reads, read_index, Q, min_len, seeds, seed_index, positions, pos_index, pos_capacity));
     if (!ctx) return KISS_HIP_E_INVALID;
-    KCHECK(hipSetDevice(ctx->device));
-    ctx->stream = stream ? (hipStream_t)stream : ctx->own_stream;
-    KTRY(kiss_workspace_ready(ctx));
+    KTRY(fm_enter(ctx, stream));
     if (Q == 0) { // seed_index[0] = pos_index[0] = 0
         KTRY(kiss_zero_u32(ctx, seed_index, 2));
         if (pos_index) KTRY(kiss_zero_u32(ctx, pos_index, 2));
@@ -426,11 +414,7 @@ int kiss_hip_fmi_seeds_dev(kiss_hip_ctx *ctx, const kiss_hip_fmi_view_ex *fmi, c
     FmEvents ev(ctx, report != nullptr);
     const int rc = seed_steps(ctx, &fmi->base, reads, read_index, Q, min_len, max_len, max_occ, both_strands, ms, seeds, seed_index,
                               seed_capacity, positions, pos_index, pos_capacity, report, ev);
-    // whichever way the steps ended: the time up to the last step that was queued, and no timer left open in the ctx
-    if (rc != KISS_HIP_OK) (void)hipStreamSynchronize(ctx->stream);
-    if (report && ev.last > 0) report->ms_total = ev.ms(0, ev.last);
-    ktimer_collect(ctx);
-    return rc;
+    return fm_leave(ctx, ev, rc, report ? &report->ms_total : nullptr);
 }
 
 int kiss_hip_fmi_seeds_host(const kiss_hip_fmi_view_ex *fmi, const uint8_t *reads, const uint64_t *read_index, uint64_t Q,
@@ -444,8 +428,7 @@ int kiss_hip_fmi_seeds_host(const kiss_hip_fmi_view_ex *fmi, const uint8_t *read
         report->V = both_strands ? 2 * Q : Q;
     }
     KTRY(seed_args_check(fmi, true, reads, read_index, Q, min_len, seeds, seed_index, positions, pos_index, pos_capacity));
-    for (uint64_t q = 0; q < Q; q++)
-        if (read_index[q + 1] <= read_index[q]) return KISS_HIP_E_INVALID;
+    if (!fm_index_ascending(read_index, Q, true)) return KISS_HIP_E_INVALID;
     const kiss_hip_fmi_view &hv = fmi->base;
     const uint32_t sa_intv = hv.sa_intv;
     const bool all = positions != nullptr;
@@ -454,41 +437,24 @@ int kiss_hip_fmi_seeds_host(const kiss_hip_fmi_view_ex *fmi, const uint8_t *read
     const uint64_t r0 = Q ? read_index[0] : 0, read_bytes = Q ? read_index[Q] - r0 : 0;
     const uint64_t V = both_strands ? 2 * Q : Q, bases = both_strands ? 2 * read_bytes : read_bytes;
     if (seed_capacity > bases) seed_capacity = bases; // (always enough)
-    uint64_t max_n = hv.n_sa > 4 * (bases + 1) ? hv.n_sa : 4 * (bases + 1); // the ends of a call are scanned in the ctx's scratch,
-    if (max_n < 4 * pos_capacity) max_n = 4 * pos_capacity;                 // its positions sorted in the LMS arrays (0.32 max_n)
-    if (max_n < (1u << 20)) max_n = 1u << 20;
-    if (max_n > KISS_HIP_MAX_N) max_n = KISS_HIP_MAX_N;
     kiss_hip_ctx *ctx = nullptr;
-    int rc = kiss_hip_ctx_create(&ctx, device, max_n);
+    // (the ends of a call are scanned in the ctx's scratch, its positions sorted in the LMS arrays)
+    int rc = kiss_hip_ctx_create(&ctx, device, fm_host_max_n(hv.n_sa, bases + 1, pos_capacity));
     if (rc) return rc;
-    DevBuf dbwt, docc1, docc2, dsa, db, dbocc, dreads, dridx, dms, dseeds, dsidx, dpos, dpidx;
+    FmIndexOnDevice idx;
+    DevBuf dreads, dridx, dms, dseeds, dsidx, dpos, dpidx;
     do {
-        if ((rc = dbwt.alloc(ctx, z.base.bwt_bytes + 8)) || (rc = docc1.alloc(ctx, z.base.occ1_entries * 4)) ||
-            (rc = docc2.alloc(ctx, z.base.occ2_bytes)) || (rc = dsa.alloc(ctx, z.base.sa_entries * 4)) ||
-            (rc = db.alloc(ctx, z.base.b_words * 8 + 8)) || (rc = dbocc.alloc(ctx, z.base.b_occ_entries * 4)) ||
-            (rc = dreads.alloc(ctx, read_bytes)) || (rc = dridx.alloc(ctx, (Q + 1) * 8)) || (rc = dseeds.alloc(ctx, seed_capacity * 16)) ||
-            (rc = dsidx.alloc(ctx, (V + 1) * 8)) || (ms && (rc = dms.alloc(ctx, bases * 4))))
+        if ((rc = idx.upload(ctx, hv, z.base)) || (rc = dreads.alloc(ctx, read_bytes)) || (rc = dridx.alloc(ctx, (Q + 1) * 8)) ||
+            (rc = dseeds.alloc(ctx, seed_capacity * 16)) || (rc = dsidx.alloc(ctx, (V + 1) * 8)) || (ms && (rc = dms.alloc(ctx, bases * 4))) ||
+            (rc = fm_h2d(ctx, dreads.p, reads + r0, read_bytes)))
             break;
-        hipError_t e = hipMemcpy(dbwt.p, hv.bwt, z.base.bwt_bytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(docc1.p, hv.occ1, z.base.occ1_entries * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(docc2.p, hv.occ2, z.base.occ2_bytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(dsa.p, hv.sa, z.base.sa_entries * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess && sa_intv != 1) e = hipMemcpy(db.p, hv.b, z.base.b_words * 8, hipMemcpyHostToDevice);
-        if (e == hipSuccess && sa_intv != 1) e = hipMemcpy(dbocc.p, hv.b_occ, z.base.b_occ_entries * 4, hipMemcpyHostToDevice);
-        if (e == hipSuccess && read_bytes) e = hipMemcpy(dreads.p, reads + r0, read_bytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess && Q) { // (the reads were copied from read_index[0] on)
+        if (Q) { // (the reads were copied from read_index[0] on)
             std::vector<uint64_t> ridx(read_index, read_index + Q + 1);
             for (auto &x : ridx) x -= r0;
-            e = hipMemcpy(dridx.p, ridx.data(), (Q + 1) * 8, hipMemcpyHostToDevice);
+            if ((rc = fm_h2d(ctx, dridx.p, ridx.data(), (Q + 1) * 8))) break;
         }
-        if (e != hipSuccess) { rc = KISS_HIP_E_HIP; break; }
         kiss_hip_fmi_view_ex v = *fmi;
-        v.base.bwt = (const uint8_t *)dbwt.p;
-        v.base.occ1 = (const uint32_t *)docc1.p;
-        v.base.occ2 = (const uint8_t *)docc2.p;
-        v.base.sa = (const uint32_t *)dsa.p;
-        v.base.b = sa_intv == 1 ? nullptr : (const uint64_t *)db.p;
-        v.base.b_occ = sa_intv == 1 ? nullptr : (const uint32_t *)dbocc.p;
+        v.base = idx.view;
         v.lookup = nullptr; // (the search does not use it)
         if (all && ((rc = dpos.alloc(ctx, pos_capacity * 4)) || (rc = dpidx.alloc(ctx, (seed_capacity + 1) * 8)))) break;
         kiss_hip_fmi_seed_report r{};
@@ -498,12 +464,11 @@ int kiss_hip_fmi_seeds_host(const kiss_hip_fmi_view_ex *fmi, const uint8_t *read
                                     all ? pos_capacity : 0, &r, nullptr);
         if (report) *report = r;
         if (rc) break;
-        e = hipMemcpy(seed_index, dsidx.p, (V + 1) * 8, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && r.seeds) e = hipMemcpy(seeds, dseeds.p, r.seeds * 16, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && ms && bases) e = hipMemcpy(ms, dms.p, bases * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && all) e = hipMemcpy(pos_index, dpidx.p, (r.seeds + 1) * 8, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && all && r.positions) e = hipMemcpy(positions, dpos.p, r.positions * 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = KISS_HIP_E_HIP;
+        rc = fm_d2h(ctx, seed_index, dsidx.p, (V + 1) * 8);
+        if (!rc) rc = fm_d2h(ctx, seeds, dseeds.p, r.seeds * 16);
+        if (!rc && ms) rc = fm_d2h(ctx, ms, dms.p, bases * 4);
+        if (!rc && all) rc = fm_d2h(ctx, pos_index, dpidx.p, (r.seeds + 1) * 8);
+        if (!rc && all) rc = fm_d2h(ctx, positions, dpos.p, r.positions * 4);
     } while (0);
     kiss_hip_ctx_destroy(ctx);
     return rc;

@@ -323,15 +323,6 @@ __global__ __launch_bounds__(SL_THREADS) void k_select_emit(const uint64_t *__re
     sl_st32(&o->ref, K.ref[s]);
 }
 
-inline unsigned sl_grid(uint64_t items) { return (unsigned)div_up(items, SL_THREADS); }
-inline uint64_t sl_up(uint64_t bytes) { return (bytes + 255) & ~255ull; }
-inline int sl_bits(uint64_t count) // bits that hold 0 .. count - 1, at least 1
-{
-    int b = 1;
-    while (b < 63 && (1ull << b) < count) b++;
-    return b;
-}
-
 int select_steps(kiss_hip_ctx *ctx, const kiss_hip_aln *alns, const uint64_t *chain_index, const uint64_t *read_index, uint64_t Q, int both,
                  uint64_t V, const uint64_t *bounds, uint64_t R, const SelectP &P, kiss_hip_hit *hits, uint64_t *hit_index,
                  uint64_t hit_capacity, kiss_hip_select_report *rep, FmEvents &ev)
@@ -339,21 +330,20 @@ int select_steps(kiss_hip_ctx *ctx, const kiss_hip_aln *alns, const uint64_t *ch
     if (V > 0x7FFFFFFFull) return KISS_HIP_E_UNSUPPORTED;
     if ((Q + 1) / 4096 + 16 > ctx->scan_tmp_cap) return KISS_HIP_E_UNSUPPORTED;
     kiss_opts_refresh(ctx);
-    DevBuf ctl, slab;
-    KTRY(ctl.take(ctx, 34, SL_CTL_WORDS * 8));
-    unsigned long long *d_ctl = (unsigned long long *)ctl.p;
-    unsigned long long h[SL_CTL_WORDS] = {0};
+    DevBuf slab;
+    FmCtl<SL_CTL_WORDS> ctl;
+    KTRY(ctl.take(ctx, FM_SLOT_SELECT_CTL));
+    unsigned long long *const d_ctl = ctl.d, *const h = ctl.h;
     ev.mark(0);
-    KTRY(kiss_zero_u32(ctx, ctl.p, SL_CTL_WORDS * 2));
+    KTRY(ctl.zero());
     {
         uint64_t items = V + 1 > Q ? V + 1 : Q;
         if (bounds && R + 1 > items) items = R + 1;
-        hipLaunchKernelGGL(k_select_head, dim3(sl_grid(items)), dim3(SL_THREADS), 0, ctx->stream, chain_index, V, read_index, Q, bounds, R,
+        hipLaunchKernelGGL(k_select_head, dim3(fm_grid(items, SL_THREADS)), dim3(SL_THREADS), 0, ctx->stream, chain_index, V, read_index, Q, bounds, R,
                            d_ctl);
         KCHECK(hipGetLastError());
     }
-    KCHECK(hipMemcpyAsync(h, ctl.p, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
-    KCHECK(hipStreamSynchronize(ctx->stream));
+    KTRY(ctl.fetch_sync());
     if (h[SL_BAD]) return KISS_HIP_E_INVALID; // chain_index or read_index decreases, a read of length 0, bounds out of order
     const uint64_t c0 = h[SL_C0], C = h[SL_C1] - c0;
     if (rep) rep->alignments = C;
@@ -366,19 +356,14 @@ int select_steps(kiss_hip_ctx *ctx, const kiss_hip_aln *alns, const uint64_t *ch
     }
     // one call: its alignments are sorted in the ctx's LMS key arrays
     if (C > ctx->m_cap) return KISS_HIP_E_UNSUPPORTED;
-    const int key_shift = (32 - sl_bits(Q)) & ~7; // the sort takes whole bytes from the top of the key
+    const int key_shift = (32 - fm_bits(Q)) & ~7; // the sort takes whole bytes from the top of the key
 
     // the per-alignment arrays of the call, one slab
-    uint64_t off = 0;
-    const auto carve = [&](uint64_t bytes) {
-        const uint64_t at = off;
-        off += sl_up(bytes);
-        return at;
-    };
+    FmSlab lay;
     uint64_t o_kept[11];
-    for (auto &o : o_kept) o = carve(C * 4);
-    const uint64_t o_refs = carve(C * 4), o_nkept = carve((Q + 1) * 8);
-    KTRY(slab.take(ctx, 35, off));
+    for (auto &o : o_kept) o = lay.carve(C * 4);
+    const uint64_t o_refs = lay.carve(C * 4), o_nkept = lay.carve((Q + 1) * 8);
+    KTRY(slab.take(ctx, FM_SLOT_SELECT_SLAB, lay.size));
     char *sb = (char *)slab.p;
     Kept K;
     uint32_t **kf[11] = {&K.rb, &K.re, &K.tb, &K.te, &K.fl, &K.aln, &K.score, &K.sub, &K.nsec, &K.head, &K.ref};
@@ -388,16 +373,11 @@ int select_steps(kiss_hip_ctx *ctx, const kiss_hip_aln *alns, const uint64_t *ch
 
     {
         KTimer t(ctx, KISS_HIP_K_FM_QUERY, C);
-        hipLaunchKernelGGL(k_select_key, dim3(sl_grid(C)), dim3(SL_THREADS), 0, ctx->stream, alns, chain_index, V, c0, C, both, bounds, R,
+        hipLaunchKernelGGL(k_select_key, dim3(fm_grid(C, SL_THREADS)), dim3(SL_THREADS), 0, ctx->stream, alns, chain_index, V, c0, C, both, bounds, R,
                            P.min_score, key_shift, ctx->keyA, ctx->posA, refs, d_ctl);
         KCHECK(hipGetLastError());
     }
-    RadixBufs rb;
-    rb.key[0] = ctx->keyA;
-    rb.key[1] = ctx->keyB;
-    rb.seg[0] = rb.seg[1] = nullptr;
-    rb.pos[0] = ctx->posA; // a
-    rb.pos[1] = ctx->posB;
+    RadixBufs rb = kiss_ctx_radix_bufs(ctx); // (the positions: a)
     int res = 0;
     KTRY(kiss_radix_sort(ctx, rb, C, key_shift, 0, &res));
     ev.mark(1);
@@ -411,7 +391,7 @@ int select_steps(kiss_hip_ctx *ctx, const kiss_hip_aln *alns, const uint64_t *ch
     ev.mark(2);
     KTRY(kiss_scan_u64(ctx, nkept, nkept, Q + 1));
     uint64_t total = 0;
-    KCHECK(hipMemcpyAsync(h, ctl.p, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+    KTRY(ctl.fetch());
     KCHECK(hipMemcpyAsync(&total, nkept + Q, 8, hipMemcpyDeviceToHost, ctx->stream));
     KTRY(kiss_radix_check(ctx)); // (synchronises)
     if (rep) {
@@ -429,7 +409,7 @@ int select_steps(kiss_hip_ctx *ctx, const kiss_hip_aln *alns, const uint64_t *ch
     if (hit_capacity < total) return KISS_HIP_E_INVALID;
     {
         KTimer t(ctx, KISS_HIP_K_FM_QUERY, C);
-        hipLaunchKernelGGL(k_select_emit, dim3(sl_grid(C > Q + 1 ? C : Q + 1)), dim3(SL_THREADS), 0, ctx->stream, chain_index, V, c0, C, Q,
+        hipLaunchKernelGGL(k_select_emit, dim3(fm_grid(C > Q + 1 ? C : Q + 1, SL_THREADS)), dim3(SL_THREADS), 0, ctx->stream, chain_index, V, c0, C, Q,
                            both, (const uint64_t *)nkept, P, K, hits, hit_index);
         KCHECK(hipGetLastError());
     }
@@ -473,27 +453,18 @@ int select_one_shot(kiss_hip_ctx *ctx, void *arg)
         (rc = dridx.alloc(ctx, (a.Q + 1) * 8)) || (a.bounds && (rc = dbounds.alloc(ctx, (a.R + 1) * 8))) ||
         (rc = dhits.alloc(ctx, hcap * sizeof(kiss_hip_hit))) || (rc = dhidx.alloc(ctx, (a.Q + 1) * 8)))
         return rc;
-    hipError_t e = hipMemcpy(dcidx.p, a.chain_index, (a.V + 1) * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dridx.p, a.read_index, (a.Q + 1) * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess && a.bounds) e = hipMemcpy(dbounds.p, a.bounds, (a.R + 1) * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess && a.C) e = hipMemcpy(dalns.p, a.alns, a.C * sizeof(kiss_hip_aln), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        ctx->last_hip_error = (int)e;
-        return KISS_HIP_E_HIP;
-    }
+    KTRY(fm_h2d(ctx, dcidx.p, a.chain_index, (a.V + 1) * 8));
+    KTRY(fm_h2d(ctx, dridx.p, a.read_index, (a.Q + 1) * 8));
+    if (a.bounds) KTRY(fm_h2d(ctx, dbounds.p, a.bounds, (a.R + 1) * 8));
+    KTRY(fm_h2d(ctx, dalns.p, a.alns, a.C * sizeof(kiss_hip_aln)));
     kiss_hip_select_report r{};
     rc = kiss_hip_fmi_select_dev(ctx, (const kiss_hip_aln *)dalns.p, (const uint64_t *)dcidx.p, (const uint64_t *)dridx.p, a.Q, a.both,
                                  a.bounds ? (const uint64_t *)dbounds.p : nullptr, a.R, a.params, (kiss_hip_hit *)dhits.p,
                                  (uint64_t *)dhidx.p, hcap, &r, nullptr);
     if (a.report) *a.report = r;
     if (rc) return rc;
-    e = hipMemcpy(a.hit_index, dhidx.p, (a.Q + 1) * 8, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && r.hits) e = hipMemcpy(a.hits, dhits.p, r.hits * sizeof(kiss_hip_hit), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) {
-        ctx->last_hip_error = (int)e;
-        return KISS_HIP_E_HIP;
-    }
-    return KISS_HIP_OK;
+    KTRY(fm_d2h(ctx, a.hit_index, dhidx.p, (a.Q + 1) * 8));
+    return fm_d2h(ctx, a.hits, dhits.p, r.hits * sizeof(kiss_hip_hit));
 }
 
 } // namespace
@@ -512,9 +483,7 @@ int kiss_hip_fmi_select_dev(kiss_hip_ctx *ctx, const kiss_hip_aln *alns, const u
     }
     KTRY(select_args_check(alns, chain_index, read_index, bounds, R, params, hits, hit_index));
     if (!ctx) return KISS_HIP_E_INVALID;
-    KCHECK(hipSetDevice(ctx->device));
-    ctx->stream = stream ? (hipStream_t)stream : ctx->own_stream;
-    KTRY(kiss_workspace_ready(ctx));
+    KTRY(fm_enter(ctx, stream));
     if (Q == 0) { // hit_index[0] = 0
         KTRY(kiss_zero_u32(ctx, hit_index, 2));
         KCHECK(hipStreamSynchronize(ctx->stream));
@@ -529,11 +498,7 @@ int kiss_hip_fmi_select_dev(kiss_hip_ctx *ctx, const kiss_hip_aln *alns, const u
     FmEvents ev(ctx, report != nullptr);
     const int rc = select_steps(ctx, alns, chain_index, read_index, Q, both_strands ? 1 : 0, V, bounds, R, P, hits, hit_index, hit_capacity,
                                 report, ev);
-    // whichever way the steps ended: the time up to the last step that was queued, and no timer left open in the ctx
-    if (rc != KISS_HIP_OK) (void)hipStreamSynchronize(ctx->stream);
-    if (report && ev.last > 0) report->ms_total = ev.ms(0, ev.last);
-    ktimer_collect(ctx);
-    return rc;
+    return fm_leave(ctx, ev, rc, report ? &report->ms_total : nullptr);
 }
 
 int kiss_hip_fmi_select_host(const kiss_hip_aln *alns, const uint64_t *chain_index, const uint64_t *read_index, uint64_t Q,
@@ -548,19 +513,13 @@ int kiss_hip_fmi_select_host(const kiss_hip_aln *alns, const uint64_t *chain_ind
     }
     KTRY(select_args_check(alns, chain_index, read_index, bounds, R, params, hits, hit_index));
     if (V > 0x7FFFFFFFull) return KISS_HIP_E_UNSUPPORTED;
-    for (uint64_t q = 0; q < Q; q++)
-        if (read_index[q + 1] <= read_index[q]) return KISS_HIP_E_INVALID;
-    for (uint64_t v = 0; v < V; v++)
-        if (chain_index[v + 1] < chain_index[v]) return KISS_HIP_E_INVALID;
+    if (!fm_index_ascending(read_index, Q, true) || !fm_index_ascending(chain_index, V, false)) return KISS_HIP_E_INVALID;
     SelectHostArgs a{alns, chain_index, read_index, Q, both_strands ? 1 : 0, bounds, R, params, hits, hit_index, hit_capacity, report, V, 0};
     a.C = chain_index[V] - chain_index[0]; // (alns is indexed from 0, as the align call writes it)
     if (report) report->alignments = a.C;
     if (a.C > 0xFFFFFFFFull) return KISS_HIP_E_UNSUPPORTED;
-    // the alignments of a call are sorted in the ctx's LMS arrays (0.32 max_n) and the reads scanned in its scratch
-    uint64_t max_n = 4 * (a.C + 1) > 4 * (V + 1) ? 4 * (a.C + 1) : 4 * (V + 1);
-    if (max_n < (1u << 20)) max_n = 1u << 20;
-    if (max_n > KISS_HIP_MAX_N) max_n = KISS_HIP_MAX_N;
-    return kiss_cached_ctx_run(device, max_n, select_one_shot, &a);
+    // the alignments of a call are sorted in the ctx's LMS arrays and the reads scanned in its scratch
+    return kiss_cached_ctx_run(device, fm_host_max_n(0, a.C + 1, V + 1), select_one_shot, &a);
 }
 
 } // extern "C"

@@ -183,12 +183,7 @@ int kiss_hip_ctx_suffix_sort_u8_dev(kiss_hip_ctx *ctx, const uint8_t *d_S, uint6
             KTimer t(ctx, KISS_HIP_K_KEYGATHER, n);
             hipLaunchKernelGGL(k_ga_keys, dim3(grid), dim3(GA_THREADS), 0, ctx->stream, d_S, n, ctx->keyA, ctx->posA);
         }
-        RadixBufs rb;
-        rb.key[0] = ctx->keyA;
-        rb.key[1] = ctx->keyB;
-        rb.pos[0] = ctx->posA;
-        rb.pos[1] = ctx->posB;
-        rb.seg[0] = rb.seg[1] = nullptr;
+        RadixBufs rb = kiss_ctx_radix_bufs(ctx);
         int res = 0;
         if ((rc = kiss_radix_sort(ctx, rb, n, 0, 0, &res))) break;
         {

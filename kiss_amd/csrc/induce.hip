@@ -1115,12 +1115,7 @@ int run_collapse(Sweep &sw, uint32_t c, int64_t beg, uint64_t N, uint32_t termma
             KCHECK(hipGetLastError());
         }
         if (E > 0) {
-            RadixBufs rb;
-            rb.key[0] = ctx->keyA;
-            rb.key[1] = ctx->keyB;
-            rb.pos[0] = ctx->posA;
-            rb.pos[1] = ctx->posB;
-            rb.seg[0] = rb.seg[1] = nullptr;
+            RadixBufs rb = kiss_ctx_radix_bufs(ctx);
             int res = 0;
             KTRY(kiss_radix_sort(ctx, rb, E, tshift, 0, &res)); // step index t sits in bits tshift..63
             KTimer t(ctx, KISS_HIP_K_INDUCE_SMALL, E);

@@ -114,6 +114,58 @@ static inline void kiss_opts_refresh(kiss_hip_ctx *) {}
 #include <cstdio>
 #define KINTERNAL() (fprintf(stderr, "[kiss_hip] internal check failed at %s:%d\n", __FILE__, __LINE__), KISS_HIP_E_INTERNAL)
 
+// ---- the pooled scratch of the FM-index batch calls (fm*.hip; DevBuf::take in fm_internal.hpp) ------------------------
+// One slot per role, in the order the calls were added: a new one goes in front of FM_SLOT_COUNT, which sizes the pool.
+enum FmSlot {
+    // kiss_hip_fmi_query_batch_dev / _ex_dev (fm.hip)
+    FM_SLOT_HEAVY,       // [0] = count, [1..] = the patterns located by a workgroup each
+    FM_SLOT_CAP,         // per pattern: offset-scratch entries it may need
+    FM_SLOT_CAP_INDEX,   // ... scanned
+    FM_SLOT_GOT,         // per pattern: offsets found
+    FM_SLOT_GOT_INDEX,   // ... scanned
+    FM_SLOT_TOTALS,      // hits, checksum, entries needed, overflow
+    FM_SLOT_FRONTIER0,   // the two frontier arrays of the locate walk
+    FM_SLOT_FRONTIER1,
+    FM_SLOT_OFFSETS,     // the offset scratch
+    FM_SLOT_FCAP,        // per pattern: frontier entries it may need
+    FM_SLOT_FCAP_INDEX,  // ... scanned
+    // The interleaved rank blocks of a DNA index, rebuilt from the caller's arrays at the start of every call.  Shared on
+    // purpose by the exact query (fm.hip), the search with mismatches (fm_mm.hip) and the seeds (fm_seed.hip): the same
+    // role, and one call at a time per ctx.
+    FM_SLOT_BLOCKS,
+    FM_SLOT_MEDIUM,      // as FM_SLOT_HEAVY: the patterns located by a wave each
+    // kiss_hip_fmi_query_mm_dev (fm_mm.hip)
+    FM_SLOT_MM_CTL,
+    FM_SLOT_MM_LEAVES,
+    FM_SLOT_MM_QTOT,     // per pattern: hits
+    FM_SLOT_MM_LEAF_SIZE,
+    FM_SLOT_MM_LEAF_INDEX,
+    FM_SLOT_MM_HEAVY,    // the patterns the lanes gave up
+    FM_SLOT_MM_HFLAG,
+    // kiss_hip_fmi8_query_dev (fm8.hip)
+    FM_SLOT_FM8_CTL,
+    FM_SLOT_FM8_COUNTS,
+    // kiss_hip_fmi_seeds_dev (fm_seed.hip)
+    FM_SLOT_SEED_CTL,
+    FM_SLOT_SEED_MS,     // matching statistics, when the caller keeps none
+    FM_SLOT_SEED_RANGES,
+    FM_SLOT_SEED_FLAGS,
+    FM_SLOT_SEED_SCANNED,
+    FM_SLOT_SEED_POS_SIZE,
+    // kiss_hip_fmi_chain_dev (fm_chain.hip)
+    FM_SLOT_CHAIN_CTL,
+    FM_SLOT_CHAIN_SLAB,  // the per-anchor arrays
+    FM_SLOT_CHAIN_VSTART,
+    // kiss_hip_fmi_align_dev (fm_align.hip)
+    FM_SLOT_ALIGN_CTL,
+    FM_SLOT_ALIGN_SLAB,  // the per-chain arrays
+    FM_SLOT_ALIGN_TRACE, // the traceback store
+    // kiss_hip_fmi_select_dev (fm_select.hip)
+    FM_SLOT_SELECT_CTL,
+    FM_SLOT_SELECT_SLAB, // the per-alignment arrays
+    FM_SLOT_COUNT
+};
+
 // ---- device workspace -----------------------------------------------------------
 struct kiss_hip_ctx {
     int device = 0;
@@ -195,12 +247,10 @@ struct kiss_hip_ctx {
     // PREFIX_DOUBLING: (position, index) pairs of the binned inverse-suffix-array build (isa.hip), allocated on first use
     uint64_t *pairs1 = nullptr, *pairs2 = nullptr;
     uint64_t pairs_cap = 0;
-    // scratch of kiss_hip_fmi_query_batch_dev (slots 0..12, fm.hip), of kiss_hip_fmi_query_mm_dev (slots 13..19,
-    // fm_mm.hip), of kiss_hip_fmi8_query_dev (slots 20.., fm8.hip), of the seeds and the chain call (22..30) and of
-    // kiss_hip_fmi_align_dev (31..33, fm_align.hip) and of kiss_hip_fmi_select_dev (34..35, fm_select.hip), kept between calls
-    void *fm_pool[36] = {};
-    uint64_t fm_pool_cap[36] = {};
-    hipEvent_t fm_mm_ev[6] = {}; // fm_mm.hip / fm8.hip / fm_seed.hip: the times of their reports (created by the first call that wants one)
+    // scratch of the FM-index batch calls, kept between calls: one buffer per FmSlot
+    void *fm_pool[FM_SLOT_COUNT] = {};
+    uint64_t fm_pool_cap[FM_SLOT_COUNT] = {};
+    hipEvent_t fm_ev[6] = {}; // the times of the FM-index reports (fm_internal.hpp: FmEvents; created by the first call that wants one)
     // near-end
     uint32_t *near_idx = nullptr, *near_fin = nullptr, *near_pos = nullptr, *near_tmp = nullptr, *near_tmp2 = nullptr; // place.hip: near_reserve
     uint64_t near_cap = 0;
@@ -293,6 +343,17 @@ struct RadixBufs {
     uint32_t *pos[2];
     const uint32_t *first_pos = nullptr; // optional: the first pass reads its positions from here instead of pos[0]
 };
+// the ctx's own key / position arrays, no segments
+static inline RadixBufs kiss_ctx_radix_bufs(kiss_hip_ctx *ctx)
+{
+    RadixBufs b;
+    b.key[0] = ctx->keyA;
+    b.key[1] = ctx->keyB;
+    b.seg[0] = b.seg[1] = nullptr;
+    b.pos[0] = ctx->posA;
+    b.pos[1] = ctx->posB;
+    return b;
+}
 int kiss_radix_sort(kiss_hip_ctx *ctx, RadixBufs &b, uint64_t count, int key_lo_bit, int seg_bits, int *result_idx);
 int kiss_radix_check(kiss_hip_ctx *ctx); // synchronises; KISS_HIP_E_INTERNAL if a look-back wait ran out
 // stages.hip: pieces of the sharded form shared with multi.hip (all queued on ctx->stream, not synchronised)
