@@ -880,6 +880,76 @@ int kiss_hip_fmi_select_host(const kiss_hip_aln *alns, const uint64_t *chain_ind
                              kiss_hip_hit *hits, uint64_t *hit_index, uint64_t hit_capacity, kiss_hip_select_report *report,
                              int device);
 
+/* ---- FM-index: the mappings of two mates paired: proper pairs, pair MAPQ, TLEN (no reference counterpart) ---------------
+ * The select call treats every read on its own.  This call takes what it wrote for a batch in which reads 2 p and 2 p + 1
+ * are mate 1 and mate 2 of pair p (so Q is even, P = Q / 2) and says which combination of their hits is the pair.  One
+ * definition in integers; tests/fm_pair_model.py restates it.  The result is a function of the input arrays and the
+ * parameters alone: no index, no text, no reads, no bounds (a hit carries ref) and no both_strands (a hit carries
+ * KISS_HIP_HIT_REVERSE).  ONLY forward-then-reverse libraries (FR: the mates face each other) are supported.
+ * Input: hits with hit_index (Q + 1 u64 over the READS) as kiss_hip_fmi_select_dev wrote them: the hits of read q are
+ * hits[hit_index[q] .. hit_index[q + 1]), and a hit's number is its place in that segment.  alns with aln_count: hit.aln
+ * indexes alns; only tbeg and tend are read.
+ * Parameters (kiss_hip_pair_params, all u32; in parentheses the defaults of Python and the command line, which are part of the
+ * definition and not measurements): ins_min (0), ins_max (1000), ins_mean (400), pen_coef (8, in 256ths of a score point per
+ * base of deviation; at most 65535), pen_max (20; at most 65535), mapq_coef (120; at most 65535), mapq_max (60; at most 255).
+ * All interval arithmetic is signed 64-bit, as in select.
+ * Eligible: the hits of a read with head == 0 (the primary and its secondaries) and tbeg < tend.  Supplementary heads and
+ * their secondaries never pair.  x and y are hit numbers of mate 1 and mate 2.
+ * Concordant: a combination (x, y) of eligible hits is concordant iff their ref fields are equal, their strands differ, and
+ * with f the forward hit and r the reverse one f.tbeg <= r.tbeg, f.tend <= r.tend and T = r.tend - f.tbeg has
+ * ins_min <= T <= ins_max.
+ * Pair score: S(x, y) = max(1, score(x) + score(y) - min(pen_max, floor(|T - ins_mean| * pen_coef / 256))).
+ * Best: the largest S; ties go to the smallest x, then the smallest y.  sub1 = the largest S over the concordant (x', y')
+ * with x' != x, 0 if there is none; sub2 the same with y' != y.  (Select has dropped the duplicates of a locus, so another
+ * x' is another locus of mate 1.)
+ * MAPQ of mate m in a proper pair: max(mapq of its chosen hit, min(mapq_max, floor(mapq_coef * (S - sub_m) / S))), in u64.
+ * So a mate in a repeat whose other copies have no concordant partner gets the full value, and a chosen hit that select
+ * called secondary (mapq 0) is lifted by the pair.  tlen = T.
+ * No concordant combination: each mate keeps its hit number 0, or KISS_HIP_PAIR_NONE when its segment is empty; score = the sum
+ * of the scores of the mates that mapped; sub1 = sub2 = 0; the MAPQs are those of the hits (0 for an unmapped mate); tlen =
+ * max(tend) - min(tbeg) of the two hits (0 if that is negative) when both mapped with equal ref, else 0.
+ * Record kiss_hip_pair, 10 u32: hit1, hit2 (indices into hits: hit_index[q] + hit number, or KISS_HIP_PAIR_NONE), flags, tlen,
+ * score, sub1, sub2, mapq1, mapq2, n_conc (the concordant combinations, saturated at 2^32 - 1).  Flags: PROPER, MATE1_MAPPED,
+ * MATE2_MAPPED (the segment is not empty), SAME_REF (both mapped and the chosen hits have equal ref), PROMOTED1, PROMOTED2 (the
+ * chosen hit is not hit number 0).  Exactly P records are written, in pair order: no capacity, no sizing call.  pairs, hits
+ * and alns need no more than the 4-byte alignment of their fields: records are read and written field by field.
+ * BAD INPUT: a pair one of whose hits -- any hit of the two segments -- has aln outside [0, aln_count) or a score of 2^30 or
+ * more (select writes neither) gets a record that is all zero but for flags = KISS_HIP_PAIR_BAD_INPUT, and counts nowhere in
+ * the report but in bad_input.  So nothing is read outside alns whatever the arrays hold, and S fits u32.
+ * Report: P, eligible (hits), combinations (the sum of |E1| * |E2|), concordant, proper (pairs), promoted (mates), lifted
+ * (mates whose MAPQ is above their hit's), bad_input (pairs), max_combinations (the largest |E1| * |E2|), times.
+ * KISS_HIP_E_INVALID: a required pointer NULL, Q odd, a hit_index that decreases, ins_min > ins_max, a parameter over its
+ * limit; pairs is untouched then.  Q == 0: KISS_HIP_OK.  KISS_HIP_E_UNSUPPORTED: Q of 2^32 or more, hit_index[Q] of
+ * 2^32 - 1 or more.
+ * KNOWN PROPERTY: one wave per pair; the hits of mate 2 live in the lanes, 64 at a time, and the eligible hits of mate 1 are
+ * handed to them one by one, twice (the best, then sub1 / sub2 / n_conc).  A pair with |E1| eligible hits of mate 1 and n2
+ * hits of mate 2 costs about 2 * |E1| * ceil(n2 / 64) steps of one wave: cap it with select's max_hits.
+ * Device times: report->ms_* (report may be NULL); the kernels also count under KISS_HIP_K_FM_QUERY. */
+#define KISS_HIP_PAIR_NONE 0xFFFFFFFFu
+#define KISS_HIP_PAIR_PROPER 1u
+#define KISS_HIP_PAIR_MATE1_MAPPED 2u
+#define KISS_HIP_PAIR_MATE2_MAPPED 4u
+#define KISS_HIP_PAIR_SAME_REF 8u
+#define KISS_HIP_PAIR_PROMOTED1 16u
+#define KISS_HIP_PAIR_PROMOTED2 32u
+#define KISS_HIP_PAIR_BAD_INPUT 64u
+typedef struct kiss_hip_pair_params { uint32_t ins_min, ins_max, ins_mean, pen_coef, pen_max, mapq_coef, mapq_max; } kiss_hip_pair_params;
+typedef struct kiss_hip_pair { uint32_t hit1, hit2, flags, tlen, score, sub1, sub2, mapq1, mapq2, n_conc; } kiss_hip_pair;
+typedef struct kiss_hip_pair_report {
+    uint64_t P, eligible, combinations, concordant, proper, promoted, lifted, bad_input, max_combinations;
+    float ms_total, ms_check, ms_pair; /* check: hit_index looked at once by the host; pair: the one kernel */
+    uint32_t reserved_;
+} kiss_hip_pair_report;
+/* every pointer except params and report is a device pointer */
+int kiss_hip_fmi_pair_dev(kiss_hip_ctx *ctx, const kiss_hip_hit *hits, const uint64_t *hit_index, uint64_t Q,
+                          const kiss_hip_aln *alns, uint64_t aln_count, const kiss_hip_pair_params *params, kiss_hip_pair *pairs,
+                          kiss_hip_pair_report *report, void *stream);
+/* the same with host pointers (the device's cached one-shot context, as kiss_hip_fmi_chain_host); hits holds hit_index[Q]
+ * records */
+int kiss_hip_fmi_pair_host(const kiss_hip_hit *hits, const uint64_t *hit_index, uint64_t Q, const kiss_hip_aln *alns,
+                           uint64_t aln_count, const kiss_hip_pair_params *params, kiss_hip_pair *pairs,
+                           kiss_hip_pair_report *report, int device);
+
 #ifdef __cplusplus
 }
 #endif

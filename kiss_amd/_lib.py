@@ -221,6 +221,27 @@ class SelectReport(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved_"}
 
 
+class PairParams(ctypes.Structure):
+    """kiss_hip_pair_params"""
+    _fields_ = [(k, ctypes.c_uint32) for k in ("ins_min", "ins_max", "ins_mean", "pen_coef", "pen_max", "mapq_coef", "mapq_max")]
+
+
+class Pair(ctypes.Structure):
+    """kiss_hip_pair"""
+    _fields_ = [(k, ctypes.c_uint32) for k in ("hit1", "hit2", "flags", "tlen", "score", "sub1", "sub2", "mapq1", "mapq2", "n_conc")]
+
+
+class PairReport(ctypes.Structure):
+    """kiss_hip_pair_report"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("P", "eligible", "combinations", "concordant", "proper", "promoted", "lifted",
+                                               "bad_input", "max_combinations")] + [
+        ("ms_total", ctypes.c_float), ("ms_check", ctypes.c_float), ("ms_pair", ctypes.c_float), ("reserved_", ctypes.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved_"}
+
+
 class Fmi8View(ctypes.Structure):
     """kiss_hip_fmi8_view"""
     _fields_ = [
@@ -380,6 +401,10 @@ def load(hooks=None):
     lib.kiss_hip_fmi_select_host.argtypes = [vp, vp, vp, u64, ctypes.c_int, vp, u64, ctypes.POINTER(SelectParams), vp, vp, u64,
                                              ctypes.POINTER(SelectReport), ctypes.c_int]
     lib.kiss_hip_fmi_select_dev.restype = lib.kiss_hip_fmi_select_host.restype = ctypes.c_int
+    lib.kiss_hip_fmi_pair_dev.argtypes = [vp, vp, vp, u64, vp, u64, ctypes.POINTER(PairParams), vp, ctypes.POINTER(PairReport), vp]
+    lib.kiss_hip_fmi_pair_host.argtypes = [vp, vp, u64, vp, u64, ctypes.POINTER(PairParams), vp, ctypes.POINTER(PairReport),
+                                           ctypes.c_int]
+    lib.kiss_hip_fmi_pair_dev.restype = lib.kiss_hip_fmi_pair_host.restype = ctypes.c_int
     lib.kiss_hip_fmi8_sizes_for.argtypes = [u64, u32, u32, ctypes.POINTER(Fmi8Sizes)]
     lib.kiss_hip_fmi8_build_dev.argtypes = [vp, vp, u64, vp, u32, u32] + [vp] * 8 + [ctypes.POINTER(u32), ctypes.POINTER(u32), vp]
     lib.kiss_hip_fmi8_build_host.argtypes = [vp, u64, vp, u32, u32] + [vp] * 8 + [ctypes.POINTER(u32), ctypes.POINTER(u32),
@@ -456,5 +481,5 @@ EXPORTED_SYMBOLS = [
     "kiss_hip_fmi8_sizes_for", "kiss_hip_fmi8_build_dev", "kiss_hip_fmi8_build_host", "kiss_hip_fmi8_query_dev",
     "kiss_hip_fmi8_query_host", "kiss_hip_fmi_seeds_dev", "kiss_hip_fmi_seeds_host",
     "kiss_hip_fmi_chain_dev", "kiss_hip_fmi_chain_host", "kiss_hip_fmi_align_dev", "kiss_hip_fmi_align_host",
-    "kiss_hip_fmi_select_dev", "kiss_hip_fmi_select_host",
+    "kiss_hip_fmi_select_dev", "kiss_hip_fmi_select_host", "kiss_hip_fmi_pair_dev", "kiss_hip_fmi_pair_host",
 ]

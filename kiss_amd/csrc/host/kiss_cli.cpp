@@ -19,6 +19,10 @@
 //    [--gap-open N] [--gap-extend N] [--align-band N] every chain is aligned to the text (kiss_hip_fmi_align_host: banded,
 //    and with --sam on top [--min-map-score N] [--overlap N] [--mapq-coef N] [--mapq-max N] [--max-hits N] the alignments of
 //    a read are turned into its mappings (kiss_hip_fmi_select_host) and stdout is SAM: one line per hit, one per unmapped read;
+//    with --mates READS2 on top [--ins-min N] [--ins-max N] [--ins-mean N] [--pair-pen-coef N] [--pair-pen-max N] read p of
+//    READS and read p of READS2 are the two mates of pair p (forward-then-reverse libraries; both strands are searched): their
+//    mappings are paired (kiss_hip_fmi_pair_host) and the SAM is paired -- the lines of the two mates adjacent, the chosen hit
+//    of a mate first with the pair's MAPQ, flags 1 / 2 / 8 / 32 / 64 / 128, RNEXT, PNEXT, signed TLEN, YS:i: and YT:Z:CP;
 //    affine gaps, local) and the line of a chain is: read strand score rbeg rend tbeg tend nm cigar)
 //   (-g / --generic: the file is a text over the byte alphabet, taken byte for byte -- no FASTA rule, no newline stripping,
 //    no % 4.  suffix_sort gives the exact suffix array (kiss_hip_suffix_sort_u8; -k and -s are ignored) and, with
@@ -113,7 +117,16 @@ void usage()
               << "                                 alignments are the same locus (in the text) or compete (in the read)\n"
               << "  --mapq-coef NUM (=120)         MAPQ = min(mapq-max, mapq-coef * (score - best secondary) / score)\n"
               << "  --mapq-max NUM (=60)\n"
-              << "  --max-hits NUM (=0)            hits written per read (0: all)\n";
+              << "  --max-hits NUM (=0)            hits written per read (0: all)\n"
+              << "  --mates READS2                 with --sam: read p of READS2 is the mate of read p of READS (forward-then-\n"
+              << "                                 reverse libraries; implies --both-strands); the mappings of the two are paired\n"
+              << "                                 and the SAM is paired: the mates adjacent, the chosen hit of a mate first, with\n"
+              << "                                 the pair's MAPQ, the mate fields, signed TLEN, YS:i: and, in a proper pair, YT:Z:CP\n"
+              << "  --ins-min NUM (=0)             shortest insert (first base of the forward mate to the last of the reverse one)\n"
+              << "  --ins-max NUM (=1000)          longest insert of a proper pair\n"
+              << "  --ins-mean NUM (=400)          the insert that costs nothing\n"
+              << "  --pair-pen-coef NUM (=8)       256ths of a score point taken off per base of deviation from --ins-mean\n"
+              << "  --pair-pen-max NUM (=20)       most points taken off\n";
 }
 
 inline uint8_t to_code(unsigned char c)
@@ -197,6 +210,8 @@ struct Args {
     kiss_hip_align_params align_params{1, 4, 6, 1, 32};
     bool sam = false; // fmindex_query --seeds READS --chain --align --sam
     kiss_hip_select_params select_params{30, 128, 120, 60, 0};
+    std::string mates; // fmindex_query --seeds READS --mates READS2 --chain --align --sam
+    kiss_hip_pair_params pair_params{0, 1000, 400, 8, 20, 120, 60};
 };
 
 Args parse(int argc, char **argv)
@@ -213,7 +228,8 @@ Args parse(int argc, char **argv)
             s == "--seeds" || s == "--min-seed-len" || s == "--max-seed-len" || s == "--max-occ" || s == "--both-strands" || s == "--chain" ||
             s == "--max-gap" || s == "--band" || s == "--gap-cost" || s == "--max-lookback" || s == "--min-chain-score" ||
             s == "--align" || s == "--match" || s == "--mismatch" || s == "--gap-open" || s == "--gap-extend" || s == "--align-band" ||
-            s == "--sam" || s == "--min-map-score" || s == "--overlap" || s == "--mapq-coef" || s == "--mapq-max" || s == "--max-hits")
+            s == "--sam" || s == "--min-map-score" || s == "--overlap" || s == "--mapq-coef" || s == "--mapq-max" || s == "--max-hits" ||
+            s == "--mates" || s == "--ins-min" || s == "--ins-max" || s == "--ins-mean" || s == "--pair-pen-coef" || s == "--pair-pen-max")
             a.seen.push_back(s);
         if (s == "-k" || s == "--kordered") a.seen.push_back("--kordered");
         if (s == "-s" || s == "--sorting-algorithm") a.seen.push_back("--sorting-algorithm");
@@ -258,6 +274,12 @@ Args parse(int argc, char **argv)
         else if (s == "--mapq-coef") a.select_params.mapq_coef = (uint32_t)std::stoul(next("--mapq-coef"));
         else if (s == "--mapq-max") a.select_params.mapq_max = (uint32_t)std::stoul(next("--mapq-max"));
         else if (s == "--max-hits") a.select_params.max_hits = (uint32_t)std::stoul(next("--max-hits"));
+        else if (s == "--mates") a.mates = next("--mates");
+        else if (s == "--ins-min") a.pair_params.ins_min = (uint32_t)std::stoul(next("--ins-min"));
+        else if (s == "--ins-max") a.pair_params.ins_max = (uint32_t)std::stoul(next("--ins-max"));
+        else if (s == "--ins-mean") a.pair_params.ins_mean = (uint32_t)std::stoul(next("--ins-mean"));
+        else if (s == "--pair-pen-coef") a.pair_params.pen_coef = (uint32_t)std::stoul(next("--pair-pen-coef"));
+        else if (s == "--pair-pen-max") a.pair_params.pen_max = (uint32_t)std::stoul(next("--pair-pen-max"));
         else if (s == "--devices") {
             const std::string list = next("--devices");
             size_t at = 0;
@@ -294,6 +316,16 @@ Args parse(int argc, char **argv)
             if (given_here(o) && !given_here("--sam")) throw std::runtime_error(std::string(o) + " goes with --sam");
         if (a.select_params.overlap > 256u || a.select_params.mapq_coef > 65535u || a.select_params.mapq_max > 255u)
             throw std::runtime_error("--overlap is at most 256, --mapq-coef at most 65535, --mapq-max at most 255");
+        if (given_here("--mates") && !given_here("--sam")) throw std::runtime_error("--mates goes with --sam");
+        for (const char *o : {"--ins-min", "--ins-max", "--ins-mean", "--pair-pen-coef", "--pair-pen-max"})
+            if (given_here(o) && !given_here("--mates")) throw std::runtime_error(std::string(o) + " goes with --mates");
+        if (a.pair_params.ins_min > a.pair_params.ins_max || a.pair_params.pen_coef > 65535u || a.pair_params.pen_max > 65535u)
+            throw std::runtime_error("--ins-min is at most --ins-max, --pair-pen-coef and --pair-pen-max at most 65535");
+        if (given_here("--mates")) { // the pair's MAPQ is on the scale of the reads'; the mates face each other
+            a.both_strands = true;
+            a.pair_params.mapq_coef = a.select_params.mapq_coef;
+            a.pair_params.mapq_max = a.select_params.mapq_max;
+        }
         if (a.align_params.match < 1 || a.align_params.match > 65535u || a.align_params.mismatch > 65535u ||
             a.align_params.gap_open > 65535u || a.align_params.gap_extend > 65535u || a.align_params.band > 0x7FFFFFFFu)
             throw std::runtime_error("--match is in 1..65535, --mismatch, --gap-open and --gap-extend are at most 65535, "
@@ -723,6 +755,116 @@ RefRecords scan_records(const std::string &path)
     return r;
 }
 
+// fmindex_query --seeds READS --mates READS2 --chain --align --sam: the hits of reads 2 p and 2 p + 1 paired, the body of the SAM
+// (out: the header).  The lines of mate 1, then those of mate 2; of a mate its chosen hit first -- without 256 / 2048, with the
+// pair's MAPQ, signed TLEN, YS:i: (the mate's score) and, in a proper pair, YT:Z:CP --, then its other hits in hit order with their
+// own flags and MAPQ (a hit number 0 that was not chosen: 256 and MAPQ 0) and TLEN 0.  Every line carries 1, 64 / 128, 8 / 32 for
+// the mate, and RNEXT / PNEXT of the mate's chosen hit; a mate that did not map lies where its partner does (SAM's convention).
+int sam_pairs(const Args &a, std::string &out, const RefRecords &ref, const std::vector<kiss_hip_aln> &alns, const std::vector<uint32_t> &cigar,
+              const std::vector<uint64_t> &oidx, const std::vector<uint8_t> &reads, const std::vector<uint64_t> &ridx,
+              const std::vector<std::string> &names, const std::vector<kiss_hip_hit> &hits, const std::vector<uint64_t> &hidx,
+              const kiss_hip_select_report &srep)
+{
+    const uint64_t Q = ridx.size() - 1, P = Q / 2, R = ref.names.size();
+    std::vector<kiss_hip_pair> pairs(P + 1);
+    kiss_hip_pair_report rep{};
+    check(kiss_hip_fmi_pair_host(hits.data(), hidx.data(), Q, alns.data(), srep.alignments, &a.pair_params, pairs.data(), &rep, a.device),
+          "kiss_hip_fmi_pair_host");
+    for (uint64_t p = 0; p < P; p++) {
+        const kiss_hip_pair &pr = pairs[p];
+        if (pr.flags & KISS_HIP_PAIR_BAD_INPUT) throw std::runtime_error("kiss_hip_fmi_pair_host: pair " + std::to_string(p) + " is bad input");
+        const uint32_t chosen[2] = {pr.hit1, pr.hit2}, mapq[2] = {pr.mapq1, pr.mapq2};
+        const bool proper = (pr.flags & KISS_HIP_PAIR_PROPER) != 0;
+        // where a mate lies: its chosen hit
+        bool mapped[2], rev[2] = {false, false};
+        std::string rname[2] = {"*", "*"};
+        uint64_t pos[2] = {0, 0}, tbeg[2] = {0, 0};
+        for (int m = 0; m < 2; m++) {
+            mapped[m] = chosen[m] != KISS_HIP_PAIR_NONE;
+            if (!mapped[m]) continue;
+            const kiss_hip_hit &t = hits[chosen[m]];
+            rev[m] = (t.flags & KISS_HIP_HIT_REVERSE) != 0;
+            if (R) rname[m] = ref.names[t.ref];
+            tbeg[m] = alns[t.aln].tbeg;
+            pos[m] = tbeg[m] - (R ? ref.bounds[t.ref] : 0) + 1;
+        }
+        for (int m = 0; m < 2; m++) {
+            const int o = 1 - m;
+            const uint64_t q = 2 * p + (uint64_t)m, L = ridx[q + 1] - ridx[q];
+            const auto seq = [&](bool reverse) {
+                std::string s(L, 'N');
+                for (uint64_t j = 0; j < L; j++) {
+                    const uint8_t c = reads[ridx[q] + (reverse ? L - 1 - j : j)];
+                    if (c <= 3) s[j] = "ACGT"[reverse ? 3 - c : c];
+                }
+                return s;
+            };
+            const unsigned base = 1u | (m ? 128u : 64u) | (mapped[o] ? 0u : 8u) | (mapped[o] && rev[o] ? 32u : 0u);
+            if (!mapped[m]) { // at its partner's place, if that has one
+                out += names[q] + '\t' + std::to_string(base | 4u) + '\t' + rname[o] + '\t' + std::to_string(pos[o]) + "\t0\t*\t" +
+                       (mapped[o] ? "=" : "*") + '\t' + std::to_string(pos[o]) + "\t0\t" + seq(false) + "\t*\n";
+                continue;
+            }
+            // the mate's place, or this read's own when the mate has none
+            const std::string &next_name = mapped[o] ? rname[o] : rname[m];
+            const uint64_t next_pos = mapped[o] ? pos[o] : pos[m];
+            long long tlen = 0;
+            if (mapped[o] && pr.tlen) tlen = (tbeg[m] < tbeg[o] || (tbeg[m] == tbeg[o] && m == 0)) ? (long long)pr.tlen : -(long long)pr.tlen;
+            const auto line = [&](uint64_t h, bool is_chosen) {
+                const kiss_hip_hit &t = hits[h];
+                const uint64_t c = t.aln;
+                const kiss_hip_aln &k = alns[c];
+                const bool reverse = (t.flags & KISS_HIP_HIT_REVERSE) != 0, head = !(t.flags & KISS_HIP_HIT_SECONDARY);
+                unsigned flag = base | (reverse ? 16u : 0u);
+                uint32_t q_mapq = t.mapq;
+                if (is_chosen) {
+                    flag |= proper ? 2u : 0u;
+                    q_mapq = mapq[m];
+                } else {
+                    flag |= (t.flags & KISS_HIP_HIT_SECONDARY ? 256u : 0u) | (t.flags & KISS_HIP_HIT_SUPPLEMENTARY ? 2048u : 0u);
+                    if (h == hidx[q]) { // the primary of the read on its own, displaced by the pair
+                        flag |= 256u;
+                        q_mapq = 0;
+                    }
+                }
+                const std::string name = R ? ref.names[t.ref] : std::string("*");
+                out += names[q] + '\t' + std::to_string(flag) + '\t' + name + '\t' +
+                       std::to_string((uint64_t)k.tbeg - (R ? ref.bounds[t.ref] : 0) + 1) + '\t' + std::to_string(q_mapq) + '\t';
+                if (k.rbeg) out += std::to_string(k.rbeg) + 'S';
+                for (uint64_t x = oidx[c]; x < oidx[c + 1]; x++) out += std::to_string(cigar[x] >> 4) + "MID"[cigar[x] & 15u];
+                if (L > k.rend) out += std::to_string(L - k.rend) + 'S';
+                out += '\t' + (name == next_name ? std::string("=") : next_name) + '\t' + std::to_string(next_pos) + '\t' +
+                       std::to_string(is_chosen ? tlen : 0ll) + '\t' + seq(reverse) + "\t*\tNM:i:" + std::to_string(k.mismatches + k.ins + k.del) +
+                       "\tAS:i:" + std::to_string(t.score);
+                if (head) out += "\tXS:i:" + std::to_string(t.sub);
+                if (is_chosen && mapped[o]) out += "\tYS:i:" + std::to_string(hits[chosen[o]].score);
+                if (is_chosen && proper) out += "\tYT:Z:CP";
+                out += '\n';
+            };
+            line(chosen[m], true);
+            for (uint64_t h = hidx[q]; h < hidx[q + 1]; h++)
+                if (h != chosen[m]) line(h, false);
+        }
+        if (out.size() > (1u << 20)) {
+            std::fwrite(out.data(), 1, out.size(), stdout);
+            out.clear();
+        }
+    }
+    std::fwrite(out.data(), 1, out.size(), stdout);
+    std::fflush(stdout);
+    std::fprintf(stderr, "[info] reads: %llu, alignments: %llu, candidates: %llu, spanning: %llu, redundant: %llu, hits: %llu, "
+                         "heads: %llu, mapped: %llu, most candidates of a read: %u\n",
+                 (unsigned long long)Q, (unsigned long long)srep.alignments, (unsigned long long)srep.candidates,
+                 (unsigned long long)srep.spanning, (unsigned long long)srep.redundant, (unsigned long long)srep.hits,
+                 (unsigned long long)srep.heads, (unsigned long long)srep.mapped, srep.max_candidates);
+    std::fprintf(stderr, "[info] pairs: %llu, eligible hits: %llu, combinations: %llu, concordant: %llu, proper: %llu, promoted: %llu, "
+                         "lifted: %llu, most combinations of a pair: %llu\n",
+                 (unsigned long long)rep.P, (unsigned long long)rep.eligible, (unsigned long long)rep.combinations,
+                 (unsigned long long)rep.concordant, (unsigned long long)rep.proper, (unsigned long long)rep.promoted,
+                 (unsigned long long)rep.lifted, (unsigned long long)rep.max_combinations);
+    return 0;
+}
+
 // fmindex_query --seeds READS --chain --align --sam: the alignments of every read turned into its mappings, stdout is SAM
 int sam_main(const Args &a, uint64_t C, uint64_t n, const std::vector<kiss_hip_aln> &alns, const std::vector<uint64_t> &cidx,
              const std::vector<uint32_t> &cigar, const std::vector<uint64_t> &oidx, const std::vector<uint8_t> &reads,
@@ -744,6 +886,7 @@ int sam_main(const Args &a, uint64_t C, uint64_t n, const std::vector<kiss_hip_a
     for (uint64_t r = 0; r < R; r++)
         out += "@SQ\tSN:" + ref.names[r] + "\tLN:" + std::to_string(ref.bounds[r + 1] - ref.bounds[r]) + '\n';
     out += std::string("@PG\tID:kiss\tPN:kiss\tVN:") + VERSION + '\n';
+    if (!a.mates.empty()) return sam_pairs(a, out, ref, alns, cigar, oidx, reads, ridx, names, hits, hidx, rep);
     for (uint64_t q = 0; q < Q; q++) {
         const uint64_t L = ridx[q + 1] - ridx[q];
         const auto seq = [&](bool reverse) {
@@ -893,36 +1036,61 @@ int chains_main(const Args &a, uint64_t V, const std::vector<kiss_hip_fmi_seed> 
 // fmindex_query --seeds: one line per seed on stdout, `read strand start len count pos...`
 int seeds_main(const Args &a, const Fmi &f)
 {
-    std::ifstream in(a.seeds);
-    if (!in) throw std::runtime_error("cannot open " + a.seeds);
-    std::vector<uint8_t> reads;
-    std::vector<uint64_t> ridx{0};
-    std::vector<std::string> names; // --sam: the word after '>' on the line directly in front of a read, else its number
-    std::string line, pending;
-    while (std::getline(in, line)) {
-        if (!line.empty() && line.back() == '\r') line.pop_back();
-        if (line.empty() || line[0] == '>') {
-            if (a.sam) {
-                const size_t ws = line.find_first_of(" \t", 1);
-                pending = line.empty() ? std::string() : line.substr(1, ws == std::string::npos ? std::string::npos : ws - 1);
+    // one file of reads: the codes of its reads one after the other, where they start, and their names
+    struct ReadFile {
+        std::vector<uint8_t> reads;
+        std::vector<uint64_t> ridx{0};
+        std::vector<std::string> names; // --sam: the word after '>' on the line directly in front of a read, else its number
+    };
+    const auto load = [&](const std::string &path) {
+        std::ifstream in(path);
+        if (!in) throw std::runtime_error("cannot open " + path);
+        ReadFile f;
+        std::string line, pending;
+        while (std::getline(in, line)) {
+            if (!line.empty() && line.back() == '\r') line.pop_back();
+            if (line.empty() || line[0] == '>') {
+                if (a.sam) {
+                    const size_t ws = line.find_first_of(" \t", 1);
+                    pending = line.empty() ? std::string() : line.substr(1, ws == std::string::npos ? std::string::npos : ws - 1);
+                }
+                continue;
             }
-            continue;
-        }
-        if (a.sam) names.push_back(pending.empty() ? std::to_string(ridx.size() - 1) : pending);
-        pending.clear();
-        for (unsigned char c : line) {
-            uint8_t code = 4; // no base
-            switch (c) {
-            case 'A': case 'a': code = 0; break;
-            case 'C': case 'c': code = 1; break;
-            case 'G': case 'g': code = 2; break;
-            case 'T': case 't': code = 3; break;
-            default: break;
+            if (a.sam) f.names.push_back(pending.empty() ? std::to_string(f.ridx.size() - 1) : pending);
+            pending.clear();
+            for (unsigned char c : line) {
+                uint8_t code = 4; // no base
+                switch (c) {
+                case 'A': case 'a': code = 0; break;
+                case 'C': case 'c': code = 1; break;
+                case 'G': case 'g': code = 2; break;
+                case 'T': case 't': code = 3; break;
+                default: break;
+                }
+                f.reads.push_back(code);
             }
-            reads.push_back(code);
+            f.ridx.push_back(f.reads.size());
         }
-        ridx.push_back(reads.size());
+        return f;
+    };
+    ReadFile one = load(a.seeds);
+    if (!a.mates.empty()) { // reads 2 p and 2 p + 1 of the batch are read p of either file
+        const ReadFile first = std::move(one), second = load(a.mates);
+        const uint64_t P = first.ridx.size() - 1;
+        if (second.ridx.size() - 1 != P)
+            throw std::runtime_error("fmindex_query --mates: " + a.seeds + " has " + std::to_string(P) + " reads, " + a.mates + " has " +
+                                     std::to_string(second.ridx.size() - 1) + " reads: a pair has one of each");
+        one = ReadFile();
+        for (uint64_t p = 0; p < P; p++)
+            for (const ReadFile *f : {&first, &second}) {
+                one.reads.insert(one.reads.end(), f->reads.begin() + (std::ptrdiff_t)f->ridx[p], f->reads.begin() + (std::ptrdiff_t)f->ridx[p + 1]);
+                one.ridx.push_back(one.reads.size());
+                one.names.push_back(f->names[p]);
+            }
     }
+    const std::vector<uint8_t> &reads = one.reads;
+    const std::vector<uint64_t> &ridx = one.ridx;
+    const std::vector<std::string> &names = one.names;
     const uint64_t Q = ridx.size() - 1, bases = (a.both_strands ? 2 : 1) * (uint64_t)reads.size();
     const uint64_t V = a.both_strands ? 2 * Q : Q;
     const kiss_hip_fmi_view_ex v = f.view_ex();

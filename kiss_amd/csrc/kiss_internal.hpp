@@ -163,6 +163,8 @@ enum FmSlot {
     // kiss_hip_fmi_select_dev (fm_select.hip)
     FM_SLOT_SELECT_CTL,
     FM_SLOT_SELECT_SLAB, // the per-alignment arrays
+    // kiss_hip_fmi_pair_dev (fm_pair.hip)
+    FM_SLOT_PAIR_CTL,
     FM_SLOT_COUNT
 };
 

@@ -659,6 +659,44 @@ class FMIndex:
         res.update(select_arrays(sel))
         return res
 
+    # ---- the mappings of two mates paired (kiss_hip_fmi_pair_dev; no reference counterpart) -----------------------------
+    def map_pairs(self, reads1, reads2, text, min_len=19, max_len=0, max_occ=500, chain_params=None, align_params=None,
+                  select_params=None, bounds=None, want_cigar=True, **pair_params):
+        """map() for paired reads (forward-then-reverse libraries; include/kiss_hip.h has the definition): reads1[p] and
+        reads2[p] are mate 1 and mate 2 of pair p, both as read from the sequencer.  They are interleaved into one batch
+        (reads 2 p and 2 p + 1), which goes through seeds, chains, alignments and select on both strands and then through the
+        pair call, everything staying on the device.  reads1 / reads2: equally many reads, each a list of uint8 arrays or
+        (concatenated, index); select_params: a dict of the select parameters of map(); pair_params: ins_min (0), ins_max
+        (1000), ins_mean (400), pen_coef (8, in 256ths), pen_max (20), mapq_coef (120), mapq_max (60).  Returns what map()
+        returns for the interleaved batch plus pairs (structured array, one per pair: hit1, hit2 -- indices into hits, or
+        0xFFFFFFFF --, flags, tlen, score, sub1, sub2, mapq1, mapq2, n_conc; flags 1 proper, 2 / 4 mate 1 / 2 mapped, 8 same
+        record, 16 / 32 mate 1 / 2 promoted from a secondary) and pair_report."""
+        from .fm_pair import pair_arrays, pair_dev, pair_params as make_pair_params
+        from .fm_select import select_arrays, select_dev, select_params as make_select_params
+        pp = make_pair_params(**pair_params)
+        sp = make_select_params(**(select_params or {}))
+
+        def as_list(reads):
+            if isinstance(reads, tuple):
+                cat = np.ascontiguousarray(reads[0], dtype=np.uint8)
+                index = np.ascontiguousarray(reads[1], dtype=np.uint64)
+                return [cat[int(index[q]):int(index[q + 1])] for q in range(index.size - 1)]
+            return [np.ascontiguousarray(r, dtype=np.uint8).ravel() for r in reads]
+
+        m1, m2 = as_list(reads1), as_list(reads2)
+        if len(m1) != len(m2):
+            raise ValueError("reads1 has %d reads, reads2 has %d: a pair has one of each" % (len(m1), len(m2)))
+        batch = [r for pair in zip(m1, m2) for r in pair]
+        res, t = self._align_dev(batch, text, min_len, max_len, max_occ, True, chain_params, want_cigar, align_params or {})
+        ctx = t["ctx"]
+        if t["C"] > 0.3 * ctx.max_n:  # (the alignments of a call are sorted in the context's LMS arrays)
+            ctx = self._context(min(_lib.MAX_N, int(3.3 * t["C"]) + (1 << 20)))
+        sel = select_dev(t["lib"], ctx, self.device, t["d_alns"], t["d_cidx"], t["d_ridx"], t["Q"], t["C"], True, bounds, sp)
+        res.update(select_arrays(sel))
+        out = pair_dev(t["lib"], ctx, self.device, sel["d_hits"], sel["d_hidx"], t["Q"], t["d_alns"], t["C"], pp)
+        res.update(pair_arrays(out))
+        return res
+
     def close(self):
         if self._ctx is not None:
             self._ctx.close()
