@@ -950,6 +950,105 @@ int kiss_hip_fmi_pair_host(const kiss_hip_hit *hits, const uint64_t *hit_index, 
                            uint64_t aln_count, const kiss_hip_pair_params *params, kiss_hip_pair *pairs,
                            kiss_hip_pair_report *report, int device);
 
+/* ---- FM-index: the missing mate looked for near its partner: the rescue plan (no reference counterpart) -----------------
+ * Every stage before the pair call treats a read on its own, so a mate without a seed has no alignment although its partner
+ * says within a few hundred bases where it must lie.  This call turns the pairs that are not proper into WINDOWS next to the
+ * hits of either mate, written as chain records that kiss_hip_fmi_align_dev takes as they are; kiss_hip_fmi_aln_merge_dev
+ * (below) then puts the alignments of those chains behind the reads' own, and the select and pair calls run once more:
+ *   pass 1: seeds -> chain -> align -> select -> pair;  rescue: plan -> align (the rescue chains) -> merge;
+ *   pass 2: select -> pair on the merged alignments.
+ * One definition in integers; tests/fm_rescue_model.py restates it.  The result is a function of the input arrays and the
+ * parameters alone: no index, no text and no read is looked at.  FR libraries only, as the pair call.
+ * Input: pairs (P = Q / 2 records as kiss_hip_fmi_pair_dev wrote them; only flags is read); hits with hit_index (Q + 1 u64 over
+ * the READS) and alns with aln_count exactly as the pair call reads them; read_index (Q + 1 u64; only the lengths are used); n,
+ * the length of the text; bounds with R, optional, as in kiss_hip_fmi_select_dev, with bounds[R] <= n (NULL: one record
+ * [0, n), a hit's ref is ignored).
+ * Parameters (kiss_hip_rescue_params, all u32; in parentheses the defaults of Python and the command line): ins_min (0),
+ * ins_max (1000) -- the pair call's --, max_anchors (4; at least 1), min_anchor_score (0), max_width (960; at least 1 and at
+ * most KISS_HIP_ALIGN_MAX_BAND).  All interval arithmetic is signed 64-bit, as in select and pair.
+ * Which pairs: pair p is rescued iff its flags has neither KISS_HIP_PAIR_PROPER nor KISS_HIP_PAIR_BAD_INPUT.
+ * Anchors: for mate m of such a pair (read q = 2 p + m of L bases; the other read is o = 2 p + 1 - m) a hit of read o QUALIFIES
+ * iff head == 0, score >= min_anchor_score and either aln >= aln_count (its interval cannot be read: see bad anchors) or
+ * tbeg < tend of alns[aln].  The anchors of mate m are the first max_anchors qualifying hits of o, in hit order.  Both mates
+ * of a pair are rescued, each from the other's hits.
+ * Bad anchors: an anchor with aln >= aln_count, or, with bounds, ref >= R, gives no window and is counted in bad_input (it
+ * still is one of the max_anchors).  So nothing is read outside alns or bounds whatever the arrays hold.
+ * Window of an anchor A (tbeg, tend of its alignment, record rho = ref): the diagonals d at which the whole mate, laid end to
+ * end as [d, d + L), would be concordant with A under the pair call's rule.
+ *   A forward (the mate is virtual read 2 q + 1): dmin = max(A.tbeg + ins_min, A.tend, A.tbeg + L) - L,
+ *                                                 dmax = A.tbeg + ins_max - L.
+ *   A reverse (the mate is virtual read 2 q):     dmin = A.tend - ins_max, dmax = min(A.tend - ins_min, A.tbeg, A.tend - L).
+ *   Clip to the record: dmin = max(dmin, lo), dmax = min(dmax, hi - L), [lo, hi) = [bounds[rho], bounds[rho + 1]) or [0, n).
+ *   dmin > dmax: no window, counted in `empty` (a read longer than its record always ends here).
+ * Split: a window of W = dmax - dmin + 1 diagonals is cut into k = ceil(W / max_width) pieces; piece j (0 <= j < k) covers
+ * the diagonals dmin + floor(j W / k) .. dmin + floor((j + 1) W / k) - 1.  Windows with k > 1 are counted in `split`.  The
+ * align call's own band widens every piece on both sides, so neighbouring pieces overlap and select drops the duplicate; with
+ * max_width = 960 and band = 32 a piece is exactly KISS_HIP_ALIGN_MAX_BAND diagonals wide.
+ * Chain record of a piece [a, b] (kiss_hip_chain): score = the anchor's score, anchors = 0 (no real chain has none), rbeg = 0,
+ * rend = L, tbeg = a, tend = b + L: the align call sees d0 = a and d1 = b.
+ * Output: chains with chain_index (2 Q + 1 u64 over the VIRTUAL reads of both strands, chain_index[0] = 0); inside a virtual
+ * read the anchors in hit order, the pieces of an anchor ascending.  origin, optional: one u32 per chain, the anchor's index
+ * into hits.
+ * chain_capacity below the total: KISS_HIP_E_INVALID with the totals in the report, nothing written; call again with room.
+ * Q * max_anchors * ceil((ins_max - ins_min + 1) / max_width) always suffices.
+ * Report: P, pairs_planned (pairs with at least one chain), anchors (bad and empty ones included), chains, split, empty,
+ * bad_input (anchors), max_chains (of a pair), times.
+ * Other KISS_HIP_E_INVALID: a required pointer NULL, Q odd, a hit_index that decreases, a read_index that does not ascend (a
+ * zero-length read), ins_min > ins_max, max_anchors or max_width out of range, bounds with bounds[0] != 0, not strictly
+ * ascending, bounds[R] > n or R == 0.  Q == 0: KISS_HIP_OK, chain_index[0] = 0.  KISS_HIP_E_UNSUPPORTED: Q of 2^31 or more, n
+ * above KISS_HIP_MAX_N, hit_index[Q] of 2^32 - 1 or more, more reads than the ctx's scratch scans.
+ * pairs, hits, alns and chains need no more than the 4-byte alignment of their fields.
+ * Device times: report->ms_* (report may be NULL); the kernels also count under KISS_HIP_K_FM_QUERY. */
+typedef struct kiss_hip_rescue_params { uint32_t ins_min, ins_max, max_anchors, min_anchor_score, max_width; } kiss_hip_rescue_params;
+typedef struct kiss_hip_rescue_report {
+    uint64_t P, pairs_planned, anchors, chains, split, empty, bad_input, max_chains;
+    float ms_total, ms_check, ms_count, ms_emit; /* count: the counting walk and the scan; emit: the writing walk */
+} kiss_hip_rescue_report;
+/* every pointer except params and report is a device pointer */
+int kiss_hip_fmi_rescue_dev(kiss_hip_ctx *ctx, const kiss_hip_pair *pairs, const kiss_hip_hit *hits, const uint64_t *hit_index,
+                            uint64_t Q, const kiss_hip_aln *alns, uint64_t aln_count, const uint64_t *read_index, uint64_t n,
+                            const uint64_t *bounds, uint64_t R, const kiss_hip_rescue_params *params, kiss_hip_chain *chains,
+                            uint64_t *chain_index, uint32_t *origin, uint64_t chain_capacity, kiss_hip_rescue_report *report,
+                            void *stream);
+/* the same with host pointers (the device's cached one-shot context, as kiss_hip_fmi_chain_host); hits holds hit_index[Q]
+ * records */
+int kiss_hip_fmi_rescue_host(const kiss_hip_pair *pairs, const kiss_hip_hit *hits, const uint64_t *hit_index, uint64_t Q,
+                             const kiss_hip_aln *alns, uint64_t aln_count, const uint64_t *read_index, uint64_t n,
+                             const uint64_t *bounds, uint64_t R, const kiss_hip_rescue_params *params, kiss_hip_chain *chains,
+                             uint64_t *chain_index, uint32_t *origin, uint64_t chain_capacity, kiss_hip_rescue_report *report,
+                             int device);
+
+/* ---- FM-index: two alignment sets of one batch made one (no reference counterpart) --------------------------------------
+ * Set A (alns_a, chain_index_a, optionally cigar_a with cigar_index_a) and set B (the same) are over the same V virtual reads,
+ * each as kiss_hip_fmi_align_dev wrote it: C_A = chain_index_a[V] - chain_index_a[0], alns_a[i] (0 <= i < C_A) belongs to the
+ * virtual read that contains chain_index_a[0] + i (either chain_index[0] may be non-zero), its ops are cigar_a[cigar_index_a[i]
+ * .. cigar_index_a[i + 1]).  Output: the merged alns with chain_index (V + 1 u64, from 0), in which every virtual read has all
+ * of A's alignments in their order and then all of B's; source, optional: one u32 per merged alignment, i for alns_a[i] and
+ * C_A + j for alns_b[j]; cigar with cigar_index (C_A + C_B + 1 u64, from 0) when the ops are asked for.  The ops of both sets
+ * and room for the merged ones are given together or not at all (anything else is KISS_HIP_E_INVALID).
+ * aln_capacity < C_A + C_B or cigar_capacity < the total of ops: KISS_HIP_E_INVALID with the totals in the report, nothing
+ * written; call again with room.  Other KISS_HIP_E_INVALID: a required pointer NULL, a chain index or cigar index that
+ * decreases.  KISS_HIP_E_UNSUPPORTED: C_A + C_B of 2^32 or more, V of 2^31 or more, more alignments than the ctx's scratch
+ * scans.  Records are read and written field by field: 4-byte alignment suffices.
+ * Device times: report->ms_* (report may be NULL); the kernels also count under KISS_HIP_K_FM_QUERY. */
+typedef struct kiss_hip_merge_report {
+    uint64_t V, alignments_a, alignments_b, alignments, cigar_ops;
+    float ms_total, ms_place, ms_copy; /* place: checks, sources, the scan of the op counts; copy: records, indices, ops */
+    uint32_t reserved_;
+} kiss_hip_merge_report;
+/* every pointer except report is a device pointer */
+int kiss_hip_fmi_aln_merge_dev(kiss_hip_ctx *ctx, const kiss_hip_aln *alns_a, const uint64_t *chain_index_a, const uint32_t *cigar_a,
+                               const uint64_t *cigar_index_a, const kiss_hip_aln *alns_b, const uint64_t *chain_index_b,
+                               const uint32_t *cigar_b, const uint64_t *cigar_index_b, uint64_t V, kiss_hip_aln *alns,
+                               uint64_t aln_capacity, uint64_t *chain_index, uint32_t *source, uint32_t *cigar,
+                               uint64_t *cigar_index, uint64_t cigar_capacity, kiss_hip_merge_report *report, void *stream);
+/* the same with host pointers (the device's cached one-shot context, as kiss_hip_fmi_chain_host) */
+int kiss_hip_fmi_aln_merge_host(const kiss_hip_aln *alns_a, const uint64_t *chain_index_a, const uint32_t *cigar_a,
+                                const uint64_t *cigar_index_a, const kiss_hip_aln *alns_b, const uint64_t *chain_index_b,
+                                const uint32_t *cigar_b, const uint64_t *cigar_index_b, uint64_t V, kiss_hip_aln *alns,
+                                uint64_t aln_capacity, uint64_t *chain_index, uint32_t *source, uint32_t *cigar,
+                                uint64_t *cigar_index, uint64_t cigar_capacity, kiss_hip_merge_report *report, int device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -242,6 +242,32 @@ class PairReport(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved_"}
 
 
+class RescueParams(ctypes.Structure):
+    """kiss_hip_rescue_params"""
+    _fields_ = [(k, ctypes.c_uint32) for k in ("ins_min", "ins_max", "max_anchors", "min_anchor_score", "max_width")]
+
+
+class RescueReport(ctypes.Structure):
+    """kiss_hip_rescue_report"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("P", "pairs_planned", "anchors", "chains", "split", "empty", "bad_input",
+                                               "max_chains")] + [
+        ("ms_total", ctypes.c_float), ("ms_check", ctypes.c_float), ("ms_count", ctypes.c_float), ("ms_emit", ctypes.c_float),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class MergeReport(ctypes.Structure):
+    """kiss_hip_merge_report"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("V", "alignments_a", "alignments_b", "alignments", "cigar_ops")] + [
+        ("ms_total", ctypes.c_float), ("ms_place", ctypes.c_float), ("ms_copy", ctypes.c_float), ("reserved_", ctypes.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved_"}
+
+
 class Fmi8View(ctypes.Structure):
     """kiss_hip_fmi8_view"""
     _fields_ = [
@@ -405,6 +431,14 @@ def load(hooks=None):
     lib.kiss_hip_fmi_pair_host.argtypes = [vp, vp, u64, vp, u64, ctypes.POINTER(PairParams), vp, ctypes.POINTER(PairReport),
                                            ctypes.c_int]
     lib.kiss_hip_fmi_pair_dev.restype = lib.kiss_hip_fmi_pair_host.restype = ctypes.c_int
+    lib.kiss_hip_fmi_rescue_dev.argtypes = [vp, vp, vp, vp, u64, vp, u64, vp, u64, vp, u64, ctypes.POINTER(RescueParams), vp, vp, vp, u64,
+                                            ctypes.POINTER(RescueReport), vp]
+    lib.kiss_hip_fmi_rescue_host.argtypes = [vp, vp, vp, u64, vp, u64, vp, u64, vp, u64, ctypes.POINTER(RescueParams), vp, vp, vp, u64,
+                                             ctypes.POINTER(RescueReport), ctypes.c_int]
+    lib.kiss_hip_fmi_rescue_dev.restype = lib.kiss_hip_fmi_rescue_host.restype = ctypes.c_int
+    lib.kiss_hip_fmi_aln_merge_dev.argtypes = [vp] * 9 + [u64, vp, u64, vp, vp, vp, vp, u64, ctypes.POINTER(MergeReport), vp]
+    lib.kiss_hip_fmi_aln_merge_host.argtypes = [vp] * 8 + [u64, vp, u64, vp, vp, vp, vp, u64, ctypes.POINTER(MergeReport), ctypes.c_int]
+    lib.kiss_hip_fmi_aln_merge_dev.restype = lib.kiss_hip_fmi_aln_merge_host.restype = ctypes.c_int
     lib.kiss_hip_fmi8_sizes_for.argtypes = [u64, u32, u32, ctypes.POINTER(Fmi8Sizes)]
     lib.kiss_hip_fmi8_build_dev.argtypes = [vp, vp, u64, vp, u32, u32] + [vp] * 8 + [ctypes.POINTER(u32), ctypes.POINTER(u32), vp]
     lib.kiss_hip_fmi8_build_host.argtypes = [vp, u64, vp, u32, u32] + [vp] * 8 + [ctypes.POINTER(u32), ctypes.POINTER(u32),
@@ -482,4 +516,5 @@ EXPORTED_SYMBOLS = [
     "kiss_hip_fmi8_query_host", "kiss_hip_fmi_seeds_dev", "kiss_hip_fmi_seeds_host",
     "kiss_hip_fmi_chain_dev", "kiss_hip_fmi_chain_host", "kiss_hip_fmi_align_dev", "kiss_hip_fmi_align_host",
     "kiss_hip_fmi_select_dev", "kiss_hip_fmi_select_host", "kiss_hip_fmi_pair_dev", "kiss_hip_fmi_pair_host",
+    "kiss_hip_fmi_rescue_dev", "kiss_hip_fmi_rescue_host", "kiss_hip_fmi_aln_merge_dev", "kiss_hip_fmi_aln_merge_host",
 ]

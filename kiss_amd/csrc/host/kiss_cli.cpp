@@ -23,6 +23,9 @@
 //    READS and read p of READS2 are the two mates of pair p (forward-then-reverse libraries; both strands are searched): their
 //    mappings are paired (kiss_hip_fmi_pair_host) and the SAM is paired -- the lines of the two mates adjacent, the chosen hit
 //    of a mate first with the pair's MAPQ, flags 1 / 2 / 8 / 32 / 64 / 128, RNEXT, PNEXT, signed TLEN, YS:i: and YT:Z:CP;
+//    with --rescue on top [--rescue-anchors N] [--rescue-min-anchor-score N] [--rescue-width N] the mates of a pair that is not
+//    proper are aligned once more inside the windows next to their partner's hits (kiss_hip_fmi_rescue_host, the align call,
+//    kiss_hip_fmi_aln_merge_host), select and pair run again, and a line that came from a window carries YR:i:1;
 //    affine gaps, local) and the line of a chain is: read strand score rbeg rend tbeg tend nm cigar)
 //   (-g / --generic: the file is a text over the byte alphabet, taken byte for byte -- no FASTA rule, no newline stripping,
 //    no % 4.  suffix_sort gives the exact suffix array (kiss_hip_suffix_sort_u8; -k and -s are ignored) and, with
@@ -126,7 +129,13 @@ void usage()
               << "  --ins-max NUM (=1000)          longest insert of a proper pair\n"
               << "  --ins-mean NUM (=400)          the insert that costs nothing\n"
               << "  --pair-pen-coef NUM (=8)       256ths of a score point taken off per base of deviation from --ins-mean\n"
-              << "  --pair-pen-max NUM (=20)       most points taken off\n";
+              << "  --pair-pen-max NUM (=20)       most points taken off\n"
+              << "  --rescue                       with --mates: a mate of a pair that is not proper is aligned once more, inside the\n"
+              << "                                 window that --ins-min / --ins-max leave next to the hits of its partner; the\n"
+              << "                                 mappings are picked and paired again with what that finds (lines from it: YR:i:1)\n"
+              << "  --rescue-anchors NUM (=4)      hits of the partner a window is laid next to\n"
+              << "  --rescue-min-anchor-score NUM (=0)  lowest score of such a hit\n"
+              << "  --rescue-width NUM (=960)      diagonals of a window aligned in one piece (1..1024)\n";
 }
 
 inline uint8_t to_code(unsigned char c)
@@ -212,6 +221,8 @@ struct Args {
     kiss_hip_select_params select_params{30, 128, 120, 60, 0};
     std::string mates; // fmindex_query --seeds READS --mates READS2 --chain --align --sam
     kiss_hip_pair_params pair_params{0, 1000, 400, 8, 20, 120, 60};
+    bool rescue = false; // fmindex_query ... --mates READS2 --sam --rescue
+    kiss_hip_rescue_params rescue_params{0, 1000, 4, 0, 960}; // (ins_min / ins_max: the pair parameters')
 };
 
 Args parse(int argc, char **argv)
@@ -229,7 +240,8 @@ Args parse(int argc, char **argv)
             s == "--max-gap" || s == "--band" || s == "--gap-cost" || s == "--max-lookback" || s == "--min-chain-score" ||
             s == "--align" || s == "--match" || s == "--mismatch" || s == "--gap-open" || s == "--gap-extend" || s == "--align-band" ||
             s == "--sam" || s == "--min-map-score" || s == "--overlap" || s == "--mapq-coef" || s == "--mapq-max" || s == "--max-hits" ||
-            s == "--mates" || s == "--ins-min" || s == "--ins-max" || s == "--ins-mean" || s == "--pair-pen-coef" || s == "--pair-pen-max")
+            s == "--mates" || s == "--ins-min" || s == "--ins-max" || s == "--ins-mean" || s == "--pair-pen-coef" || s == "--pair-pen-max" ||
+            s == "--rescue" || s == "--rescue-anchors" || s == "--rescue-min-anchor-score" || s == "--rescue-width")
             a.seen.push_back(s);
         if (s == "-k" || s == "--kordered") a.seen.push_back("--kordered");
         if (s == "-s" || s == "--sorting-algorithm") a.seen.push_back("--sorting-algorithm");
@@ -280,6 +292,10 @@ Args parse(int argc, char **argv)
         else if (s == "--ins-mean") a.pair_params.ins_mean = (uint32_t)std::stoul(next("--ins-mean"));
         else if (s == "--pair-pen-coef") a.pair_params.pen_coef = (uint32_t)std::stoul(next("--pair-pen-coef"));
         else if (s == "--pair-pen-max") a.pair_params.pen_max = (uint32_t)std::stoul(next("--pair-pen-max"));
+        else if (s == "--rescue") a.rescue = true;
+        else if (s == "--rescue-anchors") a.rescue_params.max_anchors = (uint32_t)std::stoul(next("--rescue-anchors"));
+        else if (s == "--rescue-min-anchor-score") a.rescue_params.min_anchor_score = (uint32_t)std::stoul(next("--rescue-min-anchor-score"));
+        else if (s == "--rescue-width") a.rescue_params.max_width = (uint32_t)std::stoul(next("--rescue-width"));
         else if (s == "--devices") {
             const std::string list = next("--devices");
             size_t at = 0;
@@ -321,6 +337,13 @@ Args parse(int argc, char **argv)
             if (given_here(o) && !given_here("--mates")) throw std::runtime_error(std::string(o) + " goes with --mates");
         if (a.pair_params.ins_min > a.pair_params.ins_max || a.pair_params.pen_coef > 65535u || a.pair_params.pen_max > 65535u)
             throw std::runtime_error("--ins-min is at most --ins-max, --pair-pen-coef and --pair-pen-max at most 65535");
+        if (given_here("--rescue") && !given_here("--mates")) throw std::runtime_error("--rescue goes with --mates");
+        for (const char *o : {"--rescue-anchors", "--rescue-min-anchor-score", "--rescue-width"})
+            if (given_here(o) && !given_here("--rescue")) throw std::runtime_error(std::string(o) + " goes with --rescue");
+        if (a.rescue_params.max_anchors < 1 || a.rescue_params.max_width < 1 || a.rescue_params.max_width > KISS_HIP_ALIGN_MAX_BAND)
+            throw std::runtime_error("--rescue-anchors is at least 1, --rescue-width in 1..1024");
+        a.rescue_params.ins_min = a.pair_params.ins_min;
+        a.rescue_params.ins_max = a.pair_params.ins_max;
         if (given_here("--mates")) { // the pair's MAPQ is on the scale of the reads'; the mates face each other
             a.both_strands = true;
             a.pair_params.mapq_coef = a.select_params.mapq_coef;
@@ -755,6 +778,15 @@ RefRecords scan_records(const std::string &path)
     return r;
 }
 
+// --rescue: what the second pass needs to know of the first -- the source of every merged alignment (below first_alns: a read's
+// own), the first pass's pairs and the plan's report
+struct Rescued {
+    std::vector<uint32_t> source;
+    uint64_t first_alns = 0;
+    std::vector<kiss_hip_pair> first_pairs;
+    kiss_hip_rescue_report plan{};
+};
+
 // fmindex_query --seeds READS --mates READS2 --chain --align --sam: the hits of reads 2 p and 2 p + 1 paired, the body of the SAM
 // (out: the header).  The lines of mate 1, then those of mate 2; of a mate its chosen hit first -- without 256 / 2048, with the
 // pair's MAPQ, signed TLEN, YS:i: (the mate's score) and, in a proper pair, YT:Z:CP --, then its other hits in hit order with their
@@ -763,7 +795,7 @@ RefRecords scan_records(const std::string &path)
 int sam_pairs(const Args &a, std::string &out, const RefRecords &ref, const std::vector<kiss_hip_aln> &alns, const std::vector<uint32_t> &cigar,
               const std::vector<uint64_t> &oidx, const std::vector<uint8_t> &reads, const std::vector<uint64_t> &ridx,
               const std::vector<std::string> &names, const std::vector<kiss_hip_hit> &hits, const std::vector<uint64_t> &hidx,
-              const kiss_hip_select_report &srep)
+              const kiss_hip_select_report &srep, const Rescued *rescued = nullptr)
 {
     const uint64_t Q = ridx.size() - 1, P = Q / 2, R = ref.names.size();
     std::vector<kiss_hip_pair> pairs(P + 1);
@@ -839,6 +871,7 @@ int sam_pairs(const Args &a, std::string &out, const RefRecords &ref, const std:
                 if (head) out += "\tXS:i:" + std::to_string(t.sub);
                 if (is_chosen && mapped[o]) out += "\tYS:i:" + std::to_string(hits[chosen[o]].score);
                 if (is_chosen && proper) out += "\tYT:Z:CP";
+                if (rescued && rescued->source[c] >= rescued->first_alns) out += "\tYR:i:1";
                 out += '\n';
             };
             line(chosen[m], true);
@@ -862,14 +895,88 @@ int sam_pairs(const Args &a, std::string &out, const RefRecords &ref, const std:
                  (unsigned long long)rep.P, (unsigned long long)rep.eligible, (unsigned long long)rep.combinations,
                  (unsigned long long)rep.concordant, (unsigned long long)rep.proper, (unsigned long long)rep.promoted,
                  (unsigned long long)rep.lifted, (unsigned long long)rep.max_combinations);
+    if (rescued) {
+        uint64_t now_proper = 0;
+        for (uint64_t p = 0; p < P; p++)
+            now_proper += (pairs[p].flags & KISS_HIP_PAIR_PROPER) && !(rescued->first_pairs[p].flags & KISS_HIP_PAIR_PROPER) ? 1u : 0u;
+        const kiss_hip_rescue_report &pl = rescued->plan;
+        std::fprintf(stderr, "[info] rescue: pairs planned: %llu, anchors: %llu, chains: %llu, split: %llu, empty: %llu, bad input: %llu, "
+                             "most chains of a pair: %llu, rescued: %llu\n",
+                     (unsigned long long)pl.pairs_planned, (unsigned long long)pl.anchors, (unsigned long long)pl.chains,
+                     (unsigned long long)pl.split, (unsigned long long)pl.empty, (unsigned long long)pl.bad_input,
+                     (unsigned long long)pl.max_chains, (unsigned long long)now_proper);
+    }
     return 0;
 }
 
+// fmindex_query ... --mates READS2 --sam --rescue: the first pass paired, the pairs that are not proper planned into windows
+// (kiss_hip_fmi_rescue_host), the windows aligned (the align call as it is), their alignments merged behind the reads' own
+// (kiss_hip_fmi_aln_merge_host), the mappings picked again; sam_pairs then pairs and writes the merged set
+int sam_rescue(const Args &a, std::string &out, const RefRecords &ref, const std::vector<uint8_t> &S, const std::vector<kiss_hip_aln> &alns,
+               const std::vector<uint64_t> &cidx, const std::vector<uint32_t> &cigar, const std::vector<uint64_t> &oidx,
+               const std::vector<uint8_t> &reads, const std::vector<uint64_t> &ridx, const std::vector<std::string> &names,
+               const std::vector<kiss_hip_hit> &hits, const std::vector<uint64_t> &hidx, const kiss_hip_select_report &srep)
+{
+    const uint64_t Q = ridx.size() - 1, P = Q / 2, V = 2 * Q, R = ref.names.size(), CA = srep.alignments, n = S.size();
+    const uint64_t *bounds = R ? ref.bounds.data() : nullptr;
+    Rescued rs;
+    rs.first_alns = CA;
+    rs.first_pairs.resize(P + 1);
+    check(kiss_hip_fmi_pair_host(hits.data(), hidx.data(), Q, alns.data(), CA, &a.pair_params, rs.first_pairs.data(), nullptr, a.device),
+          "kiss_hip_fmi_pair_host");
+    // the plan: the first call sizes the chains
+    std::vector<kiss_hip_chain> chains(1);
+    std::vector<uint64_t> rcidx(V + 1, 0);
+    int rc = kiss_hip_fmi_rescue_host(rs.first_pairs.data(), hits.data(), hidx.data(), Q, alns.data(), CA, ridx.data(), n, bounds, R,
+                                      &a.rescue_params, chains.data(), rcidx.data(), nullptr, 0, &rs.plan, a.device);
+    if (rc == KISS_HIP_E_INVALID && rs.plan.chains) {
+        chains.resize(rs.plan.chains);
+        rc = kiss_hip_fmi_rescue_host(rs.first_pairs.data(), hits.data(), hidx.data(), Q, alns.data(), CA, ridx.data(), n, bounds, R,
+                                      &a.rescue_params, chains.data(), rcidx.data(), nullptr, rs.plan.chains, &rs.plan, a.device);
+    }
+    check(rc, "kiss_hip_fmi_rescue_host");
+    const uint64_t CB = rs.plan.chains;
+    // the windows aligned: the first call sizes the ops
+    std::vector<kiss_hip_aln> ralns(CB + 1);
+    std::vector<uint32_t> rcigar(1);
+    std::vector<uint64_t> roidx(CB + 1, 0);
+    kiss_hip_align_report arep{};
+    rc = kiss_hip_fmi_align_host(S.data(), n, reads.data(), ridx.data(), Q, 1, chains.data(), rcidx.data(), &a.align_params, ralns.data(), CB,
+                                 rcigar.data(), roidx.data(), 0, &arep, a.device);
+    if (rc == KISS_HIP_E_INVALID && arep.cigar_ops) {
+        rcigar.resize(arep.cigar_ops);
+        rc = kiss_hip_fmi_align_host(S.data(), n, reads.data(), ridx.data(), Q, 1, chains.data(), rcidx.data(), &a.align_params, ralns.data(),
+                                     CB, rcigar.data(), roidx.data(), arep.cigar_ops, &arep, a.device);
+    }
+    if (rc == KISS_HIP_E_UNSUPPORTED && arep.cells)
+        throw std::runtime_error("fmindex_query --rescue: " + std::to_string(arep.cells) +
+                                 " DP cells are more than one call holds: split the reads");
+    check(rc, "kiss_hip_fmi_align_host");
+    // merged: capacities are known
+    const uint64_t C = CA + CB, ops = oidx[CA] + roidx[CB];
+    std::vector<kiss_hip_aln> malns(C + 1);
+    std::vector<uint64_t> mcidx(V + 1, 0), moidx(C + 1, 0);
+    std::vector<uint32_t> mcigar(ops + 1);
+    rs.source.resize(C + 1);
+    check(kiss_hip_fmi_aln_merge_host(alns.data(), cidx.data(), cigar.data(), oidx.data(), ralns.data(), rcidx.data(), rcigar.data(),
+                                      roidx.data(), V, malns.data(), C, mcidx.data(), rs.source.data(), mcigar.data(), moidx.data(), ops,
+                                      nullptr, a.device),
+          "kiss_hip_fmi_aln_merge_host");
+    std::vector<kiss_hip_hit> mhits(C + 1);
+    std::vector<uint64_t> mhidx(Q + 1, 0);
+    kiss_hip_select_report rep{};
+    check(kiss_hip_fmi_select_host(malns.data(), mcidx.data(), ridx.data(), Q, 1, bounds, R, &a.select_params, mhits.data(), mhidx.data(), C,
+                                   &rep, a.device),
+          "kiss_hip_fmi_select_host");
+    return sam_pairs(a, out, ref, malns, mcigar, moidx, reads, ridx, names, mhits, mhidx, rep, &rs);
+}
+
 // fmindex_query --seeds READS --chain --align --sam: the alignments of every read turned into its mappings, stdout is SAM
-int sam_main(const Args &a, uint64_t C, uint64_t n, const std::vector<kiss_hip_aln> &alns, const std::vector<uint64_t> &cidx,
+int sam_main(const Args &a, uint64_t C, const std::vector<uint8_t> &S, const std::vector<kiss_hip_aln> &alns, const std::vector<uint64_t> &cidx,
              const std::vector<uint32_t> &cigar, const std::vector<uint64_t> &oidx, const std::vector<uint8_t> &reads,
              const std::vector<uint64_t> &ridx, const std::vector<std::string> &names)
 {
+    const uint64_t n = S.size();
     const uint64_t Q = ridx.size() - 1;
     const RefRecords ref = scan_records(a.fasta);
     if (ref.bounds.back() != n)
@@ -886,6 +993,7 @@ int sam_main(const Args &a, uint64_t C, uint64_t n, const std::vector<kiss_hip_a
     for (uint64_t r = 0; r < R; r++)
         out += "@SQ\tSN:" + ref.names[r] + "\tLN:" + std::to_string(ref.bounds[r + 1] - ref.bounds[r]) + '\n';
     out += std::string("@PG\tID:kiss\tPN:kiss\tVN:") + VERSION + '\n';
+    if (a.rescue) return sam_rescue(a, out, ref, S, alns, cidx, cigar, oidx, reads, ridx, names, hits, hidx, rep);
     if (!a.mates.empty()) return sam_pairs(a, out, ref, alns, cigar, oidx, reads, ridx, names, hits, hidx, rep);
     for (uint64_t q = 0; q < Q; q++) {
         const uint64_t L = ridx[q + 1] - ridx[q];
@@ -960,7 +1068,7 @@ int align_main(const Args &a, uint64_t V, const std::vector<kiss_hip_chain> &cha
         throw std::runtime_error("fmindex_query --align: " + std::to_string(rep.cells) +
                                  " DP cells are more than one call holds: split the reads");
     check(rc, "kiss_hip_fmi_align_host");
-    if (a.sam) return sam_main(a, C, n, alns, cidx, cigar, oidx, reads, ridx, names);
+    if (a.sam) return sam_main(a, C, S, alns, cidx, cigar, oidx, reads, ridx, names);
     std::string out;
     for (uint64_t vr = 0; vr < V; vr++) {
         const uint64_t q = a.both_strands ? vr / 2 : vr, L = ridx[q + 1] - ridx[q];

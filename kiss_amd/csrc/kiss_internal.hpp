@@ -165,6 +165,9 @@ enum FmSlot {
     FM_SLOT_SELECT_SLAB, // the per-alignment arrays
     // kiss_hip_fmi_pair_dev (fm_pair.hip)
     FM_SLOT_PAIR_CTL,
+    // the rescue plan and the merge of two alignment sets (fm_rescue.hip)
+    FM_SLOT_RESCUE_CTL,
+    FM_SLOT_RESCUE_SLAB, // plan: the chain counts of the virtual reads; merge: the per-alignment arrays
     FM_SLOT_COUNT
 };
 

@@ -597,7 +597,7 @@ class FMIndex:
 
     def _align_dev(self, reads, text, min_len, max_len, max_occ, both_strands, chain_params, want_cigar, params):
         """align(): -> (its result, the device tensors a later stage reads: reads, read index, chain index, alignments)"""
-        from .fm_align import ALIGN_CELLS_PER_N, ALIGN_MAX_BAND, align_arrays, align_dev, align_params
+        from .fm_align import align_arrays, align_dev, align_params
         from .fm_chain import chain_params as make_chain_params, chain_dev, chain_arrays
         torch = _torch()
         p = align_params(**params)
@@ -620,23 +620,29 @@ class FMIndex:
         res = chain_arrays(out, False)
         res["seed_report"] = d["rep"].as_dict()
         C = int(out["rep"].chains)
-        # the traceback store holds ALIGN_CELLS_PER_N cells per base of the context: a context sized for this batch
         ridx = d["d_ridx"].cpu().numpy().view(np.uint64)
         lens = (ridx[1:] - ridx[:-1]).astype(np.int64)
-        per_v = np.diff(res["chain_index"].astype(np.int64))
-        vlen = np.repeat(lens, 2) if both_strands else lens
-        ch = res["chains"]
-        d0 = ch["tbeg"].astype(np.int64) - ch["rbeg"].astype(np.int64)
-        d1 = ch["tend"].astype(np.int64) - ch["rend"].astype(np.int64)
-        B = np.abs(d0 - d1) + 2 * int(p.band) + 1
-        cells = int((np.repeat(vlen, per_v) * np.where(B > ALIGN_MAX_BAND, 0, B)).sum()) if C else 0
-        if cells > ALIGN_CELLS_PER_N * ctx.max_n:
-            ctx = self._context(min(_lib.MAX_N, cells // ALIGN_CELLS_PER_N + (1 << 20)))
+        ctx = self._context_for_cells(ctx, res["chains"], res["chain_index"], lens, both_strands, int(p.band)) if C else ctx
         al = align_dev(lib, ctx, self.device, d_text, n, d["d_reads"], d["d_ridx"], d["Q"], both_strands, out["d_chains"],
                        out["d_cidx"], C, p, want_cigar)
         res.update(align_arrays(al, want_cigar))
         return res, {"lib": lib, "ctx": ctx, "d_ridx": d["d_ridx"], "Q": d["Q"], "d_cidx": out["d_cidx"], "d_alns": al["d_alns"],
-                     "C": C, "keep": (d, out, al)}
+                     "C": C, "keep": (d, out, al), "d_text": d_text, "n": n, "d_reads": d["d_reads"], "lens": lens, "align_params": p,
+                     "al": al}
+
+    def _context_for_cells(self, ctx, chains, chain_index, lens, both_strands, band):
+        """the traceback store of an align call holds ALIGN_CELLS_PER_N cells per base of the context: ctx, or a context sized
+        for these chains (numpy: the chain records, their index over the virtual reads, the read lengths)"""
+        from .fm_align import ALIGN_CELLS_PER_N, ALIGN_MAX_BAND
+        per_v = np.diff(chain_index.astype(np.int64))
+        vlen = np.repeat(lens, 2) if both_strands else lens
+        d0 = chains["tbeg"].astype(np.int64) - chains["rbeg"].astype(np.int64)
+        d1 = chains["tend"].astype(np.int64) - chains["rend"].astype(np.int64)
+        B = np.abs(d0 - d1) + 2 * band + 1
+        cells = int((np.repeat(vlen, per_v) * np.where(B > ALIGN_MAX_BAND, 0, B)).sum())
+        if cells > ALIGN_CELLS_PER_N * ctx.max_n:
+            ctx = self._context(min(_lib.MAX_N, cells // ALIGN_CELLS_PER_N + (1 << 20)))
+        return ctx
 
     # ---- the mappings of every read (kiss_hip_fmi_select_dev; no reference counterpart) ---------------------------------
     def map(self, reads, text, min_len=19, max_len=0, max_occ=500, both_strands=False, chain_params=None, align_params=None,
@@ -661,7 +667,7 @@ class FMIndex:
 
     # ---- the mappings of two mates paired (kiss_hip_fmi_pair_dev; no reference counterpart) -----------------------------
     def map_pairs(self, reads1, reads2, text, min_len=19, max_len=0, max_occ=500, chain_params=None, align_params=None,
-                  select_params=None, bounds=None, want_cigar=True, **pair_params):
+                  select_params=None, bounds=None, want_cigar=True, rescue=None, **pair_params):
         """map() for paired reads (forward-then-reverse libraries; include/kiss_hip.h has the definition): reads1[p] and
         reads2[p] are mate 1 and mate 2 of pair p, both as read from the sequencer.  They are interleaved into one batch
         (reads 2 p and 2 p + 1), which goes through seeds, chains, alignments and select on both strands and then through the
@@ -670,7 +676,17 @@ class FMIndex:
         (1000), ins_mean (400), pen_coef (8, in 256ths), pen_max (20), mapq_coef (120), mapq_max (60).  Returns what map()
         returns for the interleaved batch plus pairs (structured array, one per pair: hit1, hit2 -- indices into hits, or
         0xFFFFFFFF --, flags, tlen, score, sub1, sub2, mapq1, mapq2, n_conc; flags 1 proper, 2 / 4 mate 1 / 2 mapped, 8 same
-        record, 16 / 32 mate 1 / 2 promoted from a secondary) and pair_report."""
+        record, 16 / 32 mate 1 / 2 promoted from a secondary) and pair_report.
+        rescue: None, or True / a dict of the rescue parameters -- ins_min and ins_max (the pair parameters' unless given),
+        max_anchors (4), min_anchor_score (0), max_width (960) --: the pairs that are not proper are planned into windows next
+        to the hits of either mate (kiss_hip_fmi_rescue_dev), the windows aligned, their alignments merged behind the reads'
+        own (kiss_hip_fmi_aln_merge_dev) and select and pair run again, everything staying on the device.  alignments,
+        chain_index, cigar, cigar_index, hits, hit_index, pairs, select_report and pair_report are then those of the second
+        pass over the merged set; `chains` stays the first pass's.  Added: aln_source (merged alignment a is alignment
+        aln_source[a] of the first pass, whose chain has the same number, if that is below the first pass's count C_A, else
+        it belongs to rescue chain aln_source[a] - C_A), first_pass (pairs, hits, hit_index, select_report, pair_report,
+        alignments: C_A) and rescue (chains, chain_index, origin, report, align_report, merge_report, rescued: the pairs proper now and
+        not before)."""
         from .fm_pair import pair_arrays, pair_dev, pair_params as make_pair_params
         from .fm_select import select_arrays, select_dev, select_params as make_select_params
         pp = make_pair_params(**pair_params)
@@ -695,6 +711,48 @@ class FMIndex:
         res.update(select_arrays(sel))
         out = pair_dev(t["lib"], ctx, self.device, sel["d_hits"], sel["d_hidx"], t["Q"], t["d_alns"], t["C"], pp)
         res.update(pair_arrays(out))
+        if rescue is None or rescue is False:
+            return res
+        return self._rescue_pass(res, t, ctx, sel, out, sp, pp, bounds, want_cigar, {} if rescue is True else dict(rescue))
+
+    def _rescue_pass(self, res, t, ctx, sel, out, sp, pp, bounds, want_cigar, rescue):
+        """map_pairs(rescue=...): plan, the rescue align call, merge, and select and pair again (res: the first pass's result)"""
+        from .fm_align import align_arrays, align_dev
+        from .fm_pair import PAIR_PROPER, pair_arrays, pair_dev
+        from .fm_rescue import merge_arrays, merge_dev, rescue_arrays, rescue_dev, rescue_params
+        from .fm_select import select_arrays, select_dev
+        rescue.setdefault("ins_min", pp.ins_min)
+        rescue.setdefault("ins_max", pp.ins_max)
+        rp = rescue_params(**rescue)
+        lib, Q, CA = t["lib"], t["Q"], t["C"]
+        first = {k: res[k] for k in ("pairs", "hits", "hit_index", "select_report", "pair_report")}
+        first["alignments"] = CA
+        pl = rescue_dev(lib, ctx, self.device, out["d_pairs"], sel["d_hits"], sel["d_hidx"], Q, t["d_alns"], CA, t["d_ridx"], t["n"],
+                        bounds, rp, int(sel["rep"].hits))
+        plan = rescue_arrays(pl)
+        if pl["C"]:
+            ctx = self._context_for_cells(ctx, plan["chains"], plan["chain_index"], t["lens"], True, int(t["align_params"].band))
+        al2 = align_dev(lib, ctx, self.device, t["d_text"], t["n"], t["d_reads"], t["d_ridx"], Q, True, pl["d_chains"], pl["d_cidx"],
+                        pl["C"], t["align_params"], want_cigar)
+        al1 = t["al"]
+        a = {"d_alns": al1["d_alns"], "d_cidx": t["d_cidx"], "C": CA, "d_cigar": al1["d_cigar"], "d_oidx": al1["d_oidx"],
+             "ops": int(al1["rep"].cigar_ops)}
+        b = {"d_alns": al2["d_alns"], "d_cidx": pl["d_cidx"], "C": pl["C"], "d_cigar": al2["d_cigar"], "d_oidx": al2["d_oidx"],
+             "ops": int(al2["rep"].cigar_ops)}
+        mg = merge_dev(lib, ctx, self.device, 2 * Q, a, b, want_cigar)
+        C = mg["C"]
+        if C > 0.3 * ctx.max_n:  # (the alignments of a call are sorted in the context's LMS arrays)
+            ctx = self._context(min(_lib.MAX_N, int(3.3 * C) + (1 << 20)))
+        sel2 = select_dev(lib, ctx, self.device, mg["d_alns"], mg["d_cidx"], t["d_ridx"], Q, C, True, bounds, sp)
+        out2 = pair_dev(lib, ctx, self.device, sel2["d_hits"], sel2["d_hidx"], Q, mg["d_alns"], C, pp)
+        res.update(merge_arrays(mg, want_cigar))
+        res.update(select_arrays(sel2))
+        res.update(pair_arrays(out2))
+        proper1 = (first["pairs"]["flags"] & PAIR_PROPER) != 0
+        proper2 = (res["pairs"]["flags"] & PAIR_PROPER) != 0
+        plan.update(align_report=align_arrays(al2, False)["align_report"], merge_report=mg["rep"].as_dict(),
+                    rescued=int(np.count_nonzero(proper2 & ~proper1)))
+        res.update(first_pass=first, rescue=plan)
         return res
 
     def close(self):
