@@ -23,6 +23,21 @@
  * kernels on other streams; the results are the same (what round 3 saw go wrong there was a 16-byte load at
  * an 8-byte aligned address in one kernel, gone since round 4; the near-end tie runs are verified before they are used,
  * kiss_hip_stats.tie_run_retries).
+ *
+ * Device entries (*_dev), two promises that hold for every one of them (tests/test_dev_stream_gpu.py,
+ * tests/test_dev_placement_gpu.py):
+ *   stream   : `void *stream` is the caller's hipStream_t, NULL = the ctx's own stream.  All work of the call is queued on it, so
+ *              it is ordered behind what the caller has queued there, and the call returns after that work has completed.  A ctx
+ *              keeps no caller's stream past the call that brought it: the entries that take no stream (kiss_hip_get_stats,
+ *              kiss_hip_ctx_get_stage_outputs, kiss_hip_stage_local_lms, kiss_hip_stage_view, kiss_hip_stage_reserve, the debug
+ *              hooks) run on the ctx's own stream and wait for no other.
+ *   alignment: a device array needs the NATURAL ALIGNMENT OF ITS ELEMENT and no more, unless its entry says otherwise: byte
+ *              arrays (texts, reads, patterns, raw file bytes, mismatches, bwt and occ2 of the DNA index) any address, uint16_t
+ *              2, uint32_t 4, uint64_t 8 bytes; arrays of records whose fields are uint32_t (kiss_hip_fmi_seed, kiss_hip_chain,
+ *              kiss_hip_chain_anchor, kiss_hip_aln, kiss_hip_hit, kiss_hip_pair) 4 bytes: records are read and written field
+ *              by field.  The one array that needs more is the bwt of the byte index (kiss_hip_fmi8_view: 16 bytes, anything
+ *              else is KISS_HIP_E_INVALID).  No entry reads a byte in front of or behind an input whose value reaches a result,
+ *              and none writes outside the capacity it is given.  Every entry below repeats what it needs.
  */
 #ifndef KISS_HIP_H
 #define KISS_HIP_H
@@ -193,7 +208,8 @@ int kiss_hip_ctx_suffix_sort_dna_u32(kiss_hip_ctx *ctx, const uint8_t *S, uint64
 
 /* Device-resident form: d_S (n bytes) and d_SA (n+1 u32) are DEVICE pointers on the
  * ctx's device.  stream is a hipStream_t (NULL = the ctx's own stream).  The call
- * returns after the work on `stream` has completed. */
+ * returns after the work on `stream` has completed.
+ * Alignment: d_S any address (16-byte loads are taken only where the address allows them), d_SA 4 bytes. */
 int kiss_hip_ctx_suffix_sort_dna_u32_dev(kiss_hip_ctx *ctx, const uint8_t *d_S, uint64_t n, uint32_t k, int algo,
                                          uint32_t *d_SA, void *stream);
 
@@ -239,7 +255,9 @@ int kiss_hip_suffix_sort_dna_u32_multi(const uint8_t *S, uint64_t n, uint32_t k,
  * 64-bit sum that any host can recompute (kiss_hip_sa_digest_host).  order_violations is meaningful only when SA is a
  * permutation of [0, n] (the k >= n proof reads ranks that a non-permutation never wrote; ok = 0 either way, and
  * out_of_range, duplicates and sa0_ok are exact for every input).  Allocates its own scratch (n/8 bytes, plus
- * 4(n+1) bytes for k >= n) and frees it before returning; the ctx is only used for the device and the stream. */
+ * 4(n+1) bytes for k >= n) and frees it before returning; the ctx is only used for the device and the stream.
+ * Alignment: d_S any address (the aligned 8-byte words around a text position are read and the bytes outside the text shifted
+ * out: nothing outside [d_S, d_S + n) reaches the result), d_SA 4 bytes. */
 typedef struct kiss_hip_verify_report {
     uint64_t n;
     uint32_t k;
@@ -283,7 +301,8 @@ int kiss_hip_ctx_get_stage_outputs(kiss_hip_ctx *ctx, uint32_t *lms_ascending, u
  *   stage_sort      : k-ordered sort of `count` far LMS suffixes (ascending position order inside equal keys on input)
  *                                                                        (lms_suffix_direct_sort_dna, kiss1_core.hpp:24-145)
  *   stage_induce    : near-end rule + placement + L/S induction from the concatenated sorted far list, the near-end
- *                     suffixes (ascending positions) and the global counts -> SA     (kiss1_core.hpp:259-267)        */
+ *                     suffixes (ascending positions) and the global counts -> SA     (kiss1_core.hpp:259-267)
+ * Alignment: natural alignment of the element for every array (d_S any address, uint32_t arrays 4, uint64_t arrays 8 bytes).  */
 int kiss_hip_stage_classify(kiss_hip_ctx *ctx, const uint8_t *d_S, uint64_t n, uint32_t k, uint64_t lo, uint64_t hi,
                             uint64_t counts13[13], void *stream);
 int kiss_hip_stage_local_lms(kiss_hip_ctx *ctx, uint64_t *d_keys_out /* may be NULL: sizes only */,
@@ -296,7 +315,10 @@ int kiss_hip_stage_local_lms(kiss_hip_ctx *ctx, uint64_t *d_keys_out /* may be N
  *   SORTED / SORTED_CTX     : output of stage_sort (u32 / u32) = source of the gather; on the rank that runs the
  *                             induction also its destination and the input of stage_induce
  * kiss_hip_stage_reserve: makes the arrays hold lms_capacity entries; their CONTENTS ARE LOST when it has to regrow
- * (call it before stage_classify, or classify again).  The pointers change then: ask for the views afterwards. */
+ * (call it before stage_classify, or classify again).  The pointers change then: ask for the views afterwards.  It waits for
+ * no stream but the ctx's own: the arrays a regrowth replaces are freed by the next call on the ctx that takes a stream (old
+ * and new arrays exist side by side until then, both counted by kiss_hip_ctx_workspace_bytes; where they do not fit, the old
+ * ones are freed first). */
 enum {
     KISS_HIP_VIEW_LOCAL_KEYS = 0,
     KISS_HIP_VIEW_LOCAL_POS = 1,
@@ -370,6 +392,8 @@ typedef struct kiss_hip_fmi_view {
  *       (exclusive prefix of hit counts), offsets receives the hit positions of pattern q
  *       at [offsets_index[q], offsets_index[q+1]) in get_offsets order; pass NULL to skip.
  *   offsets_capacity : entries available in `offsets`
+ * Alignment: natural alignment of the element -- patterns and the view's bwt (a pointer into a loaded .fmi will do) and occ2
+ * any address; beg, end, offsets and the view's occ1, sa, b_occ 4 bytes; offsets_index and the view's b 8 bytes.
  */
 int kiss_hip_fmi_query_batch_dev(kiss_hip_ctx *ctx, const kiss_hip_fmi_view *fmi, const uint8_t *patterns, uint32_t L,
                                  uint64_t Q, uint32_t *beg, uint32_t *end, uint64_t *hit_count_total,
@@ -380,6 +404,8 @@ int kiss_hip_fmi_query_batch_dev(kiss_hip_ctx *ctx, const kiss_hip_fmi_view *fmi
  * FM-index construction from a text and its suffix array, both device resident
  * (FMIndex::build(ref, ori_sa), fm_index.hpp:390-451).  Output arrays are device
  * buffers sized as in kiss_hip_fmi_view; cnt/pri are written to the host struct.
+ * Alignment: natural alignment of the element -- d_S, d_bwt, d_occ2 any address; d_SA, d_occ1, d_sa_sampled, d_b_occ 4 bytes;
+ * d_b 8 bytes.  Exactly the sizes of kiss_hip_fmi_sizes_for are written, nothing behind them.
  */
 int kiss_hip_fmi_build_dev(kiss_hip_ctx *ctx, const uint8_t *d_S, uint64_t n, const uint32_t *d_SA, uint32_t sa_intv,
                            uint8_t *d_bwt, uint32_t *d_occ1, uint8_t *d_occ2, uint32_t *d_sa_sampled, uint64_t *d_b,
@@ -420,14 +446,16 @@ typedef struct kiss_hip_fmi_sizes_ex {
 } kiss_hip_fmi_sizes_ex;
 int kiss_hip_fmi_sizes_ex_for(uint64_t n, uint32_t sa_intv, uint32_t lookup_len, kiss_hip_fmi_sizes_ex *out);
 /* build from a device text and its SA: the arrays of kiss_hip_fmi_build_dev plus lookup_ (d_lookup, lookup_entries);
- * d_b / d_b_occ may be NULL when sa_intv == 1.  Device times under KISS_HIP_K_FM_BUILD. */
+ * d_b / d_b_occ may be NULL when sa_intv == 1.  Device times under KISS_HIP_K_FM_BUILD.
+ * Alignment: as kiss_hip_fmi_build_dev; d_lookup 4 bytes. */
 int kiss_hip_fmi_build_ex_dev(kiss_hip_ctx *ctx, const uint8_t *d_S, uint64_t n, const uint32_t *d_SA, uint32_t sa_intv,
                               uint32_t lookup_len, uint8_t *d_bwt, uint32_t *d_occ1, uint8_t *d_occ2, uint32_t *d_sa,
                               uint64_t *d_b, uint32_t *d_b_occ, uint32_t *d_lookup, uint32_t cnt_out[4], uint32_t *pri_out,
                               void *stream);
 /* get_range(pattern, stop_cnt) (fm_index.hpp:553-584) then get_offsets(beg, end) (:453-501) for every pattern; the
  * arguments of kiss_hip_fmi_query_batch_dev plus stop_cnt (0: no early stop; 0xFFFFFFFF: stop_cnt + 1 wraps to 0, never
- * stops) and offs (device, Q entries, may be NULL): get_range's third value, the characters left unmatched. */
+ * stops) and offs (device, Q entries, may be NULL): get_range's third value, the characters left unmatched.
+ * Alignment: as kiss_hip_fmi_query_batch_dev; offs and the view's lookup 4 bytes. */
 int kiss_hip_fmi_query_ex_dev(kiss_hip_ctx *ctx, const kiss_hip_fmi_view_ex *fmi, const uint8_t *patterns, uint32_t L,
                               uint64_t Q, uint32_t stop_cnt, uint32_t *beg, uint32_t *end, uint32_t *offs,
                               uint64_t *hit_count_total, uint64_t *checksum, uint32_t *offsets, uint64_t *offsets_index,
@@ -474,7 +502,9 @@ typedef struct kiss_hip_fmi_mm_report {
     uint64_t checksum;       /* sum of all hit positions (0 without positions) */
     float ms_total, ms_search, ms_locate, ms_sort;
 } kiss_hip_fmi_mm_report;
-/* every pointer except report is a device pointer; report may be NULL */
+/* every pointer except report is a device pointer; report may be NULL.  Alignment: natural alignment of the element -- patterns,
+ * mismatches and the view's bwt and occ2 any address; counts, positions and the view's occ1, sa, b_occ 4 bytes; index and the
+ * view's b 8 bytes. */
 int kiss_hip_fmi_query_mm_dev(kiss_hip_ctx *ctx, const kiss_hip_fmi_view *fmi, const uint8_t *patterns, uint32_t L, uint64_t Q,
                               uint32_t max_mismatches, uint32_t *counts, uint32_t *positions, uint8_t *mismatches,
                               uint64_t *index, uint64_t capacity, kiss_hip_fmi_mm_report *report, void *stream);
@@ -487,7 +517,8 @@ int kiss_hip_fmi_query_mm_host(const kiss_hip_fmi_view *fmi, const uint8_t *patt
  * Replaces KISS1Sorter::get_suffix_array -> kiss1_suffix_array (kiss1_core.hpp:270-311), reachable only from the
  * reference's tests / experiments.  For that entry only the k-order property is defined (its comparator has no
  * index tie-break); the exact suffix array (shorter suffix first on a tie, SA[0] = n, n + 1 entries) satisfies it for
- * every k.  7-character keys + rank doubling over all suffixes; no induction.  n <= ctx max_n. */
+ * every k.  7-character keys + rank doubling over all suffixes; no induction.  n <= ctx max_n.
+ * Alignment (_dev): d_S any address, d_SA 4 bytes. */
 int kiss_hip_suffix_sort_u8(const uint8_t *S, uint64_t n, uint32_t *SA, int device);
 int kiss_hip_ctx_suffix_sort_u8_dev(kiss_hip_ctx *ctx, const uint8_t *d_S, uint64_t n, uint32_t *d_SA, void *stream);
 
@@ -518,7 +549,8 @@ typedef struct kiss_hip_lcp_report {
     uint32_t reserved2_;
 } kiss_hip_lcp_report;
 /* device-resident: d_S (n symbols), d_SA (n + 1), d_LCP (n + 1) on the ctx's device; d_LCP may be d_SA (the LCP then
- * replaces the SA); report may be NULL.  stream: as kiss_hip_ctx_suffix_sort_dna_u32_dev; returns after the work is done. */
+ * replaces the SA); report may be NULL.  stream: as kiss_hip_ctx_suffix_sort_dna_u32_dev; returns after the work is done.
+ * Alignment: d_S any address (no byte behind d_S + n reaches a result), d_SA and d_LCP 4 bytes. */
 int kiss_hip_ctx_lcp_dna_u32_dev(kiss_hip_ctx *ctx, const uint8_t *d_S, uint64_t n, const uint32_t *d_SA, uint32_t *d_LCP,
                                  kiss_hip_lcp_report *report, void *stream);
 int kiss_hip_ctx_lcp_u8_dev(kiss_hip_ctx *ctx, const uint8_t *d_S, uint64_t n, const uint32_t *d_SA, uint32_t *d_LCP,
@@ -539,7 +571,9 @@ int kiss_hip_lcp_u8(const uint8_t *S, uint64_t n, const uint32_t *SA_or_null, ui
  * kiss_hip_ctx_load_text_file: streams the file through pinned buffers into device memory and parses it there;
  *   *d_S_out is a device buffer owned by the caller (kiss_hip_free_dev).  No base is touched on the host.
  * kiss_hip_alloc_dev / kiss_hip_copy_to_host / kiss_hip_free_dev: for hosts that do not link HIP (the CLI, ctypes);
- *   they act on the current device of the calling thread (the one the last ctx call selected). */
+ *   they act on the current device of the calling thread (the one the last ctx call selected).
+ * Alignment (kiss_hip_ctx_parse_text_dev): d_raw and d_S any address.  Only the first *n_out bytes of d_S are defined; nothing is
+ * written behind d_S + bytes. */
 int kiss_hip_file_size(const char *path, uint64_t *bytes);
 int kiss_hip_ctx_parse_text_dev(kiss_hip_ctx *ctx, const uint8_t *d_raw, uint64_t bytes, uint8_t *d_S, uint64_t *n_out,
                                 void *stream);
@@ -593,7 +627,10 @@ typedef struct kiss_hip_fmi8_report {
  * two forms: d_bwt == NULL is the census -- it writes *sigma_out (and d_C / d_map when given) and nothing else; otherwise the
  * arrays are sized by kiss_hip_fmi8_sizes_for(n, sa_intv, sigma_capacity), sigma_capacity >= the text's sigma (smaller:
  * KISS_HIP_E_INVALID with *sigma_out set), and occ1 / occ2 are laid out for *sigma_out rows.  d_b / d_b_occ may be NULL when
- * sa_intv == 1.  n = 0 builds the index of one row.  Device times under KISS_HIP_K_FM_BUILD. */
+ * sa_intv == 1.  n = 0 builds the index of one row.  Device times under KISS_HIP_K_FM_BUILD.
+ * Alignment: d_bwt 16 bytes (anything else: KISS_HIP_E_INVALID before anything is launched, nothing written); every other array
+ * the natural alignment of its element -- d_S, d_map any address; d_occ2 2 bytes; d_SA, d_C, d_occ1, d_sa, d_b_occ 4 bytes; d_b 8
+ * bytes. */
 int kiss_hip_fmi8_build_dev(kiss_hip_ctx *ctx, const uint8_t *d_S, uint64_t n, const uint32_t *d_SA, uint32_t sa_intv,
                             uint32_t sigma_capacity, uint32_t *d_C, uint8_t *d_map, uint8_t *d_bwt, uint32_t *d_occ1,
                             uint16_t *d_occ2, uint32_t *d_sa, uint64_t *d_b, uint32_t *d_b_occ, uint32_t *sigma_out,
@@ -616,7 +653,10 @@ int kiss_hip_fmi8_build_host(const uint8_t *S, uint64_t n, const uint32_t *SA_or
  * call are sorted in the ctx's LMS work arrays (their contents are lost): more hits than those hold is
  * KISS_HIP_E_UNSUPPORTED with the totals reported -- split the batch.  A row that reaches no sampled row (an index that was not
  * built from an exact suffix array) is counted in walk_failures and the call returns KISS_HIP_E_INVALID.
- * Device times: report->ms_* (report may be NULL); the kernels also count under KISS_HIP_K_FM_QUERY when that class is profiled. */
+ * Device times: report->ms_* (report may be NULL); the kernels also count under KISS_HIP_K_FM_QUERY when that class is profiled.
+ * Alignment: the view's bwt 16 bytes (see above: KISS_HIP_E_INVALID otherwise, decided from the address, no output touched);
+ * every other array the natural alignment of its element -- patterns and the view's map any address; occ2 2 bytes; beg, end,
+ * positions and the view's C, occ1, sa, b_occ 4 bytes; pat_index, index and the view's b 8 bytes. */
 int kiss_hip_fmi8_query_dev(kiss_hip_ctx *ctx, const kiss_hip_fmi8_view *fmi, const uint8_t *patterns, const uint64_t *pat_index,
                             uint64_t Q, uint32_t *beg, uint32_t *end, uint64_t *hit_count_total, uint64_t *checksum,
                             uint32_t *positions, uint64_t *index, uint64_t capacity, kiss_hip_fmi8_report *report, void *stream);
@@ -667,7 +707,9 @@ typedef struct kiss_hip_fmi_seed_report {
     uint32_t max_ms, reserved_;
     float ms_total, ms_search, ms_compact, ms_locate, ms_sort;
 } kiss_hip_fmi_seed_report;
-/* every pointer except fmi and report is a device pointer (the arrays of the view too) */
+/* every pointer except fmi and report is a device pointer (the arrays of the view too).  Alignment: natural alignment of the
+ * element -- reads and the view's bwt and occ2 any address; ms, positions, seeds (records of uint32_t) and the view's occ1, sa,
+ * b_occ 4 bytes; read_index, seed_index, pos_index and the view's b 8 bytes. */
 int kiss_hip_fmi_seeds_dev(kiss_hip_ctx *ctx, const kiss_hip_fmi_view_ex *fmi, const uint8_t *reads, const uint64_t *read_index,
                            uint64_t Q, uint32_t min_len, uint32_t max_len, uint32_t max_occ, int both_strands, uint32_t *ms,
                            kiss_hip_fmi_seed *seeds, uint64_t *seed_index, uint64_t seed_capacity, uint32_t *positions,
@@ -724,7 +766,9 @@ typedef struct kiss_hip_chain_report {
     uint32_t max_anchors, best_score; /* the largest A of a virtual read; the largest score of a reported chain */
     float ms_total, ms_sort, ms_dp, ms_emit; /* sort: expand, order, gather; emit: tree ends, scan, totals, records */
 } kiss_hip_chain_report;
-/* every pointer except params and report is a device pointer */
+/* every pointer except params and report is a device pointer.  Alignment: natural alignment of the element -- seeds, chains
+ * and chain_anchors (records of uint32_t, read and written field by field) and positions 4 bytes; seed_index, pos_index,
+ * chain_index and anchor_index 8 bytes. */
 int kiss_hip_fmi_chain_dev(kiss_hip_ctx *ctx, const kiss_hip_fmi_seed *seeds, const uint64_t *seed_index, uint64_t V,
                            const uint32_t *positions, const uint64_t *pos_index, const kiss_hip_chain_params *params,
                            kiss_hip_chain *chains, uint64_t *chain_index, uint64_t chain_capacity, kiss_hip_chain_anchor *chain_anchors,
@@ -796,7 +840,9 @@ typedef struct kiss_hip_align_report {
     uint32_t best_score, max_band;         /* the largest score; the largest B of a chain that was not too wide */
     float ms_total, ms_dp, ms_trace, ms_emit; /* trace: the walk back and the op counts; emit: scan, totals, records, ops */
 } kiss_hip_align_report;
-/* every pointer except params and report is a device pointer */
+/* every pointer except params and report is a device pointer.  Alignment: natural alignment of the element -- text and reads
+ * any address; chains and alns (records of uint32_t, read and written field by field) and cigar 4 bytes; read_index,
+ * chain_index and cigar_index 8 bytes. */
 int kiss_hip_fmi_align_dev(kiss_hip_ctx *ctx, const uint8_t *text, uint64_t n, const uint8_t *reads, const uint64_t *read_index,
                            uint64_t Q, int both_strands, const kiss_hip_chain *chains, const uint64_t *chain_index,
                            const kiss_hip_align_params *params, kiss_hip_aln *alns, uint64_t aln_capacity, uint32_t *cigar,
@@ -869,7 +915,8 @@ typedef struct kiss_hip_select_report {
     uint32_t max_candidates, reserved_;
     float ms_total, ms_sort, ms_walk, ms_emit; /* sort: checks, keys, the radix sort; emit: scan, totals, records */
 } kiss_hip_select_report;
-/* every pointer except params and report is a device pointer */
+/* every pointer except params and report is a device pointer.  Alignment: alns and hits 4 bytes (above); chain_index,
+ * read_index, bounds and hit_index 8 bytes. */
 int kiss_hip_fmi_select_dev(kiss_hip_ctx *ctx, const kiss_hip_aln *alns, const uint64_t *chain_index, const uint64_t *read_index,
                             uint64_t Q, int both_strands, const uint64_t *bounds, uint64_t R, const kiss_hip_select_params *params,
                             kiss_hip_hit *hits, uint64_t *hit_index, uint64_t hit_capacity, kiss_hip_select_report *report,
@@ -940,7 +987,8 @@ typedef struct kiss_hip_pair_report {
     float ms_total, ms_check, ms_pair; /* check: hit_index looked at once by the host; pair: the one kernel */
     uint32_t reserved_;
 } kiss_hip_pair_report;
-/* every pointer except params and report is a device pointer */
+/* every pointer except params and report is a device pointer.  Alignment: hits, alns and pairs 4 bytes (above); hit_index 8
+ * bytes. */
 int kiss_hip_fmi_pair_dev(kiss_hip_ctx *ctx, const kiss_hip_hit *hits, const uint64_t *hit_index, uint64_t Q,
                           const kiss_hip_aln *alns, uint64_t aln_count, const kiss_hip_pair_params *params, kiss_hip_pair *pairs,
                           kiss_hip_pair_report *report, void *stream);
@@ -1004,7 +1052,8 @@ typedef struct kiss_hip_rescue_report {
     uint64_t P, pairs_planned, anchors, chains, split, empty, bad_input, max_chains;
     float ms_total, ms_check, ms_count, ms_emit; /* count: the counting walk and the scan; emit: the writing walk */
 } kiss_hip_rescue_report;
-/* every pointer except params and report is a device pointer */
+/* every pointer except params and report is a device pointer.  Alignment: pairs, hits, alns, chains (above) and origin 4
+ * bytes; hit_index, read_index, bounds and chain_index 8 bytes. */
 int kiss_hip_fmi_rescue_dev(kiss_hip_ctx *ctx, const kiss_hip_pair *pairs, const kiss_hip_hit *hits, const uint64_t *hit_index,
                             uint64_t Q, const kiss_hip_aln *alns, uint64_t aln_count, const uint64_t *read_index, uint64_t n,
                             const uint64_t *bounds, uint64_t R, const kiss_hip_rescue_params *params, kiss_hip_chain *chains,
@@ -1036,7 +1085,8 @@ typedef struct kiss_hip_merge_report {
     float ms_total, ms_place, ms_copy; /* place: checks, sources, the scan of the op counts; copy: records, indices, ops */
     uint32_t reserved_;
 } kiss_hip_merge_report;
-/* every pointer except report is a device pointer */
+/* every pointer except report is a device pointer.  Alignment: the alignment records (above), the cigar arrays and source 4
+ * bytes; the chain and cigar indexes 8 bytes. */
 int kiss_hip_fmi_aln_merge_dev(kiss_hip_ctx *ctx, const kiss_hip_aln *alns_a, const uint64_t *chain_index_a, const uint32_t *cigar_a,
                                const uint64_t *cigar_index_a, const kiss_hip_aln *alns_b, const uint64_t *chain_index_b,
                                const uint32_t *cigar_b, const uint64_t *cigar_index_b, uint64_t V, kiss_hip_aln *alns,

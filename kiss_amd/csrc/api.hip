@@ -182,6 +182,13 @@ bool kiss_host_is_pinned(const void *p); // xfer.hip
 void *kiss_prefault_start(kiss_hip_ctx *ctx, void *p, uint64_t bytes);
 void kiss_prefault_join(void *handle);
 
+void kiss_drain_deferred(kiss_hip_ctx *ctx)
+{
+    for (void *p : ctx->deferred_free) (void)hipFree(p);
+    ctx->deferred_free.clear();
+    ctx->deferred_bytes = 0;
+}
+
 namespace {
 
 template <typename T>
@@ -207,7 +214,14 @@ int dmalloc(kiss_hip_ctx *ctx, T **p, uint64_t count)
     return KISS_HIP_OK;
 }
 
-void free_tied(kiss_hip_ctx *ctx)
+// gives a work array back: at once (hipFree waits for the whole device), or, deferred, at the next call that takes a stream
+void release(kiss_hip_ctx *ctx, void *p, bool defer)
+{
+    if (defer) ctx->deferred_free.push_back(p);
+    else (void)hipFree(p);
+}
+
+void free_tied(kiss_hip_ctx *ctx, bool defer = false)
 {
     void **ptrs[] = {(void **)&ctx->segA, (void **)&ctx->segB, (void **)&ctx->slotA, (void **)&ctx->slotB,
                      (void **)&ctx->segstartA, (void **)&ctx->segstartB, (void **)&ctx->bkeyA, (void **)&ctx->bkeyB,
@@ -215,33 +229,36 @@ void free_tied(kiss_hip_ctx *ctx)
                      (void **)&ctx->bslot, (void **)&ctx->flags};
     for (void **p : ptrs)
         if (*p) {
-            (void)hipFree(*p);
+            release(ctx, *p, defer);
             *p = nullptr;
         }
+    if (defer) ctx->deferred_bytes += ctx->tied_bytes;
     ctx->ws_bytes -= ctx->tied_bytes;
     ctx->tied_bytes = 0;
     ctx->t_cap = 0;
     ctx->flags_cap = 0;
 }
 
-void free_lms_side(kiss_hip_ctx *ctx)
+void free_lms_side(kiss_hip_ctx *ctx, bool defer = false)
 {
-    free_tied(ctx);
+    free_tied(ctx, defer);
     void **ptrs[] = {(void **)&ctx->lms_pos, (void **)&ctx->keyA, (void **)&ctx->keyB, (void **)&ctx->posA,
                      (void **)&ctx->posB, (void **)&ctx->lms_sorted_far, (void **)&ctx->lms_ctx_far,
                      (void **)&ctx->lmsP, (void **)&ctx->lmsC, (void **)&ctx->tile_hist, (void **)&ctx->scan_tmp,
                      (void **)&ctx->rx_desc, (void **)&ctx->rx_ghist, (void **)&ctx->fc_desc};
     for (void **p : ptrs)
         if (*p) {
-            (void)hipFree(*p);
+            release(ctx, *p, defer);
             *p = nullptr;
         }
+    if (defer) ctx->deferred_bytes += ctx->lms_bytes;
     ctx->ws_bytes -= ctx->lms_bytes;
     ctx->lms_bytes = 0;
 }
 
 void free_all(kiss_hip_ctx *ctx)
 {
+    kiss_drain_deferred(ctx);
     free_lms_side(ctx);
     void *ptrs[] = {ctx->pk, ctx->tile_gp, ctx->tile_cnt, ctx->cl_part, ctx->d_counts, ctx->CTX, ctx->CLS, ctx->ind_counts, ctx->ind_desc,
                     ctx->d_small, ctx->near_idx, ctx->near_fin, ctx->near_pos, ctx->near_tmp, ctx->near_tmp2, ctx->pairs1, ctx->pairs2, ctx->rx_ctl, ctx->refine_heads, ctx->ga_codes};
@@ -293,7 +310,7 @@ int sort_dev_unlocked(kiss_hip_ctx *ctx, const uint8_t *d_S, uint64_t n, uint32_
     if (n > KISS_HIP_MAX_N || n > ctx->max_n) return KISS_HIP_E_INVALID;
     if (algo != KISS_HIP_ALGO_PARALLEL_SORTING && algo != KISS_HIP_ALGO_PREFIX_DOUBLING) return KISS_HIP_E_INVALID;
     KCHECK(hipSetDevice(ctx->device));
-    ctx->stream = stream ? (hipStream_t)stream : ctx->own_stream;
+    KissCallStream call_stream(ctx, stream); // the caller's stream for this call, the ctx's own again on every way out
     KTRY(kiss_workspace_ready(ctx));
     std::memset(&ctx->stats, 0, sizeof ctx->stats);
     ctx->stats.n = n;
@@ -443,11 +460,25 @@ int kiss_need_ctx_words(kiss_hip_ctx *ctx)
     return KISS_HIP_OK;
 }
 
-int kiss_lms_reserve(kiss_hip_ctx *ctx, uint64_t m_cap, uint64_t t_cap_wanted)
+// kiss_lms_reserve for kiss_hip_stage_reserve, an entry that takes no stream and so waits for none: the arrays it replaces are
+// freed by the next call that takes a stream (KissCallStream, fm_enter: it waits for the device's work anyway) or with the
+// ctx.  Old and new arrays exist side by side until then; where they do not fit, the old way.
+int kiss_lms_reserve_deferred(kiss_hip_ctx *ctx, uint64_t m_cap)
+{
+    int rc = kiss_lms_reserve(ctx, m_cap, 0, true);
+    if (rc == KISS_HIP_E_NOMEM) {
+        kiss_drain_deferred(ctx);
+        (void)hipGetLastError();
+        rc = kiss_lms_reserve(ctx, m_cap);
+    }
+    return rc;
+}
+
+int kiss_lms_reserve(kiss_hip_ctx *ctx, uint64_t m_cap, uint64_t t_cap_wanted, bool defer_frees)
 {
     const bool dbg = ctx->opts.debug;
     const auto t_begin = std::chrono::steady_clock::now();
-    free_lms_side(ctx);
+    free_lms_side(ctx, defer_frees);
     if (dbg)
         fprintf(stderr, "[kiss_hip] lms_reserve(%llu): freed the old arrays in %.3f s\n", (unsigned long long)m_cap,
                 std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count());
@@ -587,7 +618,6 @@ int kiss_host_sort(kiss_hip_ctx *ctx, const uint8_t *S, uint64_t n, uint32_t k, 
 {
     KCHECK(hipSetDevice(ctx->device));
     kiss_opts_refresh(ctx);
-    ctx->stream = ctx->own_stream;
     KTRY(kiss_io_reserve(ctx, n));
     using clk = std::chrono::steady_clock;
     const auto t0 = clk::now();
@@ -808,7 +838,7 @@ int kiss_hip_ctx_release_io_buffers(kiss_hip_ctx *ctx)
 int kiss_hip_ctx_workspace_bytes(const kiss_hip_ctx *ctx, uint64_t *bytes)
 {
     if (!ctx || !bytes) return KISS_HIP_E_INVALID;
-    *bytes = ctx->ws_bytes;
+    *bytes = ctx->ws_bytes + ctx->deferred_bytes; // (arrays a kiss_hip_stage_reserve replaced are held until the next stream call)
     return KISS_HIP_OK;
 }
 
@@ -910,7 +940,6 @@ int kiss_hip_debug_radix_sort(kiss_hip_ctx *ctx, uint64_t *keys, uint32_t *pos, 
 {
     if (!ctx || !keys || !pos || count > ctx->m_cap) return KISS_HIP_E_INVALID;
     KCHECK(hipSetDevice(ctx->device));
-    ctx->stream = ctx->own_stream;
     KCHECK(hipMemcpy(ctx->keyA, keys, count * 8, hipMemcpyHostToDevice));
     KCHECK(hipMemcpy(ctx->posA, pos, count * 4, hipMemcpyHostToDevice));
     RadixBufs rb = kiss_ctx_radix_bufs(ctx);
@@ -949,7 +978,6 @@ int kiss_hip_debug_scan_u32(kiss_hip_ctx *ctx, uint32_t *data, uint64_t count)
 {
     if (!ctx || !data || count > ctx->m_cap) return KISS_HIP_E_INVALID;
     KCHECK(hipSetDevice(ctx->device));
-    ctx->stream = ctx->own_stream;
     KCHECK(hipMemcpy(ctx->posA, data, count * 4, hipMemcpyHostToDevice));
     KTRY(kiss_scan_u32(ctx, ctx->posA, ctx->posB, count));
     KCHECK(hipStreamSynchronize(ctx->stream));
@@ -964,7 +992,6 @@ int kiss_hip_ctx_get_stage_outputs(kiss_hip_ctx *ctx, uint32_t *lms_ascending, u
     if (lms_ascending && ctx->m)
         KCHECK(hipMemcpy(lms_ascending, ctx->lms_pos, ctx->m * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (lms_sorted && ctx->m) {
-        ctx->stream = ctx->own_stream;
         KTRY(kiss_merge_lms(ctx)); // the sort itself never builds the merged list (place.hip)
         KCHECK(hipStreamSynchronize(ctx->stream));
     }

@@ -261,7 +261,7 @@ int kiss_hip_ctx_parse_text_dev(kiss_hip_ctx *ctx, const uint8_t *d_raw, uint64_
     if (!ctx || !n_out || (bytes && (!d_raw || !d_S))) return KISS_HIP_E_INVALID;
     if (bytes > 0xFFFFFFF0ull) return KISS_HIP_E_INVALID; // line numbers and offsets are 32-bit (n < 2^32 anyway)
     KCHECK(hipSetDevice(ctx->device));
-    ctx->stream = stream ? (hipStream_t)stream : ctx->own_stream;
+    KissCallStream call_stream(ctx, stream); // the caller's stream for this call, the ctx's own again on every way out
     KTRY(kiss_workspace_ready(ctx));
     *n_out = 0;
     if (bytes == 0) return KISS_HIP_OK;
@@ -333,7 +333,6 @@ int kiss_hip_ctx_load_text_file(kiss_hip_ctx *ctx, const char *path, uint8_t **d
     int rc = kiss_hip_file_size(path, &bytes);
     if (rc) return rc;
     KCHECK(hipSetDevice(ctx->device));
-    ctx->stream = ctx->own_stream;
     const int fd = open(path, O_RDONLY);
     if (fd < 0) return KISS_HIP_E_IO;
     uint8_t *d_raw = nullptr, *d_S = nullptr;

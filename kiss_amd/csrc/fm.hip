@@ -921,6 +921,7 @@ int kiss_hip_fmi_query_batch_dev(kiss_hip_ctx *ctx, const kiss_hip_fmi_view *fmi
                                  uint64_t *checksum, uint32_t *offsets, uint64_t *offsets_index,
                                  uint64_t offsets_capacity, void *stream)
 {
+    KissOwnStreamAtExit own_stream_at_exit(ctx); // a ctx keeps no caller's stream past the call (kiss_internal.hpp)
     if (!ctx || !fmi || !beg || !end || (Q && !patterns)) return KISS_HIP_E_INVALID;
     if (fmi->sa_intv != 4) return KISS_HIP_E_UNSUPPORTED; // the CLI's FMIndex<4, ...> (fmindex_build.hpp:27)
     return fmi_query(ctx, fmi, nullptr, 0, 1u, nullptr, patterns, L, Q, beg, end, hit_count_total, checksum, offsets,
@@ -1033,6 +1034,7 @@ int kiss_hip_fmi_build_dev(kiss_hip_ctx *ctx, const uint8_t *d_S, uint64_t n, co
                            uint8_t *d_bwt, uint32_t *d_occ1, uint8_t *d_occ2, uint32_t *d_sa_sampled, uint64_t *d_b,
                            uint32_t *d_b_occ, uint32_t cnt_out[4], uint32_t *pri_out, void *stream)
 {
+    KissOwnStreamAtExit own_stream_at_exit(ctx); // a ctx keeps no caller's stream past the call (kiss_internal.hpp)
     if (!ctx || !d_SA || (n && !d_S) || !d_bwt || !d_occ1 || !d_occ2 || !d_sa_sampled || !d_b || !d_b_occ || !cnt_out ||
         !pri_out)
         return KISS_HIP_E_INVALID;
@@ -1048,6 +1050,7 @@ int kiss_hip_fmi_build_ex_dev(kiss_hip_ctx *ctx, const uint8_t *d_S, uint64_t n,
                               uint64_t *d_b, uint32_t *d_b_occ, uint32_t *d_lookup, uint32_t cnt_out[4], uint32_t *pri_out,
                               void *stream)
 {
+    KissOwnStreamAtExit own_stream_at_exit(ctx); // a ctx keeps no caller's stream past the call (kiss_internal.hpp)
     if (!fm_params_ok(sa_intv, lookup_len)) return KISS_HIP_E_UNSUPPORTED;
     if (!ctx || !d_SA || (n && !d_S) || !d_bwt || !d_occ1 || !d_occ2 || !d_sa || !d_lookup || !cnt_out || !pri_out ||
         (sa_intv != 1 && (!d_b || !d_b_occ)))
@@ -1063,6 +1066,7 @@ int kiss_hip_fmi_query_ex_dev(kiss_hip_ctx *ctx, const kiss_hip_fmi_view_ex *fmi
                               uint64_t *hit_count_total, uint64_t *checksum, uint32_t *offsets, uint64_t *offsets_index,
                               uint64_t offsets_capacity, void *stream)
 {
+    KissOwnStreamAtExit own_stream_at_exit(ctx); // a ctx keeps no caller's stream past the call (kiss_internal.hpp)
     if (!fmi) return KISS_HIP_E_INVALID;
     if (!fm_params_ok(fmi->base.sa_intv, fmi->lookup_len)) return KISS_HIP_E_UNSUPPORTED;
     if (!ctx || !beg || !end || (Q && !patterns) || !fmi->lookup || (fmi->base.sa_intv != 1 && (!fmi->base.b || !fmi->base.b_occ)))

@@ -523,6 +523,7 @@ int kiss_hip_fmi8_build_dev(kiss_hip_ctx *ctx, const uint8_t *d_S, uint64_t n, c
                             uint16_t *d_occ2, uint32_t *d_sa, uint64_t *d_b, uint32_t *d_b_occ, uint32_t *sigma_out,
                             uint32_t *pri_out, void *stream)
 {
+    KissOwnStreamAtExit own_stream_at_exit(ctx); // a ctx keeps no caller's stream past the call (kiss_internal.hpp)
     if (!fm_sa_intv_ok(sa_intv)) return KISS_HIP_E_UNSUPPORTED;
     if (!ctx || (n && !d_S) || n > KISS_HIP_MAX_N || !sigma_out) return KISS_HIP_E_INVALID;
     if (d_bwt && (!d_SA || !d_C || !d_map || !d_sa || !pri_out || ((uintptr_t)d_bwt & 15) || (n && (!d_occ1 || !d_occ2)) ||
@@ -539,6 +540,7 @@ int kiss_hip_fmi8_query_dev(kiss_hip_ctx *ctx, const kiss_hip_fmi8_view *fmi, co
                             uint64_t Q, uint32_t *beg, uint32_t *end, uint64_t *hit_count_total, uint64_t *checksum,
                             uint32_t *positions, uint64_t *index, uint64_t capacity, kiss_hip_fmi8_report *report, void *stream)
 {
+    KissOwnStreamAtExit own_stream_at_exit(ctx); // a ctx keeps no caller's stream past the call (kiss_internal.hpp)
     if (report) {
         *report = kiss_hip_fmi8_report{};
         report->Q = Q;

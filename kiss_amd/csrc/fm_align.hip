@@ -545,6 +545,7 @@ int kiss_hip_fmi_align_dev(kiss_hip_ctx *ctx, const uint8_t *text, uint64_t n, c
                            const kiss_hip_align_params *params, kiss_hip_aln *alns, uint64_t aln_capacity, uint32_t *cigar,
                            uint64_t *cigar_index, uint64_t cigar_capacity, kiss_hip_align_report *report, void *stream)
 {
+    KissOwnStreamAtExit own_stream_at_exit(ctx); // a ctx keeps no caller's stream past the call (kiss_internal.hpp)
     const uint64_t V = both_strands ? 2 * Q : Q;
     if (report) {
         *report = kiss_hip_align_report{};

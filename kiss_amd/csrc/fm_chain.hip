@@ -547,6 +547,7 @@ int kiss_hip_fmi_chain_dev(kiss_hip_ctx *ctx, const kiss_hip_fmi_seed *seeds, co
                            kiss_hip_chain *chains, uint64_t *chain_index, uint64_t chain_capacity, kiss_hip_chain_anchor *chain_anchors,
                            uint64_t *anchor_index, uint64_t anchor_capacity, kiss_hip_chain_report *report, void *stream)
 {
+    KissOwnStreamAtExit own_stream_at_exit(ctx); // a ctx keeps no caller's stream past the call (kiss_internal.hpp)
     if (report) {
         *report = kiss_hip_chain_report{};
         report->V = V;

@@ -205,6 +205,7 @@ static inline int fm_enter(kiss_hip_ctx *ctx, void *stream)
 {
     KCHECK(hipSetDevice(ctx->device));
     ctx->stream = stream ? (hipStream_t)stream : ctx->own_stream;
+    if (!ctx->deferred_free.empty()) kiss_drain_deferred(ctx);
     return kiss_workspace_ready(ctx);
 }
 static inline int fm_leave(kiss_hip_ctx *ctx, FmEvents &ev, int rc, float *ms_total)

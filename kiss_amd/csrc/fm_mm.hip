@@ -579,6 +579,7 @@ int kiss_hip_fmi_query_mm_dev(kiss_hip_ctx *ctx, const kiss_hip_fmi_view *fmi, c
                               uint32_t max_mismatches, uint32_t *counts, uint32_t *positions, uint8_t *mismatches,
                               uint64_t *index, uint64_t capacity, kiss_hip_fmi_mm_report *report, void *stream)
 {
+    KissOwnStreamAtExit own_stream_at_exit(ctx); // a ctx keeps no caller's stream past the call (kiss_internal.hpp)
     if (report) {
         *report = kiss_hip_fmi_mm_report{};
         report->Q = Q;
@@ -593,8 +594,7 @@ int kiss_hip_fmi_query_mm_dev(kiss_hip_ctx *ctx, const kiss_hip_fmi_view *fmi, c
         return KISS_HIP_E_INVALID;
     if (all && (!fmi->sa || (fmi->sa_intv != 1 && (!fmi->b || !fmi->b_occ)))) return KISS_HIP_E_INVALID;
     if (all && Q == 0) { // index[0] = 0
-        KCHECK(hipSetDevice(ctx->device));
-        ctx->stream = stream ? (hipStream_t)stream : ctx->own_stream;
+        KTRY(fm_enter(ctx, stream));
         KTRY(kiss_zero_u32(ctx, index, 2));
         KCHECK(hipStreamSynchronize(ctx->stream));
     }

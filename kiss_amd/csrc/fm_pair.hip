@@ -397,6 +397,7 @@ int kiss_hip_fmi_pair_dev(kiss_hip_ctx *ctx, const kiss_hip_hit *hits, const uin
                           uint64_t aln_count, const kiss_hip_pair_params *params, kiss_hip_pair *pairs, kiss_hip_pair_report *report,
                           void *stream)
 {
+    KissOwnStreamAtExit own_stream_at_exit(ctx); // a ctx keeps no caller's stream past the call (kiss_internal.hpp)
     if (report) {
         *report = kiss_hip_pair_report{};
         report->P = Q / 2;

@@ -613,6 +613,7 @@ int kiss_hip_fmi_rescue_dev(kiss_hip_ctx *ctx, const kiss_hip_pair *pairs, const
                             uint64_t R, const kiss_hip_rescue_params *params, kiss_hip_chain *chains, uint64_t *chain_index,
                             uint32_t *origin, uint64_t chain_capacity, kiss_hip_rescue_report *report, void *stream)
 {
+    KissOwnStreamAtExit own_stream_at_exit(ctx); // a ctx keeps no caller's stream past the call (kiss_internal.hpp)
     if (report) {
         *report = kiss_hip_rescue_report{};
         report->P = Q / 2;
@@ -669,6 +670,7 @@ int kiss_hip_fmi_aln_merge_dev(kiss_hip_ctx *ctx, const kiss_hip_aln *alns_a, co
                                uint64_t aln_capacity, uint64_t *chain_index, uint32_t *source, uint32_t *cigar, uint64_t *cigar_index,
                                uint64_t cigar_capacity, kiss_hip_merge_report *report, void *stream)
 {
+    KissOwnStreamAtExit own_stream_at_exit(ctx); // a ctx keeps no caller's stream past the call (kiss_internal.hpp)
     if (report) {
         *report = kiss_hip_merge_report{};
         report->V = V;

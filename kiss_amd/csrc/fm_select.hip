@@ -475,6 +475,7 @@ int kiss_hip_fmi_select_dev(kiss_hip_ctx *ctx, const kiss_hip_aln *alns, const u
                             uint64_t Q, int both_strands, const uint64_t *bounds, uint64_t R, const kiss_hip_select_params *params,
                             kiss_hip_hit *hits, uint64_t *hit_index, uint64_t hit_capacity, kiss_hip_select_report *report, void *stream)
 {
+    KissOwnStreamAtExit own_stream_at_exit(ctx); // a ctx keeps no caller's stream past the call (kiss_internal.hpp)
     const uint64_t V = both_strands ? 2 * Q : Q;
     if (report) {
         *report = kiss_hip_select_report{};

@@ -111,7 +111,7 @@ int kiss_hip_ctx_suffix_sort_u8_dev(kiss_hip_ctx *ctx, const uint8_t *d_S, uint6
     kiss_opts_refresh(ctx);
     ctx->hfar = ctx->hmerged = nullptr;
     ctx->h_depth = 0;
-    ctx->stream = stream ? (hipStream_t)stream : ctx->own_stream;
+    KissCallStream call_stream(ctx, stream); // the caller's stream for this call, the ctx's own again on every way out
     KTRY(kiss_workspace_ready(ctx));
     std::memset(&ctx->stats, 0, sizeof ctx->stats);
     ctx->stats.n = n;

@@ -47,10 +47,14 @@ __device__ __forceinline__ void isa_partition_tile(const uint32_t *__restrict__ 
     __syncthreads();
     uint64_t pr[IB_ITEMS];
     uint32_t rk[IB_ITEMS];
-    // the order of the items inside a bin is irrelevant: a thread takes IB_ITEMS consecutive ones (16-byte loads)
+    // the order of the items inside a bin is irrelevant: a thread takes IB_ITEMS consecutive ones (16-byte loads).  SA may be
+    // the caller's array, which owes no more than 4-byte alignment (include/kiss_hip.h): the wide loads are taken only where
+    // the address allows them, as k_pack does (never a 16-byte load at a less aligned address); pairs_in is
+    // the ctx's own scratch
     const uint32_t l0 = threadIdx.x * IB_ITEMS;
-    if (l0 + IB_ITEMS <= tile_count) {
-        const uint64_t g0 = tile_base + l0;
+    const uint64_t g0 = tile_base + l0;
+    const bool wide = !FROM_SA || (reinterpret_cast<uintptr_t>(SA + base + g0) & 15u) == 0;
+    if (l0 + IB_ITEMS <= tile_count && wide) {
         if (FROM_SA) {
 #pragma unroll
             for (int q = 0; q < IB_ITEMS / 4; q++) {

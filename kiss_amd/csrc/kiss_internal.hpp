@@ -192,6 +192,10 @@ struct kiss_hip_ctx {
     uint64_t tied_bytes = 0;
     uint64_t ws_bytes = 0;
     uint64_t lms_bytes = 0;
+    // kiss_hip_stage_reserve: hipFree waits for EVERY stream of the device, a caller's busy one included, so the arrays a
+    // regrowth replaces are put here and freed by the next call on this ctx that takes a stream, or with the ctx
+    std::vector<void *> deferred_free;
+    uint64_t deferred_bytes = 0; // what they hold: still counted by kiss_hip_ctx_workspace_bytes
 
     // text
     uint64_t *pk = nullptr;        // 2-bit packed text, base i at bits [63-2(i%32), 62-2(i%32)] of word i/32
@@ -302,6 +306,30 @@ struct kiss_hip_ctx {
     size_t ev_used = 0;
 };
 
+// The stream of one call: the caller's handle, or the ctx's own stream for NULL, and on EVERY way out of the
+// call the ctx's own stream again.  A ctx does not keep a caller's stream past the call that brought it: the entries that
+// take no stream (kiss_hip_stage_local_lms, kiss_hip_stage_reserve, kiss_hip_ctx_get_stage_outputs, the debug hooks) would
+// otherwise queue their work behind whatever the caller has put on that stream since, or use a handle that no longer exists.
+// KissOwnStreamAtExit is the second half alone, for the FM frames whose fm_enter selects the stream (fm_internal.hpp).
+void kiss_drain_deferred(kiss_hip_ctx *ctx); // api.hip: frees what kiss_hip_stage_reserve replaced (hipFree: waits for the device)
+struct KissOwnStreamAtExit {
+    kiss_hip_ctx *ctx;
+    explicit KissOwnStreamAtExit(kiss_hip_ctx *c) : ctx(c) {}
+    ~KissOwnStreamAtExit()
+    {
+        if (ctx) ctx->stream = ctx->own_stream;
+    }
+    KissOwnStreamAtExit(const KissOwnStreamAtExit &) = delete;
+    KissOwnStreamAtExit &operator=(const KissOwnStreamAtExit &) = delete;
+};
+struct KissCallStream : KissOwnStreamAtExit {
+    KissCallStream(kiss_hip_ctx *c, void *stream) : KissOwnStreamAtExit(c)
+    {
+        ctx->stream = stream ? (hipStream_t)stream : ctx->own_stream;
+        if (!ctx->deferred_free.empty()) kiss_drain_deferred(ctx);
+    }
+};
+
 // RAII-less helper: times one kernel class when profiling is on
 struct KTimer {
     kiss_hip_ctx *ctx;
@@ -315,7 +343,8 @@ static inline uint64_t div_up(uint64_t a, uint64_t b) { return (a + b - 1) / b; 
 
 // ---- stages (host drivers) -------------------------------------------------------
 // (re)allocates every LMS-sized array for at least m_cap suffixes
-int kiss_lms_reserve(kiss_hip_ctx *ctx, uint64_t m_cap, uint64_t t_cap_wanted = 0);
+int kiss_lms_reserve(kiss_hip_ctx *ctx, uint64_t m_cap, uint64_t t_cap_wanted = 0, bool defer_frees = false);
+int kiss_lms_reserve_deferred(kiss_hip_ctx *ctx, uint64_t m_cap); // (kiss_hip_stage_reserve: waits for no stream but the ctx's own)
 // (re)allocates the tied-segment arrays (seg*, slot*, segstart*, bkey*, bpos*, bseg*, bslot, flags) for t_cap items;
 // their contents are lost
 int kiss_tied_reserve(kiss_hip_ctx *ctx, uint64_t t_cap);

@@ -492,7 +492,7 @@ int lcp_dev(kiss_hip_ctx *ctx, const uint8_t *d_S, uint64_t n, const uint32_t *d
     std::unique_lock<std::mutex> lock(kiss_device_mutex(ctx->device), std::defer_lock);
     if (!ctx->opts.no_serialize) lock.lock(); // the lock of the sorts (api.hip: sort_dev)
     KCHECK(hipSetDevice(ctx->device));
-    ctx->stream = stream ? (hipStream_t)stream : ctx->own_stream;
+    KissCallStream call_stream(ctx, stream); // the caller's stream for this call, the ctx's own again on every way out
     KTRY(kiss_workspace_ready(ctx));
     KTRY(kiss_need_ctx_words(ctx));
     ctx->ctx_words_valid = false; // CTX is about to hold Phi / PLCP (and CLS the byte text): no taint words to reuse
@@ -544,7 +544,6 @@ int lcp_one_shot(kiss_hip_ctx *ctx, void *arg)
     const OneShot &a = *static_cast<const OneShot *>(arg);
     const uint64_t sa_bytes = (a.n + 1) * sizeof(uint32_t);
     KCHECK(hipSetDevice(ctx->device));
-    ctx->stream = ctx->own_stream;
     if (!a.SA_in && !a.bytes) {
         // the DNA sort's own host-pointer path: S goes up into ctx->io_S, the exact SA stays in ctx->io_SA as well
         uint32_t *dst = a.SA_out ? a.SA_out : a.LCP;
@@ -561,7 +560,6 @@ int lcp_one_shot(kiss_hip_ctx *ctx, void *arg)
         if (a.SA_in && a.SA_out && a.SA_out != a.SA_in) std::memcpy(a.SA_out, a.SA_in, sa_bytes);
     }
     KTRY(lcp_dev(ctx, ctx->io_S, a.n, ctx->io_SA, ctx->io_SA, nullptr, nullptr, a.bytes));
-    ctx->stream = ctx->own_stream;
     return kiss_xfer_d2h(ctx, a.LCP, ctx->io_SA, sa_bytes);
 }
 

@@ -383,7 +383,6 @@ int multi_sort_dev(kiss_hip_multi *mc, const uint8_t *d_S, uint64_t n, uint32_t 
     if (n == 0) { // kiss1_core.hpp:237-238
         kiss_hip_ctx *ctx = mc->ctx[0];
         KCHECK(hipSetDevice(ctx->device));
-        ctx->stream = ctx->own_stream;
         KTRY(kiss_zero_u32(ctx, d_SA, 1));
         KCHECK(hipStreamSynchronize(ctx->stream));
         return KISS_HIP_OK;
@@ -414,7 +413,6 @@ int multi_sort_dev(kiss_hip_multi *mc, const uint8_t *d_S, uint64_t n, uint32_t 
             kiss_hip_ctx *ctx = mc->ctx[r];
             int rc = KISS_HIP_OK;
             if (hipSetDevice(ctx->device) != hipSuccess) rc = KISS_HIP_E_HIP;
-            ctx->stream = ctx->own_stream;
             if (!rc) rc = kiss_workspace_ready(ctx);
             std::memset(&ctx->stats, 0, sizeof ctx->stats);
             ctx->stats.n = n;

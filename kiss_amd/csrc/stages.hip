@@ -128,7 +128,7 @@ int kiss_hip_stage_classify(kiss_hip_ctx *ctx, const uint8_t *d_S, uint64_t n, u
     // synchronised, so the lock is held for exactly its device work
     std::unique_lock<std::mutex> device_lock;
     if (!ctx->opts.no_serialize) device_lock = std::unique_lock<std::mutex>(kiss_device_mutex(ctx->device));
-    ctx->stream = stream ? (hipStream_t)stream : ctx->own_stream;
+    KissCallStream call_stream(ctx, stream); // the caller's stream for this call, the ctx's own again on every way out
     ctx->hfar = ctx->hmerged = nullptr; // (tie flags of an exact-order sort_dev: never a stage call's, see api.hip)
     ctx->h_depth = 0;
     KTRY(kiss_workspace_ready(ctx));
@@ -185,8 +185,8 @@ int kiss_hip_stage_reserve(kiss_hip_ctx *ctx, uint64_t lms_capacity)
     KCHECK(hipSetDevice(ctx->device));
     KTRY(kiss_workspace_ready(ctx));
     if (lms_capacity <= ctx->m_cap) return KISS_HIP_OK;
-    KCHECK(hipStreamSynchronize(ctx->stream));
-    return kiss_lms_reserve(ctx, lms_capacity + lms_capacity / 64 + 1024);
+    KCHECK(hipStreamSynchronize(ctx->stream)); // (the ctx's own stream: no call leaves a caller's here, kiss_internal.hpp)
+    return kiss_lms_reserve_deferred(ctx, lms_capacity + lms_capacity / 64 + 1024);
 }
 
 int kiss_hip_stage_key_hist(kiss_hip_ctx *ctx, const uint64_t *d_keys, uint64_t count, int bits, uint64_t *d_hist,
@@ -199,7 +199,7 @@ int kiss_hip_stage_key_hist(kiss_hip_ctx *ctx, const uint64_t *d_keys, uint64_t 
     // synchronised, so the lock is held for exactly its device work
     std::unique_lock<std::mutex> device_lock;
     if (!ctx->opts.no_serialize) device_lock = std::unique_lock<std::mutex>(kiss_device_mutex(ctx->device));
-    ctx->stream = stream ? (hipStream_t)stream : ctx->own_stream;
+    KissCallStream call_stream(ctx, stream); // the caller's stream for this call, the ctx's own again on every way out
     ctx->hfar = ctx->hmerged = nullptr; // (tie flags of an exact-order sort_dev: never a stage call's, see api.hip)
     ctx->h_depth = 0;
     KTRY(kiss_workspace_ready(ctx));
@@ -221,7 +221,7 @@ int kiss_hip_stage_partition(kiss_hip_ctx *ctx, const uint64_t *d_keys, const ui
     // synchronised, so the lock is held for exactly its device work
     std::unique_lock<std::mutex> device_lock;
     if (!ctx->opts.no_serialize) device_lock = std::unique_lock<std::mutex>(kiss_device_mutex(ctx->device));
-    ctx->stream = stream ? (hipStream_t)stream : ctx->own_stream;
+    KissCallStream call_stream(ctx, stream); // the caller's stream for this call, the ctx's own again on every way out
     ctx->hfar = ctx->hmerged = nullptr; // (tie flags of an exact-order sort_dev: never a stage call's, see api.hip)
     ctx->h_depth = 0;
     KTRY(kiss_workspace_ready(ctx));
@@ -247,7 +247,7 @@ int kiss_hip_stage_sort(kiss_hip_ctx *ctx, const uint64_t *d_keys, const uint32_
     // synchronised, so the lock is held for exactly its device work
     std::unique_lock<std::mutex> device_lock;
     if (!ctx->opts.no_serialize) device_lock = std::unique_lock<std::mutex>(kiss_device_mutex(ctx->device));
-    ctx->stream = stream ? (hipStream_t)stream : ctx->own_stream;
+    KissCallStream call_stream(ctx, stream); // the caller's stream for this call, the ctx's own again on every way out
     ctx->hfar = ctx->hmerged = nullptr; // (tie flags of an exact-order sort_dev: never a stage call's, see api.hip)
     ctx->h_depth = 0;
     KTRY(kiss_workspace_ready(ctx));
@@ -292,7 +292,7 @@ static int stage_induce_impl(kiss_hip_ctx *ctx, uint64_t n, uint32_t k, uint32_t
     // synchronised, so the lock is held for exactly its device work
     std::unique_lock<std::mutex> device_lock;
     if (!ctx->opts.no_serialize) device_lock = std::unique_lock<std::mutex>(kiss_device_mutex(ctx->device));
-    ctx->stream = stream ? (hipStream_t)stream : ctx->own_stream;
+    KissCallStream call_stream(ctx, stream); // the caller's stream for this call, the ctx's own again on every way out
     ctx->hfar = ctx->hmerged = nullptr; // (tie flags of an exact-order sort_dev: never a stage call's, see api.hip)
     ctx->h_depth = 0;
     KTRY(kiss_workspace_ready(ctx));
@@ -365,7 +365,7 @@ int kiss_hip_stage_refine_exact(kiss_hip_ctx *ctx, uint64_t n, uint32_t h0, uint
     // synchronised, so the lock is held for exactly its device work
     std::unique_lock<std::mutex> device_lock;
     if (!ctx->opts.no_serialize) device_lock = std::unique_lock<std::mutex>(kiss_device_mutex(ctx->device));
-    ctx->stream = stream ? (hipStream_t)stream : ctx->own_stream;
+    KissCallStream call_stream(ctx, stream); // the caller's stream for this call, the ctx's own again on every way out
     ctx->hfar = ctx->hmerged = nullptr; // (tie flags of an exact-order sort_dev: never a stage call's, see api.hip)
     ctx->h_depth = 0;
     KTRY(kiss_workspace_ready(ctx));

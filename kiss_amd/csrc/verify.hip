@@ -160,7 +160,8 @@ extern "C" int kiss_hip_ctx_verify_sa_dev(kiss_hip_ctx *ctx, const uint8_t *d_S,
 {
     if (!ctx || !out || !d_SA || (n && !d_S) || n > KISS_HIP_MAX_N) return KISS_HIP_E_INVALID;
     KCHECK(hipSetDevice(ctx->device));
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->own_stream;
+    KissCallStream call_stream(ctx, stream); // the caller's stream for this call, the ctx's own again on every way out
+    const hipStream_t st = ctx->stream;
     std::memset(out, 0, sizeof *out);
     out->n = n;
     out->k = k;
@@ -187,7 +188,6 @@ extern "C" int kiss_hip_ctx_verify_sa_dev(kiss_hip_ctx *ctx, const uint8_t *d_S,
             break;
         }
         (void)hipEventRecord(e0, st);
-        ctx->stream = st;
         if ((rc = kiss_zero_u32(ctx, bitmap, c_off_words + VC * 2))) break; // (a kernel, not hipMemsetAsync: see kiss_fill_u32)
         const unsigned long long big = ~0ull;
         if (hipMemcpyAsync(&c[3], &big, 8, hipMemcpyHostToDevice, st) != hipSuccess) {
