@@ -1,0 +1,186 @@
+// cli_reads.hpp -- `kiss fmindex_query --seeds READS ...`: the read-mapping pipeline.  One State (cli_format.hpp), filled stage by
+// stage; a stage is a function of (Args, State) around its library call; map_reads() at the end runs them and leaves after the
+// last one the command line asks for, with the printer of cli_format.hpp for what that made.
+#pragma once
+#include "cli_common.hpp"
+#include "cli_format.hpp"
+
+namespace kiss_cli {
+
+// The size-then-fill protocol of the chain, align and rescue calls: call(capacity) is made with capacity 0; if it answers
+// KISS_HIP_E_INVALID and its report now says how many entries it needs, `out` grows to that and the call is made once more.
+template <class T, class Call> int sized_call(std::vector<T> &out, const uint64_t &needed, Call call)
+{
+    int rc = call(uint64_t(0));
+    if (rc == KISS_HIP_E_INVALID && needed) {
+        out.resize(needed);
+        rc = call(needed);
+    }
+    return rc;
+}
+
+// READS, with --mates READS2 interleaved with it
+inline void load_reads(const Args &a, State &s)
+{
+    s.rd = read_file(a.seeds, a.sam);
+    if (!a.mates.empty()) { // reads 2 p and 2 p + 1 of the batch are read p of either file
+        const ReadFile first = std::move(s.rd), second = read_file(a.mates, a.sam);
+        const uint64_t P = first.ridx.size() - 1;
+        if (second.ridx.size() - 1 != P)
+            throw std::runtime_error("fmindex_query --mates: " + a.seeds + " has " + std::to_string(P) + " reads, " + a.mates + " has " +
+                                     std::to_string(second.ridx.size() - 1) + " reads: a pair has one of each");
+        s.rd = ReadFile();
+        for (uint64_t p = 0; p < P; p++)
+            for (const ReadFile *f : {&first, &second}) {
+                s.rd.reads.insert(s.rd.reads.end(), f->reads.begin() + (std::ptrdiff_t)f->ridx[p], f->reads.begin() + (std::ptrdiff_t)f->ridx[p + 1]);
+                s.rd.ridx.push_back(s.rd.reads.size());
+                s.rd.names.push_back(f->names[p]);
+            }
+    }
+    s.Q = s.rd.ridx.size() - 1;
+    s.V = a.both_strands ? 2 * s.Q : s.Q;
+}
+
+// (its own protocol: the first call passes no position arrays, returns OK and sizes them)
+inline void find_seeds(const Args &a, State &s)
+{
+    const uint64_t bases = (a.both_strands ? 2 : 1) * (uint64_t)s.rd.reads.size();
+    s.seeds.resize(bases + 1);
+    s.sidx.assign(s.V + 1, 0);
+    const auto call = [&](uint32_t *pos, uint64_t *pidx, uint64_t capacity) {
+        return kiss_hip_fmi_seeds_host(&s.index, s.rd.reads.data(), s.rd.ridx.data(), s.Q, a.min_seed_len, a.max_seed_len, a.max_occ, a.both_strands,
+                                       nullptr, s.seeds.data(), s.sidx.data(), bases, pos, pidx, capacity, &s.seed_rep, a.device);
+    };
+    check(call(nullptr, nullptr, 0), "kiss_hip_fmi_seeds_host");
+    s.pos.resize(s.seed_rep.positions + 1);
+    s.pidx.resize(s.seed_rep.seeds + 1);
+    const int rc = call(s.pos.data(), s.pidx.data(), s.seed_rep.positions);
+    if (rc == KISS_HIP_E_INVALID && s.seed_rep.walk_failures)
+        throw std::runtime_error("fmindex_query --seeds: " + std::to_string(s.seed_rep.walk_failures) +
+                                 " rows of the index reached no sampled row: the positions need an index built with "
+                                 "fmindex_build --exact");
+    check(rc, "kiss_hip_fmi_seeds_host");
+}
+
+// --chain: the positions of the seeds of a virtual read chained into candidate loci
+inline void chain_seeds(const Args &a, State &s)
+{
+    s.ch.chains.resize(1);
+    s.ch.cidx.assign(s.V + 1, 0);
+    check(sized_call(s.ch.chains, s.chain_rep.chains, [&](uint64_t capacity) {
+              return kiss_hip_fmi_chain_host(s.seeds.data(), s.sidx.data(), s.V, s.pos.data(), s.pidx.data(), &a.chain_params, s.ch.chains.data(),
+                                             s.ch.cidx.data(), capacity, nullptr, nullptr, 0, &s.chain_rep, a.device);
+          }),
+          "kiss_hip_fmi_chain_host");
+}
+
+// the C chains `ch` of the reads aligned to the text into `al`; option: the one named when the call refuses the batch
+inline void align(const Args &a, const State &s, int both_strands, const Chains &ch, uint64_t C, Alignments &al, const char *option)
+{
+    al.alns.resize(C + 1);
+    al.cigar.resize(1);
+    al.oidx.assign(C + 1, 0);
+    const int rc = sized_call(al.cigar, al.rep.cigar_ops, [&](uint64_t capacity) {
+        return kiss_hip_fmi_align_host(s.S.data(), s.S.size(), s.rd.reads.data(), s.rd.ridx.data(), s.Q, both_strands, ch.chains.data(), ch.cidx.data(),
+                                       &a.align_params, al.alns.data(), C, al.cigar.data(), al.oidx.data(), capacity, &al.rep, a.device);
+    });
+    if (rc == KISS_HIP_E_UNSUPPORTED && al.rep.cells)
+        throw std::runtime_error(std::string("fmindex_query ") + option + ": " + std::to_string(al.rep.cells) +
+                                 " DP cells are more than one call holds: split the reads");
+    check(rc, "kiss_hip_fmi_align_host");
+}
+
+// --align: the text loaded as the index was built from it, every chain aligned to it
+inline void align_chains(const Args &a, State &s)
+{
+    s.S = DeviceText(a.fasta, a.device).to_host();
+    s.S.reserve(1); // (a pointer that is not NULL)
+    align(a, s, a.both_strands, s.ch, s.ch.cidx[s.V], s.al, "--align");
+}
+
+// the mappings of every read picked from s.al (the first pass's alignments, or the merged ones)
+inline void select(const Args &a, State &s)
+{
+    const uint64_t R = s.ref.names.size(), C = s.al.alns.size() - 1;
+    s.hits.assign(C + 1, kiss_hip_hit{}); // (a read keeps no more hits than it has alignments: one call)
+    s.hidx.assign(s.Q + 1, 0);
+    s.select_rep = kiss_hip_select_report{};
+    check(kiss_hip_fmi_select_host(s.al.alns.data(), s.ch.cidx.data(), s.rd.ridx.data(), s.Q, a.both_strands, R ? s.ref.bounds.data() : nullptr, R,
+                                   &a.select_params, s.hits.data(), s.hidx.data(), C, &s.select_rep, a.device),
+          "kiss_hip_fmi_select_host");
+}
+
+// --sam: the records of the reference, which must add up to the text, and the mappings of every read
+inline void select_hits(const Args &a, State &s)
+{
+    s.ref = scan_records(a.fasta);
+    if (s.ref.bounds.back() != s.S.size())
+        throw std::runtime_error("fmindex_query --sam: the records of " + a.fasta + " have " + std::to_string(s.ref.bounds.back()) +
+                                 " bases, the parsed text has " + std::to_string(s.S.size()));
+    select(a, s);
+}
+
+// The first pass paired, the pairs that are not proper planned into windows, the windows aligned, their alignments merged
+// behind the reads' own (they take the first pass's place in the State), the mappings picked again
+inline void rescue_mates(const Args &a, State &s)
+{
+    const uint64_t Q = s.Q, V = 2 * Q, R = s.ref.names.size(), CA = s.select_rep.alignments, n = s.S.size();
+    const uint64_t *bounds = R ? s.ref.bounds.data() : nullptr;
+    s.first_alns = CA;
+    s.first_pairs.resize(Q / 2 + 1);
+    check(kiss_hip_fmi_pair_host(s.hits.data(), s.hidx.data(), Q, s.al.alns.data(), CA, &a.pair_params, s.first_pairs.data(), nullptr, a.device),
+          "kiss_hip_fmi_pair_host");
+    Chains win;
+    win.chains.resize(1);
+    win.cidx.assign(V + 1, 0);
+    check(sized_call(win.chains, s.plan.chains, [&](uint64_t capacity) {
+              return kiss_hip_fmi_rescue_host(s.first_pairs.data(), s.hits.data(), s.hidx.data(), Q, s.al.alns.data(), CA, s.rd.ridx.data(), n, bounds, R,
+                                              &a.rescue_params, win.chains.data(), win.cidx.data(), nullptr, capacity, &s.plan, a.device);
+          }),
+          "kiss_hip_fmi_rescue_host");
+    const uint64_t CB = s.plan.chains;
+    Alignments wal, mal;
+    align(a, s, 1, win, CB, wal, "--rescue");
+    const uint64_t C = CA + CB, ops = s.al.oidx[CA] + wal.oidx[CB]; // merged: capacities are known
+    mal.alns.resize(C + 1);
+    mal.oidx.assign(C + 1, 0);
+    mal.cigar.resize(ops + 1);
+    std::vector<uint64_t> mcidx(V + 1, 0);
+    s.source.resize(C + 1);
+    check(kiss_hip_fmi_aln_merge_host(s.al.alns.data(), s.ch.cidx.data(), s.al.cigar.data(), s.al.oidx.data(), wal.alns.data(), win.cidx.data(),
+                                      wal.cigar.data(), wal.oidx.data(), V, mal.alns.data(), C, mcidx.data(), s.source.data(), mal.cigar.data(),
+                                      mal.oidx.data(), ops, nullptr, a.device),
+          "kiss_hip_fmi_aln_merge_host");
+    s.al = std::move(mal);
+    s.ch.cidx = std::move(mcidx);
+    select(a, s);
+}
+
+// --mates: the mappings of reads 2 p and 2 p + 1 paired
+inline void pair_mates(const Args &a, State &s)
+{
+    s.pairs.resize(s.Q / 2 + 1);
+    check(kiss_hip_fmi_pair_host(s.hits.data(), s.hidx.data(), s.Q, s.al.alns.data(), s.select_rep.alignments, &a.pair_params, s.pairs.data(),
+                                 &s.pair_rep, a.device),
+          "kiss_hip_fmi_pair_host");
+}
+
+// fmindex_query --seeds: `index` is the view of the .fmi of a.fasta
+inline int map_reads(const Args &a, const kiss_hip_fmi_view_ex &index)
+{
+    State s;
+    s.index = index;
+    load_reads(a, s);
+    find_seeds(a, s);
+    if (!a.chain) return print_seeds(s, a.both_strands);
+    chain_seeds(a, s);
+    if (!a.align) return print_chains(s, a.both_strands);
+    align_chains(a, s);
+    if (!a.sam) return print_alignments(s, a.both_strands);
+    select_hits(a, s);
+    if (a.rescue) rescue_mates(a, s);
+    if (!a.mates.empty()) pair_mates(a, s);
+    return print_sam(s, !a.mates.empty(), a.rescue, VERSION);
+}
+
+} // namespace kiss_cli

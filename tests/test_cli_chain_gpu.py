@@ -1,9 +1,8 @@
 """`kiss fmindex_query --seeds READS --chain` on a small FASTA built with `fmindex_build --exact`, against the chain model run
 on the seed model's seeds; the usage errors; and `--seeds` alone, byte for byte the lines of
-tests/golden/cli_seeds_before_chain_*.txt.  Those files were meant to be recorded from the binary before --chain on these
-inputs; no device could be reached when they were made, so they hold the lines that tests/test_cli_seeds_gpu.expected --
-the statement that binary is tested against -- gives for these inputs.  Replace them by a recording of that binary's
-output when one can be made (tests.test_cli_chain_gpu.make_inputs gives the files)."""
+tests/golden/cli_seeds_before_chain_*.txt.  Those files were written from tests/test_cli_seeds_gpu.expected, the statement
+the binary before --chain is tested against; a recording of the binary of commit a0b0b58 on these inputs
+(tests.test_cli_chain_gpu.make_inputs gives the files) is byte for byte the same, so they stand as they are."""
 import os
 
 import numpy as np
