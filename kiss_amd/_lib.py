@@ -268,6 +268,18 @@ class MergeReport(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved_"}
 
 
+class ReadsReport(ctypes.Structure):
+    """kiss_hip_reads_report (include/kiss_hip_reads.h)"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("lines", "reads", "bases", "no_base", "empty_reads", "first_empty", "bad_records",
+                                               "first_bad")] + [
+        ("format", ctypes.c_uint32), ("has_qual", ctypes.c_uint32), ("first_bad_kind", ctypes.c_uint32), ("reserved_", ctypes.c_uint32),
+        ("ms_total", ctypes.c_float), ("ms_lines", ctypes.c_float), ("ms_reads", ctypes.c_float), ("ms_copy", ctypes.c_float),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved_"}
+
+
 class Fmi8View(ctypes.Structure):
     """kiss_hip_fmi8_view"""
     _fields_ = [
@@ -439,6 +451,12 @@ def load(hooks=None):
     lib.kiss_hip_fmi_aln_merge_dev.argtypes = [vp] * 9 + [u64, vp, u64, vp, vp, vp, vp, u64, ctypes.POINTER(MergeReport), vp]
     lib.kiss_hip_fmi_aln_merge_host.argtypes = [vp] * 8 + [u64, vp, u64, vp, vp, vp, vp, u64, ctypes.POINTER(MergeReport), ctypes.c_int]
     lib.kiss_hip_fmi_aln_merge_dev.restype = lib.kiss_hip_fmi_aln_merge_host.restype = ctypes.c_int
+    lib.kiss_hip_reads_parse_dev.argtypes = [vp, vp, u64, ctypes.c_int, vp, vp, u64, vp, vp, vp, u64, ctypes.POINTER(ReadsReport), vp]
+    lib.kiss_hip_reads_parse_host.argtypes = [vp, u64, ctypes.c_int, vp, vp, u64, vp, vp, vp, u64, ctypes.POINTER(ReadsReport), ctypes.c_int]
+    lib.kiss_hip_reads_interleave_dev.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, u64, vp, vp, vp, u64, ctypes.POINTER(u64), vp]
+    lib.kiss_hip_reads_interleave_host.argtypes = [vp, vp, vp, u64, vp, vp, vp, u64, vp, vp, vp, u64, ctypes.POINTER(u64), ctypes.c_int]
+    for name in READS_EXPORTED_SYMBOLS:
+        getattr(lib, name).restype = ctypes.c_int
     lib.kiss_hip_fmi8_sizes_for.argtypes = [u64, u32, u32, ctypes.POINTER(Fmi8Sizes)]
     lib.kiss_hip_fmi8_build_dev.argtypes = [vp, vp, u64, vp, u32, u32] + [vp] * 8 + [ctypes.POINTER(u32), ctypes.POINTER(u32), vp]
     lib.kiss_hip_fmi8_build_host.argtypes = [vp, u64, vp, u32, u32] + [vp] * 8 + [ctypes.POINTER(u32), ctypes.POINTER(u32),
@@ -518,3 +536,10 @@ EXPORTED_SYMBOLS = [
     "kiss_hip_fmi_select_dev", "kiss_hip_fmi_select_host", "kiss_hip_fmi_pair_dev", "kiss_hip_fmi_pair_host",
     "kiss_hip_fmi_rescue_dev", "kiss_hip_fmi_rescue_host", "kiss_hip_fmi_aln_merge_dev", "kiss_hip_fmi_aln_merge_host",
 ]
+
+# every symbol include/kiss_hip_reads.h declares (tests/test_reads_model.py)
+READS_EXPORTED_SYMBOLS = [
+    "kiss_hip_reads_parse_dev", "kiss_hip_reads_parse_host", "kiss_hip_reads_interleave_dev", "kiss_hip_reads_interleave_host",
+]
+READS_AUTO, READS_LINES, READS_FASTQ = 0, 1, 2
+READS_NONE = 0xFFFFFFFFFFFFFFFF

@@ -100,6 +100,24 @@ inline void usage()
               << "  --rescue-width NUM (=960)      diagonals of a window aligned in one piece (1..1024)\n";
 }
 
+// The help of the read files (`kiss --help-reads`).  Kept apart from usage(): what `kiss -h` prints is recorded byte for byte
+// (tests/golden/cli_parse_recording.json) and stays as it is.
+inline void usage_reads()
+{
+    std::cerr << "The read files of ./kiss fmindex_query --seeds READS [--mates READS2]:\n"
+              << "  --reads-format FORMAT (=auto)  auto: FASTQ if the first byte of the file is '@', otherwise lines;\n"
+              << "                                 lines: one read per line, ACGT, any other letter is no base; empty lines and\n"
+              << "                                 lines that start with '>' are no reads, the word behind '>' on the line\n"
+              << "                                 directly in front of a read is its name (else its number);\n"
+              << "                                 fastq: records of four lines: @name, the bases, +, the qualities (as many as\n"
+              << "                                 bases); anything else is refused with the number of the first bad record\n"
+              << "                                 (no multi-line FASTQ, no gzip).  With --sam the QUAL column of a FASTQ read is\n"
+              << "                                 its quality string, reversed where SEQ is; of a read from lines it is *.\n"
+              << "                                 With --mates both files have one format, and a FASTQ name that ends in /1 or\n"
+              << "                                 /2 loses those two bytes.  A FASTQ read without bases stops the command.\n"
+              << "                                 The files are parsed on the device (line ends may be \\n or \\r\\n).\n";
+}
+
 inline void check(int rc, const char *where)
 {
     if (rc != KISS_HIP_OK) throw std::runtime_error(std::string(where) + ": " + kiss_hip_strerror(rc));
@@ -167,6 +185,7 @@ struct Args {
     std::vector<std::string> seen; // the long names of the options given (what -g refuses is named)
     int mismatches = -1; // fmindex_query --mismatches (-1: the exact query of the reference)
     std::string seeds;   // fmindex_query --seeds READS
+    std::string reads_format = "auto"; // --reads-format auto | lines | fastq
     uint32_t min_seed_len = 19, max_seed_len = 0, max_occ = 500;
     bool both_strands = false;
     bool chain = false; // fmindex_query --seeds READS --chain
@@ -217,6 +236,7 @@ inline const Opt OPTIONS[] = {
     {"--max-seed-len", nullptr, KISS_AT(max_seed_len), true, {"--seeds"}},
     {"--max-occ", nullptr, KISS_AT(max_occ), true, {"--seeds"}},
     {"--both-strands", nullptr, KISS_AT(both_strands), true, {"--seeds"}},
+    {"--reads-format", nullptr, KISS_AT(reads_format), true, {"--seeds"}},
     {"--max-gap", nullptr, KISS_AT(chain_params.max_gap), true, {"--chain"}},
     {"--band", nullptr, KISS_AT(chain_params.band), true, {"--chain"}},
     {"--gap-cost", nullptr, KISS_AT(chain_params.gap_cost), true, {"--chain"}},
@@ -256,6 +276,7 @@ inline Args parse(int argc, char **argv)
         const std::string s = argv[i];
         if (s == "-h" || s == "--help") { usage(); std::exit(1); }
         if (s == "-v" || s == "--version") { std::cerr << VERSION << std::endl; std::exit(1); }
+        if (s == "--help-reads") { usage_reads(); std::exit(1); }
         const Opt *o = std::find_if(std::begin(OPTIONS), std::end(OPTIONS), [&](const Opt &x) { return s == x.name || (x.alias && s == x.alias); });
         if (o == std::end(OPTIONS)) {
             if (!s.empty() && s[0] == '-' && s.size() > 1) throw std::runtime_error("unrecognised option '" + s + "'");
@@ -321,6 +342,8 @@ inline Args parse(int argc, char **argv)
         if (!a.query.empty() || !a.batch.empty() || a.mismatches >= 0)
             throw std::runtime_error("--seeds cannot be combined with -q, -b or --mismatches");
         if (a.min_seed_len < 1) throw std::runtime_error("--min-seed-len must be at least 1");
+        if (a.reads_format != "auto" && a.reads_format != "lines" && a.reads_format != "fastq")
+            throw std::runtime_error("--reads-format is one of auto, lines, fastq (kiss --help-reads)");
     }
     if (a.devices.empty())
         for (int g = 0; g < a.gpus; g++) a.devices.push_back(a.device + g);

@@ -68,7 +68,13 @@ inline RefRecords scan_records(const std::string &path) // (streamed: a file may
 // One file of reads, one per line ('\r' before the '\n' dropped; empty lines and lines that start with '>' are no reads): the
 // codes of the reads one after the other (ACGTacgt -> 0..3, every other letter 4, no base -- in the text it is 0), where they
 // start, and with_names their names: the word after '>' on the line directly in front of a read, else its number
-struct ReadFile { std::vector<uint8_t> reads; std::vector<uint64_t> ridx{0}; std::vector<std::string> names; };
+struct ReadFile {
+    std::vector<uint8_t> reads;
+    std::vector<uint64_t> ridx{0};
+    std::vector<std::string> names;
+    bool has_qual = false;     // the reads came from FASTQ (cli_reads.hpp: load_reads; read_file below gives none):
+    std::vector<uint8_t> qual; // the quality byte of every entry of reads
+};
 inline ReadFile read_file(const std::string &path, bool with_names)
 {
     std::ifstream in(path);
@@ -120,6 +126,33 @@ inline std::string read_letters(const std::vector<uint8_t> &reads, const std::ve
         if (c <= 3) s[j] = "ACGT"[reverse ? 3 - c : c];
     }
     return s;
+}
+
+// QUAL of read q: its quality string as the file has it, reversed (not complemented) where SEQ is; * for a file without qualities
+inline std::string read_qual(const ReadFile &rd, uint64_t q, bool reverse)
+{
+    if (!rd.has_qual) return "*";
+    const uint64_t L = rd.ridx[q + 1] - rd.ridx[q];
+    std::string s(L, '!');
+    for (uint64_t j = 0; j < L; j++) s[j] = (char)rd.qual[rd.ridx[q] + (reverse ? L - 1 - j : j)];
+    return s;
+}
+
+// the names of Q reads from their spans in the bytes of the file; the number of the read where the span is empty (as read_file)
+inline std::vector<std::string> names_from_spans(const std::vector<uint8_t> &raw, const std::vector<uint64_t> &off, const std::vector<uint32_t> &len,
+                                                 uint64_t Q)
+{
+    std::vector<std::string> names;
+    for (uint64_t q = 0; q < Q; q++)
+        names.push_back(len[q] ? std::string((const char *)raw.data() + off[q], len[q]) : std::to_string(q));
+    return names;
+}
+
+// FASTQ mates: a name that ends in /1 or /2 loses those two bytes, so that both mates of a pair carry one QNAME
+inline void strip_mate_suffix(std::string &name)
+{
+    const size_t n = name.size();
+    if (n >= 2 && name[n - 2] == '/' && (name[n - 1] == '1' || name[n - 1] == '2')) name.resize(n - 2);
 }
 
 // What the stages make, in their order.  Alignment c: al.alns[c] and the ops al.oidx[c] .. al.oidx[c + 1]; the hits of read q:
@@ -222,14 +255,15 @@ struct MateFields {
 };
 
 // The one SAM line of hit t of read q, or with t == nullptr of a read that did not map (FLAG 4; a mate lies where rnext / pnext
-// say its partner does).  POS is 1-based in the record; SEQ is reversed where the hit is; the tags are NM, AS, XS (heads
-// only), then YS, YT, YR.  Without records (R == 0) RNAME is *.
+// say its partner does).  POS is 1-based in the record; SEQ is reversed where the hit is, and so is QUAL (the qualities of a FASTQ
+// read; * otherwise); the tags are NM, AS, XS (heads only), then YS, YT, YR.  Without records (R == 0) RNAME is *.
 inline void sam_line(std::string &out, const State &m, uint64_t q, const kiss_hip_hit *t, const MateFields &f)
 {
     const uint64_t R = m.ref.names.size(), L = m.rd.ridx[q + 1] - m.rd.ridx[q];
     if (!t) {
         out += m.rd.names[q] + '\t' + std::to_string(f.flag | 4u) + '\t' + (f.rnext ? *f.rnext : "*") + '\t' + std::to_string(f.pnext) + "\t0\t*\t" +
-               (f.rnext ? "=" : "*") + '\t' + std::to_string(f.pnext) + "\t0\t" + read_letters(m.rd.reads, m.rd.ridx, q, false) + "\t*\n";
+               (f.rnext ? "=" : "*") + '\t' + std::to_string(f.pnext) + "\t0\t" + read_letters(m.rd.reads, m.rd.ridx, q, false) + '\t' +
+               read_qual(m.rd, q, false) + '\n';
         return;
     }
     const kiss_hip_aln &k = m.al.alns[t->aln];
@@ -241,7 +275,8 @@ inline void sam_line(std::string &out, const State &m, uint64_t q, const kiss_hi
            std::to_string(f.mapq >= 0 ? (uint32_t)f.mapq : t->mapq) + '\t';
     cigar_with_clips(out, k, m.al.cigar.data() + m.al.oidx[t->aln], m.al.oidx[t->aln + 1] - m.al.oidx[t->aln], L);
     out += '\t' + (!f.rnext ? std::string("*") : name == *f.rnext ? std::string("=") : *f.rnext) + '\t' + std::to_string(f.pnext) + '\t' +
-           std::to_string(f.tlen) + '\t' + read_letters(m.rd.reads, m.rd.ridx, q, reverse) + "\t*\tNM:i:" + std::to_string(k.mismatches + k.ins + k.del) +
+           std::to_string(f.tlen) + '\t' + read_letters(m.rd.reads, m.rd.ridx, q, reverse) + '\t' + read_qual(m.rd, q, reverse) +
+           "\tNM:i:" + std::to_string(k.mismatches + k.ins + k.del) +
            "\tAS:i:" + std::to_string(t->score);
     if (head) out += "\tXS:i:" + std::to_string(t->sub);
     if (f.mate_score >= 0) out += "\tYS:i:" + std::to_string(f.mate_score);

@@ -1,9 +1,12 @@
 // cli_reads.hpp -- `kiss fmindex_query --seeds READS ...`: the read-mapping pipeline.  One State (cli_format.hpp), filled stage by
 // stage; a stage is a function of (Args, State) around its library call; map_reads() at the end runs them and leaves after the
-// last one the command line asks for, with the printer of cli_format.hpp for what that made.
+// last one the command line asks for, with the printer of cli_format.hpp for what that made.  The read files are parsed on the
+// device (kiss_hip_reads.h): one read per line, or FASTQ, whose qualities reach the QUAL column of the SAM.
 #pragma once
 #include "cli_common.hpp"
 #include "cli_format.hpp"
+#include "../../../include/kiss_hip_reads.h"
+#include <iterator>
 
 namespace kiss_cli {
 
@@ -19,21 +22,80 @@ template <class T, class Call> int sized_call(std::vector<T> &out, const uint64_
     return rc;
 }
 
-// READS, with --mates READS2 interleaved with it
+// One file of reads parsed on the device (kiss_hip_reads_parse_host, size then fill): the codes, the index, the qualities of a FASTQ
+// file, and with_names the names from their spans in the file; *format: the one that was parsed.  The host reads the file
+// into memory and looks at no byte of it but the names'.
+inline ReadFile parse_read_file(const Args &a, const std::string &path, bool with_names, int *format)
+{
+    std::ifstream in(path, std::ios::binary);
+    if (!in) throw std::runtime_error("cannot open " + path);
+    std::vector<uint8_t> raw((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+    raw.reserve(1); // (a pointer that is not NULL)
+    const int wanted = a.reads_format == "lines" ? KISS_HIP_READS_LINES : a.reads_format == "fastq" ? KISS_HIP_READS_FASTQ : KISS_HIP_READS_AUTO;
+    ReadFile f;
+    kiss_hip_reads_report rep{};
+    std::vector<uint64_t> off;
+    std::vector<uint32_t> len;
+    const auto call = [&](uint64_t bases, uint64_t reads) {
+        f.reads.resize(bases + 1);
+        f.qual.resize(bases + 1);
+        f.ridx.assign(reads + 1, 0);
+        off.assign(reads + 1, 0);
+        len.assign(reads + 1, 0);
+        return kiss_hip_reads_parse_host(raw.data(), raw.size(), wanted, f.reads.data(), f.qual.data(), bases, f.ridx.data(),
+                                         with_names ? off.data() : nullptr, with_names ? len.data() : nullptr, reads, &rep, a.device);
+    };
+    int rc = call(0, 0);
+    if (rc == KISS_HIP_E_INVALID && !rep.bad_records && (rep.reads || rep.bases)) rc = call(rep.bases, rep.reads);
+    if (rc == KISS_HIP_E_INVALID && rep.bad_records) {
+        static const char *const kinds[] = {"", "its first line does not start with '@'", "its third line does not start with '+'",
+                                            "its sequence and its quality string differ in length", "the file ends inside it"};
+        throw std::runtime_error("fmindex_query --seeds: " + path + " is no FASTQ file: " + std::to_string(rep.bad_records) +
+                                 " bad records, the first is record " + std::to_string(rep.first_bad) + ": " + kinds[rep.first_bad_kind % 5]);
+    }
+    check(rc, "kiss_hip_reads_parse_host");
+    if (rep.empty_reads)
+        throw std::runtime_error("fmindex_query --seeds: read " + std::to_string(rep.first_empty) + " of " + path + " has no bases (" +
+                                 std::to_string(rep.empty_reads) + " such reads)");
+    f.has_qual = rep.has_qual != 0;
+    f.reads.resize(rep.bases);
+    f.qual.resize(f.has_qual ? rep.bases : 0);
+    if (with_names) f.names = names_from_spans(raw, off, len, rep.reads);
+    *format = (int)rep.format;
+    return f;
+}
+
+// READS, with --mates READS2 interleaved with it (kiss_hip_reads_interleave_host)
 inline void load_reads(const Args &a, State &s)
 {
-    s.rd = read_file(a.seeds, a.sam);
+    int format = 0;
+    s.rd = parse_read_file(a, a.seeds, a.sam, &format);
     if (!a.mates.empty()) { // reads 2 p and 2 p + 1 of the batch are read p of either file
-        const ReadFile first = std::move(s.rd), second = read_file(a.mates, a.sam);
+        int format2 = 0;
+        ReadFile first = std::move(s.rd), second = parse_read_file(a, a.mates, a.sam, &format2);
         const uint64_t P = first.ridx.size() - 1;
         if (second.ridx.size() - 1 != P)
             throw std::runtime_error("fmindex_query --mates: " + a.seeds + " has " + std::to_string(P) + " reads, " + a.mates + " has " +
                                      std::to_string(second.ridx.size() - 1) + " reads: a pair has one of each");
+        if (format != format2)
+            throw std::runtime_error("fmindex_query --mates: " + a.seeds + " and " + a.mates + " differ in format (one is FASTQ, one has a read per line): "
+                                     "name it with --reads-format");
         s.rd = ReadFile();
-        for (uint64_t p = 0; p < P; p++)
-            for (const ReadFile *f : {&first, &second}) {
-                s.rd.reads.insert(s.rd.reads.end(), f->reads.begin() + (std::ptrdiff_t)f->ridx[p], f->reads.begin() + (std::ptrdiff_t)f->ridx[p + 1]);
-                s.rd.ridx.push_back(s.rd.reads.size());
+        s.rd.has_qual = first.has_qual;
+        uint64_t bases = first.reads.size() + second.reads.size();
+        s.rd.reads.resize(bases + 1);
+        s.rd.qual.resize(bases + 1);
+        s.rd.ridx.assign(2 * P + 1, 0);
+        first.reads.reserve(1), second.reads.reserve(1), first.qual.reserve(1), second.qual.reserve(1);
+        check(kiss_hip_reads_interleave_host(first.reads.data(), first.ridx.data(), first.has_qual ? first.qual.data() : nullptr, P, second.reads.data(),
+                                             second.ridx.data(), first.has_qual ? second.qual.data() : nullptr, P, s.rd.reads.data(),
+                                             s.rd.ridx.data(), first.has_qual ? s.rd.qual.data() : nullptr, bases, &bases, a.device),
+              "kiss_hip_reads_interleave_host");
+        s.rd.reads.resize(bases);
+        s.rd.qual.resize(first.has_qual ? bases : 0);
+        for (uint64_t p = 0; p < P && a.sam; p++)
+            for (ReadFile *f : {&first, &second}) {
+                if (format == KISS_HIP_READS_FASTQ) strip_mate_suffix(f->names[p]);
                 s.rd.names.push_back(f->names[p]);
             }
     }

@@ -168,6 +168,11 @@ enum FmSlot {
     // the rescue plan and the merge of two alignment sets (fm_rescue.hip)
     FM_SLOT_RESCUE_CTL,
     FM_SLOT_RESCUE_SLAB, // plan: the chain counts of the virtual reads; merge: the per-alignment arrays
+    // kiss_hip_reads_parse_dev / kiss_hip_reads_interleave_dev (reads.hip)
+    FM_SLOT_READS_CTL,
+    FM_SLOT_READS_TILES, // per tile of the file: its newlines, scanned
+    FM_SLOT_READS_LINES, // per line: where it starts; the read it is
+    FM_SLOT_READS_INDEX, // per read: where it starts in the codes; its line
     FM_SLOT_COUNT
 };
 
