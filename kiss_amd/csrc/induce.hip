@@ -34,6 +34,7 @@ constexpr int IN_WAVES = IN_THREADS / 64;
 constexpr int IN_TILE = IN_THREADS * IN_ITEMS;   // 2048
 constexpr int SM_THREADS = 1024;
 constexpr uint64_t SMALL_MAX = 8192;             // rounds up to this size run in the single-workgroup kernel
+// (its self-class loop is reached only with KISS_HIP_COLLAPSE_N below 8192: tests/test_induce_paths_gpu.py, row small_chain)
 
 // word an induced item inherits: the parent's without its nearest base; the taint bit stays where it is
 __device__ __forceinline__ uint32_t child_ctx(uint32_t parent)
