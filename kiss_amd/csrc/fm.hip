@@ -1095,39 +1095,36 @@ static int fmi_build_host(const uint8_t *S, uint64_t n, const uint32_t *SA_or_nu
                           const kiss_hip_fmi_sizes_ex &z, uint8_t *bwt, uint32_t *occ1, uint8_t *occ2, uint32_t *sa, uint64_t *b,
                           uint32_t *b_occ, uint32_t *lookup, uint32_t cnt_out[4], uint32_t *pri_out, int device)
 {
-    kiss_hip_ctx *ctx = nullptr;
-    int rc = kiss_hip_ctx_create(&ctx, device, n);
-    if (rc) return rc;
-    DevBuf dS, dSA, dbwt, docc1, docc2, dsa, db, dbocc, dlookup;
-    do {
-        if ((rc = dS.alloc(ctx, n)) || (rc = dSA.alloc(ctx, (n + 1) * 4)) || (rc = dbwt.alloc(ctx, z.base.bwt_bytes + 8)) ||
-            (rc = docc1.alloc(ctx, z.base.occ1_entries * 4)) || (rc = docc2.alloc(ctx, z.base.occ2_bytes)) ||
-            (rc = dsa.alloc(ctx, z.base.sa_entries * 4)) || (rc = db.alloc(ctx, z.base.b_words * 8 + 8)) ||
-            (rc = dbocc.alloc(ctx, z.base.b_occ_entries * 4)) || (lookup && (rc = dlookup.alloc(ctx, z.lookup_entries * 4))))
-            break;
-        if ((rc = fm_h2d(ctx, dS.p, S, n))) break;
-        // FMIndex::build sorts with k = 32 whatever the caller's flags say (fm_index.hpp:384-386)
-        if ((rc = SA_or_null ? fm_h2d(ctx, dSA.p, SA_or_null, (n + 1) * 4)
-                             : kiss_hip_ctx_suffix_sort_dna_u32_dev(ctx, (const uint8_t *)dS.p, n, 32u, KISS_HIP_ALGO_PARALLEL_SORTING,
-                                                                    (uint32_t *)dSA.p, nullptr)))
-            break;
-        if ((rc = lookup ? kiss_hip_fmi_build_ex_dev(ctx, (const uint8_t *)dS.p, n, (const uint32_t *)dSA.p, sa_intv, lookup_len,
-                                                     (uint8_t *)dbwt.p, (uint32_t *)docc1.p, (uint8_t *)docc2.p, (uint32_t *)dsa.p,
-                                                     (uint64_t *)db.p, (uint32_t *)dbocc.p, (uint32_t *)dlookup.p, cnt_out, pri_out,
-                                                     nullptr)
-                         : kiss_hip_fmi_build_dev(ctx, (const uint8_t *)dS.p, n, (const uint32_t *)dSA.p, sa_intv, (uint8_t *)dbwt.p,
-                                                  (uint32_t *)docc1.p, (uint8_t *)docc2.p, (uint32_t *)dsa.p, (uint64_t *)db.p,
-                                                  (uint32_t *)dbocc.p, cnt_out, pri_out, nullptr)))
-            break;
-        // (sa_intv == 1: no b / b_occ, their sizes are 0)
-        if ((rc = fm_d2h(ctx, bwt, dbwt.p, z.base.bwt_bytes)) || (rc = fm_d2h(ctx, occ1, docc1.p, z.base.occ1_entries * 4)) ||
-            (rc = fm_d2h(ctx, occ2, docc2.p, z.base.occ2_bytes)) || (rc = fm_d2h(ctx, sa, dsa.p, z.base.sa_entries * 4)) ||
-            (lookup && (rc = fm_d2h(ctx, lookup, dlookup.p, z.lookup_entries * 4))) || (rc = fm_d2h(ctx, b, db.p, z.base.b_words * 8)))
-            break;
-        rc = fm_d2h(ctx, b_occ, dbocc.p, z.base.b_occ_entries * 4);
-    } while (0);
-    kiss_hip_ctx_destroy(ctx);
-    return rc;
+    return kiss_one_shot_own(device, n, [&](kiss_hip_ctx *ctx) -> int {
+        const kiss_hip_fmi_sizes &zb = z.base;
+        FmStage st(ctx);
+        const uint8_t *dS = st.up(S, n);
+        const uint32_t *dSA = st.up(SA_or_null, (n + 1) * 4);
+        uint32_t *sorted = st.room<uint32_t>(!SA_or_null, (n + 1) * 4);
+        uint8_t *dbwt = st.room<uint8_t>(true, zb.bwt_bytes, 8);
+        uint32_t *docc1 = st.room<uint32_t>(true, zb.occ1_entries * 4);
+        uint8_t *docc2 = st.room<uint8_t>(true, zb.occ2_bytes);
+        uint32_t *dsa = st.room<uint32_t>(true, zb.sa_entries * 4);
+        uint64_t *db = st.room<uint64_t>(true, zb.b_words * 8, 8);
+        uint32_t *dbocc = st.room<uint32_t>(true, zb.b_occ_entries * 4);
+        uint32_t *dlookup = st.room<uint32_t>(lookup != nullptr, z.lookup_entries * 4);
+        if (st.rc) return st.rc;
+        if (sorted) { // FMIndex::build sorts with k = 32 whatever the caller's flags say (fm_index.hpp:384-386)
+            KTRY(kiss_hip_ctx_suffix_sort_dna_u32_dev(ctx, dS, n, 32u, KISS_HIP_ALGO_PARALLEL_SORTING, sorted, nullptr));
+            dSA = sorted;
+        }
+        KTRY(lookup ? kiss_hip_fmi_build_ex_dev(ctx, dS, n, dSA, sa_intv, lookup_len, dbwt, docc1, docc2, dsa, db, dbocc, dlookup, cnt_out,
+                                                pri_out, nullptr)
+                    : kiss_hip_fmi_build_dev(ctx, dS, n, dSA, sa_intv, dbwt, docc1, docc2, dsa, db, dbocc, cnt_out, pri_out, nullptr));
+        st.down(bwt, dbwt, zb.bwt_bytes);
+        st.down(occ1, docc1, zb.occ1_entries * 4);
+        st.down(occ2, docc2, zb.occ2_bytes);
+        st.down(sa, dsa, zb.sa_entries * 4);
+        if (lookup) st.down(lookup, dlookup, z.lookup_entries * 4);
+        st.down(b, db, zb.b_words * 8); // (sa_intv == 1: no b / b_occ, their sizes are 0)
+        st.down(b_occ, dbocc, zb.b_occ_entries * 4);
+        return st.rc;
+    });
 }
 
 // both host forms of the query (z: the sizes of the index's arrays).  ex == nullptr: the classic entry,
@@ -1137,43 +1134,33 @@ static int fmi_query_host(const kiss_hip_fmi_view &base, const kiss_hip_fmi_view
                           uint64_t *hit_count_total, uint64_t *checksum, uint32_t *offsets, uint64_t *offsets_index,
                           uint64_t offsets_capacity, int device)
 {
-    kiss_hip_ctx *ctx = nullptr;
+    // (not fm_host_max_n: that one clamps, and an index of KISS_HIP_MAX_N + 1 rows is E_INVALID here, from the ctx)
     uint64_t max_n = base.n_sa > 4 * Q ? base.n_sa : 4 * Q;
     if (max_n < (1u << 20)) max_n = 1u << 20;
-    int rc = kiss_hip_ctx_create(&ctx, device, max_n);
-    if (rc) return rc;
-    FmIndexOnDevice idx;
-    DevBuf dlookup, dpat, dbeg, dend, doffs, doff, didx;
-    do {
-        if ((rc = idx.upload(ctx, base, z.base)) || (ex && (rc = dlookup.alloc(ctx, z.lookup_entries * 4))) ||
-            (rc = dpat.alloc(ctx, Q * L)) || (rc = dbeg.alloc(ctx, Q * 4)) || (rc = dend.alloc(ctx, Q * 4)) ||
-            (offs && (rc = doffs.alloc(ctx, Q * 4))) || (ex && (rc = fm_h2d(ctx, dlookup.p, ex->lookup, z.lookup_entries * 4))) ||
-            (rc = fm_h2d(ctx, dpat.p, patterns, Q * L)))
-            break;
+    return kiss_one_shot_own(device, max_n, [&](kiss_hip_ctx *ctx) -> int {
         const bool want = offsets && offsets_index && offsets_capacity;
-        if (want && ((rc = doff.alloc(ctx, offsets_capacity * 4)) || (rc = didx.alloc(ctx, (Q + 1) * 8)))) break;
-        uint32_t *d_offsets = want ? (uint32_t *)doff.p : nullptr;
-        uint64_t *d_index = want ? (uint64_t *)didx.p : nullptr;
+        FmStage st(ctx);
+        kiss_hip_fmi_view_ex v{};
+        if (ex) v = *ex;
+        v.base = fm_upload_index(st, base, z.base);
+        v.lookup = ex ? st.up(ex->lookup, z.lookup_entries * 4) : nullptr;
+        const uint8_t *dpat = st.up(patterns, Q * L);
+        uint32_t *dbeg = st.room<uint32_t>(true, Q * 4), *dend = st.room<uint32_t>(true, Q * 4);
+        uint32_t *doffs = st.room<uint32_t>(offs != nullptr, Q * 4);
+        uint32_t *doff = st.room<uint32_t>(want, offsets_capacity * 4);
+        uint64_t *didx = st.room<uint64_t>(want, (Q + 1) * 8);
         const uint64_t cap = want ? offsets_capacity : 0;
-        if (ex) {
-            kiss_hip_fmi_view_ex v = *ex;
-            v.base = idx.view;
-            v.lookup = (const uint32_t *)dlookup.p;
-            rc = kiss_hip_fmi_query_ex_dev(ctx, &v, (const uint8_t *)dpat.p, L, Q, stop_cnt, (uint32_t *)dbeg.p, (uint32_t *)dend.p,
-                                           offs ? (uint32_t *)doffs.p : nullptr, hit_count_total, checksum, d_offsets, d_index, cap,
-                                           nullptr);
-        } else {
-            rc = kiss_hip_fmi_query_batch_dev(ctx, &idx.view, (const uint8_t *)dpat.p, L, Q, (uint32_t *)dbeg.p, (uint32_t *)dend.p,
-                                              hit_count_total, checksum, d_offsets, d_index, cap, nullptr);
-        }
-        if (!rc) rc = fm_d2h(ctx, beg, dbeg.p, Q * 4);
-        if (!rc) rc = fm_d2h(ctx, end, dend.p, Q * 4);
-        if (!rc && offs) rc = fm_d2h(ctx, offs, doffs.p, Q * 4);
-        if (!rc && want) rc = fm_d2h(ctx, offsets_index, didx.p, (Q + 1) * 8);
-        if (!rc && want) rc = fm_d2h(ctx, offsets, doff.p, offsets_capacity * 4);
-    } while (0);
-    kiss_hip_ctx_destroy(ctx);
-    return rc;
+        if (st.rc) return st.rc;
+        KTRY(ex ? kiss_hip_fmi_query_ex_dev(ctx, &v, dpat, L, Q, stop_cnt, dbeg, dend, doffs, hit_count_total, checksum, doff, didx, cap,
+                                            nullptr)
+                : kiss_hip_fmi_query_batch_dev(ctx, &v.base, dpat, L, Q, dbeg, dend, hit_count_total, checksum, doff, didx, cap, nullptr));
+        st.down(beg, dbeg, Q * 4);
+        st.down(end, dend, Q * 4);
+        if (offs) st.down(offs, doffs, Q * 4);
+        if (want) st.down(offsets_index, didx, (Q + 1) * 8);
+        if (want) st.down(offsets, doff, offsets_capacity * 4);
+        return st.rc;
+    });
 }
 
 int kiss_hip_fmi_build_host(const uint8_t *S, uint64_t n, const uint32_t *SA_or_null, uint8_t *bwt, uint32_t *occ1,

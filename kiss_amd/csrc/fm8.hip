@@ -499,6 +499,25 @@ int f8_view_check(const kiss_hip_fmi8_view *v, bool want)
     return KISS_HIP_OK;
 }
 
+// a host view (f8_view_check passed, z: the sizes of its arrays) on the device.  Another kind of view than fm_upload_index
+// uploads: C, map, 16-bit occ2.  sigma == 0 has no occ1 / occ2 entries, sa_intv == 1 no b / b_occ: allocated all the same,
+// the last two null in the view.
+kiss_hip_fmi8_view f8_upload_view(FmStage &st, const kiss_hip_fmi8_view &h, const kiss_hip_fmi8_sizes &z)
+{
+    const bool bits = h.sa_intv != 1;
+    kiss_hip_fmi8_view v = h;
+    v.C = st.up(h.C, 257 * 4);
+    v.map = st.up(h.map, 256);
+    v.bwt = st.up(h.bwt, z.bwt_bytes);
+    v.occ1 = h.occ1 ? st.up(h.occ1, z.occ1_entries * 4) : st.room<uint32_t>(true, 0);
+    v.occ2 = h.occ2 ? st.up(h.occ2, z.occ2_entries * 2) : st.room<uint16_t>(true, 0);
+    v.sa = st.up(h.sa, z.sa_entries * 4);
+    v.b = bits ? st.up(h.b, z.b_words * 8, 8) : nullptr;
+    v.b_occ = bits ? st.up(h.b_occ, z.b_occ_entries * 4) : nullptr;
+    if (!bits) (void)(st.room<uint64_t>(true, z.b_words * 8, 8), st.room<uint32_t>(true, z.b_occ_entries * 4));
+    return v;
+}
+
 } // namespace
 
 extern "C" {
@@ -573,45 +592,41 @@ int kiss_hip_fmi8_build_host(const uint8_t *S, uint64_t n, const uint32_t *SA_or
     KTRY(kiss_hip_fmi8_sizes_for(n, sa_intv, sigma_capacity > 256 ? 256 : sigma_capacity, &z));
     if ((n && !S) || !sigma_out) return KISS_HIP_E_INVALID;
     if (bwt && (!C || !map || !sa || !pri_out || (n && (!occ1 || !occ2)) || (sa_intv != 1 && (!b || !b_occ)))) return KISS_HIP_E_INVALID;
-    kiss_hip_ctx *ctx = nullptr;
-    int rc = kiss_hip_ctx_create(&ctx, device, n < (1u << 20) ? (1u << 20) : n);
-    if (rc) return rc;
-    DevBuf dS, dSA, dC, dmap, dbwt, docc1, docc2, dsa, db, dbocc;
-    do {
-        if ((rc = dS.alloc(ctx, n)) || (rc = dC.alloc(ctx, 257 * 4)) || (rc = dmap.alloc(ctx, 256))) break;
-        if ((rc = fm_h2d(ctx, dS.p, S, n))) break;
-        if (!bwt) { // the census
-            rc = kiss_hip_fmi8_build_dev(ctx, (const uint8_t *)dS.p, n, nullptr, sa_intv, 0, (uint32_t *)dC.p, (uint8_t *)dmap.p, nullptr,
-                                         nullptr, nullptr, nullptr, nullptr, nullptr, sigma_out, nullptr, nullptr);
-        } else {
-            if ((rc = dSA.alloc(ctx, (n + 1) * 4)) || (rc = dbwt.alloc(ctx, z.bwt_bytes)) || (rc = docc1.alloc(ctx, z.occ1_entries * 4)) ||
-                (rc = docc2.alloc(ctx, z.occ2_entries * 2)) || (rc = dsa.alloc(ctx, z.sa_entries * 4)) ||
-                (rc = db.alloc(ctx, z.b_words * 8 + 8)) || (rc = dbocc.alloc(ctx, z.b_occ_entries * 4)))
-                break;
-            if (SA_or_null) {
-                if ((rc = fm_h2d(ctx, dSA.p, SA_or_null, (n + 1) * 4))) break;
-            } else if ((rc = kiss_hip_ctx_suffix_sort_u8_dev(ctx, (const uint8_t *)dS.p, n, (uint32_t *)dSA.p, nullptr))) {
-                break;
-            }
-            rc = kiss_hip_fmi8_build_dev(ctx, (const uint8_t *)dS.p, n, (const uint32_t *)dSA.p, sa_intv, sigma_capacity, (uint32_t *)dC.p,
-                                         (uint8_t *)dmap.p, (uint8_t *)dbwt.p, (uint32_t *)docc1.p, (uint16_t *)docc2.p, (uint32_t *)dsa.p,
-                                         (uint64_t *)db.p, (uint32_t *)dbocc.p, sigma_out, pri_out, nullptr);
+    return kiss_one_shot_own(device, n < (1u << 20) ? (1u << 20) : n, [&](kiss_hip_ctx *ctx) -> int {
+        const bool full = bwt != nullptr; // (else the census: C, map and sigma alone)
+        FmStage st(ctx);
+        const uint8_t *dS = S ? st.up(S, n) : st.room<uint8_t>(true, 0); // (n == 0: no text, still a pointer)
+        uint32_t *dC = st.room<uint32_t>(true, 257 * 4);
+        uint8_t *dmap = st.room<uint8_t>(true, 256);
+        const uint32_t *dSA = full ? st.up(SA_or_null, (n + 1) * 4) : nullptr;
+        uint32_t *sorted = st.room<uint32_t>(full && !SA_or_null, (n + 1) * 4);
+        uint8_t *dbwt = st.room<uint8_t>(full, z.bwt_bytes);
+        uint32_t *docc1 = st.room<uint32_t>(full, z.occ1_entries * 4);
+        uint16_t *docc2 = st.room<uint16_t>(full, z.occ2_entries * 2);
+        uint32_t *dsa = st.room<uint32_t>(full, z.sa_entries * 4);
+        uint64_t *db = st.room<uint64_t>(full, z.b_words * 8, 8);
+        uint32_t *dbocc = st.room<uint32_t>(full, z.b_occ_entries * 4);
+        if (st.rc) return st.rc;
+        if (sorted) {
+            KTRY(kiss_hip_ctx_suffix_sort_u8_dev(ctx, dS, n, sorted, nullptr));
+            dSA = sorted;
         }
-        if (rc) break;
-        if (C) rc = fm_d2h(ctx, C, dC.p, 257 * 4);
-        if (!rc && map) rc = fm_d2h(ctx, map, dmap.p, 256);
-        if (!rc && bwt) {
+        KTRY(kiss_hip_fmi8_build_dev(ctx, dS, n, dSA, sa_intv, full ? sigma_capacity : 0, dC, dmap, dbwt, docc1, docc2, dsa, db, dbocc,
+                                     sigma_out, full ? pri_out : nullptr, nullptr));
+        if (C) st.down(C, dC, 257 * 4);
+        if (map) st.down(map, dmap, 256);
+        if (full) {
             kiss_hip_fmi8_sizes zs; // occ1 / occ2 are laid out for the text's own sigma
             (void)kiss_hip_fmi8_sizes_for(n, sa_intv, *sigma_out, &zs);
-            if ((rc = fm_d2h(ctx, bwt, dbwt.p, zs.bwt_bytes)) || (rc = fm_d2h(ctx, occ1, docc1.p, zs.occ1_entries * 4)) ||
-                (rc = fm_d2h(ctx, occ2, docc2.p, zs.occ2_entries * 2)) || (rc = fm_d2h(ctx, sa, dsa.p, zs.sa_entries * 4)) ||
-                (rc = fm_d2h(ctx, b, db.p, zs.b_words * 8)))
-                break;
-            rc = fm_d2h(ctx, b_occ, dbocc.p, zs.b_occ_entries * 4);
+            st.down(bwt, dbwt, zs.bwt_bytes);
+            st.down(occ1, docc1, zs.occ1_entries * 4);
+            st.down(occ2, docc2, zs.occ2_entries * 2);
+            st.down(sa, dsa, zs.sa_entries * 4);
+            st.down(b, db, zs.b_words * 8);
+            st.down(b_occ, dbocc, zs.b_occ_entries * 4);
         }
-    } while (0);
-    kiss_hip_ctx_destroy(ctx);
-    return rc;
+        return st.rc;
+    });
 }
 
 int kiss_hip_fmi8_query_host(const kiss_hip_fmi8_view *fmi, const uint8_t *patterns, const uint64_t *pat_index, uint64_t Q,
@@ -631,48 +646,27 @@ int kiss_hip_fmi8_query_host(const kiss_hip_fmi8_view *fmi, const uint8_t *patte
     kiss_hip_fmi8_sizes z;
     KTRY(kiss_hip_fmi8_sizes_for(fmi->n_sa - 1, fmi->sa_intv, fmi->sigma, &z));
     const uint64_t pat_bytes = Q ? pat_index[Q] : 0;
-    kiss_hip_ctx *ctx = nullptr;
     // (the hits of a call are sorted in the ctx's LMS arrays)
-    int rc = kiss_hip_ctx_create(&ctx, device, fm_host_max_n(fmi->n_sa, Q, capacity));
-    if (rc) return rc;
-    DevBuf dC, dmap, dbwt, docc1, docc2, dsa, db, dbocc, dpat, dpidx, dbeg, dend, dpos, didx;
-    do {
-        if ((rc = dC.alloc(ctx, 257 * 4)) || (rc = dmap.alloc(ctx, 256)) || (rc = dbwt.alloc(ctx, z.bwt_bytes)) ||
-            (rc = docc1.alloc(ctx, z.occ1_entries * 4)) || (rc = docc2.alloc(ctx, z.occ2_entries * 2)) ||
-            (rc = dsa.alloc(ctx, z.sa_entries * 4)) || (rc = db.alloc(ctx, z.b_words * 8 + 8)) ||
-            (rc = dbocc.alloc(ctx, z.b_occ_entries * 4)) || (rc = dpat.alloc(ctx, pat_bytes)) || (rc = dpidx.alloc(ctx, (Q + 1) * 8)) ||
-            (rc = dbeg.alloc(ctx, Q * 4)) || (rc = dend.alloc(ctx, Q * 4)))
-            break;
-        // (another kind of view than FmIndexOnDevice uploads: C, map, 16-bit occ2; sa_intv == 1: the sizes of b / b_occ are 0)
-        if ((rc = fm_h2d(ctx, dC.p, fmi->C, 257 * 4)) || (rc = fm_h2d(ctx, dmap.p, fmi->map, 256)) ||
-            (rc = fm_h2d(ctx, dbwt.p, fmi->bwt, z.bwt_bytes)) || (rc = fm_h2d(ctx, docc1.p, fmi->occ1, z.occ1_entries * 4)) ||
-            (rc = fm_h2d(ctx, docc2.p, fmi->occ2, z.occ2_entries * 2)) || (rc = fm_h2d(ctx, dsa.p, fmi->sa, z.sa_entries * 4)) ||
-            (rc = fm_h2d(ctx, db.p, fmi->b, z.b_words * 8)) || (rc = fm_h2d(ctx, dbocc.p, fmi->b_occ, z.b_occ_entries * 4)) ||
-            (rc = fm_h2d(ctx, dpat.p, patterns, pat_bytes)) || (Q && (rc = fm_h2d(ctx, dpidx.p, pat_index, (Q + 1) * 8))))
-            break;
-        kiss_hip_fmi8_view v = *fmi;
-        v.C = (const uint32_t *)dC.p;
-        v.map = (const uint8_t *)dmap.p;
-        v.bwt = (const uint8_t *)dbwt.p;
-        v.occ1 = (const uint32_t *)docc1.p;
-        v.occ2 = (const uint16_t *)docc2.p;
-        v.sa = (const uint32_t *)dsa.p;
-        v.b = fmi->sa_intv == 1 ? nullptr : (const uint64_t *)db.p;
-        v.b_occ = fmi->sa_intv == 1 ? nullptr : (const uint32_t *)dbocc.p;
-        if (all && ((rc = dpos.alloc(ctx, capacity * 4)) || (rc = didx.alloc(ctx, (Q + 1) * 8)))) break;
+    return kiss_one_shot_own(device, fm_host_max_n(fmi->n_sa, Q, capacity), [&](kiss_hip_ctx *ctx) -> int {
+        FmStage st(ctx);
+        const kiss_hip_fmi8_view v = f8_upload_view(st, *fmi, z);
+        const uint8_t *dpat = st.up(patterns, pat_bytes);
+        const uint64_t *dpidx = st.up(Q ? pat_index : nullptr, (Q + 1) * 8);
+        uint32_t *dbeg = st.room<uint32_t>(true, Q * 4), *dend = st.room<uint32_t>(true, Q * 4);
+        uint32_t *dpos = st.room<uint32_t>(all, capacity * 4);
+        uint64_t *didx = st.room<uint64_t>(all, (Q + 1) * 8);
+        if (st.rc) return st.rc;
         uint64_t total = 0;
-        rc = kiss_hip_fmi8_query_dev(ctx, &v, (const uint8_t *)dpat.p, (const uint64_t *)dpidx.p, Q, (uint32_t *)dbeg.p,
-                                     (uint32_t *)dend.p, &total, checksum, all ? (uint32_t *)dpos.p : nullptr,
-                                     all ? (uint64_t *)didx.p : nullptr, all ? capacity : 0, report, nullptr);
+        const int rc = kiss_hip_fmi8_query_dev(ctx, &v, dpat, dpidx, Q, dbeg, dend, &total, checksum, dpos, didx, all ? capacity : 0, report,
+                                               nullptr);
         if (hit_count_total) *hit_count_total = total;
-        if (rc) break;
-        rc = fm_d2h(ctx, beg, dbeg.p, Q * 4);
-        if (!rc) rc = fm_d2h(ctx, end, dend.p, Q * 4);
-        if (!rc && all) rc = fm_d2h(ctx, index, didx.p, (Q + 1) * 8);
-        if (!rc && all) rc = fm_d2h(ctx, positions, dpos.p, total * 4);
-    } while (0);
-    kiss_hip_ctx_destroy(ctx);
-    return rc;
+        if (rc) return rc;
+        st.down(beg, dbeg, Q * 4);
+        st.down(end, dend, Q * 4);
+        if (all) st.down(index, didx, (Q + 1) * 8);
+        if (all) st.down(positions, dpos, total * 4);
+        return st.rc;
+    });
 }
 
 } // extern "C"

@@ -487,55 +487,6 @@ int align_args_check(const uint8_t *text, const uint8_t *reads, const uint64_t *
     return KISS_HIP_OK;
 }
 
-struct AlignHostArgs {
-    const uint8_t *text;
-    uint64_t n;
-    const uint8_t *reads;
-    const uint64_t *read_index;
-    uint64_t Q;
-    int both;
-    const kiss_hip_chain *chains;
-    const uint64_t *chain_index;
-    const kiss_hip_align_params *params;
-    kiss_hip_aln *alns;
-    uint64_t aln_capacity;
-    uint32_t *cigar;
-    uint64_t *cigar_index;
-    uint64_t cigar_capacity;
-    kiss_hip_align_report *report;
-    uint64_t V, nchains, nbases, max_ops;
-};
-
-int align_one_shot(kiss_hip_ctx *ctx, void *arg)
-{
-    const AlignHostArgs &a = *(const AlignHostArgs *)arg;
-    const bool all = a.cigar != nullptr;
-    const uint64_t C = a.chain_index[a.V] - a.chain_index[0];
-    const uint64_t acap = a.aln_capacity < C ? a.aln_capacity : C, ocap = a.cigar_capacity < a.max_ops ? a.cigar_capacity : a.max_ops;
-    DevBuf dtext, dreads, dridx, dchains, dcidx, dalns, dcig, doidx;
-    int rc;
-    if ((rc = dtext.alloc(ctx, a.n)) || (rc = dreads.alloc(ctx, a.nbases)) || (rc = dridx.alloc(ctx, (a.Q + 1) * 8)) ||
-        (rc = dchains.alloc(ctx, a.nchains * sizeof(kiss_hip_chain))) || (rc = dcidx.alloc(ctx, (a.V + 1) * 8)) ||
-        (rc = dalns.alloc(ctx, acap * sizeof(kiss_hip_aln))) ||
-        (all && ((rc = dcig.alloc(ctx, ocap * 4)) || (rc = doidx.alloc(ctx, (C + 1) * 8)))))
-        return rc;
-    KTRY(fm_h2d(ctx, dridx.p, a.read_index, (a.Q + 1) * 8));
-    KTRY(fm_h2d(ctx, dcidx.p, a.chain_index, (a.V + 1) * 8));
-    KTRY(fm_h2d(ctx, dtext.p, a.text, a.n));
-    KTRY(fm_h2d(ctx, dreads.p, a.reads, a.nbases));
-    KTRY(fm_h2d(ctx, dchains.p, a.chains, a.nchains * sizeof(kiss_hip_chain)));
-    kiss_hip_align_report r{};
-    rc = kiss_hip_fmi_align_dev(ctx, (const uint8_t *)dtext.p, a.n, (const uint8_t *)dreads.p, (const uint64_t *)dridx.p, a.Q, a.both,
-                                (const kiss_hip_chain *)dchains.p, (const uint64_t *)dcidx.p, a.params, (kiss_hip_aln *)dalns.p, acap,
-                                all ? (uint32_t *)dcig.p : nullptr, all ? (uint64_t *)doidx.p : nullptr, all ? ocap : 0, &r, nullptr);
-    if (a.report) *a.report = r;
-    if (rc) return rc;
-    KTRY(fm_d2h(ctx, a.alns, dalns.p, C * sizeof(kiss_hip_aln)));
-    if (!all) return KISS_HIP_OK;
-    KTRY(fm_d2h(ctx, a.cigar_index, doidx.p, (C + 1) * 8));
-    return fm_d2h(ctx, a.cigar, dcig.p, r.cigar_ops * 4);
-}
-
 } // namespace
 
 extern "C" {
@@ -583,25 +534,44 @@ int kiss_hip_fmi_align_host(const uint8_t *text, uint64_t n, const uint8_t *read
     }
     KTRY(align_args_check(text, reads, read_index, chains, chain_index, params, alns, cigar, cigar_index, cigar_capacity));
     if (!fm_index_ascending(read_index, Q, true) || !fm_index_ascending(chain_index, V, false)) return KISS_HIP_E_INVALID;
-    AlignHostArgs a{text, n, reads, read_index, Q, both_strands ? 1 : 0, chains, chain_index, params, alns, aln_capacity, cigar,
-                    cigar_index, cigar_capacity, report, V, 0, 0, 0};
-    a.nchains = chain_index[V]; // (the arrays are uploaded from their first entry)
-    a.nbases = read_index[Q];
+    const uint64_t nchains = chain_index[V], nbases = read_index[Q]; // (the arrays are uploaded from their first entry)
     // the cells of the call decide the size of the context (KISS_HIP_ALIGN_CELLS_PER_N cells per base of max_n); no
     // alignment has more ops than 2 L + 1
-    uint64_t cells = 0;
+    uint64_t cells = 0, max_ops = 0;
     for (uint64_t v = 0; v < V; v++) {
         const uint64_t q = both_strands ? v >> 1 : v, L = read_index[q + 1] - read_index[q];
         for (uint64_t c = chain_index[v]; c < chain_index[v + 1]; c++) {
             const Band b = band_of(chains[c], params->band);
             if (b.B <= (unsigned long long)AL_MAXB) {
                 cells += L * b.B;
-                a.max_ops += 2 * L + 1;
+                max_ops += 2 * L + 1;
             }
         }
     }
-    const uint64_t C = a.nchains - chain_index[0];
-    return kiss_cached_ctx_run(device, fm_host_max_n(cells / KISS_HIP_ALIGN_CELLS_PER_N + 1, C + 1, V + 1), align_one_shot, &a);
+    const uint64_t C = nchains - chain_index[0];
+    return kiss_one_shot_cached(device, fm_host_max_n(cells / KISS_HIP_ALIGN_CELLS_PER_N + 1, C + 1, V + 1), [&](kiss_hip_ctx *ctx) -> int {
+        const bool all = cigar != nullptr;
+        const uint64_t acap = aln_capacity < C ? aln_capacity : C, ocap = cigar_capacity < max_ops ? cigar_capacity : max_ops;
+        FmStage st(ctx);
+        const uint8_t *dtext = st.up(text, n);
+        const uint8_t *dreads = st.up(reads, nbases);
+        const uint64_t *dridx = st.up(read_index, (Q + 1) * 8);
+        const kiss_hip_chain *dchains = st.up(chains, nchains * sizeof(kiss_hip_chain));
+        const uint64_t *dcidx = st.up(chain_index, (V + 1) * 8);
+        kiss_hip_aln *dalns = st.room<kiss_hip_aln>(true, acap * sizeof(kiss_hip_aln));
+        uint32_t *dcig = st.room<uint32_t>(all, ocap * 4);
+        uint64_t *doidx = st.room<uint64_t>(all, (C + 1) * 8);
+        if (st.rc) return st.rc;
+        kiss_hip_align_report r{};
+        const int rc = kiss_hip_fmi_align_dev(ctx, dtext, n, dreads, dridx, Q, both_strands ? 1 : 0, dchains, dcidx, params, dalns, acap, dcig,
+                                              doidx, all ? ocap : 0, &r, nullptr);
+        if (report) *report = r;
+        if (rc) return rc;
+        st.down(alns, dalns, C * sizeof(kiss_hip_aln));
+        if (all) st.down(cigar_index, doidx, (C + 1) * 8);
+        if (all) st.down(cigar, dcig, r.cigar_ops * 4);
+        return st.rc;
+    });
 }
 
 } // extern "C"

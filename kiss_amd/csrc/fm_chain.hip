@@ -490,54 +490,6 @@ int chain_args_check(const kiss_hip_fmi_seed *seeds, const uint64_t *seed_index,
     return KISS_HIP_OK;
 }
 
-struct ChainHostArgs {
-    const kiss_hip_fmi_seed *seeds;
-    const uint64_t *seed_index;
-    uint64_t V;
-    const uint32_t *positions;
-    const uint64_t *pos_index;
-    const kiss_hip_chain_params *params;
-    kiss_hip_chain *chains;
-    uint64_t *chain_index;
-    uint64_t chain_capacity;
-    kiss_hip_chain_anchor *chain_anchors;
-    uint64_t *anchor_index;
-    uint64_t anchor_capacity;
-    kiss_hip_chain_report *report;
-    uint64_t nseeds, npos;
-};
-
-int chain_one_shot(kiss_hip_ctx *ctx, void *arg)
-{
-    const ChainHostArgs &a = *(const ChainHostArgs *)arg;
-    const bool all = a.chain_anchors != nullptr;
-    // (no more chains than anchors, no more chain anchors than anchors)
-    const uint64_t ccap = a.chain_capacity < a.npos ? a.chain_capacity : a.npos, acap = a.anchor_capacity < a.npos ? a.anchor_capacity : a.npos;
-    DevBuf dseeds, dsidx, dpos, dpidx, dchains, dcidx, danc, daidx;
-    int rc;
-    if ((rc = dseeds.alloc(ctx, a.nseeds * 16)) || (rc = dsidx.alloc(ctx, (a.V + 1) * 8)) || (rc = dpos.alloc(ctx, a.npos * 4)) ||
-        (rc = dpidx.alloc(ctx, (a.nseeds + 1) * 8)) || (rc = dchains.alloc(ctx, ccap * sizeof(kiss_hip_chain))) ||
-        (rc = dcidx.alloc(ctx, (a.V + 1) * 8)) || (all && ((rc = danc.alloc(ctx, acap * sizeof(kiss_hip_chain_anchor))) ||
-                                                         (rc = daidx.alloc(ctx, (ccap + 1) * 8)))))
-        return rc;
-    KTRY(fm_h2d(ctx, dsidx.p, a.seed_index, (a.V + 1) * 8));
-    KTRY(fm_h2d(ctx, dpidx.p, a.pos_index, (a.nseeds + 1) * 8));
-    KTRY(fm_h2d(ctx, dseeds.p, a.seeds, a.nseeds * 16));
-    KTRY(fm_h2d(ctx, dpos.p, a.positions, a.npos * 4));
-    kiss_hip_chain_report r{};
-    rc = kiss_hip_fmi_chain_dev(ctx, (const kiss_hip_fmi_seed *)dseeds.p, (const uint64_t *)dsidx.p, a.V, (const uint32_t *)dpos.p,
-                                (const uint64_t *)dpidx.p, a.params, (kiss_hip_chain *)dchains.p, (uint64_t *)dcidx.p, ccap,
-                                all ? (kiss_hip_chain_anchor *)danc.p : nullptr, all ? (uint64_t *)daidx.p : nullptr, all ? acap : 0, &r,
-                                nullptr);
-    if (a.report) *a.report = r;
-    if (rc) return rc;
-    KTRY(fm_d2h(ctx, a.chain_index, dcidx.p, (a.V + 1) * 8));
-    KTRY(fm_d2h(ctx, a.chains, dchains.p, r.chains * sizeof(kiss_hip_chain)));
-    if (!all) return KISS_HIP_OK;
-    KTRY(fm_d2h(ctx, a.anchor_index, daidx.p, (r.chains + 1) * 8));
-    return fm_d2h(ctx, a.chain_anchors, danc.p, r.chain_anchors * sizeof(kiss_hip_chain_anchor));
-}
-
 } // namespace
 
 extern "C" {
@@ -586,13 +538,35 @@ int kiss_hip_fmi_chain_host(const kiss_hip_fmi_seed *seeds, const uint64_t *seed
     KTRY(chain_args_check(seeds, seed_index, positions, pos_index, params, chains, chain_index, chain_anchors, anchor_index,
                           anchor_capacity));
     if (!fm_index_ascending(seed_index, V, false)) return KISS_HIP_E_INVALID;
-    ChainHostArgs a{seeds, seed_index, V, positions, pos_index, params, chains, chain_index, chain_capacity, chain_anchors, anchor_index,
-                    anchor_capacity, report, 0, 0};
-    a.nseeds = seed_index[V]; // (the arrays are uploaded from their first entry)
-    if (!fm_index_ascending(pos_index, a.nseeds, false)) return KISS_HIP_E_INVALID;
-    a.npos = pos_index[a.nseeds];
+    const uint64_t nseeds = seed_index[V]; // (the arrays are uploaded from their first entry)
+    if (!fm_index_ascending(pos_index, nseeds, false)) return KISS_HIP_E_INVALID;
+    const uint64_t npos = pos_index[nseeds];
     // the anchors of a call are sorted in the ctx's LMS arrays and scanned in its scratch
-    return kiss_cached_ctx_run(device, fm_host_max_n(0, a.npos + 1, V + 1), chain_one_shot, &a);
+    return kiss_one_shot_cached(device, fm_host_max_n(0, npos + 1, V + 1), [&](kiss_hip_ctx *ctx) -> int {
+        const bool all = chain_anchors != nullptr;
+        // (no more chains than anchors, no more chain anchors than anchors)
+        const uint64_t ccap = chain_capacity < npos ? chain_capacity : npos, acap = anchor_capacity < npos ? anchor_capacity : npos;
+        FmStage st(ctx);
+        const kiss_hip_fmi_seed *dseeds = st.up(seeds, nseeds * 16);
+        const uint64_t *dsidx = st.up(seed_index, (V + 1) * 8);
+        const uint32_t *dpos = st.up(positions, npos * 4);
+        const uint64_t *dpidx = st.up(pos_index, (nseeds + 1) * 8);
+        kiss_hip_chain *dchains = st.room<kiss_hip_chain>(true, ccap * sizeof(kiss_hip_chain));
+        uint64_t *dcidx = st.room<uint64_t>(true, (V + 1) * 8);
+        kiss_hip_chain_anchor *danc = st.room<kiss_hip_chain_anchor>(all, acap * sizeof(kiss_hip_chain_anchor));
+        uint64_t *daidx = st.room<uint64_t>(all, (ccap + 1) * 8);
+        if (st.rc) return st.rc;
+        kiss_hip_chain_report r{};
+        const int rc = kiss_hip_fmi_chain_dev(ctx, dseeds, dsidx, V, dpos, dpidx, params, dchains, dcidx, ccap, danc, daidx, all ? acap : 0,
+                                              &r, nullptr);
+        if (report) *report = r;
+        if (rc) return rc;
+        st.down(chain_index, dcidx, (V + 1) * 8);
+        st.down(chains, dchains, r.chains * sizeof(kiss_hip_chain));
+        if (all) st.down(anchor_index, daidx, (r.chains + 1) * 8);
+        if (all) st.down(chain_anchors, danc, r.chain_anchors * sizeof(kiss_hip_chain_anchor));
+        return st.rc;
+    });
 }
 
 } // extern "C"

@@ -1,12 +1,16 @@
-// fm_internal.hpp -- what the seven FM-index translation units share (fm.hip: exact queries + construction; fm_mm.hip: the
-// search with mismatches; fm8.hip: the byte alphabet; fm_seed.hip: maximal exact match seeds; fm_chain.hip: chains of seeds;
-// fm_align.hip: banded alignment of the chains; fm_select.hip: the mappings of a read).  Device side: the device view of an
-// index, the one-sector rank blocks and the LF arithmetic on them, the rank of the sampling bit-vector, the bounded locate walk
-// of one row.  Host side, the frame around a batch call: the pooled scratch buffers (DevBuf, slots named by FmSlot in
-// kiss_internal.hpp), the events behind a report's times (FmEvents), the prologue and epilogue of a _dev entry (fm_enter /
-// fm_leave), the control words of a call with their host mirror (FmCtl), the small arithmetic (fm_up256, fm_bits, fm_grid,
-// FmSlab) and what the _host entries need: the checked copies (fm_h2d / fm_d2h), an index uploaded (FmIndexOnDevice), the
-// ascending check of an index array and the size of the one-shot ctx (fm_host_max_n).
+// fm_internal.hpp -- what the translation units of the batch calls share: the FM-index ones (fm.hip: exact queries +
+// construction; fm_mm.hip: the search with mismatches; fm8.hip: the byte alphabet; fm_seed.hip: maximal exact match seeds;
+// fm_chain.hip: chains of seeds; fm_align.hip: banded alignment of the chains; fm_select.hip: the mappings of a read;
+// fm_pair.hip: the mappings of two mates; fm_rescue.hip: the missing mate, two alignment sets merged) and reads.hip, the read
+// files; general.hip takes the staging of its one-shot entry from here.  Device side: the device view of an index, the
+// one-sector rank blocks and the LF arithmetic on them, the rank of the sampling bit-vector, the bounded locate walk of one
+// row.  Host side, the frame around a _dev call: the pooled scratch buffers (DevBuf, slots named by FmSlot in
+// kiss_internal.hpp), the events behind a report's times (FmEvents), the prologue and epilogue (fm_enter / fm_leave), the
+// control words of a call with their host mirror (FmCtl), the small arithmetic (fm_up256, fm_bits, fm_grid, FmSlab).  And the
+// frame around a _host call, which runs its _dev twin on a one-shot ctx (kiss_one_shot_own / kiss_one_shot_cached in
+// kiss_internal.hpp): the checked copies (fm_h2d / fm_d2h), the arrays of the call on the device (FmStage: up, room, down),
+// a DNA index uploaded through it (fm_upload_index), the ascending check of an index array and the size of the ctx
+// (fm_host_max_n).
 #pragma once
 #include "kiss_internal.hpp"
 
@@ -287,32 +291,55 @@ static inline int fm_d2h(kiss_hip_ctx *ctx, void *dst, const void *src, uint64_t
     return fm_copy(ctx, dst, src, bytes, hipMemcpyDeviceToHost);
 }
 
-// a host kiss_hip_fmi_view on the device: its six arrays (z: their sizes; bwt and b with 8 spare bytes behind them) and the
-// view over the copies.  sa_intv == 1 keeps no bit-vector: b / b_occ are allocated, not copied, and null in the view.
-struct FmIndexOnDevice {
-    DevBuf bwt, occ1, occ2, sa, b, b_occ;
-    kiss_hip_fmi_view view;
-    int upload(kiss_hip_ctx *ctx, const kiss_hip_fmi_view &h, const kiss_hip_fmi_sizes &z)
+// The arrays of one _host call on the device.  up(): a host array allocated and copied (null stays null; an empty one is still
+// a valid pointer); room(): an output allocated, when it is wanted; down(): a result copied back.  The buffers are freed with
+// the stage.  rc keeps the first failure (no memory: KISS_HIP_E_NOMEM, a copy: KISS_HIP_E_HIP, the HIP code in the ctx) and
+// everything after it does nothing, so an entry looks at rc once before its _dev call and once after its downloads.
+struct FmStage {
+    kiss_hip_ctx *ctx;
+    int rc = KISS_HIP_OK;
+    int used = 0;
+    DevBuf buf[16];
+    explicit FmStage(kiss_hip_ctx *c) : ctx(c) {}
+    template <class T>
+    T *room(bool wanted, uint64_t bytes, uint64_t spare = 0)
     {
-        const bool bits = h.sa_intv != 1;
-        int rc;
-        if ((rc = bwt.alloc(ctx, z.bwt_bytes + 8)) || (rc = occ1.alloc(ctx, z.occ1_entries * 4)) || (rc = occ2.alloc(ctx, z.occ2_bytes)) ||
-            (rc = sa.alloc(ctx, z.sa_entries * 4)) || (rc = b.alloc(ctx, z.b_words * 8 + 8)) || (rc = b_occ.alloc(ctx, z.b_occ_entries * 4)))
-            return rc;
-        if ((rc = fm_h2d(ctx, bwt.p, h.bwt, z.bwt_bytes)) || (rc = fm_h2d(ctx, occ1.p, h.occ1, z.occ1_entries * 4)) ||
-            (rc = fm_h2d(ctx, occ2.p, h.occ2, z.occ2_bytes)) || (rc = fm_h2d(ctx, sa.p, h.sa, z.sa_entries * 4)) ||
-            (bits && ((rc = fm_h2d(ctx, b.p, h.b, z.b_words * 8)) || (rc = fm_h2d(ctx, b_occ.p, h.b_occ, z.b_occ_entries * 4)))))
-            return rc;
-        view = h;
-        view.bwt = (const uint8_t *)bwt.p;
-        view.occ1 = (const uint32_t *)occ1.p;
-        view.occ2 = (const uint8_t *)occ2.p;
-        view.sa = (const uint32_t *)sa.p;
-        view.b = bits ? (const uint64_t *)b.p : nullptr;
-        view.b_occ = bits ? (const uint32_t *)b_occ.p : nullptr;
-        return KISS_HIP_OK;
+        if (!wanted || rc) return nullptr;
+        if (used == (int)(sizeof buf / sizeof buf[0])) {
+            rc = KINTERNAL();
+            return nullptr;
+        }
+        rc = buf[used].alloc(ctx, bytes + spare);
+        return (T *)buf[used++].p;
+    }
+    template <class T>
+    const T *up(const T *host, uint64_t bytes, uint64_t spare = 0)
+    {
+        T *d = room<T>(host != nullptr, bytes, spare);
+        if (d) rc = fm_h2d(ctx, d, host, bytes);
+        return rc ? nullptr : d;
+    }
+    void down(void *host, const void *dev, uint64_t bytes)
+    {
+        if (!rc) rc = fm_d2h(ctx, host, dev, bytes);
     }
 };
+
+// a host kiss_hip_fmi_view on the device: its six arrays (z: their sizes; bwt and b with 8 spare bytes behind them) and the
+// view over the copies.  sa_intv == 1 keeps no bit-vector: b / b_occ are allocated, not copied, and null in the view.
+static inline kiss_hip_fmi_view fm_upload_index(FmStage &st, const kiss_hip_fmi_view &h, const kiss_hip_fmi_sizes &z)
+{
+    const bool bits = h.sa_intv != 1;
+    kiss_hip_fmi_view v = h;
+    v.bwt = st.up(h.bwt, z.bwt_bytes, 8);
+    v.occ1 = st.up(h.occ1, z.occ1_entries * 4);
+    v.occ2 = st.up(h.occ2, z.occ2_bytes);
+    v.sa = st.up(h.sa, z.sa_entries * 4);
+    v.b = bits ? st.up(h.b, z.b_words * 8, 8) : nullptr;
+    v.b_occ = bits ? st.up(h.b_occ, z.b_occ_entries * 4) : nullptr;
+    if (!bits) (void)(st.room<uint64_t>(true, z.b_words * 8, 8), st.room<uint32_t>(true, z.b_occ_entries * 4));
+    return v;
+}
 
 // idx[0 .. count] never decreases (strict: and no two neighbours are equal)
 static inline bool fm_index_ascending(const uint64_t *idx, uint64_t count, bool strict)

@@ -620,34 +620,29 @@ int kiss_hip_fmi_query_mm_host(const kiss_hip_fmi_view *fmi, const uint8_t *patt
         return KISS_HIP_E_INVALID;
     kiss_hip_fmi_sizes_ex z;
     KTRY(kiss_hip_fmi_sizes_ex_for(fmi->n_sa - 1, sa_intv, 0, &z));
-    kiss_hip_ctx *ctx = nullptr;
     // (the hits of a call are sorted in the ctx's LMS arrays)
-    int rc = kiss_hip_ctx_create(&ctx, device, fm_host_max_n(fmi->n_sa, Q, capacity));
-    if (rc) return rc;
-    const uint32_t e1 = max_mismatches + 1;
-    FmIndexOnDevice idx;
-    DevBuf dpat, dcnt, dpos, dmm, didx;
-    do {
-        if ((rc = idx.upload(ctx, *fmi, z.base)) || (rc = dpat.alloc(ctx, Q * L)) || (rc = dcnt.alloc(ctx, Q * e1 * 4)) ||
-            (rc = fm_h2d(ctx, dpat.p, patterns, Q * L)))
-            break;
-        if (all && ((rc = dpos.alloc(ctx, capacity * 4)) || (rc = dmm.alloc(ctx, capacity)) || (rc = didx.alloc(ctx, (Q + 1) * 8))))
-            break;
+    return kiss_one_shot_own(device, fm_host_max_n(fmi->n_sa, Q, capacity), [&](kiss_hip_ctx *ctx) -> int {
+        const uint64_t cnt_bytes = Q * (max_mismatches + 1) * 4;
+        FmStage st(ctx);
+        const kiss_hip_fmi_view v = fm_upload_index(st, *fmi, z.base);
+        const uint8_t *dpat = st.up(patterns, Q * L);
+        uint32_t *dcnt = st.room<uint32_t>(true, cnt_bytes);
+        uint32_t *dpos = st.room<uint32_t>(all, capacity * 4);
+        uint8_t *dmm = st.room<uint8_t>(all, capacity);
+        uint64_t *didx = st.room<uint64_t>(all, (Q + 1) * 8);
+        if (st.rc) return st.rc;
         kiss_hip_fmi_mm_report r{};
-        rc = kiss_hip_fmi_query_mm_dev(ctx, &idx.view, (const uint8_t *)dpat.p, L, Q, max_mismatches, (uint32_t *)dcnt.p,
-                                       all ? (uint32_t *)dpos.p : nullptr, all ? (uint8_t *)dmm.p : nullptr,
-                                       all ? (uint64_t *)didx.p : nullptr, all ? capacity : 0, &r, nullptr);
+        const int rc = kiss_hip_fmi_query_mm_dev(ctx, &v, dpat, L, Q, max_mismatches, dcnt, dpos, dmm, didx, all ? capacity : 0, &r, nullptr);
         if (report) *report = r;
-        if (rc) break;
+        if (rc) return rc;
         uint64_t total = 0;
         for (int j = 0; j < 4; j++) total += r.hits[j];
-        rc = fm_d2h(ctx, counts, dcnt.p, Q * e1 * 4);
-        if (!rc && all) rc = fm_d2h(ctx, index, didx.p, (Q + 1) * 8);
-        if (!rc && all) rc = fm_d2h(ctx, positions, dpos.p, total * 4);
-        if (!rc && all) rc = fm_d2h(ctx, mismatches, dmm.p, total);
-    } while (0);
-    kiss_hip_ctx_destroy(ctx);
-    return rc;
+        st.down(counts, dcnt, cnt_bytes);
+        if (all) st.down(index, didx, (Q + 1) * 8);
+        if (all) st.down(positions, dpos, total * 4);
+        if (all) st.down(mismatches, dmm, total);
+        return st.rc;
+    });
 }
 
 } // extern "C"

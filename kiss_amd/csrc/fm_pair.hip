@@ -358,37 +358,6 @@ int pair_args_check(const kiss_hip_hit *hits, const uint64_t *hit_index, uint64_
     return KISS_HIP_OK;
 }
 
-struct PairHostArgs {
-    const kiss_hip_hit *hits;
-    const uint64_t *hit_index;
-    uint64_t Q;
-    const kiss_hip_aln *alns;
-    uint64_t aln_count;
-    const kiss_hip_pair_params *params;
-    kiss_hip_pair *pairs;
-    kiss_hip_pair_report *report;
-    uint64_t H;
-};
-
-int pair_one_shot(kiss_hip_ctx *ctx, void *arg)
-{
-    const PairHostArgs &a = *(const PairHostArgs *)arg;
-    DevBuf dhits, dhidx, dalns, dpairs;
-    int rc;
-    if ((rc = dhits.alloc(ctx, a.H * sizeof(kiss_hip_hit))) || (rc = dhidx.alloc(ctx, (a.Q + 1) * 8)) ||
-        (rc = dalns.alloc(ctx, a.aln_count * sizeof(kiss_hip_aln))) || (rc = dpairs.alloc(ctx, (a.Q / 2) * sizeof(kiss_hip_pair))))
-        return rc;
-    KTRY(fm_h2d(ctx, dhits.p, a.hits, a.H * sizeof(kiss_hip_hit)));
-    KTRY(fm_h2d(ctx, dhidx.p, a.hit_index, (a.Q + 1) * 8));
-    KTRY(fm_h2d(ctx, dalns.p, a.alns, a.aln_count * sizeof(kiss_hip_aln)));
-    kiss_hip_pair_report r{};
-    rc = kiss_hip_fmi_pair_dev(ctx, (const kiss_hip_hit *)dhits.p, (const uint64_t *)dhidx.p, a.Q, (const kiss_hip_aln *)dalns.p, a.aln_count,
-                               a.params, (kiss_hip_pair *)dpairs.p, &r, nullptr);
-    if (a.report) *a.report = r;
-    if (rc) return rc;
-    return fm_d2h(ctx, a.pairs, dpairs.p, (a.Q / 2) * sizeof(kiss_hip_pair));
-}
-
 } // namespace
 
 extern "C" {
@@ -429,9 +398,22 @@ int kiss_hip_fmi_pair_host(const kiss_hip_hit *hits, const uint64_t *hit_index, 
     KTRY(pair_args_check(hits, hit_index, Q, alns, params, pairs));
     if (Q == 0) return KISS_HIP_OK;
     if (!fm_index_ascending(hit_index, Q, false)) return KISS_HIP_E_INVALID;
-    PairHostArgs a{hits, hit_index, Q, alns, aln_count, params, pairs, report, hit_index[Q]};
-    if (a.H >= 0xFFFFFFFFull) return KISS_HIP_E_UNSUPPORTED;
-    return kiss_cached_ctx_run(device, fm_host_max_n(0, 0), pair_one_shot, &a);
+    const uint64_t H = hit_index[Q];
+    if (H >= 0xFFFFFFFFull) return KISS_HIP_E_UNSUPPORTED;
+    return kiss_one_shot_cached(device, fm_host_max_n(0, 0), [&](kiss_hip_ctx *ctx) -> int {
+        FmStage st(ctx);
+        const kiss_hip_hit *dhits = st.up(hits, H * sizeof(kiss_hip_hit));
+        const uint64_t *dhidx = st.up(hit_index, (Q + 1) * 8);
+        const kiss_hip_aln *dalns = st.up(alns, aln_count * sizeof(kiss_hip_aln));
+        kiss_hip_pair *dpairs = st.room<kiss_hip_pair>(true, (Q / 2) * sizeof(kiss_hip_pair));
+        if (st.rc) return st.rc;
+        kiss_hip_pair_report r{};
+        const int rc = kiss_hip_fmi_pair_dev(ctx, dhits, dhidx, Q, dalns, aln_count, params, dpairs, &r, nullptr);
+        if (report) *report = r;
+        if (rc) return rc;
+        st.down(pairs, dpairs, (Q / 2) * sizeof(kiss_hip_pair));
+        return st.rc;
+    });
 }
 
 } // extern "C"

@@ -320,58 +320,6 @@ int rescue_args_check(const kiss_hip_pair *pairs, const kiss_hip_hit *hits, cons
     return KISS_HIP_OK;
 }
 
-struct RescueHostArgs {
-    const kiss_hip_pair *pairs;
-    const kiss_hip_hit *hits;
-    const uint64_t *hit_index;
-    uint64_t Q;
-    const kiss_hip_aln *alns;
-    uint64_t aln_count;
-    const uint64_t *read_index;
-    uint64_t n;
-    const uint64_t *bounds;
-    uint64_t R;
-    const kiss_hip_rescue_params *params;
-    kiss_hip_chain *chains;
-    uint64_t *chain_index;
-    uint32_t *origin;
-    uint64_t chain_capacity;
-    kiss_hip_rescue_report *report;
-    uint64_t H, room;
-};
-
-int rescue_one_shot(kiss_hip_ctx *ctx, void *arg)
-{
-    const RescueHostArgs &a = *(const RescueHostArgs *)arg;
-    const uint64_t P = a.Q / 2, V = 2 * a.Q;
-    const uint64_t cap = a.chain_capacity < a.room ? a.chain_capacity : a.room; // (no more chains than the header's bound)
-    DevBuf dpairs, dhits, dhidx, dalns, dridx, dbounds, dchains, dcidx, dorigin;
-    int rc;
-    if ((rc = dpairs.alloc(ctx, P * sizeof(kiss_hip_pair))) || (rc = dhits.alloc(ctx, a.H * sizeof(kiss_hip_hit))) ||
-        (rc = dhidx.alloc(ctx, (a.Q + 1) * 8)) || (rc = dalns.alloc(ctx, a.aln_count * sizeof(kiss_hip_aln))) ||
-        (rc = dridx.alloc(ctx, (a.Q + 1) * 8)) || (a.bounds && (rc = dbounds.alloc(ctx, (a.R + 1) * 8))) ||
-        (rc = dchains.alloc(ctx, cap * sizeof(kiss_hip_chain))) || (rc = dcidx.alloc(ctx, (V + 1) * 8)) ||
-        (a.origin && (rc = dorigin.alloc(ctx, cap * 4))))
-        return rc;
-    KTRY(fm_h2d(ctx, dpairs.p, a.pairs, P * sizeof(kiss_hip_pair)));
-    KTRY(fm_h2d(ctx, dhits.p, a.hits, a.H * sizeof(kiss_hip_hit)));
-    KTRY(fm_h2d(ctx, dhidx.p, a.hit_index, (a.Q + 1) * 8));
-    KTRY(fm_h2d(ctx, dalns.p, a.alns, a.aln_count * sizeof(kiss_hip_aln)));
-    KTRY(fm_h2d(ctx, dridx.p, a.read_index, (a.Q + 1) * 8));
-    if (a.bounds) KTRY(fm_h2d(ctx, dbounds.p, a.bounds, (a.R + 1) * 8));
-    kiss_hip_rescue_report r{};
-    rc = kiss_hip_fmi_rescue_dev(ctx, (const kiss_hip_pair *)dpairs.p, (const kiss_hip_hit *)dhits.p, (const uint64_t *)dhidx.p, a.Q,
-                                 (const kiss_hip_aln *)dalns.p, a.aln_count, (const uint64_t *)dridx.p, a.n,
-                                 a.bounds ? (const uint64_t *)dbounds.p : nullptr, a.R, a.params, (kiss_hip_chain *)dchains.p,
-                                 (uint64_t *)dcidx.p, a.origin ? (uint32_t *)dorigin.p : nullptr, cap, &r, nullptr);
-    if (a.report) *a.report = r;
-    if (rc) return rc;
-    KTRY(fm_d2h(ctx, a.chain_index, dcidx.p, (V + 1) * 8));
-    KTRY(fm_d2h(ctx, a.chains, dchains.p, r.chains * sizeof(kiss_hip_chain)));
-    if (a.origin) KTRY(fm_d2h(ctx, a.origin, dorigin.p, r.chains * 4));
-    return KISS_HIP_OK;
-}
-
 // ---- merge --------------------------------------------------------------------------------------------------------------
 
 // chain indices that decrease; their ends
@@ -547,63 +495,6 @@ int merge_args_check(const MergeIn &A, const MergeIn &B, const kiss_hip_aln *aln
     return KISS_HIP_OK;
 }
 
-struct MergeHostArgs {
-    MergeIn A, B;
-    uint64_t V;
-    kiss_hip_aln *alns;
-    uint64_t aln_capacity;
-    uint64_t *chain_index;
-    uint32_t *source, *cigar;
-    uint64_t *cigar_index;
-    uint64_t cigar_capacity;
-    kiss_hip_merge_report *report;
-    uint64_t CA, CB, OA, OB; // alignments and ops of either set
-};
-
-int merge_one_shot(kiss_hip_ctx *ctx, void *arg)
-{
-    const MergeHostArgs &a = *(const MergeHostArgs *)arg;
-    const bool ops = a.cigar != nullptr;
-    const uint64_t C = a.CA + a.CB, O = a.OA + a.OB;
-    const uint64_t acap = a.aln_capacity < C ? a.aln_capacity : C, ocap = a.cigar_capacity < O ? a.cigar_capacity : O;
-    DevBuf da, db, dia, dib, dca, dcb, doa, dob, dalns, dcidx, dsrc, dcig, doidx;
-    int rc;
-    if ((rc = da.alloc(ctx, a.CA * sizeof(kiss_hip_aln))) || (rc = db.alloc(ctx, a.CB * sizeof(kiss_hip_aln))) ||
-        (rc = dia.alloc(ctx, (a.V + 1) * 8)) || (rc = dib.alloc(ctx, (a.V + 1) * 8)) || (rc = dalns.alloc(ctx, acap * sizeof(kiss_hip_aln))) ||
-        (rc = dcidx.alloc(ctx, (a.V + 1) * 8)) || (a.source && (rc = dsrc.alloc(ctx, acap * 4))) ||
-        (ops && ((rc = dca.alloc(ctx, a.OA * 4)) || (rc = dcb.alloc(ctx, a.OB * 4)) || (rc = doa.alloc(ctx, (a.CA + 1) * 8)) ||
-                 (rc = dob.alloc(ctx, (a.CB + 1) * 8)) || (rc = dcig.alloc(ctx, ocap * 4)) || (rc = doidx.alloc(ctx, (C + 1) * 8)))))
-        return rc;
-    KTRY(fm_h2d(ctx, da.p, a.A.alns, a.CA * sizeof(kiss_hip_aln)));
-    KTRY(fm_h2d(ctx, db.p, a.B.alns, a.CB * sizeof(kiss_hip_aln)));
-    KTRY(fm_h2d(ctx, dia.p, a.A.chain_index, (a.V + 1) * 8));
-    KTRY(fm_h2d(ctx, dib.p, a.B.chain_index, (a.V + 1) * 8));
-    if (ops) {
-        // (the ops are uploaded from the first one a set uses, its index from 0: the kernels see cigar_index[0] = 0)
-        KTRY(fm_h2d(ctx, dca.p, a.A.cigar + a.A.cigar_index[0], a.OA * 4));
-        KTRY(fm_h2d(ctx, dcb.p, a.B.cigar + a.B.cigar_index[0], a.OB * 4));
-        std::vector<uint64_t> ia(a.CA + 1), ib(a.CB + 1);
-        for (uint64_t i = 0; i <= a.CA; i++) ia[i] = a.A.cigar_index[i] - a.A.cigar_index[0];
-        for (uint64_t i = 0; i <= a.CB; i++) ib[i] = a.B.cigar_index[i] - a.B.cigar_index[0];
-        KTRY(fm_h2d(ctx, doa.p, ia.data(), (a.CA + 1) * 8));
-        KTRY(fm_h2d(ctx, dob.p, ib.data(), (a.CB + 1) * 8));
-    }
-    kiss_hip_merge_report r{};
-    rc = kiss_hip_fmi_aln_merge_dev(ctx, (const kiss_hip_aln *)da.p, (const uint64_t *)dia.p, ops ? (const uint32_t *)dca.p : nullptr,
-                                    ops ? (const uint64_t *)doa.p : nullptr, (const kiss_hip_aln *)db.p, (const uint64_t *)dib.p,
-                                    ops ? (const uint32_t *)dcb.p : nullptr, ops ? (const uint64_t *)dob.p : nullptr, a.V,
-                                    (kiss_hip_aln *)dalns.p, acap, (uint64_t *)dcidx.p, a.source ? (uint32_t *)dsrc.p : nullptr,
-                                    ops ? (uint32_t *)dcig.p : nullptr, ops ? (uint64_t *)doidx.p : nullptr, ops ? ocap : 0, &r, nullptr);
-    if (a.report) *a.report = r;
-    if (rc) return rc;
-    KTRY(fm_d2h(ctx, a.alns, dalns.p, C * sizeof(kiss_hip_aln)));
-    KTRY(fm_d2h(ctx, a.chain_index, dcidx.p, (a.V + 1) * 8));
-    if (a.source) KTRY(fm_d2h(ctx, a.source, dsrc.p, C * 4));
-    if (!ops) return KISS_HIP_OK;
-    KTRY(fm_d2h(ctx, a.cigar_index, doidx.p, (C + 1) * 8));
-    return fm_d2h(ctx, a.cigar, dcig.p, r.cigar_ops * 4);
-}
-
 } // namespace
 
 extern "C" {
@@ -653,15 +544,37 @@ int kiss_hip_fmi_rescue_host(const kiss_hip_pair *pairs, const kiss_hip_hit *hit
         return KISS_HIP_OK;
     }
     if (!fm_index_ascending(hit_index, Q, false) || !fm_index_ascending(read_index, Q, true)) return KISS_HIP_E_INVALID;
-    RescueHostArgs a{pairs, hits,   hit_index,   Q,      alns,           aln_count, read_index,   n, bounds, R,
-                     params, chains, chain_index, origin, chain_capacity, report,    hit_index[Q], 0};
-    if (a.H >= 0xFFFFFFFFull) return KISS_HIP_E_UNSUPPORTED;
+    const uint64_t H = hit_index[Q];
+    if (H >= 0xFFFFFFFFull) return KISS_HIP_E_UNSUPPORTED;
     // Q * max_anchors * ceil((ins_max - ins_min + 1) / max_width) chains always suffice, and no anchor is used twice
     const uint64_t per = ((uint64_t)(params->ins_max - params->ins_min) + params->max_width) / params->max_width; // (at most 2^32)
     uint64_t anchors = Q * (uint64_t)params->max_anchors;                                                         // (below 2^63)
-    if (anchors > a.H) anchors = a.H;
-    a.room = anchors * per; // (H is below 2^32)
-    return kiss_cached_ctx_run(device, fm_host_max_n(0, 2 * Q + 1), rescue_one_shot, &a);
+    if (anchors > H) anchors = H;
+    const uint64_t bound = anchors * per; // (H is below 2^32)
+    return kiss_one_shot_cached(device, fm_host_max_n(0, 2 * Q + 1), [&](kiss_hip_ctx *ctx) -> int {
+        const uint64_t P = Q / 2, V = 2 * Q;
+        const uint64_t cap = chain_capacity < bound ? chain_capacity : bound; // (no more chains than the header's bound)
+        FmStage st(ctx);
+        const kiss_hip_pair *dpairs = st.up(pairs, P * sizeof(kiss_hip_pair));
+        const kiss_hip_hit *dhits = st.up(hits, H * sizeof(kiss_hip_hit));
+        const uint64_t *dhidx = st.up(hit_index, (Q + 1) * 8);
+        const kiss_hip_aln *dalns = st.up(alns, aln_count * sizeof(kiss_hip_aln));
+        const uint64_t *dridx = st.up(read_index, (Q + 1) * 8);
+        const uint64_t *dbounds = st.up(bounds, (R + 1) * 8);
+        kiss_hip_chain *dchains = st.room<kiss_hip_chain>(true, cap * sizeof(kiss_hip_chain));
+        uint64_t *dcidx = st.room<uint64_t>(true, (V + 1) * 8);
+        uint32_t *dorigin = st.room<uint32_t>(origin != nullptr, cap * 4);
+        if (st.rc) return st.rc;
+        kiss_hip_rescue_report r{};
+        const int rc = kiss_hip_fmi_rescue_dev(ctx, dpairs, dhits, dhidx, Q, dalns, aln_count, dridx, n, dbounds, R, params, dchains, dcidx,
+                                               dorigin, cap, &r, nullptr);
+        if (report) *report = r;
+        if (rc) return rc;
+        st.down(chain_index, dcidx, (V + 1) * 8);
+        st.down(chains, dchains, r.chains * sizeof(kiss_hip_chain));
+        if (origin) st.down(origin, dorigin, r.chains * 4);
+        return st.rc;
+    });
 }
 
 int kiss_hip_fmi_aln_merge_dev(kiss_hip_ctx *ctx, const kiss_hip_aln *alns_a, const uint64_t *chain_index_a, const uint32_t *cigar_a,
@@ -694,25 +607,53 @@ int kiss_hip_fmi_aln_merge_host(const kiss_hip_aln *alns_a, const uint64_t *chai
         *report = kiss_hip_merge_report{};
         report->V = V;
     }
-    MergeHostArgs a{{alns_a, chain_index_a, cigar_a, cigar_index_a}, {alns_b, chain_index_b, cigar_b, cigar_index_b}, V, alns, aln_capacity,
-                    chain_index, source, cigar, cigar_index, cigar_capacity, report, 0, 0, 0, 0};
-    KTRY(merge_args_check(a.A, a.B, alns, chain_index, cigar, cigar_index, cigar_capacity));
+    const MergeIn A{alns_a, chain_index_a, cigar_a, cigar_index_a}, B{alns_b, chain_index_b, cigar_b, cigar_index_b};
+    KTRY(merge_args_check(A, B, alns, chain_index, cigar, cigar_index, cigar_capacity));
     if (V > 0x7FFFFFFFull) return KISS_HIP_E_UNSUPPORTED;
     if (!fm_index_ascending(chain_index_a, V, false) || !fm_index_ascending(chain_index_b, V, false)) return KISS_HIP_E_INVALID;
-    a.CA = chain_index_a[V] - chain_index_a[0]; // (alns_a and alns_b are indexed from 0, as the align call writes them)
-    a.CB = chain_index_b[V] - chain_index_b[0];
+    // (alns_a and alns_b are indexed from 0, as the align call writes them)
+    const uint64_t CA = chain_index_a[V] - chain_index_a[0], CB = chain_index_b[V] - chain_index_b[0], C = CA + CB;
     if (report) {
-        report->alignments_a = a.CA;
-        report->alignments_b = a.CB;
-        report->alignments = a.CA + a.CB;
+        report->alignments_a = CA;
+        report->alignments_b = CB;
+        report->alignments = C;
     }
-    if (a.CA > 0xFFFFFFFFull || a.CB > 0xFFFFFFFFull || a.CA + a.CB > 0xFFFFFFFFull) return KISS_HIP_E_UNSUPPORTED;
-    if (cigar) {
-        if (!fm_index_ascending(cigar_index_a, a.CA, false) || !fm_index_ascending(cigar_index_b, a.CB, false)) return KISS_HIP_E_INVALID;
-        a.OA = cigar_index_a[a.CA] - cigar_index_a[0];
-        a.OB = cigar_index_b[a.CB] - cigar_index_b[0];
+    if (CA > 0xFFFFFFFFull || CB > 0xFFFFFFFFull || C > 0xFFFFFFFFull) return KISS_HIP_E_UNSUPPORTED;
+    const bool ops = cigar != nullptr;
+    // (the ops are uploaded from the first one a set uses, its index from 0: the kernels see cigar_index[0] = 0)
+    std::vector<uint64_t> ia(ops ? CA + 1 : 0), ib(ops ? CB + 1 : 0);
+    if (ops) {
+        if (!fm_index_ascending(cigar_index_a, CA, false) || !fm_index_ascending(cigar_index_b, CB, false)) return KISS_HIP_E_INVALID;
+        for (uint64_t i = 0; i <= CA; i++) ia[i] = cigar_index_a[i] - cigar_index_a[0];
+        for (uint64_t i = 0; i <= CB; i++) ib[i] = cigar_index_b[i] - cigar_index_b[0];
     }
-    return kiss_cached_ctx_run(device, fm_host_max_n(0, a.CA + a.CB + 1, V + 1), merge_one_shot, &a);
+    const uint64_t OA = ops ? ia[CA] : 0, OB = ops ? ib[CB] : 0, O = OA + OB; // the ops of either set
+    return kiss_one_shot_cached(device, fm_host_max_n(0, C + 1, V + 1), [&](kiss_hip_ctx *ctx) -> int {
+        const uint64_t acap = aln_capacity < C ? aln_capacity : C, ocap = cigar_capacity < O ? cigar_capacity : O;
+        FmStage st(ctx);
+        const kiss_hip_aln *da = st.up(alns_a, CA * sizeof(kiss_hip_aln)), *db = st.up(alns_b, CB * sizeof(kiss_hip_aln));
+        const uint64_t *dia = st.up(chain_index_a, (V + 1) * 8), *dib = st.up(chain_index_b, (V + 1) * 8);
+        const uint32_t *dca = ops ? st.up(cigar_a + cigar_index_a[0], OA * 4) : nullptr;
+        const uint32_t *dcb = ops ? st.up(cigar_b + cigar_index_b[0], OB * 4) : nullptr;
+        const uint64_t *doa = ops ? st.up(ia.data(), (CA + 1) * 8) : nullptr, *dob = ops ? st.up(ib.data(), (CB + 1) * 8) : nullptr;
+        kiss_hip_aln *dalns = st.room<kiss_hip_aln>(true, acap * sizeof(kiss_hip_aln));
+        uint64_t *dcidx = st.room<uint64_t>(true, (V + 1) * 8);
+        uint32_t *dsrc = st.room<uint32_t>(source != nullptr, acap * 4);
+        uint32_t *dcig = st.room<uint32_t>(ops, ocap * 4);
+        uint64_t *doidx = st.room<uint64_t>(ops, (C + 1) * 8);
+        if (st.rc) return st.rc;
+        kiss_hip_merge_report r{};
+        const int rc = kiss_hip_fmi_aln_merge_dev(ctx, da, dia, dca, doa, db, dib, dcb, dob, V, dalns, acap, dcidx, dsrc, dcig, doidx,
+                                                  ops ? ocap : 0, &r, nullptr);
+        if (report) *report = r;
+        if (rc) return rc;
+        st.down(alns, dalns, C * sizeof(kiss_hip_aln));
+        st.down(chain_index, dcidx, (V + 1) * 8);
+        if (source) st.down(source, dsrc, C * 4);
+        if (ops) st.down(cigar_index, doidx, (C + 1) * 8);
+        if (ops) st.down(cigar, dcig, r.cigar_ops * 4);
+        return st.rc;
+    });
 }
 
 } // extern "C"

@@ -438,41 +438,35 @@ int kiss_hip_fmi_seeds_host(const kiss_hip_fmi_view_ex *fmi, const uint8_t *read
     const uint64_t r0 = Q ? read_index[0] : 0, read_bytes = Q ? read_index[Q] - r0 : 0;
     const uint64_t V = both_strands ? 2 * Q : Q, bases = both_strands ? 2 * read_bytes : read_bytes;
     if (seed_capacity > bases) seed_capacity = bases; // (always enough)
-    kiss_hip_ctx *ctx = nullptr;
+    std::vector<uint64_t> ridx(Q + 1, 0); // (the reads are copied from read_index[0] on)
+    if (Q)
+        for (uint64_t q = 0; q <= Q; q++) ridx[q] = read_index[q] - r0;
     // (the ends of a call are scanned in the ctx's scratch, its positions sorted in the LMS arrays)
-    int rc = kiss_hip_ctx_create(&ctx, device, fm_host_max_n(hv.n_sa, bases + 1, pos_capacity));
-    if (rc) return rc;
-    FmIndexOnDevice idx;
-    DevBuf dreads, dridx, dms, dseeds, dsidx, dpos, dpidx;
-    do {
-        if ((rc = idx.upload(ctx, hv, z.base)) || (rc = dreads.alloc(ctx, read_bytes)) || (rc = dridx.alloc(ctx, (Q + 1) * 8)) ||
-            (rc = dseeds.alloc(ctx, seed_capacity * 16)) || (rc = dsidx.alloc(ctx, (V + 1) * 8)) || (ms && (rc = dms.alloc(ctx, bases * 4))) ||
-            (rc = fm_h2d(ctx, dreads.p, reads + r0, read_bytes)))
-            break;
-        if (Q) { // (the reads were copied from read_index[0] on)
-            std::vector<uint64_t> ridx(read_index, read_index + Q + 1);
-            for (auto &x : ridx) x -= r0;
-            if ((rc = fm_h2d(ctx, dridx.p, ridx.data(), (Q + 1) * 8))) break;
-        }
+    return kiss_one_shot_own(device, fm_host_max_n(hv.n_sa, bases + 1, pos_capacity), [&](kiss_hip_ctx *ctx) -> int {
+        FmStage st(ctx);
         kiss_hip_fmi_view_ex v = *fmi;
-        v.base = idx.view;
+        v.base = fm_upload_index(st, hv, z.base);
         v.lookup = nullptr; // (the search does not use it)
-        if (all && ((rc = dpos.alloc(ctx, pos_capacity * 4)) || (rc = dpidx.alloc(ctx, (seed_capacity + 1) * 8)))) break;
+        const uint8_t *dreads = st.up(reads ? reads + r0 : nullptr, read_bytes);
+        const uint64_t *dridx = st.up(ridx.data(), (Q + 1) * 8);
+        uint32_t *dms = st.room<uint32_t>(ms != nullptr, bases * 4);
+        kiss_hip_fmi_seed *dseeds = st.room<kiss_hip_fmi_seed>(true, seed_capacity * 16);
+        uint64_t *dsidx = st.room<uint64_t>(true, (V + 1) * 8);
+        uint32_t *dpos = st.room<uint32_t>(all, pos_capacity * 4);
+        uint64_t *dpidx = st.room<uint64_t>(all, (seed_capacity + 1) * 8);
+        if (st.rc) return st.rc;
         kiss_hip_fmi_seed_report r{};
-        rc = kiss_hip_fmi_seeds_dev(ctx, &v, (const uint8_t *)dreads.p, (const uint64_t *)dridx.p, Q, min_len, max_len, max_occ,
-                                    both_strands, ms ? (uint32_t *)dms.p : nullptr, (kiss_hip_fmi_seed *)dseeds.p, (uint64_t *)dsidx.p,
-                                    seed_capacity, all ? (uint32_t *)dpos.p : nullptr, all ? (uint64_t *)dpidx.p : nullptr,
-                                    all ? pos_capacity : 0, &r, nullptr);
+        const int rc = kiss_hip_fmi_seeds_dev(ctx, &v, dreads, dridx, Q, min_len, max_len, max_occ, both_strands, dms, dseeds, dsidx,
+                                              seed_capacity, dpos, dpidx, all ? pos_capacity : 0, &r, nullptr);
         if (report) *report = r;
-        if (rc) break;
-        rc = fm_d2h(ctx, seed_index, dsidx.p, (V + 1) * 8);
-        if (!rc) rc = fm_d2h(ctx, seeds, dseeds.p, r.seeds * 16);
-        if (!rc && ms) rc = fm_d2h(ctx, ms, dms.p, bases * 4);
-        if (!rc && all) rc = fm_d2h(ctx, pos_index, dpidx.p, (r.seeds + 1) * 8);
-        if (!rc && all) rc = fm_d2h(ctx, positions, dpos.p, r.positions * 4);
-    } while (0);
-    kiss_hip_ctx_destroy(ctx);
-    return rc;
+        if (rc) return rc;
+        st.down(seed_index, dsidx, (V + 1) * 8);
+        st.down(seeds, dseeds, r.seeds * 16);
+        if (ms) st.down(ms, dms, bases * 4);
+        if (all) st.down(pos_index, dpidx, (r.seeds + 1) * 8);
+        if (all) st.down(positions, dpos, r.positions * 4);
+        return st.rc;
+    });
 }
 
 } // extern "C"

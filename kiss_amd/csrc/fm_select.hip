@@ -428,45 +428,6 @@ int select_args_check(const kiss_hip_aln *alns, const uint64_t *chain_index, con
     return KISS_HIP_OK;
 }
 
-struct SelectHostArgs {
-    const kiss_hip_aln *alns;
-    const uint64_t *chain_index, *read_index;
-    uint64_t Q;
-    int both;
-    const uint64_t *bounds;
-    uint64_t R;
-    const kiss_hip_select_params *params;
-    kiss_hip_hit *hits;
-    uint64_t *hit_index;
-    uint64_t hit_capacity;
-    kiss_hip_select_report *report;
-    uint64_t V, C;
-};
-
-int select_one_shot(kiss_hip_ctx *ctx, void *arg)
-{
-    const SelectHostArgs &a = *(const SelectHostArgs *)arg;
-    const uint64_t hcap = a.hit_capacity < a.C ? a.hit_capacity : a.C; // (no more hits than alignments)
-    DevBuf dalns, dcidx, dridx, dbounds, dhits, dhidx;
-    int rc;
-    if ((rc = dalns.alloc(ctx, a.C * sizeof(kiss_hip_aln))) || (rc = dcidx.alloc(ctx, (a.V + 1) * 8)) ||
-        (rc = dridx.alloc(ctx, (a.Q + 1) * 8)) || (a.bounds && (rc = dbounds.alloc(ctx, (a.R + 1) * 8))) ||
-        (rc = dhits.alloc(ctx, hcap * sizeof(kiss_hip_hit))) || (rc = dhidx.alloc(ctx, (a.Q + 1) * 8)))
-        return rc;
-    KTRY(fm_h2d(ctx, dcidx.p, a.chain_index, (a.V + 1) * 8));
-    KTRY(fm_h2d(ctx, dridx.p, a.read_index, (a.Q + 1) * 8));
-    if (a.bounds) KTRY(fm_h2d(ctx, dbounds.p, a.bounds, (a.R + 1) * 8));
-    KTRY(fm_h2d(ctx, dalns.p, a.alns, a.C * sizeof(kiss_hip_aln)));
-    kiss_hip_select_report r{};
-    rc = kiss_hip_fmi_select_dev(ctx, (const kiss_hip_aln *)dalns.p, (const uint64_t *)dcidx.p, (const uint64_t *)dridx.p, a.Q, a.both,
-                                 a.bounds ? (const uint64_t *)dbounds.p : nullptr, a.R, a.params, (kiss_hip_hit *)dhits.p,
-                                 (uint64_t *)dhidx.p, hcap, &r, nullptr);
-    if (a.report) *a.report = r;
-    if (rc) return rc;
-    KTRY(fm_d2h(ctx, a.hit_index, dhidx.p, (a.Q + 1) * 8));
-    return fm_d2h(ctx, a.hits, dhits.p, r.hits * sizeof(kiss_hip_hit));
-}
-
 } // namespace
 
 extern "C" {
@@ -515,12 +476,29 @@ int kiss_hip_fmi_select_host(const kiss_hip_aln *alns, const uint64_t *chain_ind
     KTRY(select_args_check(alns, chain_index, read_index, bounds, R, params, hits, hit_index));
     if (V > 0x7FFFFFFFull) return KISS_HIP_E_UNSUPPORTED;
     if (!fm_index_ascending(read_index, Q, true) || !fm_index_ascending(chain_index, V, false)) return KISS_HIP_E_INVALID;
-    SelectHostArgs a{alns, chain_index, read_index, Q, both_strands ? 1 : 0, bounds, R, params, hits, hit_index, hit_capacity, report, V, 0};
-    a.C = chain_index[V] - chain_index[0]; // (alns is indexed from 0, as the align call writes it)
-    if (report) report->alignments = a.C;
-    if (a.C > 0xFFFFFFFFull) return KISS_HIP_E_UNSUPPORTED;
+    const uint64_t C = chain_index[V] - chain_index[0]; // (alns is indexed from 0, as the align call writes it)
+    if (report) report->alignments = C;
+    if (C > 0xFFFFFFFFull) return KISS_HIP_E_UNSUPPORTED;
     // the alignments of a call are sorted in the ctx's LMS arrays and the reads scanned in its scratch
-    return kiss_cached_ctx_run(device, fm_host_max_n(0, a.C + 1, V + 1), select_one_shot, &a);
+    return kiss_one_shot_cached(device, fm_host_max_n(0, C + 1, V + 1), [&](kiss_hip_ctx *ctx) -> int {
+        const uint64_t hcap = hit_capacity < C ? hit_capacity : C; // (no more hits than alignments)
+        FmStage st(ctx);
+        const kiss_hip_aln *dalns = st.up(alns, C * sizeof(kiss_hip_aln));
+        const uint64_t *dcidx = st.up(chain_index, (V + 1) * 8);
+        const uint64_t *dridx = st.up(read_index, (Q + 1) * 8);
+        const uint64_t *dbounds = st.up(bounds, (R + 1) * 8);
+        kiss_hip_hit *dhits = st.room<kiss_hip_hit>(true, hcap * sizeof(kiss_hip_hit));
+        uint64_t *dhidx = st.room<uint64_t>(true, (Q + 1) * 8);
+        if (st.rc) return st.rc;
+        kiss_hip_select_report r{};
+        const int rc = kiss_hip_fmi_select_dev(ctx, dalns, dcidx, dridx, Q, both_strands ? 1 : 0, dbounds, R, params, dhits, dhidx, hcap, &r,
+                                               nullptr);
+        if (report) *report = r;
+        if (rc) return rc;
+        st.down(hit_index, dhidx, (Q + 1) * 8);
+        st.down(hits, dhits, r.hits * sizeof(kiss_hip_hit));
+        return st.rc;
+    });
 }
 
 } // extern "C"

@@ -12,7 +12,7 @@
 //            is a proper prefix of another sorts first), stable LSD radix sort of (key, p) over 63 bits;
 //   SA[0] = n, SA[1 + i] = sorted position i, group heads where the key changes;
 //   rank doubling from h = 7 on the tied suffixes (lms_sort.hip: kiss_exact_refine with the heads given).
-#include "kiss_internal.hpp"
+#include "fm_internal.hpp" // (FmStage: the arrays of the one-shot entry)
 #include <cstdlib>
 #include <cstring>
 
@@ -222,27 +222,15 @@ int kiss_hip_suffix_sort_u8(const uint8_t *S, uint64_t n, uint32_t *SA, int devi
         SA[0] = 0;
         return KISS_HIP_OK;
     }
-    kiss_hip_ctx *ctx = nullptr;
-    int rc = kiss_hip_ctx_create(&ctx, device, n);
-    if (rc) return rc;
-    uint8_t *d_S = nullptr;
-    uint32_t *d_SA = nullptr;
-    do {
-        if (hipMalloc((void **)&d_S, n) != hipSuccess || hipMalloc((void **)&d_SA, (n + 1) * sizeof(uint32_t)) != hipSuccess) {
-            rc = KISS_HIP_E_NOMEM;
-            break;
-        }
-        if (hipMemcpy(d_S, S, n, hipMemcpyHostToDevice) != hipSuccess) {
-            rc = KISS_HIP_E_HIP;
-            break;
-        }
-        if ((rc = kiss_hip_ctx_suffix_sort_u8_dev(ctx, d_S, n, d_SA, nullptr))) break;
-        if (hipMemcpy(SA, d_SA, (n + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) rc = KISS_HIP_E_HIP;
-    } while (0);
-    if (d_S) (void)hipFree(d_S);
-    if (d_SA) (void)hipFree(d_SA);
-    kiss_hip_ctx_destroy(ctx);
-    return rc;
+    return kiss_one_shot_own(device, n, [&](kiss_hip_ctx *ctx) -> int {
+        FmStage st(ctx);
+        const uint8_t *d_S = st.up(S, n);
+        uint32_t *d_SA = st.room<uint32_t>(true, (n + 1) * sizeof(uint32_t));
+        if (st.rc) return st.rc;
+        KTRY(kiss_hip_ctx_suffix_sort_u8_dev(ctx, d_S, n, d_SA, nullptr));
+        st.down(SA, d_SA, (n + 1) * sizeof(uint32_t));
+        return st.rc;
+    });
 }
 
 } // extern "C"

@@ -434,6 +434,23 @@ int kiss_xfer_h2d(kiss_hip_ctx *ctx, void *d_dst, const void *h_src, uint64_t by
 int kiss_io_reserve(kiss_hip_ctx *ctx, uint64_t n);
 // api.hip: fn(ctx, arg) on the one-shot context the library keeps for `device`, grown to n bases, under its lock
 int kiss_cached_ctx_run(int device, uint64_t n, int (*fn)(kiss_hip_ctx *, void *), void *arg);
+// the body of a one-shot entry, f(ctx), on that cached context ...
+template <class F>
+static inline int kiss_one_shot_cached(int device, uint64_t max_n, const F &f)
+{
+    return kiss_cached_ctx_run(device, max_n, [](kiss_hip_ctx *ctx, void *p) { return (*static_cast<const F *>(p))(ctx); }, (void *)&f);
+}
+// ... or on a context of the call's own, destroyed behind it
+template <class F>
+static inline int kiss_one_shot_own(int device, uint64_t max_n, const F &f)
+{
+    kiss_hip_ctx *ctx = nullptr;
+    int rc = kiss_hip_ctx_create(&ctx, device, max_n);
+    if (rc) return rc;
+    rc = f(ctx);
+    kiss_hip_ctx_destroy(ctx);
+    return rc;
+}
 int kiss_xfer_d2h(kiss_hip_ctx *ctx, void *h_dst, const void *d_src, uint64_t bytes);
 void kiss_xfer_free(kiss_hip_ctx *ctx);
 // induced sort sweeps -> d_SA

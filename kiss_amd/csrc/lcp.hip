@@ -531,38 +531,6 @@ int lcp_dev(kiss_hip_ctx *ctx, const uint8_t *d_S, uint64_t n, const uint32_t *d
 
 // host-pointer one-shot on the device's cached context: S (and SA when given) up, SA down when it was sorted here,
 // LCP computed over the device copy of SA in place and brought down
-struct OneShot {
-    const uint8_t *S;
-    uint64_t n;
-    const uint32_t *SA_in;
-    uint32_t *SA_out, *LCP;
-    bool bytes;
-};
-
-int lcp_one_shot(kiss_hip_ctx *ctx, void *arg)
-{
-    const OneShot &a = *static_cast<const OneShot *>(arg);
-    const uint64_t sa_bytes = (a.n + 1) * sizeof(uint32_t);
-    KCHECK(hipSetDevice(ctx->device));
-    if (!a.SA_in && !a.bytes) {
-        // the DNA sort's own host-pointer path: S goes up into ctx->io_S, the exact SA stays in ctx->io_SA as well
-        uint32_t *dst = a.SA_out ? a.SA_out : a.LCP;
-        KTRY(kiss_hip_ctx_suffix_sort_dna_u32(ctx, a.S, a.n, 0xFFFFFFFFu, KISS_HIP_ALGO_PREFIX_DOUBLING, dst));
-    } else {
-        KTRY(kiss_io_reserve(ctx, a.n));
-        KTRY(kiss_xfer_h2d(ctx, ctx->io_S, a.S, a.n));
-        if (a.SA_in) {
-            KTRY(kiss_xfer_h2d(ctx, ctx->io_SA, a.SA_in, sa_bytes));
-        } else {
-            KTRY(kiss_hip_ctx_suffix_sort_u8_dev(ctx, ctx->io_S, a.n, ctx->io_SA, nullptr));
-            if (a.SA_out) KTRY(kiss_xfer_d2h(ctx, a.SA_out, ctx->io_SA, sa_bytes));
-        }
-        if (a.SA_in && a.SA_out && a.SA_out != a.SA_in) std::memcpy(a.SA_out, a.SA_in, sa_bytes);
-    }
-    KTRY(lcp_dev(ctx, ctx->io_S, a.n, ctx->io_SA, ctx->io_SA, nullptr, nullptr, a.bytes));
-    return kiss_xfer_d2h(ctx, a.LCP, ctx->io_SA, sa_bytes);
-}
-
 int lcp_host(const uint8_t *S, uint64_t n, const uint32_t *SA_or_null, uint32_t *SA_out, uint32_t *LCP, int device, bool bytes)
 {
     if (!LCP || (n && !S)) return KISS_HIP_E_INVALID;
@@ -573,8 +541,27 @@ int lcp_host(const uint8_t *S, uint64_t n, const uint32_t *SA_or_null, uint32_t 
         LCP[0] = 0;
         return KISS_HIP_OK;
     }
-    OneShot a{S, n, SA_or_null, SA_out, LCP, bytes};
-    return kiss_cached_ctx_run(device, n, lcp_one_shot, &a);
+    return kiss_one_shot_cached(device, n, [&](kiss_hip_ctx *ctx) -> int {
+        const uint64_t sa_bytes = (n + 1) * sizeof(uint32_t);
+        KCHECK(hipSetDevice(ctx->device));
+        if (!SA_or_null && !bytes) {
+            // the DNA sort's own host-pointer path: S goes up into ctx->io_S, the exact SA stays in ctx->io_SA as well
+            uint32_t *dst = SA_out ? SA_out : LCP;
+            KTRY(kiss_hip_ctx_suffix_sort_dna_u32(ctx, S, n, 0xFFFFFFFFu, KISS_HIP_ALGO_PREFIX_DOUBLING, dst));
+        } else {
+            KTRY(kiss_io_reserve(ctx, n));
+            KTRY(kiss_xfer_h2d(ctx, ctx->io_S, S, n));
+            if (SA_or_null) {
+                KTRY(kiss_xfer_h2d(ctx, ctx->io_SA, SA_or_null, sa_bytes));
+            } else {
+                KTRY(kiss_hip_ctx_suffix_sort_u8_dev(ctx, ctx->io_S, n, ctx->io_SA, nullptr));
+                if (SA_out) KTRY(kiss_xfer_d2h(ctx, SA_out, ctx->io_SA, sa_bytes));
+            }
+            if (SA_or_null && SA_out && SA_out != SA_or_null) std::memcpy(SA_out, SA_or_null, sa_bytes);
+        }
+        KTRY(lcp_dev(ctx, ctx->io_S, n, ctx->io_SA, ctx->io_SA, nullptr, nullptr, bytes));
+        return kiss_xfer_d2h(ctx, LCP, ctx->io_SA, sa_bytes);
+    });
 }
 
 } // namespace

@@ -518,33 +518,6 @@ kiss_hip_reads_report empty_report(int format)
     return r;
 }
 
-int parse_one_shot(kiss_hip_ctx *ctx, void *arg)
-{
-    const ParseArgs &a = *(const ParseArgs *)arg;
-    const bool names = a.name_off != nullptr;
-    DevBuf draw, dcodes, dqual, didx, dnoff, dnlen;
-    int rc;
-    if ((rc = draw.alloc(ctx, a.bytes)) || (rc = dcodes.alloc(ctx, a.bases_capacity)) || (rc = dqual.alloc(ctx, a.qual ? a.bases_capacity : 0)) ||
-        (rc = didx.alloc(ctx, (a.reads_capacity + 1) * 8)) || (rc = dnoff.alloc(ctx, names ? a.reads_capacity * 8 : 0)) ||
-        (rc = dnlen.alloc(ctx, names ? a.reads_capacity * 4 : 0)))
-        return rc;
-    KTRY(fm_h2d(ctx, draw.p, a.raw, a.bytes));
-    kiss_hip_reads_report r{};
-    rc = kiss_hip_reads_parse_dev(ctx, (const uint8_t *)draw.p, a.bytes, a.format, (uint8_t *)dcodes.p, a.qual ? (uint8_t *)dqual.p : nullptr,
-                                  a.bases_capacity, (uint64_t *)didx.p, names ? (uint64_t *)dnoff.p : nullptr, names ? (uint32_t *)dnlen.p : nullptr,
-                                  a.reads_capacity, &r, nullptr);
-    if (a.report) *a.report = r;
-    if (rc) return rc;
-    KTRY(fm_d2h(ctx, a.codes, dcodes.p, r.bases));
-    if (a.qual && r.has_qual) KTRY(fm_d2h(ctx, a.qual, dqual.p, r.bases));
-    KTRY(fm_d2h(ctx, a.read_index, didx.p, (r.reads + 1) * 8));
-    if (names) {
-        KTRY(fm_d2h(ctx, a.name_off, dnoff.p, r.reads * 8));
-        KTRY(fm_d2h(ctx, a.name_len, dnlen.p, r.reads * 4));
-    }
-    return KISS_HIP_OK;
-}
-
 // ---- interleave ------------------------------------------------------------------------------------------------------------
 // an index that does not start at 0 or decreases; the totals
 __global__ __launch_bounds__(RD_THREADS) void k_il_check(const uint64_t *__restrict__ ia, const uint64_t *__restrict__ ib, uint64_t P,
@@ -646,35 +619,6 @@ int interleave_steps(kiss_hip_ctx *ctx, const InterleaveArgs &a)
     return KISS_HIP_OK;
 }
 
-int interleave_one_shot(kiss_hip_ctx *ctx, void *arg)
-{
-    const InterleaveArgs &a = *(const InterleaveArgs *)arg;
-    const uint64_t P = a.P_a, na = a.index_a[P], nb = a.index_b[P];
-    DevBuf dca, dia, dqa, dcb, dib, dqb, dc, di, dq;
-    int rc;
-    if ((rc = dca.alloc(ctx, na)) || (rc = dia.alloc(ctx, (P + 1) * 8)) || (rc = dqa.alloc(ctx, a.qual ? na : 0)) || (rc = dcb.alloc(ctx, nb)) ||
-        (rc = dib.alloc(ctx, (P + 1) * 8)) || (rc = dqb.alloc(ctx, a.qual ? nb : 0)) || (rc = dc.alloc(ctx, a.bases_capacity)) ||
-        (rc = di.alloc(ctx, (2 * P + 1) * 8)) || (rc = dq.alloc(ctx, a.qual ? a.bases_capacity : 0)))
-        return rc;
-    KTRY(fm_h2d(ctx, dca.p, a.codes_a, na));
-    KTRY(fm_h2d(ctx, dia.p, a.index_a, (P + 1) * 8));
-    KTRY(fm_h2d(ctx, dcb.p, a.codes_b, nb));
-    KTRY(fm_h2d(ctx, dib.p, a.index_b, (P + 1) * 8));
-    if (a.qual) {
-        KTRY(fm_h2d(ctx, dqa.p, a.qual_a, na));
-        KTRY(fm_h2d(ctx, dqb.p, a.qual_b, nb));
-    }
-    uint64_t total = 0;
-    rc = kiss_hip_reads_interleave_dev(ctx, (const uint8_t *)dca.p, (const uint64_t *)dia.p, a.qual ? (const uint8_t *)dqa.p : nullptr, P,
-                                       (const uint8_t *)dcb.p, (const uint64_t *)dib.p, a.qual ? (const uint8_t *)dqb.p : nullptr, P, (uint8_t *)dc.p,
-                                       (uint64_t *)di.p, a.qual ? (uint8_t *)dq.p : nullptr, a.bases_capacity, &total, nullptr);
-    if (a.bases_out) *a.bases_out = total;
-    if (rc) return rc;
-    KTRY(fm_d2h(ctx, a.codes, dc.p, total));
-    if (a.qual) KTRY(fm_d2h(ctx, a.qual, dq.p, total));
-    return fm_d2h(ctx, a.read_index, di.p, (2 * P + 1) * 8);
-}
-
 } // namespace
 
 extern "C" {
@@ -709,9 +653,29 @@ int kiss_hip_reads_parse_host(const uint8_t *raw, uint64_t bytes, int format, ui
                               int device)
 {
     if (report) *report = empty_report(format);
-    ParseArgs a{raw, bytes, format, codes, qual, bases_capacity, read_index, name_off, name_len, reads_capacity, report};
-    KTRY(parse_args_check(a));
-    return kiss_cached_ctx_run(device, fm_host_max_n(0, bytes + 2), parse_one_shot, &a);
+    KTRY(parse_args_check(ParseArgs{raw, bytes, format, codes, qual, bases_capacity, read_index, name_off, name_len, reads_capacity, report}));
+    return kiss_one_shot_cached(device, fm_host_max_n(0, bytes + 2), [&](kiss_hip_ctx *ctx) -> int {
+        const bool names = name_off != nullptr;
+        FmStage st(ctx);
+        const uint8_t *draw = st.up(raw, bytes);
+        uint8_t *dcodes = st.room<uint8_t>(true, bases_capacity);
+        uint8_t *dqual = st.room<uint8_t>(qual != nullptr, bases_capacity);
+        uint64_t *didx = st.room<uint64_t>(true, (reads_capacity + 1) * 8);
+        uint64_t *dnoff = st.room<uint64_t>(names, reads_capacity * 8);
+        uint32_t *dnlen = st.room<uint32_t>(names, reads_capacity * 4);
+        if (st.rc) return st.rc;
+        kiss_hip_reads_report r{};
+        const int rc = kiss_hip_reads_parse_dev(ctx, draw, bytes, format, dcodes, dqual, bases_capacity, didx, dnoff, dnlen, reads_capacity, &r,
+                                                nullptr);
+        if (report) *report = r;
+        if (rc) return rc;
+        st.down(codes, dcodes, r.bases);
+        if (qual && r.has_qual) st.down(qual, dqual, r.bases);
+        st.down(read_index, didx, (r.reads + 1) * 8);
+        if (names) st.down(name_off, dnoff, r.reads * 8);
+        if (names) st.down(name_len, dnlen, r.reads * 4);
+        return st.rc;
+    });
 }
 
 int kiss_hip_reads_interleave_dev(kiss_hip_ctx *ctx, const uint8_t *codes_a, const uint64_t *index_a, const uint8_t *qual_a, uint64_t P_a,
@@ -733,11 +697,29 @@ int kiss_hip_reads_interleave_host(const uint8_t *codes_a, const uint64_t *index
                                    uint64_t bases_capacity, uint64_t *bases_out, int device)
 {
     if (bases_out) *bases_out = 0;
-    InterleaveArgs a{codes_a, index_a, qual_a, P_a, codes_b, index_b, qual_b, P_b, codes, read_index, qual, bases_capacity, bases_out};
-    KTRY(interleave_args_check(a));
+    KTRY(interleave_args_check(
+        InterleaveArgs{codes_a, index_a, qual_a, P_a, codes_b, index_b, qual_b, P_b, codes, read_index, qual, bases_capacity, bases_out}));
     if (index_a[0] != 0 || index_b[0] != 0 || !fm_index_ascending(index_a, P_a, false) || !fm_index_ascending(index_b, P_b, false))
         return KISS_HIP_E_INVALID;
-    return kiss_cached_ctx_run(device, fm_host_max_n(0, 0), interleave_one_shot, &a);
+    return kiss_one_shot_cached(device, fm_host_max_n(0, 0), [&](kiss_hip_ctx *ctx) -> int {
+        const uint64_t P = P_a, na = index_a[P], nb = index_b[P];
+        FmStage st(ctx);
+        const uint8_t *dca = st.up(codes_a, na), *dcb = st.up(codes_b, nb);
+        const uint64_t *dia = st.up(index_a, (P + 1) * 8), *dib = st.up(index_b, (P + 1) * 8);
+        const uint8_t *dqa = st.up(qual_a, na), *dqb = st.up(qual_b, nb); // (all three of the qualities, or none)
+        uint8_t *dc = st.room<uint8_t>(true, bases_capacity);
+        uint64_t *di = st.room<uint64_t>(true, (2 * P + 1) * 8);
+        uint8_t *dq = st.room<uint8_t>(qual != nullptr, bases_capacity);
+        if (st.rc) return st.rc;
+        uint64_t total = 0;
+        const int rc = kiss_hip_reads_interleave_dev(ctx, dca, dia, dqa, P, dcb, dib, dqb, P, dc, di, dq, bases_capacity, &total, nullptr);
+        if (bases_out) *bases_out = total;
+        if (rc) return rc;
+        st.down(codes, dc, total);
+        if (qual) st.down(qual, dq, total);
+        st.down(read_index, di, (2 * P + 1) * 8);
+        return st.rc;
+    });
 }
 
 } // extern "C"

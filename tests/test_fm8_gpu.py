@@ -282,6 +282,26 @@ def test_host_entry_points_equal_the_device_ones(sa_intv):
         fm.close()
 
 
+def test_host_query_empty_batch_and_size_then_fill():
+    import kiss_amd
+    S = b"abracadabra" * 50
+    arr, sigma, pri, _lib = host_build(S, 4)
+    v = host_view(arr, len(S) + 1, sigma, pri, 4, _lib)
+    index, tot, chk = np.full(1, 7, np.uint64), ctypes.c_uint64(9), ctypes.c_uint64(9)
+    pos = np.zeros(1, np.uint32)
+    rc = kiss_amd.load().kiss_hip_fmi8_query_host(ctypes.byref(v), None, None, 0, None, None, ctypes.byref(tot), ctypes.byref(chk),
+                                                  _np_ptr(pos), _np_ptr(index), 0, None, 0)  # Q = 0: index[0] = 0
+    assert rc == 0 and index.tolist() == [0] and (tot.value, chk.value) == (0, 0)
+    pats = [b"a", b"zz", b"abra"]  # many hits, none, some
+    want = [m.brute(S, p) for p in pats]
+    total = sum(len(w) for w in want)
+    res = host_query(v, pats, True, capacity=0)  # the sizing call: the total comes back
+    assert res["rc"] == _lib.KISS_HIP_E_INVALID and res["total_hits"] == total and res["report"]["hits"] == total
+    res = host_query(v, pats, True, capacity=total)
+    assert res["rc"] == 0 and res["index"].tolist() == np.concatenate([[0], np.cumsum([len(w) for w in want])]).tolist()
+    assert res["positions"].tolist() == [p for w in want for p in w]
+
+
 def test_error_codes():
     import torch
     import kiss_amd

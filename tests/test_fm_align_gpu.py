@@ -210,6 +210,9 @@ def test_reads_without_chains_an_offset_index_and_empty_batches():
     quads = unused + [(0, 100, 200, 300), (5, 90, 205, 290), (0, 100, 1000, 1100), (0, 100, 800, 900)]
     want = run(S, reads, quads, [3, 3, 6, 6, 6, 7])
     assert want["alignments"].shape[0] == 4 and want["alignments"][3, 0] > 50
+    res = kiss_amd.align_chains(S, reads, np.asarray(quads, np.int64), [3, 3, 6, 6, 6, 7], want_cigar=False)  # the records alone
+    assert "cigar" not in res and "cigar_index" not in res
+    check(res, want, cigar=False)
     # no chains at all, and no reads at all
     res = kiss_amd.align_chains(S, reads, np.zeros((0, 4), np.int64), [0] * 6)
     assert res["alignments"].shape == (0,) and list(res["cigar_index"]) == [0] and res["report"]["chains"] == 0

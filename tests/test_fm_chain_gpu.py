@@ -251,6 +251,9 @@ def test_error_contract_of_the_c_call():
     assert rep.dp_pairs == want["dp_pairs"] and rep.best_score == want["best_score"] and rep.ms_total > 0
     rc, rep, chains, cidx, anc, aidx = raw_dev(start, length, sidx, pos, pidx, n, None, **params)
     assert rc == 0 and anc is None and np.array_equal(chains.view(np.uint32).astype(np.int64), want["chains"])
+    res = kiss_amd.chain_seeds(np.stack([start, length], axis=1), sidx, pos, pidx, want_anchors=False, **params)  # (the host entry)
+    assert "anchors" not in res and "anchor_index" not in res
+    check(res, want, anchors=False)
     # a seed_index that decreases, a pos_index that decreases, a located seed of length 0
     down = sidx.copy()
     down[2] = down[1] - 1

@@ -210,6 +210,54 @@ def test_error_contract_of_the_c_call():
         g.close()
 
 
+def host_view(f):
+    """the arrays of index f in host memory and a kiss_hip_fmi_view over them (sa_intv == 1: no b / b_occ) -> view, arrays"""
+    from kiss_amd import _lib
+    v = _lib.FmiView()
+    v.n_sa, v.pri, v.sa_intv = f.N, f.pri, f.sa_intv
+    for c in range(4):
+        v.cnt[c] = int(f.cnt[c])
+    arrays = {k: getattr(f, k).cpu().numpy() for k in ("bwt", "occ1", "occ2", "sa", "b", "b_occ") if getattr(f, k) is not None}
+    for k, a in arrays.items():
+        setattr(v, k, a.ctypes.data)
+    return v, arrays
+
+
+@pytest.mark.parametrize("sa_intv", (1, 4))
+def test_host_entry_empty_batch_counts_alone_and_size_then_fill(sa_intv):
+    """kiss_hip_fmi_query_mm_host on host copies of the index (with and without the sampling bit-vector) against the text"""
+    from kiss_amd import _lib
+    lib = _lib.load()
+    f = index_of("genome", sa_intv)
+    pats, want = case("genome", 20, 2)
+    pats = np.ascontiguousarray(pats, np.uint8)
+    Q, L = pats.shape
+    total = int(want[0].sum())
+    assert total > 2 and (want[0].sum(axis=1) == 0).any() and (want[0].sum(axis=1) > 1).any()  # no hit; several
+    v, arrays = host_view(f)
+
+    def call(Q, capacity):
+        """capacity None: counts alone"""
+        counts, idx = np.full((Q, 3), 7, np.uint32), np.full(Q + 1, 7, np.uint64)
+        pos, mis = np.zeros(max(capacity or 0, 1), np.uint32), np.zeros(max(capacity or 0, 1), np.uint8)
+        rep = _lib.FmiMmReport()
+        outs = (pos.ctypes.data, mis.ctypes.data, idx.ctypes.data, capacity) if capacity is not None else (None, None, None, 0)
+        rc = lib.kiss_hip_fmi_query_mm_host(ctypes.byref(v), pats.ctypes.data if Q else None, L, Q, 2, counts.ctypes.data if Q else None,
+                                            *outs, ctypes.byref(rep), 0)
+        return rc, rep, counts, pos, mis, idx
+
+    rc, rep, counts, pos, mis, idx = call(0, 0)  # the empty batch: index[0] = 0
+    assert rc == 0 and idx.tolist() == [0] and sum(int(x) for x in rep.hits) == 0
+    rc, rep, counts, *_ = call(Q, None)
+    assert rc == 0 and np.array_equal(counts.astype(np.int64), want[0]) and [int(x) for x in rep.hits][:3] == want[0].sum(axis=0).tolist()
+    rc, rep, *_ = call(Q, 0)  # the sizing call: the totals come back
+    assert rc == _lib.KISS_HIP_E_INVALID and sum(int(x) for x in rep.hits) == total
+    rc, rep, counts, pos, mis, idx = call(Q, total)
+    assert rc == 0 and rep.walk_failures == 0 and rep.checksum == int(want[1].sum())
+    assert np.array_equal(counts.astype(np.int64), want[0]) and np.array_equal(idx.astype(np.int64), want[3])
+    assert np.array_equal(pos.astype(np.int64), want[1]) and np.array_equal(mis.astype(np.int64), want[2])
+
+
 @functools.lru_cache(maxsize=None)
 def large():
     import kiss_amd

@@ -215,6 +215,72 @@ def test_4_0_through_the_new_entry_points(oracle):
     old.close()
 
 
+@pytest.mark.parametrize("sa_intv", (1, 4))
+def test_host_entries_build_and_query_equal_the_model(sa_intv):
+    """kiss_hip_fmi_build_ex_host (sorting itself, and from a suffix array) and kiss_hip_fmi_query_ex_host on its arrays, with and
+    without the sampling bit-vector: the empty batch, the call without any optional output, the call with all of them"""
+    from kiss_amd import _lib
+    lib = _lib.load()
+    n, lookup_len, L, Q = 4095, 3, 7, 64
+    S, SA = text_and_sa("iid", n, 7)
+    m = FmModel(S, SA, sa_intv, lookup_len)
+    z = _lib.FmiSizesEx()
+    assert lib.kiss_hip_fmi_sizes_ex_for(n, sa_intv, lookup_len, ctypes.byref(z)) == 0
+    Sc, SAc = np.ascontiguousarray(S), np.ascontiguousarray(SA, np.uint32)
+    assert SAc.size == n + 1
+
+    def build(sa):
+        a = {"bwt": np.zeros(z.base.bwt_bytes, np.uint8), "occ1": np.zeros(z.base.occ1_entries, np.uint32),
+             "occ2": np.zeros(z.base.occ2_bytes, np.uint8), "sa": np.zeros(z.base.sa_entries, np.uint32),
+             "b": np.zeros(z.base.b_words, np.uint64), "b_occ": np.zeros(z.base.b_occ_entries, np.uint32),
+             "lookup": np.zeros(z.lookup_entries, np.uint32)}
+        cnt, pri = (ctypes.c_uint32 * 4)(), ctypes.c_uint32()
+        p = {k: x.ctypes.data if x.size else None for k, x in a.items()}  # (sa_intv == 1: no b / b_occ)
+        assert lib.kiss_hip_fmi_build_ex_host(Sc.ctypes.data, n, sa.ctypes.data if sa is not None else None, sa_intv, lookup_len, p["bwt"],
+                                              p["occ1"], p["occ2"], p["sa"], p["b"], p["b_occ"], p["lookup"], ctypes.addressof(cnt),
+                                              ctypes.addressof(pri), 0) == 0
+        return a, list(cnt), pri.value
+
+    a, cnt, pri = build(None)
+    a2, cnt2, pri2 = build(SAc)
+    assert (cnt, pri) == (cnt2, pri2) and all(np.array_equal(a[k], a2[k]) for k in a)
+    import kiss_amd.fm_index as fm
+    f = fm.FMIndex(sa_intv=sa_intv, lookup_len=lookup_len).build(S, sa=SA)  # the device entry (its bytes: test_fmi_bytes_equal_the_model)
+    assert cnt == f.cnt.tolist() and pri == f.pri
+    for k, x in a.items():
+        assert np.array_equal(x, getattr(f, k).cpu().numpy().view(x.dtype)[:x.size]) if x.size else getattr(f, k) is None, k
+    f.close()
+    v = _lib.FmiViewEx()
+    v.base.n_sa, v.base.pri, v.base.sa_intv, v.lookup_len, v.lookup = n + 1, pri, sa_intv, lookup_len, a["lookup"].ctypes.data
+    for c in range(4):
+        v.base.cnt[c] = cnt[c]
+    for k in ("bwt", "occ1", "occ2", "sa", "b", "b_occ"):
+        setattr(v.base, k, a[k].ctypes.data if a[k].size else None)
+    pats = patterns_of(S, Q, L, 3, mut=0.3)
+    want = m.query_batch(pats, stop_cnt=0)
+    hits = (want["end"] - want["beg"]).astype(np.int64)
+    assert (hits == 0).any() and (hits > 1).any()
+
+    def query(Q, optional, cap):
+        beg, end, offs = np.full(Q + 1, 7, np.uint32), np.full(Q + 1, 7, np.uint32), np.full(Q + 1, 7, np.uint32)
+        offsets, oidx = np.zeros(max(cap, 1), np.uint32), np.full(Q + 1, 7, np.uint64)
+        tot, chk = ctypes.c_uint64(99), ctypes.c_uint64(99)
+        rc = lib.kiss_hip_fmi_query_ex_host(ctypes.byref(v), pats.ctypes.data if Q else None, L, Q, 0, beg.ctypes.data, end.ctypes.data,
+                                            offs.ctypes.data if optional else None, ctypes.byref(tot) if optional else None,
+                                            ctypes.byref(chk) if optional else None, offsets.ctypes.data if optional else None,
+                                            oidx.ctypes.data if optional else None, cap if optional else 0, 0)
+        return rc, beg[:Q], end[:Q], offs[:Q], tot.value, chk.value, offsets[:cap], oidx
+
+    rc, beg, end, offs, tot, chk, offsets, oidx = query(0, True, 0)  # the empty batch
+    assert rc == 0 and (tot, chk) == (0, 0)
+    rc, beg, end, offs, tot, chk, offsets, oidx = query(Q, False, 0)
+    assert rc == 0 and np.array_equal(beg, want["beg"]) and np.array_equal(end, want["end"]) and (tot, chk) == (99, 99)
+    rc, beg, end, offs, tot, chk, offsets, oidx = query(Q, True, want["total_hits"])
+    assert rc == 0 and np.array_equal(beg, want["beg"]) and np.array_equal(end, want["end"]) and np.array_equal(offs, want["offs"])
+    assert (tot, chk) == (want["total_hits"], want["checksum"])
+    assert np.array_equal(oidx, want["offsets_index"]) and np.array_equal(offsets, want["offsets"])
+
+
 def test_from_bytes_rejects_a_mismatched_file():
     import kiss_amd.fm_index as fm
     S, f, _ = built(1, 14)

@@ -211,6 +211,15 @@ def test_capacity_protocol_and_error_contract_of_the_plan_call():
     rc, rep, ch, cidx, org = raw_plan(pairs, hits, hidx, alns, lens, 3000, 8, C, want_origin=False, **kw)
     assert rc == 0 and np.array_equal(ch[:C].view(np.uint32).astype(np.int64), want["chains"]) and (org == -1).all()
     check_plan(kiss_amd.plan_rescue(pairs, np.array(hits, np.int64), hidx, np.array(alns, np.int64), lens, 3000, **kw), want)
+    # ... and the host entry without origin
+    pr, ht, al = (fm_rescue._records(x, d, "a record") for x, d in ((pairs, fm_rescue.PAIR_DTYPE), (np.array(hits, np.int64), fm_rescue.HIT_DTYPE),
+                                                                    (np.array(alns, np.int64), fm_rescue.ALN_DTYPE)))
+    hi, ri = np.array(hidx, np.uint64), np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
+    ch, ci, rep, p = np.zeros(C, fm_rescue.CHAIN_DTYPE), np.zeros(17, np.uint64), _lib.RescueReport(), fm_rescue.rescue_params(**kw)
+    assert _lib.load().kiss_hip_fmi_rescue_host(pr.ctypes.data, ht.ctypes.data, hi.ctypes.data, 8, al.ctypes.data, al.size, ri.ctypes.data, 3000,
+                                                None, 0, ctypes.byref(p), ch.ctypes.data, ci.ctypes.data, None, C, ctypes.byref(rep), 0) == 0
+    assert np.array_equal(ch.view(np.uint32).reshape(C, 6).astype(np.int64), want["chains"]) and np.array_equal(ci, want["chain_index"])
+    assert {k: getattr(rep, k) for k in rm.REPORT_COUNTS} == want["report"]
     # too little room: the totals, nothing written
     for cap in (0, C - 1):
         rc, rep, ch, cidx, org = raw_plan(pairs, hits, hidx, alns, lens, 3000, 8, cap, **kw)
@@ -347,6 +356,29 @@ def test_capacity_protocol_and_error_contract_of_the_merge_call():
         assert all((v == -1).all() for v in d.values()), (acap, ocap)
     rc, rep, d = call(C, 0, cigar=False)
     assert rc == 0 and np.array_equal(d["alns"].view(np.uint32).astype(np.int64), want["alignments"]) and (d["cig"] == -1).all()
+    # the host entry: short capacities give the totals, then the call with room, with and without source
+    from kiss_amd import fm_rescue
+    h = {k: np.ascontiguousarray(v, np.uint64) for k, v in dict(ia=ia, ib=ib, oa=oa, ob=ob).items()}
+    h.update(A=fm_rescue._records(A, fm_rescue.ALN_DTYPE, "an alignment record"), B=fm_rescue._records(B, fm_rescue.ALN_DTYPE, "an alignment record"),
+             ca=np.ascontiguousarray(ca, np.uint32), cb=np.ascontiguousarray(cb, np.uint32))
+
+    def host(acap, ocap, source=True):
+        o = dict(alns=np.zeros((max(acap, 1), 12), np.uint32), cidx=np.full(5, 7, np.uint64), src=np.full(max(acap, 1), 7, np.uint32),
+                 cig=np.zeros(max(ocap, 1), np.uint32), oidx=np.full(C + 1, 7, np.uint64))
+        rep = _lib.MergeReport()
+        rc = lib.kiss_hip_fmi_aln_merge_host(h["A"].ctypes.data, h["ia"].ctypes.data, h["ca"].ctypes.data, h["oa"].ctypes.data, h["B"].ctypes.data,
+                                             h["ib"].ctypes.data, h["cb"].ctypes.data, h["ob"].ctypes.data, 4, o["alns"].ctypes.data, acap,
+                                             o["cidx"].ctypes.data, o["src"].ctypes.data if source else None, o["cig"].ctypes.data,
+                                             o["oidx"].ctypes.data, ocap, ctypes.byref(rep), 0)
+        return rc, rep, o
+
+    rc, rep, o = host(0, 0)
+    assert rc == _lib.KISS_HIP_E_INVALID and (rep.alignments, rep.cigar_ops) == (C, O)
+    for source in (True, False):
+        rc, rep, o = host(C, O, source)
+        assert rc == 0 and np.array_equal(o["alns"].astype(np.int64), want["alignments"]) and np.array_equal(o["cidx"], want["chain_index"])
+        assert np.array_equal(o["cig"], want["cigar"]) and np.array_equal(o["oidx"], want["cigar_index"])
+        assert np.array_equal(o["src"], want["source"]) if source else (o["src"] == 7).all()
     # an index that decreases, a required pointer NULL
     bad = ia.copy()
     bad[2] = bad[1] - 1

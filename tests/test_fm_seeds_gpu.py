@@ -253,3 +253,58 @@ def test_error_contract_of_the_c_call():
         f.seeds(reads, 0)
     with pytest.raises(ValueError):
         f.seeds([np.zeros(0, np.uint8)])
+
+
+@pytest.mark.parametrize("sa_intv", (1, 4))
+def test_host_entry_equals_the_device_call(sa_intv):
+    """kiss_hip_fmi_seeds_host on host copies of the index (with and without the sampling bit-vector): the empty batch, the sizing
+    call, the fill call with every optional output behind a read index that does not start at 0, and the call without them"""
+    from kiss_amd import _lib
+    from tests.test_fm_mm_gpu import host_view
+    lib = _lib.load()
+    name, params = "genome", PARAMS[1]
+    f = index_of(name, sa_intv)
+    reads = [r for r in reads_of(name) if 2 <= r.size <= 150]
+    want = f.seeds(reads, *params, both_strands=True, want_ms=True)
+    per_read = np.diff(want["seed_index"].astype(np.int64))
+    nseeds, npos = int(want["seeds"].size), int(want["positions"].size)
+    assert len(reads) <= 64 and (per_read == 0).any() and (per_read > 1).any() and nseeds > 2 and npos > 2
+    lead = 5
+    cat = np.concatenate([np.full(lead, 9, np.uint8)] + reads)
+    index = (lead + np.concatenate([[0], np.cumsum([r.size for r in reads])])).astype(np.uint64)
+    bases = 2 * int(index[-1] - index[0])
+    vex = _lib.FmiViewEx()
+    vex.base, arrays = host_view(f)
+    vex.lookup_len, vex.lookup = 0, None
+
+    def call(Q, seed_capacity, pos_capacity, want_ms):
+        """pos_capacity None: no positions"""
+        seeds, sidx = np.zeros((max(seed_capacity, 1), 4), np.uint32), np.full(2 * Q + 1, 7, np.uint64)
+        pos, pidx = np.zeros(max(pos_capacity or 0, 1), np.uint32), np.full(seed_capacity + 1, 7, np.uint64)
+        ms = np.full(max(bases, 1), 7, np.uint32)
+        rep = _lib.FmiSeedReport()
+        outs = (pos.ctypes.data, pidx.ctypes.data, pos_capacity) if pos_capacity is not None else (None, None, 0)
+        rc = lib.kiss_hip_fmi_seeds_host(ctypes.byref(vex), cat.ctypes.data if Q else None, index.ctypes.data if Q else None, Q, params[0],
+                                         params[1], params[2], 1, ms.ctypes.data if want_ms else None, seeds.ctypes.data, sidx.ctypes.data,
+                                         seed_capacity, *outs, ctypes.byref(rep), 0)
+        return rc, rep, seeds, sidx, pos, pidx, ms
+
+    def same_seeds(seeds, sidx):
+        assert np.array_equal(sidx, want["seed_index"])
+        for j, k in enumerate(("start", "len", "sa_beg", "sa_end")):
+            assert np.array_equal(seeds[:nseeds, j], want["seeds"][k]), k
+
+    rc, rep, seeds, sidx, pos, pidx, ms = call(0, 0, 0, False)  # the empty batch: seed_index[0] = pos_index[0] = 0
+    assert rc == 0 and sidx.tolist() == [0] and pidx.tolist() == [0] and rep.seeds == 0
+    rc, rep, *_ = call(len(reads), 0, 0, False)  # the sizing call: the totals come back
+    assert rc == _lib.KISS_HIP_E_INVALID and (rep.seeds, rep.positions) == (nseeds, npos)
+    rc, rep, seeds, sidx, pos, pidx, ms = call(len(reads), nseeds, npos, True)
+    assert rc == 0
+    same_seeds(seeds, sidx)
+    assert np.array_equal(pidx, want["pos_index"]) and np.array_equal(pos[:npos], want["positions"])
+    assert np.array_equal(ms[:bases], want["ms"])
+    assert {k: x for k, x in rep.as_dict().items() if not k.startswith("ms_")} == \
+        {k: x for k, x in want["report"].items() if not k.startswith("ms_")}
+    rc, rep, seeds, sidx, pos, pidx, ms = call(len(reads), nseeds, None, False)
+    assert rc == 0 and (ms == 7).all()
+    same_seeds(seeds, sidx)
