@@ -280,6 +280,16 @@ class ReadsReport(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved_"}
 
 
+class MdReport(ctypes.Structure):
+    """kiss_hip_md_report (include/kiss_hip_md.h)"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("items", "bad", "md_bytes", "mismatch_columns", "deleted_bases", "longest")] + [
+        ("ms_total", ctypes.c_float), ("ms_count", ctypes.c_float), ("ms_emit", ctypes.c_float), ("reserved_", ctypes.c_uint32),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved_"}
+
+
 class Fmi8View(ctypes.Structure):
     """kiss_hip_fmi8_view"""
     _fields_ = [
@@ -457,6 +467,12 @@ def load(hooks=None):
     lib.kiss_hip_reads_interleave_host.argtypes = [vp, vp, vp, u64, vp, vp, vp, u64, vp, vp, vp, u64, ctypes.POINTER(u64), ctypes.c_int]
     for name in READS_EXPORTED_SYMBOLS:
         getattr(lib, name).restype = ctypes.c_int
+    lib.kiss_hip_fmi_md_dev.argtypes = [vp, vp, u64, vp, vp, u64, ctypes.c_int, vp, vp, vp, vp, vp, u64, vp, vp, vp, u64,
+                                        ctypes.POINTER(MdReport), vp]
+    lib.kiss_hip_fmi_md_host.argtypes = [vp, u64, vp, vp, u64, ctypes.c_int, vp, vp, vp, vp, vp, u64, vp, vp, vp, u64,
+                                         ctypes.POINTER(MdReport), ctypes.c_int]
+    for name in MD_EXPORTED_SYMBOLS:
+        getattr(lib, name).restype = ctypes.c_int
     lib.kiss_hip_fmi8_sizes_for.argtypes = [u64, u32, u32, ctypes.POINTER(Fmi8Sizes)]
     lib.kiss_hip_fmi8_build_dev.argtypes = [vp, vp, u64, vp, u32, u32] + [vp] * 8 + [ctypes.POINTER(u32), ctypes.POINTER(u32), vp]
     lib.kiss_hip_fmi8_build_host.argtypes = [vp, u64, vp, u32, u32] + [vp] * 8 + [ctypes.POINTER(u32), ctypes.POINTER(u32),
@@ -541,5 +557,7 @@ EXPORTED_SYMBOLS = [
 READS_EXPORTED_SYMBOLS = [
     "kiss_hip_reads_parse_dev", "kiss_hip_reads_parse_host", "kiss_hip_reads_interleave_dev", "kiss_hip_reads_interleave_host",
 ]
+# every symbol include/kiss_hip_md.h declares (tests/test_fm_md_abi.py)
+MD_EXPORTED_SYMBOLS = ["kiss_hip_fmi_md_dev", "kiss_hip_fmi_md_host"]
 READS_AUTO, READS_LINES, READS_FASTQ = 0, 1, 2
 READS_NONE = 0xFFFFFFFFFFFFFFFF

@@ -118,6 +118,18 @@ inline void usage_reads()
               << "                                 The files are parsed on the device (line ends may be \\n or \\r\\n).\n";
 }
 
+// The help of the SAM tags that are asked for (`kiss --help-sam`): apart from usage() for the same reason.
+inline void usage_sam()
+{
+    std::cerr << "The optional SAM tags of ./kiss fmindex_query --seeds READS --chain --align --sam:\n"
+              << "  --md                           with --sam: every mapped line carries MD:Z:, directly behind NM:i: -- the text\n"
+              << "                                 under the alignment for a reader without the genome: numbers of matching\n"
+              << "                                 columns, the text's letter at a mismatch (a read letter that is no base never\n"
+              << "                                 matches), ^ and the text's letters at a deletion; an insertion does not end a\n"
+              << "                                 run of matches.  The strings are written on the device.  Unmapped lines carry\n"
+              << "                                 none.  Without --md every byte of the output is what it was.\n";
+}
+
 inline void check(int rc, const char *where)
 {
     if (rc != KISS_HIP_OK) throw std::runtime_error(std::string(where) + ": " + kiss_hip_strerror(rc));
@@ -197,6 +209,7 @@ struct Args {
     std::string mates; // fmindex_query --seeds READS --mates READS2 --chain --align --sam
     kiss_hip_pair_params pair_params{0, 1000, 400, 8, 20, 120, 60};
     bool rescue = false; // fmindex_query ... --mates READS2 --sam --rescue
+    bool md = false;     // fmindex_query ... --sam --md
     kiss_hip_rescue_params rescue_params{0, 1000, 4, 0, 960}; // (ins_min / ins_max: the pair parameters')
 };
 
@@ -265,6 +278,7 @@ inline const Opt OPTIONS[] = {
     {"--rescue-anchors", nullptr, KISS_AT(rescue_params.max_anchors), true, {"--rescue"}},
     {"--rescue-min-anchor-score", nullptr, KISS_AT(rescue_params.min_anchor_score), true, {"--rescue"}},
     {"--rescue-width", nullptr, KISS_AT(rescue_params.max_width), true, {"--rescue"}},
+    {"--md", nullptr, KISS_AT(md), true, {"--sam"}},
 };
 #undef KISS_AT
 
@@ -277,6 +291,7 @@ inline Args parse(int argc, char **argv)
         if (s == "-h" || s == "--help") { usage(); std::exit(1); }
         if (s == "-v" || s == "--version") { std::cerr << VERSION << std::endl; std::exit(1); }
         if (s == "--help-reads") { usage_reads(); std::exit(1); }
+        if (s == "--help-sam") { usage_sam(); std::exit(1); }
         const Opt *o = std::find_if(std::begin(OPTIONS), std::end(OPTIONS), [&](const Opt &x) { return s == x.name || (x.alias && s == x.alias); });
         if (o == std::end(OPTIONS)) {
             if (!s.empty() && s[0] == '-' && s.size() > 1) throw std::runtime_error("unrecognised option '" + s + "'");
@@ -324,6 +339,7 @@ inline Args parse(int argc, char **argv)
     goes_with_through("--rescue-width");
     if (a.rescue_params.max_anchors < 1 || a.rescue_params.max_width < 1 || a.rescue_params.max_width > KISS_HIP_ALIGN_MAX_BAND)
         throw std::runtime_error("--rescue-anchors is at least 1, --rescue-width in 1..1024");
+    goes_with_through("--md");
     a.rescue_params.ins_min = a.pair_params.ins_min;
     a.rescue_params.ins_max = a.pair_params.ins_max;
     if (given(a, "--mates")) { // the pair's MAPQ is on the scale of the reads'; the mates face each other

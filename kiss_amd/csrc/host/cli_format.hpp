@@ -181,6 +181,9 @@ struct State {
     std::vector<kiss_hip_pair> first_pairs;
     kiss_hip_rescue_report plan{};
     std::vector<kiss_hip_pair> pairs; // pair_mates
+    // md_tags (--md): the MD string of hit h is md[midx[h]] .. md[midx[h + 1]]; midx empty: no MD tags
+    std::vector<uint8_t> md;
+    std::vector<uint64_t> midx;
     kiss_hip_pair_report pair_rep{};
 };
 
@@ -256,7 +259,7 @@ struct MateFields {
 
 // The one SAM line of hit t of read q, or with t == nullptr of a read that did not map (FLAG 4; a mate lies where rnext / pnext
 // say its partner does).  POS is 1-based in the record; SEQ is reversed where the hit is, and so is QUAL (the qualities of a FASTQ
-// read; * otherwise); the tags are NM, AS, XS (heads only), then YS, YT, YR.  Without records (R == 0) RNAME is *.
+// read; * otherwise); the tags are NM, MD (--md), AS, XS (heads only), then YS, YT, YR.  Without records (R == 0) RNAME is *.
 inline void sam_line(std::string &out, const State &m, uint64_t q, const kiss_hip_hit *t, const MateFields &f)
 {
     const uint64_t R = m.ref.names.size(), L = m.rd.ridx[q + 1] - m.rd.ridx[q];
@@ -276,8 +279,13 @@ inline void sam_line(std::string &out, const State &m, uint64_t q, const kiss_hi
     cigar_with_clips(out, k, m.al.cigar.data() + m.al.oidx[t->aln], m.al.oidx[t->aln + 1] - m.al.oidx[t->aln], L);
     out += '\t' + (!f.rnext ? std::string("*") : name == *f.rnext ? std::string("=") : *f.rnext) + '\t' + std::to_string(f.pnext) + '\t' +
            std::to_string(f.tlen) + '\t' + read_letters(m.rd.reads, m.rd.ridx, q, reverse) + '\t' + read_qual(m.rd, q, reverse) +
-           "\tNM:i:" + std::to_string(k.mismatches + k.ins + k.del) +
-           "\tAS:i:" + std::to_string(t->score);
+           "\tNM:i:" + std::to_string(k.mismatches + k.ins + k.del);
+    if (!m.midx.empty()) {
+        const uint64_t h = (uint64_t)(t - m.hits.data());
+        out += "\tMD:Z:";
+        out.append(reinterpret_cast<const char *>(m.md.data()) + m.midx[h], m.midx[h + 1] - m.midx[h]);
+    }
+    out += "\tAS:i:" + std::to_string(t->score);
     if (head) out += "\tXS:i:" + std::to_string(t->sub);
     if (f.mate_score >= 0) out += "\tYS:i:" + std::to_string(f.mate_score);
     if (f.proper) out += "\tYT:Z:CP";

@@ -6,6 +6,7 @@
 #include "cli_common.hpp"
 #include "cli_format.hpp"
 #include "../../../include/kiss_hip_reads.h"
+#include "../../../include/kiss_hip_md.h"
 #include <iterator>
 
 namespace kiss_cli {
@@ -218,6 +219,22 @@ inline void rescue_mates(const Args &a, State &s)
     select(a, s);
 }
 
+// --md: the MD strings of the hits that the last select picked, written on the device (size then fill)
+inline void md_tags(const Args &a, State &s)
+{
+    const uint64_t H = s.select_rep.hits;
+    s.midx.assign(H + 1, 0);
+    s.md.resize(1);
+    kiss_hip_md_report rep{};
+    check(sized_call(s.md, rep.md_bytes, [&](uint64_t capacity) {
+              return kiss_hip_fmi_md_host(s.S.data(), s.S.size(), s.rd.reads.data(), s.rd.ridx.data(), s.Q, a.both_strands, s.al.alns.data(),
+                                          s.ch.cidx.data(), s.al.cigar.data(), s.al.oidx.data(), s.hits.data(), H, s.md.data(), s.midx.data(), nullptr,
+                                          capacity, &rep, a.device);
+          }),
+          "kiss_hip_fmi_md_host");
+    if (rep.bad) throw std::runtime_error("fmindex_query --md: " + std::to_string(rep.bad) + " alignments do not fit their reads");
+}
+
 // --mates: the mappings of reads 2 p and 2 p + 1 paired
 inline void pair_mates(const Args &a, State &s)
 {
@@ -242,6 +259,7 @@ inline int map_reads(const Args &a, const kiss_hip_fmi_view_ex &index)
     select_hits(a, s);
     if (a.rescue) rescue_mates(a, s);
     if (!a.mates.empty()) pair_mates(a, s);
+    if (a.md) md_tags(a, s);
     return print_sam(s, !a.mates.empty(), a.rescue, VERSION);
 }
 

@@ -173,6 +173,9 @@ enum FmSlot {
     FM_SLOT_READS_TILES, // per tile of the file: its newlines, scanned
     FM_SLOT_READS_LINES, // per line: where it starts; the read it is
     FM_SLOT_READS_INDEX, // per read: where it starts in the codes; its line
+    // kiss_hip_fmi_md_dev (fm_md.hip)
+    FM_SLOT_MD_CTL,
+    FM_SLOT_MD_SLAB,     // per item: the bytes of its string, scanned
     FM_SLOT_COUNT
 };
 

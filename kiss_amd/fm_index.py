@@ -646,16 +646,20 @@ class FMIndex:
 
     # ---- the mappings of every read (kiss_hip_fmi_select_dev; no reference counterpart) ---------------------------------
     def map(self, reads, text, min_len=19, max_len=0, max_occ=500, both_strands=False, chain_params=None, align_params=None,
-            bounds=None, want_cigar=True, **select_params):
+            bounds=None, want_cigar=True, want_md=False, **select_params):
         """Seeds, chains, alignments and the selection of every read's mappings (include/kiss_hip.h has the definition),
         with everything staying on the device between the four calls.  reads, text and the seed parameters as in align();
         chain_params / align_params: dicts of the parameters of chains() / align(); bounds: the starts of the R records of
         the text plus n (R + 1 ascending values, the first 0), None: one record; select_params: min_score (30), overlap
         (128, in 256ths), mapq_coef (120), mapq_max (60), max_hits (0: all).  Returns what align() returns plus hits
         (structured array: aln, flags, mapq, score, sub, n_sec, head, ref; flags 1 reverse, 2 secondary, 4 supplementary),
-        hit_index (Q + 1: the hits of read q are hits[hit_index[q]:hit_index[q + 1]], the primary first) and select_report."""
+        hit_index (Q + 1: the hits of read q are hits[hit_index[q]:hit_index[q + 1]], the primary first) and select_report.
+        want_md (it needs want_cigar): also md, md_index, md_counts and md_report -- the MD:Z string of every hit, in the order
+        of hits (kiss_hip_fmi_md_dev, include/kiss_hip_md.h; kiss_amd.fm_md.md_strings() splits the bytes)."""
         from .fm_select import select_arrays, select_dev, select_params as make_select_params
         sp = make_select_params(**select_params)
+        if want_md and not want_cigar:
+            raise ValueError("want_md needs the ops: want_cigar=True")
         res, t = self._align_dev(reads, text, min_len, max_len, max_occ, both_strands, chain_params, want_cigar,
                                  align_params or {})
         ctx = t["ctx"]
@@ -663,11 +667,20 @@ class FMIndex:
             ctx = self._context(min(_lib.MAX_N, int(3.3 * t["C"]) + (1 << 20)))
         sel = select_dev(t["lib"], ctx, self.device, t["d_alns"], t["d_cidx"], t["d_ridx"], t["Q"], t["C"], both_strands, bounds, sp)
         res.update(select_arrays(sel))
+        if want_md:
+            res.update(self._md_of_hits(t, ctx, t["d_alns"], t["d_cidx"], t["C"], t["al"]["d_cigar"], t["al"]["d_oidx"], both_strands, sel))
         return res
+
+    def _md_of_hits(self, t, ctx, d_alns, d_cidx, C, d_cigar, d_oidx, both_strands, sel):
+        """map(want_md=True): the MD strings of the hits of a select call, from the buffers that are on the device"""
+        from .fm_md import md_arrays, md_dev
+        out = md_dev(t["lib"], ctx, self.device, t["d_text"], t["n"], t["d_reads"], t["d_ridx"], t["Q"], both_strands, d_alns, d_cidx, C,
+                     d_cigar, d_oidx, sel["d_hits"], int(sel["rep"].hits))
+        return md_arrays(out)
 
     # ---- the mappings of two mates paired (kiss_hip_fmi_pair_dev; no reference counterpart) -----------------------------
     def map_pairs(self, reads1, reads2, text, min_len=19, max_len=0, max_occ=500, chain_params=None, align_params=None,
-                  select_params=None, bounds=None, want_cigar=True, rescue=None, **pair_params):
+                  select_params=None, bounds=None, want_cigar=True, rescue=None, want_md=False, **pair_params):
         """map() for paired reads (forward-then-reverse libraries; include/kiss_hip.h has the definition): reads1[p] and
         reads2[p] are mate 1 and mate 2 of pair p, both as read from the sequencer.  They are interleaved into one batch
         (reads 2 p and 2 p + 1), which goes through seeds, chains, alignments and select on both strands and then through the
@@ -686,11 +699,15 @@ class FMIndex:
         aln_source[a] of the first pass, whose chain has the same number, if that is below the first pass's count C_A, else
         it belongs to rescue chain aln_source[a] - C_A), first_pass (pairs, hits, hit_index, select_report, pair_report,
         alignments: C_A) and rescue (chains, chain_index, origin, report, align_report, merge_report, rescued: the pairs proper now and
-        not before)."""
+        not before).
+        want_md (it needs want_cigar): also md, md_index, md_counts and md_report, the MD:Z strings of `hits` as in map(); with
+        rescue those of the second pass, from the merged alignments."""
         from .fm_pair import pair_arrays, pair_dev, pair_params as make_pair_params
         from .fm_select import select_arrays, select_dev, select_params as make_select_params
         pp = make_pair_params(**pair_params)
         sp = make_select_params(**(select_params or {}))
+        if want_md and not want_cigar:
+            raise ValueError("want_md needs the ops: want_cigar=True")
 
         def as_list(reads):
             if isinstance(reads, tuple):
@@ -712,10 +729,12 @@ class FMIndex:
         out = pair_dev(t["lib"], ctx, self.device, sel["d_hits"], sel["d_hidx"], t["Q"], t["d_alns"], t["C"], pp)
         res.update(pair_arrays(out))
         if rescue is None or rescue is False:
+            if want_md:
+                res.update(self._md_of_hits(t, ctx, t["d_alns"], t["d_cidx"], t["C"], t["al"]["d_cigar"], t["al"]["d_oidx"], True, sel))
             return res
-        return self._rescue_pass(res, t, ctx, sel, out, sp, pp, bounds, want_cigar, {} if rescue is True else dict(rescue))
+        return self._rescue_pass(res, t, ctx, sel, out, sp, pp, bounds, want_cigar, {} if rescue is True else dict(rescue), want_md)
 
-    def _rescue_pass(self, res, t, ctx, sel, out, sp, pp, bounds, want_cigar, rescue):
+    def _rescue_pass(self, res, t, ctx, sel, out, sp, pp, bounds, want_cigar, rescue, want_md=False):
         """map_pairs(rescue=...): plan, the rescue align call, merge, and select and pair again (res: the first pass's result)"""
         from .fm_align import align_arrays, align_dev
         from .fm_pair import PAIR_PROPER, pair_arrays, pair_dev
@@ -748,6 +767,8 @@ class FMIndex:
         res.update(merge_arrays(mg, want_cigar))
         res.update(select_arrays(sel2))
         res.update(pair_arrays(out2))
+        if want_md:
+            res.update(self._md_of_hits(t, ctx, mg["d_alns"], mg["d_cidx"], C, mg["d_cigar"], mg["d_oidx"], True, sel2))
         proper1 = (first["pairs"]["flags"] & PAIR_PROPER) != 0
         proper2 = (res["pairs"]["flags"] & PAIR_PROPER) != 0
         plan.update(align_report=align_arrays(al2, False)["align_report"], merge_report=mg["rep"].as_dict(),

@@ -36,7 +36,8 @@ def select_call(f, alns, cidx, d_index, Q, params, hits, hidx, cap):
     return rc, rep.as_dict()
 
 
-def workload(S, n, Q, L, sub_rate, min_len, max_occ, sa_intv, steps, dev):
+def workload(S, n, Q, L, sub_rate, min_len, max_occ, sa_intv, steps, dev, after_select=None):
+    """after_select(f, state) -> dict: a later stage timed on the buffers of this run (tools/bench_md.py); its result is merged in"""
     f = fm.FMIndex(sa_intv=sa_intv)
     bases = 2 * Q * L
     ctx = f._context(max(n + 1, 4 * (bases + 1)))
@@ -121,6 +122,9 @@ def workload(S, n, Q, L, sub_rate, min_len, max_occ, sa_intv, steps, dev):
         "align_call_ms_total_same_run": round(align["ms_total"], 3),
         "select_over_align_call": best["ms_total"] / align["ms_total"] if align["ms_total"] > 0 else 0.0,
     }
+    if after_select:
+        res.update(after_select(f, dict(S=S, n=n, reads=reads, d_index=d_index, Q=Q, alns=out["alns"], cidx=ch["cidx"], C=C, cigar=out["cigar"],
+                                        oidx=out["oidx"], hits=hits, H=int(best["hits"]), steps=steps, dev=dev)))
     f.close()
     return res
 
