@@ -290,6 +290,22 @@ class MdReport(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved_"}
 
 
+class InsertParams(ctypes.Structure):
+    """kiss_hip_insert_params (include/kiss_hip_insert.h)"""
+    _fields_ = [(k, ctypes.c_uint32) for k in ("min_mapq", "max_insert", "min_samples", "out_mult", "map_mult", "sd_mult")]
+
+
+class InsertReport(ctypes.Structure):
+    """kiss_hip_insert_report (include/kiss_hip_insert.h)"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("P", "unmapped", "bad_input", "low_mapq", "discordant", "too_long", "samples", "used")] + [
+        (k, ctypes.c_uint32) for k in ("flags", "q25", "q50", "q75", "mean", "sd", "ins_min", "ins_max", "ins_mean")] + [
+        ("ms_total", ctypes.c_float), ("ms_hist", ctypes.c_float), ("ms_stats", ctypes.c_float),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class Fmi8View(ctypes.Structure):
     """kiss_hip_fmi8_view"""
     _fields_ = [
@@ -473,6 +489,11 @@ def load(hooks=None):
                                          ctypes.POINTER(MdReport), ctypes.c_int]
     for name in MD_EXPORTED_SYMBOLS:
         getattr(lib, name).restype = ctypes.c_int
+    lib.kiss_hip_fmi_insert_dev.argtypes = [vp, vp, vp, u64, vp, u64, ctypes.POINTER(InsertParams), vp, ctypes.POINTER(InsertReport), vp]
+    lib.kiss_hip_fmi_insert_host.argtypes = [vp, vp, u64, vp, u64, ctypes.POINTER(InsertParams), vp, ctypes.POINTER(InsertReport),
+                                             ctypes.c_int]
+    for name in INSERT_EXPORTED_SYMBOLS:
+        getattr(lib, name).restype = ctypes.c_int
     lib.kiss_hip_fmi8_sizes_for.argtypes = [u64, u32, u32, ctypes.POINTER(Fmi8Sizes)]
     lib.kiss_hip_fmi8_build_dev.argtypes = [vp, vp, u64, vp, u32, u32] + [vp] * 8 + [ctypes.POINTER(u32), ctypes.POINTER(u32), vp]
     lib.kiss_hip_fmi8_build_host.argtypes = [vp, u64, vp, u32, u32] + [vp] * 8 + [ctypes.POINTER(u32), ctypes.POINTER(u32),
@@ -559,5 +580,9 @@ READS_EXPORTED_SYMBOLS = [
 ]
 # every symbol include/kiss_hip_md.h declares (tests/test_fm_md_abi.py)
 MD_EXPORTED_SYMBOLS = ["kiss_hip_fmi_md_dev", "kiss_hip_fmi_md_host"]
+# every symbol include/kiss_hip_insert.h declares (tests/test_fm_insert_abi.py)
+INSERT_EXPORTED_SYMBOLS = ["kiss_hip_fmi_insert_dev", "kiss_hip_fmi_insert_host"]
+INSERT_MAX = 65535
+INSERT_OK = 1
 READS_AUTO, READS_LINES, READS_FASTQ = 0, 1, 2
 READS_NONE = 0xFFFFFFFFFFFFFFFF

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../../include/kiss_hip.h"
+#include "../../../include/kiss_hip_insert.h"
 
 namespace kiss_cli {
 
@@ -130,6 +131,27 @@ inline void usage_sam()
               << "                                 none.  Without --md every byte of the output is what it was.\n";
 }
 
+// The help of the options of --mates that `kiss -h` does not list (`kiss --help-pairs`): apart from usage() for the same reason.
+inline void usage_pairs()
+{
+    std::cerr << "The insert size of ./kiss fmindex_query --seeds READS --mates READS2 --chain --align --sam:\n"
+              << "  --ins-auto                     with --mates: --ins-min, --ins-max and --ins-mean are estimated from the reads, on the\n"
+              << "                                 device, before the mates are paired (and before --rescue lays its windows): from\n"
+              << "                                 the pairs whose first mappings lie on one record, face each other in order and\n"
+              << "                                 have a MAPQ of --ins-auto-min-mapq or more, the quartiles of the insert, then mean\n"
+              << "                                 and deviation without the outliers (more than 2 interquartile ranges outside the\n"
+              << "                                 quartiles); --ins-min = min(q25 - 3 IQR, mean - 4 sd), not below 0, --ins-max =\n"
+              << "                                 max(q75 + 3 IQR, mean + 4 sd), --ins-mean = mean.  With fewer than\n"
+              << "                                 --ins-auto-min-pairs such pairs the values given (or their defaults) are used.\n"
+              << "                                 One line on stderr says what was found:\n"
+              << "                                 [insert] pairs= samples= used= q25= q50= q75= mean= sd= ins_min= ins_max= applied=\n"
+              << "                                 Forward-then-reverse libraries only.  Without --ins-auto every byte of the output\n"
+              << "                                 is what it was.\n"
+              << "  --ins-auto-min-mapq NUM (=20)  lowest MAPQ of either mate of a pair that is looked at\n"
+              << "  --ins-auto-max NUM (=10000)    longest insert that is looked at (1..65535)\n"
+              << "  --ins-auto-min-pairs NUM (=25) fewest such pairs for an estimate\n";
+}
+
 inline void check(int rc, const char *where)
 {
     if (rc != KISS_HIP_OK) throw std::runtime_error(std::string(where) + ": " + kiss_hip_strerror(rc));
@@ -210,7 +232,9 @@ struct Args {
     kiss_hip_pair_params pair_params{0, 1000, 400, 8, 20, 120, 60};
     bool rescue = false; // fmindex_query ... --mates READS2 --sam --rescue
     bool md = false;     // fmindex_query ... --sam --md
-    kiss_hip_rescue_params rescue_params{0, 1000, 4, 0, 960}; // (ins_min / ins_max: the pair parameters')
+    kiss_hip_rescue_params rescue_params{0, 1000, 4, 0, 960}; // (ins_min / ins_max: the pair parameters' that are used, set in map_reads)
+    bool ins_auto = false; // fmindex_query ... --mates READS2 --sam --ins-auto
+    kiss_hip_insert_params insert_params{20, 10000, 25, 2, 3, 4};
 };
 
 inline bool given(const Args &a, const char *name) { return std::find(a.seen.begin(), a.seen.end(), name) != a.seen.end(); }
@@ -279,6 +303,10 @@ inline const Opt OPTIONS[] = {
     {"--rescue-min-anchor-score", nullptr, KISS_AT(rescue_params.min_anchor_score), true, {"--rescue"}},
     {"--rescue-width", nullptr, KISS_AT(rescue_params.max_width), true, {"--rescue"}},
     {"--md", nullptr, KISS_AT(md), true, {"--sam"}},
+    {"--ins-auto", nullptr, KISS_AT(ins_auto), true, {"--mates"}},
+    {"--ins-auto-min-mapq", nullptr, KISS_AT(insert_params.min_mapq), true, {"--ins-auto"}},
+    {"--ins-auto-max", nullptr, KISS_AT(insert_params.max_insert), true, {"--ins-auto"}},
+    {"--ins-auto-min-pairs", nullptr, KISS_AT(insert_params.min_samples), true, {"--ins-auto"}},
 };
 #undef KISS_AT
 
@@ -292,6 +320,7 @@ inline Args parse(int argc, char **argv)
         if (s == "-v" || s == "--version") { std::cerr << VERSION << std::endl; std::exit(1); }
         if (s == "--help-reads") { usage_reads(); std::exit(1); }
         if (s == "--help-sam") { usage_sam(); std::exit(1); }
+        if (s == "--help-pairs") { usage_pairs(); std::exit(1); }
         const Opt *o = std::find_if(std::begin(OPTIONS), std::end(OPTIONS), [&](const Opt &x) { return s == x.name || (x.alias && s == x.alias); });
         if (o == std::end(OPTIONS)) {
             if (!s.empty() && s[0] == '-' && s.size() > 1) throw std::runtime_error("unrecognised option '" + s + "'");
@@ -340,8 +369,9 @@ inline Args parse(int argc, char **argv)
     if (a.rescue_params.max_anchors < 1 || a.rescue_params.max_width < 1 || a.rescue_params.max_width > KISS_HIP_ALIGN_MAX_BAND)
         throw std::runtime_error("--rescue-anchors is at least 1, --rescue-width in 1..1024");
     goes_with_through("--md");
-    a.rescue_params.ins_min = a.pair_params.ins_min;
-    a.rescue_params.ins_max = a.pair_params.ins_max;
+    goes_with_through("--ins-auto-min-pairs");
+    if (a.insert_params.max_insert < 1 || a.insert_params.max_insert > KISS_HIP_INSERT_MAX)
+        throw std::runtime_error("--ins-auto-max is in 1..65535");
     if (given(a, "--mates")) { // the pair's MAPQ is on the scale of the reads'; the mates face each other
         a.both_strands = true;
         a.pair_params.mapq_coef = a.select_params.mapq_coef;

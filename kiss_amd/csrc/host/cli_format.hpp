@@ -185,6 +185,9 @@ struct State {
     std::vector<uint8_t> md;
     std::vector<uint64_t> midx;
     kiss_hip_pair_report pair_rep{};
+    // the pair and rescue parameters that are used: the command line's, or with --ins-auto the estimated insert in them
+    kiss_hip_pair_params pair_params{};
+    kiss_hip_rescue_params rescue_params{};
 };
 
 // ---- the printers: stdout, then the [info] line on stderr -------------------------------------------------------------------

@@ -7,6 +7,7 @@
 #include "cli_format.hpp"
 #include "../../../include/kiss_hip_reads.h"
 #include "../../../include/kiss_hip_md.h"
+#include "../../../include/kiss_hip_insert.h"
 #include <iterator>
 
 namespace kiss_cli {
@@ -183,6 +184,32 @@ inline void select_hits(const Args &a, State &s)
     select(a, s);
 }
 
+// --mates: the parameters of the pair call and of the rescue plan.  With --ins-auto the insert size is estimated from the first
+// hits of the pairs (the first select call's) and, with enough samples, takes the place of --ins-min / --ins-max / --ins-mean;
+// the rescue windows are laid with the values that are used.  One line on stderr says what was found.
+inline void insert_size(const Args &a, State &s)
+{
+    s.pair_params = a.pair_params;
+    if (a.ins_auto) {
+        kiss_hip_insert_report rep{};
+        check(kiss_hip_fmi_insert_host(s.hits.data(), s.hidx.data(), s.Q, s.al.alns.data(), s.select_rep.alignments, &a.insert_params, nullptr, &rep,
+                                       a.device),
+              "kiss_hip_fmi_insert_host");
+        const bool applied = (rep.flags & KISS_HIP_INSERT_OK) != 0;
+        if (applied) {
+            s.pair_params.ins_min = rep.ins_min;
+            s.pair_params.ins_max = rep.ins_max;
+            s.pair_params.ins_mean = rep.ins_mean;
+        }
+        std::cerr << "[insert] pairs=" << rep.P << " samples=" << rep.samples << " used=" << rep.used << " q25=" << rep.q25 << " q50=" << rep.q50
+                  << " q75=" << rep.q75 << " mean=" << rep.mean << " sd=" << rep.sd << " ins_min=" << rep.ins_min << " ins_max=" << rep.ins_max
+                  << " applied=" << (applied ? 1 : 0) << "\n";
+    }
+    s.rescue_params = a.rescue_params;
+    s.rescue_params.ins_min = s.pair_params.ins_min;
+    s.rescue_params.ins_max = s.pair_params.ins_max;
+}
+
 // The first pass paired, the pairs that are not proper planned into windows, the windows aligned, their alignments merged
 // behind the reads' own (they take the first pass's place in the State), the mappings picked again
 inline void rescue_mates(const Args &a, State &s)
@@ -191,14 +218,14 @@ inline void rescue_mates(const Args &a, State &s)
     const uint64_t *bounds = R ? s.ref.bounds.data() : nullptr;
     s.first_alns = CA;
     s.first_pairs.resize(Q / 2 + 1);
-    check(kiss_hip_fmi_pair_host(s.hits.data(), s.hidx.data(), Q, s.al.alns.data(), CA, &a.pair_params, s.first_pairs.data(), nullptr, a.device),
+    check(kiss_hip_fmi_pair_host(s.hits.data(), s.hidx.data(), Q, s.al.alns.data(), CA, &s.pair_params, s.first_pairs.data(), nullptr, a.device),
           "kiss_hip_fmi_pair_host");
     Chains win;
     win.chains.resize(1);
     win.cidx.assign(V + 1, 0);
     check(sized_call(win.chains, s.plan.chains, [&](uint64_t capacity) {
               return kiss_hip_fmi_rescue_host(s.first_pairs.data(), s.hits.data(), s.hidx.data(), Q, s.al.alns.data(), CA, s.rd.ridx.data(), n, bounds, R,
-                                              &a.rescue_params, win.chains.data(), win.cidx.data(), nullptr, capacity, &s.plan, a.device);
+                                              &s.rescue_params, win.chains.data(), win.cidx.data(), nullptr, capacity, &s.plan, a.device);
           }),
           "kiss_hip_fmi_rescue_host");
     const uint64_t CB = s.plan.chains;
@@ -239,7 +266,7 @@ inline void md_tags(const Args &a, State &s)
 inline void pair_mates(const Args &a, State &s)
 {
     s.pairs.resize(s.Q / 2 + 1);
-    check(kiss_hip_fmi_pair_host(s.hits.data(), s.hidx.data(), s.Q, s.al.alns.data(), s.select_rep.alignments, &a.pair_params, s.pairs.data(),
+    check(kiss_hip_fmi_pair_host(s.hits.data(), s.hidx.data(), s.Q, s.al.alns.data(), s.select_rep.alignments, &s.pair_params, s.pairs.data(),
                                  &s.pair_rep, a.device),
           "kiss_hip_fmi_pair_host");
 }
@@ -257,6 +284,7 @@ inline int map_reads(const Args &a, const kiss_hip_fmi_view_ex &index)
     align_chains(a, s);
     if (!a.sam) return print_alignments(s, a.both_strands);
     select_hits(a, s);
+    if (!a.mates.empty()) insert_size(a, s);
     if (a.rescue) rescue_mates(a, s);
     if (!a.mates.empty()) pair_mates(a, s);
     if (a.md) md_tags(a, s);

@@ -20,6 +20,8 @@
 //       --mates READS2   the mappings of two mates paired   kiss_hip_fmi_pair_host  -> paired SAM
 //       --rescue  before that, the missing mate sought near its partner: kiss_hip_fmi_pair_host, kiss_hip_fmi_rescue_host, the
 //                 align call, kiss_hip_fmi_aln_merge_host, the select call again
+//       --ins-auto  before the pairing (and the rescue), --ins-min / --ins-max / --ins-mean estimated from the pairs on the
+//                 device   kiss_hip_fmi_insert_host (kiss --help-pairs)
 //       --md      MD:Z: behind NM:i: on the mapped lines, written on the device   kiss_hip_fmi_md_host (kiss --help-sam)
 //   * -g / --generic with any of the three: the file is a text over the byte alphabet, byte for byte (no FASTA rule, no newline
 //     stripping, no % 4): kiss_hip_suffix_sort_u8 (-k, -s ignored), kiss_hip_lcp_u8, kiss_hip_fmi8_build_host -> <file>.fmi8

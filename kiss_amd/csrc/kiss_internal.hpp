@@ -176,6 +176,9 @@ enum FmSlot {
     // kiss_hip_fmi_md_dev (fm_md.hip)
     FM_SLOT_MD_CTL,
     FM_SLOT_MD_SLAB,     // per item: the bytes of its string, scanned
+    // kiss_hip_fmi_insert_dev (fm_insert.hip)
+    FM_SLOT_INSERT_CTL,
+    FM_SLOT_INSERT_HIST, // the histogram, when the caller keeps none
     FM_SLOT_COUNT
 };
 

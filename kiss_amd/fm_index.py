@@ -680,7 +680,7 @@ class FMIndex:
 
     # ---- the mappings of two mates paired (kiss_hip_fmi_pair_dev; no reference counterpart) -----------------------------
     def map_pairs(self, reads1, reads2, text, min_len=19, max_len=0, max_occ=500, chain_params=None, align_params=None,
-                  select_params=None, bounds=None, want_cigar=True, rescue=None, want_md=False, **pair_params):
+                  select_params=None, bounds=None, want_cigar=True, rescue=None, want_md=False, insert=None, **pair_params):
         """map() for paired reads (forward-then-reverse libraries; include/kiss_hip.h has the definition): reads1[p] and
         reads2[p] are mate 1 and mate 2 of pair p, both as read from the sequencer.  They are interleaved into one batch
         (reads 2 p and 2 p + 1), which goes through seeds, chains, alignments and select on both strands and then through the
@@ -701,13 +701,24 @@ class FMIndex:
         alignments: C_A) and rescue (chains, chain_index, origin, report, align_report, merge_report, rescued: the pairs proper now and
         not before).
         want_md (it needs want_cigar): also md, md_index, md_counts and md_report, the MD:Z strings of `hits` as in map(); with
-        rescue those of the second pass, from the merged alignments."""
+        rescue those of the second pass, from the merged alignments.
+        insert: None, or "auto" / True / a dict of the insert parameters -- min_mapq (20), max_insert (10000), min_samples (25),
+        out_mult (2), map_mult (3), sd_mult (4) --: the insert size is estimated from the first hits of the pairs between the
+        select and the pair call (kiss_hip_fmi_insert_dev, include/kiss_hip_insert.h).  With enough samples ins_min, ins_max and
+        ins_mean of the pair parameters are replaced by the estimate (every other pair parameter stays the caller's) and the
+        rescue plan's ins_min / ins_max default to the estimated ones; otherwise the caller's or default values apply.  Added:
+        insert (report, hist, applied, ins_min, ins_max, ins_mean: the three values used).  With rescue both passes use the
+        same values: the estimate is taken once, from the first pass."""
         from .fm_pair import pair_arrays, pair_dev, pair_params as make_pair_params
         from .fm_select import select_arrays, select_dev, select_params as make_select_params
         pp = make_pair_params(**pair_params)
         sp = make_select_params(**(select_params or {}))
         if want_md and not want_cigar:
             raise ValueError("want_md needs the ops: want_cigar=True")
+        ip = None
+        if insert is not None and insert is not False:
+            from .fm_insert import insert_params as make_insert_params
+            ip = make_insert_params(**({} if insert is True or insert == "auto" else dict(insert)))
 
         def as_list(reads):
             if isinstance(reads, tuple):
@@ -726,6 +737,8 @@ class FMIndex:
             ctx = self._context(min(_lib.MAX_N, int(3.3 * t["C"]) + (1 << 20)))
         sel = select_dev(t["lib"], ctx, self.device, t["d_alns"], t["d_cidx"], t["d_ridx"], t["Q"], t["C"], True, bounds, sp)
         res.update(select_arrays(sel))
+        if ip is not None:
+            pp = self._insert_estimate(res, t, ctx, sel, pp, ip)
         out = pair_dev(t["lib"], ctx, self.device, sel["d_hits"], sel["d_hidx"], t["Q"], t["d_alns"], t["C"], pp)
         res.update(pair_arrays(out))
         if rescue is None or rescue is False:
@@ -733,6 +746,18 @@ class FMIndex:
                 res.update(self._md_of_hits(t, ctx, t["d_alns"], t["d_cidx"], t["C"], t["al"]["d_cigar"], t["al"]["d_oidx"], True, sel))
             return res
         return self._rescue_pass(res, t, ctx, sel, out, sp, pp, bounds, want_cigar, {} if rescue is True else dict(rescue), want_md)
+
+    def _insert_estimate(self, res, t, ctx, sel, pp, ip):
+        """map_pairs(insert=...): the estimate from the hits of the first select call -> the pair parameters to use"""
+        from .fm_insert import INSERT_OK, insert_arrays, insert_dev
+        got = insert_arrays(insert_dev(t["lib"], ctx, self.device, sel["d_hits"], sel["d_hidx"], t["Q"], t["d_alns"], t["C"], ip))
+        rep = got["report"]
+        applied = bool(rep["flags"] & INSERT_OK)
+        if applied:
+            pp = _lib.PairParams(rep["ins_min"], rep["ins_max"], rep["ins_mean"], pp.pen_coef, pp.pen_max, pp.mapq_coef, pp.mapq_max)
+        res["insert"] = dict(report=rep, hist=got["hist"], applied=applied, ins_min=int(pp.ins_min), ins_max=int(pp.ins_max),
+                             ins_mean=int(pp.ins_mean))
+        return pp
 
     def _rescue_pass(self, res, t, ctx, sel, out, sp, pp, bounds, want_cigar, rescue, want_md=False):
         """map_pairs(rescue=...): plan, the rescue align call, merge, and select and pair again (res: the first pass's result)"""

@@ -65,7 +65,8 @@ def best_of(steps, call, name, f):
     return min(runs, key=lambda r: r["ms_total"]), runs
 
 
-def workload(S, n, P, L, sub_rate, frag_mean, frag_sd, min_len, max_occ, sa_intv, steps, dev):
+def workload(S, n, P, L, sub_rate, frag_mean, frag_sd, min_len, max_occ, sa_intv, steps, dev, after_pair=None):
+    """after_pair(f, state) -> dict: a later stage timed on the buffers of this run (tools/bench_insert.py); its result is merged in"""
     f = fm.FMIndex(sa_intv=sa_intv)
     Q = 2 * P
     bases = 2 * Q * L
@@ -151,6 +152,8 @@ def workload(S, n, P, L, sub_rate, frag_mean, frag_sd, min_len, max_occ, sa_intv
         "align_call_ms_total_same_run": round(align["ms_total"], 3), "select_call_ms_total_same_run": round(select["ms_total"], 3),
         "pair_over_select_call": best["ms_total"] / select["ms_total"] if select["ms_total"] > 0 else 0.0,
     }
+    if after_pair:
+        res.update(after_pair(f, dict(hits=hits, hidx=hidx, Q=Q, P=P, alns=out["alns"], C=C, pairs=pairs, frag=frag, steps=steps, dev=dev)))
     f.close()
     return res
 
