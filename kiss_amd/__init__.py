@@ -15,3 +15,4 @@ from .fm_rescue import RESCUE_DEFAULTS, merge_alignments, plan_rescue, rescue_pa
 from .reads import interleave_reads, interleave_reads_dev, parse_reads, parse_reads_dev  # noqa: F401,E402
 from .fm_md import md_strings, md_tags  # noqa: F401,E402
 from .fm_insert import INSERT_DEFAULTS, estimate_insert, insert_params  # noqa: F401,E402
+from .fm_sam import sam_header  # noqa: F401,E402
