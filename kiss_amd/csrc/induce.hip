@@ -20,6 +20,7 @@
 // The LMS suffixes are never copied into SA (put_lms_suffix disappears): the L sweep reads them from
 // the sorted LMS array, and the S sweep overwrites every S-type slot anyway (induced_clear disappears).
 #include "kiss_internal.hpp"
+#include "induce_count.hpp"
 #include <cstdio>
 #include <cstdlib>
 
@@ -160,9 +161,172 @@ __device__ __forceinline__ uint32_t wave_scan_add(uint32_t x)
 }
 
 // ---- pass 1: per-tile class counts ---------------------------------------------------
-// One WAVE per tile (a workgroup = IN_WAVES tiles): counting does not care about order, so a lane takes four
-// consecutive items per step (16-byte loads, all of the tile's steps in flight at once) and keeps the four class
-// counts in 16-bit fields of one 64-bit word (a tile has 2048 items); no LDS, no barrier, no atomic.
+// One WAVE per tile (a workgroup = IN_WAVES waves): counting does not care about order, so a lane takes 16-byte pieces of
+// the tile, all of them in flight at once, and keeps its four class counts in 8-bit fields of one register (a lane has at
+// most 36 items); no LDS, no barrier, no atomic.  Three forms of a tile:
+//   bytes    a full tile of an array that has class bytes (srcK): 2 KiB read instead of 8, counted four bytes at a time
+//            (induce_count.hpp);
+//   words    a full tile of context words: the far LMS list (REMAP, no near-end suffix inside), or the hooks build without
+//            class bytes;
+//   partial  the last tile of a pass, or a REMAP tile with a near-end suffix inside: item by item.
+// Bytes and words count the items that have bases in straight-line code.  The items that have none (a word run empty, or
+// a far LMS suffix that left the sort without a word) are rare beside SA but not in the LMS passes -- a third of their
+// tiles hold one -- so they are collected in a bit mask per lane and worked off by refresh_pending, a loop
+// outside the register budget of the straight-line code.  The kernel is held to 64 registers: 8 waves per SIMD
+// (tests/test_induce_count_resources.py).  Several tiles per wave were measured, loaded together and one ahead: no
+// faster, so a wave has one.
+
+// The items of a lane whose word has no bases, one bit each in `pend`; item b lies at index base + step * (b >> SH) +
+// (b & ((1 << SH) - 1)), or at tail + (b - 32) for b >= 32 (the 129th piece of a byte stretch).  Every lane with a bit
+// left takes its lowest one per round: the position is read, the word gathered from the text and kept (with its class
+// byte where the array has them, and with the taint bit it had), the class counted, the bit cleared.  A round clears one
+// bit in every lane that has one and sets none, so the loop ends after at most 36 rounds; it waits for no other wave.
+// -> the lane's 8-bit class counts (no emit mask applied) with these items added.
+template <int SH>
+__device__ __forceinline__ uint32_t refresh_pending(const uint64_t *__restrict__ pk, const uint32_t *srcP, uint32_t *srcC,
+                                                    uint8_t *srcK, uint64_t pend, int64_t base, int64_t step, int64_t tail,
+                                                    uint32_t cnt8, bool counted_before)
+{
+    while (__ballot(pend != 0ull) != 0ull) {
+        if (pend != 0ull) {
+            const uint32_t b = (uint32_t)__ffsll((unsigned long long)pend) - 1u;
+            pend &= pend - 1ull;
+            const int64_t idx = b < 32u ? base + step * (int64_t)(b >> SH) + (int64_t)(b & ((1u << SH) - 1u)) : tail + (int64_t)(b - 32u);
+            const uint32_t old = srcC[idx];
+            if (counted_before) cnt8 -= 1u << ((old & 3u) << 3); // (the straight-line code took the old word's class bits)
+            const uint32_t v = srcP[idx];
+            if (v != 0u) { // (position 0 has nothing in front of it: class 4, the word stays as it is)
+                const uint32_t c = kiss_load_ctx(pk, v) | (old & KISS_CTX_TAINT);
+                srcC[idx] = c; // keep the refreshed word: the scatter pass (and the other sweep) reuse it
+                if (srcK) srcK[idx] = (uint8_t)cls_byte(c);
+                cnt8 += 1u << ((c & 3u) << 3);
+            }
+        }
+    }
+    return cnt8;
+}
+
+// totals of the wave: the 8-bit fields spread to 16 bits (a tile has 2048 items), two DPP prefix sums, the last lane holds the sums
+__device__ __forceinline__ void put_counts(uint32_t *__restrict__ counts, uint64_t tiles, uint64_t tile, uint32_t cnt8)
+{
+    const uint32_t lane = lane_id();
+    const uint32_t lo = (cnt8 & 0xFFu) | ((cnt8 & 0xFF00u) << 8), hi = ((cnt8 >> 16) & 0xFFu) | ((cnt8 >> 8) & 0xFF0000u);
+    const uint32_t slo = (uint32_t)__builtin_amdgcn_readlane((int)wave_scan_add(lo), 63);
+    const uint32_t shi = (uint32_t)__builtin_amdgcn_readlane((int)wave_scan_add(hi), 63);
+    if (lane < 4) counts[(uint64_t)lane * tiles + tile] = (((lane & 2u) ? shi : slo) >> (16u * (lane & 1u))) & 0xFFFFu;
+}
+
+// A full tile of class bytes: the byte stretch [A, A + 2048) read as aligned 16-byte pieces, two per lane and, when A is
+// not aligned (`mis`, the same in all lanes), a 129th of which lanes 0-3 take one word each -- an aligned stretch skips
+// that piece and its word with a scalar branch.  Bytes outside the stretch are replaced by 8 ("skip").
+__device__ __forceinline__ void count_byte_tile(const uint64_t *__restrict__ pk, const uint32_t *srcP, uint32_t *srcC,
+                                                uint8_t *srcK, int64_t beg, int dir, uint32_t emitmask,
+                                                uint32_t *__restrict__ counts, uint64_t tiles, uint64_t tile)
+{
+    static_assert(IN_TILE == 2048, "64 lanes x 2 x 16 bytes");
+    const uint32_t lane = lane_id();
+    const uint64_t t0 = tile * IN_TILE;
+    const int64_t lo_index = dir > 0 ? beg + (int64_t)t0 : beg - (int64_t)(t0 + IN_TILE - 1); // lowest index of the stretch
+    const uint32_t mis = (uint32_t)__builtin_amdgcn_readfirstlane((int)(reinterpret_cast<uintptr_t>(srcK + lo_index) & 15u));
+    const int64_t first = lo_index - (int64_t)mis; // index of byte 0 of the first piece
+    const uint4 *const ap = reinterpret_cast<const uint4 *>(srcK + first);
+    uint32_t w[9];
+    {
+        const uint4 q0 = ap[lane], q1 = ap[64 + lane];
+        w[0] = q0.x, w[1] = q0.y, w[2] = q0.z, w[3] = q0.w;
+        w[4] = q1.x, w[5] = q1.y, w[6] = q1.z, w[7] = q1.w;
+        w[8] = 0x08080808u;
+    }
+    if (mis != 0u) { // (scalar branch)
+        if (lane < 4u) w[8] = reinterpret_cast<const uint32_t *>(ap + 128)[lane];
+#pragma unroll
+        for (int i = 0; i < 4; i++) { // lane 0, first piece: the bytes in front of A
+            const int nb = (int)mis - 4 * i; // bytes of word i that lie below byte `mis` of a piece
+            const uint32_t lowmask = nb >= 4 ? 0xFFFFFFFFu : (nb <= 0 ? 0u : ~(0xFFFFFFFFu << (8 * (nb & 3))));
+            if (lane == 0u) w[i] = (w[i] & ~lowmask) | (0x08080808u & lowmask);
+        }
+        // lanes 0-3, 129th piece: the stretch's last bytes are the ones below byte `mis`
+        const int nb = (int)mis - 4 * (int)lane;
+        const uint32_t lowmask = nb >= 4 ? 0xFFFFFFFFu : (nb <= 0 ? 0u : ~(0xFFFFFFFFu << (8 * (nb & 3))));
+        w[8] = (w[8] & lowmask) | (0x08080808u & ~lowmask); // (lanes 4-63: all skip either way)
+    }
+    KissClsAcc acc = {{0u, 0u, 0u, 0u}};
+    uint32_t any = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        kiss_cls_acc_add(acc, w[i]);
+        any |= w[i];
+    }
+    if (mis != 0u) {
+        kiss_cls_acc_add(acc, w[8]);
+        any |= w[8];
+    }
+    uint32_t cnt8 = kiss_cls_acc_sum(acc);
+    if (__ballot((any & 0x04040404u) != 0u) != 0ull) { // a byte says "no bases left" (bit 3 never goes with bit 2)
+        uint64_t pend = 0;
+#pragma unroll
+        for (int i = 0; i < 9; i++) {
+            const uint32_t p = (w[i] >> 2) & ~(w[i] >> 3) & 0x01010101u;
+            pend |= (uint64_t)(((p * 0x00204081u) >> 21) & 0xFu) << (4 * i); // bits 0, 8, 16, 24 -> 0, 1, 2, 3
+        }
+        cnt8 = refresh_pending<4>(pk, srcP, srcC, srcK, pend, first + 16 * (int64_t)lane, 1024, first + 2048 + 4 * (int64_t)lane,
+                                  cnt8, false);
+    }
+    put_counts(counts, tiles, tile, kiss_cls_emit(cnt8, emitmask));
+}
+
+// a full tile of context words, `shift` entries below their index (REMAP: see k_induce_count): a lane takes four
+// consecutive words of each of the tile's eight steps of 256
+__device__ __forceinline__ void count_word_tile(const uint64_t *__restrict__ pk, const uint32_t *srcP, uint32_t *srcC, int64_t beg,
+                                                int dir, uint32_t emitmask, uint32_t *__restrict__ counts, uint64_t tiles,
+                                                uint64_t tile, int64_t shift)
+{
+    struct __attribute__((packed, aligned(4))) U4 {
+        uint32_t v[4];
+    };
+    constexpr int STEPS = IN_TILE / 256; // 256 items per wave step
+    static_assert(STEPS * 4 == 32, "one bit per item of a lane in the low half of refresh_pending's mask");
+    static_assert(IN_TILE / 64 <= 255, "8-bit counters per lane");
+    const uint64_t i0 = tile * IN_TILE + 4 * lane_id();
+    const int64_t p0 = (dir > 0 ? beg + (int64_t)i0 : beg - (int64_t)(i0 + 3)) - shift; // lowest address of my four items of step 0
+    const int64_t pstep = dir > 0 ? 256 : -256;
+    U4 t[STEPS];
+#pragma unroll
+    for (int q = 0; q < STEPS; q++) t[q] = *reinterpret_cast<const U4 *>(srcC + (p0 + q * pstep));
+    uint32_t cnt8 = 0, least = 0xFFFFFFFFu;
+#pragma unroll
+    for (int q = 0; q < STEPS; q++) {
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            cnt8 += 1u << ((t[q].v[e] << 3) & 31u); // class c = bits 1:0 -> field c
+            least = min(least, t[q].v[e] & 0x7FFFFFFEu);
+        }
+    }
+    if (__ballot(least == 0u) != 0ull) { // a word without bases
+        uint32_t pend = 0;
+#pragma unroll
+        for (int q = 0; q < STEPS; q++)
+#pragma unroll
+            for (int e = 0; e < 4; e++) pend |= ((t[q].v[e] & 0x7FFFFFFEu) == 0u ? 1u : 0u) << (4 * q + e);
+        cnt8 = refresh_pending<2>(pk, srcP, srcC, nullptr, (uint64_t)pend, p0, pstep, 0, cnt8, true);
+    }
+    put_counts(counts, tiles, tile, kiss_cls_emit(cnt8, emitmask));
+}
+
+template <bool REMAP>
+__device__ __forceinline__ void count_partial_tile(const uint64_t *__restrict__ pk, const uint32_t *srcP, uint32_t *srcC, int64_t beg,
+                                                   uint64_t N, int dir, uint32_t emitmask, uint32_t *__restrict__ counts,
+                                                   uint64_t tiles, uint64_t tile, const LmsRemap &rm, uint8_t *srcK)
+{
+    const uint64_t t0 = tile * IN_TILE;
+    uint32_t cnt8 = 0; // (a lane takes at most 32 items)
+    for (uint64_t i = t0 + lane_id(); i < N && i < t0 + IN_TILE; i += 64) {
+        const uint32_t cls = item_class_only<REMAP>(pk, srcP, srcC, beg + (int64_t)dir * (int64_t)i, emitmask, rm, REMAP ? nullptr : srcK);
+        cnt8 += (cls < 4u ? 1u : 0u) << ((cls & 3u) << 3);
+    }
+    put_counts(counts, tiles, tile, cnt8);
+}
+
 template <bool REMAP>
 __global__ __launch_bounds__(IN_THREADS) void k_induce_count(const uint64_t *__restrict__ pk, const uint32_t *srcP,
                                                             uint32_t *srcC, int64_t beg, uint64_t N, int dir,
@@ -170,125 +334,24 @@ __global__ __launch_bounds__(IN_THREADS) void k_induce_count(const uint64_t *__r
                                                             uint64_t tiles, LmsRemap rm, uint8_t *srcK)
 {
     if (blockIdx.x == 0 && threadIdx.x == 4) counts[4 * tiles] = 0; // the extra last entry of the scan input
-    const uint64_t tile = (uint64_t)blockIdx.x * IN_WAVES + (threadIdx.x >> 6);
+    // the wave's number is read as a scalar, so that everything derived from it (tile, addresses, alignment) stays in
+    // scalar registers
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint64_t tile = (uint64_t)blockIdx.x * IN_WAVES + wave;
     if (tile >= tiles) return;
-    struct __attribute__((packed, aligned(4))) U4 {
-        uint32_t v[4];
-    };
-    constexpr int STEPS = IN_TILE / 256; // 256 items per wave step
-    const uint32_t lane = lane_id();
     const uint64_t t0 = tile * IN_TILE;
-    uint64_t acc = 0;
     // REMAP (dir > 0 only): the tile is read as a block when no near-end suffix falls inside it -- then its items are
     // consecutive entries of the far list, `shift` entries below their merged index
     int64_t shift = 0;
     bool block = t0 + IN_TILE <= N;
-    if (REMAP && block) { // (t0 is the same in all lanes of the wave)
+    if (REMAP && block) {
         const uint32_t b0 = remap_below_wave(rm, (uint64_t)beg + t0);
         block = b0 == remap_below_wave(rm, (uint64_t)beg + t0 + IN_TILE);
         shift = (int64_t)b0;
     }
-    // srcK (may be null): one class byte per word of srcC (cls_byte).  A full tile then reads 2 KiB instead of 8: the
-    // byte stretch [A, A + 2048) as aligned 16-byte pieces -- two per lane, and a 129th for lane 0 when A is not aligned;
-    // bytes outside the stretch are replaced by 8 ("skip").  A byte that says "no bases left" sends the whole tile to
-    // the word path below, which refreshes the word (and its byte).
-    bool counted = false;
-    if (!REMAP && srcK != nullptr && block) { // (wave-uniform)
-        const int64_t lo_index = dir > 0 ? beg + (int64_t)t0 : beg - (int64_t)(t0 + IN_TILE - 1);
-        const uint8_t *const A = srcK + lo_index;
-        const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(A) & 15u);
-        const uint4 *const ap = reinterpret_cast<const uint4 *>(A - mis);
-        static_assert(IN_TILE == 2048, "64 lanes x 2 x 16 bytes");
-        uint32_t w[12];
-        {
-            const uint4 q0 = ap[lane], q1 = ap[64 + lane];
-            w[0] = q0.x, w[1] = q0.y, w[2] = q0.z, w[3] = q0.w;
-            w[4] = q1.x, w[5] = q1.y, w[6] = q1.z, w[7] = q1.w;
-            w[8] = w[9] = w[10] = w[11] = 0x08080808u;
-        }
-        if (mis != 0 && lane == 0) {
-            const uint4 q2 = ap[128];
-            const uint32_t tail[4] = {q2.x, q2.y, q2.z, q2.w};
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const int nb = (int)mis - 4 * i; // bytes of this word that lie below byte `mis` of the piece
-                const uint32_t lowmask = nb >= 4 ? 0xFFFFFFFFu : (nb <= 0 ? 0u : ~(0xFFFFFFFFu << (8 * nb)));
-                w[i] = (w[i] & ~lowmask) | (0x08080808u & lowmask);         // first piece: in front of A
-                w[8 + i] = (tail[i] & lowmask) | (0x08080808u & ~lowmask);  // 129th piece: the stretch's last bytes
-            }
-        }
-        uint32_t any = 0;
-#pragma unroll
-        for (int i = 0; i < 12; i++) any |= w[i];
-        if (__ballot((any & 0x04040404u) != 0u) == 0ull) {
-            uint32_t cnt8 = 0; // (a lane has at most 48 items)
-#pragma unroll
-            for (int i = 0; i < 12; i++) {
-#pragma unroll
-                for (int e = 0; e < 4; e++) {
-                    const uint32_t b = (w[i] >> (8 * e)) & 0xFFu;
-                    const uint32_t pc = b & 3u;
-                    cnt8 += ((emitmask >> pc) & ~(b >> 3) & 1u) << (pc << 3);
-                }
-            }
-            acc = (uint64_t)((cnt8 & 0xFFu) | ((cnt8 & 0xFF00u) << 8)) | ((uint64_t)(((cnt8 >> 16) & 0xFFu) | ((cnt8 >> 8) & 0xFF0000u)) << 32);
-            counted = true;
-        }
-    }
-    if (counted) {
-    } else if (block) {
-        U4 t[STEPS];
-        int64_t p0[STEPS];
-        uint32_t least = 0xFFFFFFFFu; // (a word without bases: refreshed from the text -- rare, one test per wave)
-#pragma unroll
-        for (int q = 0; q < STEPS; q++) {
-            const uint64_t i0 = t0 + (uint64_t)q * 256 + 4 * lane;
-            p0[q] = (dir > 0 ? beg + (int64_t)i0 : beg - (int64_t)(i0 + 3)) - shift; // lowest address of my four items
-            t[q] = *reinterpret_cast<const U4 *>(srcC + p0[q]);
-        }
-#pragma unroll
-        for (int q = 0; q < STEPS; q++)
-#pragma unroll
-            for (int e = 0; e < 4; e++) least = min(least, t[q].v[e] & 0x7FFFFFFEu);
-        uint32_t cnt8 = 0; // my items per class, 8-bit fields (a lane has 32 items of the tile)
-        if (__ballot(least == 0u) == 0ull) {
-#pragma unroll
-            for (int q = 0; q < STEPS; q++) {
-#pragma unroll
-                for (int e = 0; e < 4; e++) {
-                    const uint32_t pc = t[q].v[e] & 3u;
-                    cnt8 += ((emitmask >> pc) & 1u) << (pc << 3);
-                }
-            }
-        } else {
-#pragma unroll
-            for (int q = 0; q < STEPS; q++) {
-#pragma unroll
-                for (int e = 0; e < 4; e++) {
-                    const uint32_t c = t[q].v[e];
-                    uint32_t cls;
-                    if (KISS_CTX_WORD(c) <= KISS_EMPTY_CTX) cls = item_class_only<false>(pk, srcP, srcC, p0[q] + e, emitmask, rm, REMAP ? nullptr : srcK); // refresh path
-                    else {
-                        const uint32_t pc = c & 3u;
-                        cls = ((emitmask >> pc) & 1u) ? pc : 4u;
-                    }
-                    cnt8 += (cls < 4u ? 1u : 0u) << ((cls & 3u) << 3);
-                }
-            }
-        }
-        static_assert(IN_TILE / 64 <= 255, "8-bit counters per lane");
-        acc = (uint64_t)((cnt8 & 0xFFu) | ((cnt8 & 0xFF00u) << 8)) | ((uint64_t)(((cnt8 >> 16) & 0xFFu) | ((cnt8 >> 8) & 0xFF0000u)) << 32);
-    } else {
-        for (uint64_t i = t0 + lane; i < N && i < t0 + IN_TILE; i += 64) {
-            const uint32_t cls = item_class_only<REMAP>(pk, srcP, srcC, beg + (int64_t)dir * (int64_t)i, emitmask, rm, REMAP ? nullptr : srcK);
-            acc += cls < 4u ? 1ull << (16 * cls) : 0ull;
-        }
-    }
-    // totals of the wave: two DPP prefix sums over the 16-bit fields, the last lane holds the sums
-    const uint32_t slo = (uint32_t)__builtin_amdgcn_readlane((int)wave_scan_add((uint32_t)acc), 63);
-    const uint32_t shi = (uint32_t)__builtin_amdgcn_readlane((int)wave_scan_add((uint32_t)(acc >> 32)), 63);
-    acc = ((uint64_t)shi << 32) | slo;
-    if (lane < 4) counts[(uint64_t)lane * tiles + tile] = (uint32_t)(acc >> (16 * lane)) & 0xFFFFu;
+    if (!block) count_partial_tile<REMAP>(pk, srcP, srcC, beg, N, dir, emitmask, counts, tiles, tile, rm, srcK);
+    else if (!REMAP && srcK != nullptr) count_byte_tile(pk, srcP, srcC, srcK, beg, dir, emitmask, counts, tiles, tile);
+    else count_word_tile(pk, srcP, srcC, beg, dir, emitmask, counts, tiles, tile, shift);
 }
 
 struct DstPos {
