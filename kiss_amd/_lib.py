@@ -30,6 +30,14 @@ KERNEL_CLASSES = [
 ]
 
 
+class Report(ctypes.Structure):
+    """what the library fills in for its caller: as_dict lists the fields but the reserved ones.  (A struct whose dict has
+    more to it than that -- Stats, MultiStats, FmiMmReport -- has an as_dict of its own.)"""
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
+
+
 class Stats(ctypes.Structure):
     _fields_ = [
         ("n", ctypes.c_uint64), ("m", ctypes.c_uint64), ("k", ctypes.c_uint32), ("depth", ctypes.c_uint32),
@@ -69,7 +77,7 @@ class MultiStats(ctypes.Structure):
         return d
 
 
-class VerifyReport(ctypes.Structure):
+class VerifyReport(Report):
     _fields_ = [
         ("n", ctypes.c_uint64), ("k", ctypes.c_uint32), ("exact", ctypes.c_uint32), ("ok", ctypes.c_uint32),
         ("sa0_ok", ctypes.c_uint32), ("out_of_range", ctypes.c_uint64), ("duplicates", ctypes.c_uint64),
@@ -77,20 +85,14 @@ class VerifyReport(ctypes.Structure):
         ("digest", ctypes.c_uint64), ("ms", ctypes.c_float), ("reserved_", ctypes.c_uint32),
     ]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved_"}
 
-
-class LcpReport(ctypes.Structure):
+class LcpReport(Report):
     _fields_ = [
         ("n", ctypes.c_uint64), ("irreducible", ctypes.c_uint64), ("long_pairs", ctypes.c_uint64),
         ("lcp_sum", ctypes.c_uint64), ("max_lcp", ctypes.c_uint32), ("reserved_", ctypes.c_uint32),
         ("ms_total", ctypes.c_float), ("ms_phi", ctypes.c_float), ("ms_short", ctypes.c_float), ("ms_long", ctypes.c_float),
         ("ms_scan_gather", ctypes.c_float), ("reserved2_", ctypes.c_uint32),
     ]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("reserved")}
 
 
 class FmiView(ctypes.Structure):
@@ -135,7 +137,7 @@ class FmiSeed(ctypes.Structure):
     _fields_ = [("start", ctypes.c_uint32), ("len", ctypes.c_uint32), ("sa_beg", ctypes.c_uint32), ("sa_end", ctypes.c_uint32)]
 
 
-class FmiSeedReport(ctypes.Structure):
+class FmiSeedReport(Report):
     """kiss_hip_fmi_seed_report"""
     _fields_ = [
         ("Q", ctypes.c_uint64), ("V", ctypes.c_uint64), ("bases", ctypes.c_uint64), ("seeds", ctypes.c_uint64),
@@ -144,9 +146,6 @@ class FmiSeedReport(ctypes.Structure):
         ("reserved_", ctypes.c_uint32), ("ms_total", ctypes.c_float), ("ms_search", ctypes.c_float),
         ("ms_compact", ctypes.c_float), ("ms_locate", ctypes.c_float), ("ms_sort", ctypes.c_float),
     ]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved_"}
 
 
 class ChainParams(ctypes.Structure):
@@ -164,16 +163,13 @@ class ChainAnchor(ctypes.Structure):
     _fields_ = [(k, ctypes.c_uint32) for k in ("rstart", "tpos", "len")]
 
 
-class ChainReport(ctypes.Structure):
+class ChainReport(Report):
     """kiss_hip_chain_report"""
     _fields_ = [
         ("V", ctypes.c_uint64), ("anchors", ctypes.c_uint64), ("chains", ctypes.c_uint64), ("chain_anchors", ctypes.c_uint64),
         ("dp_pairs", ctypes.c_uint64), ("max_anchors", ctypes.c_uint32), ("best_score", ctypes.c_uint32),
         ("ms_total", ctypes.c_float), ("ms_sort", ctypes.c_float), ("ms_dp", ctypes.c_float), ("ms_emit", ctypes.c_float),
     ]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class AlignParams(ctypes.Structure):
@@ -187,16 +183,13 @@ class Aln(ctypes.Structure):
                                                "del", "gaps", "band")]
 
 
-class AlignReport(ctypes.Structure):
+class AlignReport(Report):
     """kiss_hip_align_report"""
     _fields_ = [
         ("V", ctypes.c_uint64), ("chains", ctypes.c_uint64), ("aligned", ctypes.c_uint64), ("too_wide", ctypes.c_uint64),
         ("cells", ctypes.c_uint64), ("cigar_ops", ctypes.c_uint64), ("best_score", ctypes.c_uint32), ("max_band", ctypes.c_uint32),
         ("ms_total", ctypes.c_float), ("ms_dp", ctypes.c_float), ("ms_trace", ctypes.c_float), ("ms_emit", ctypes.c_float),
     ]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class SelectParams(ctypes.Structure):
@@ -209,16 +202,13 @@ class Hit(ctypes.Structure):
     _fields_ = [(k, ctypes.c_uint32) for k in ("aln", "flags", "mapq", "score", "sub", "n_sec", "head", "ref")]
 
 
-class SelectReport(ctypes.Structure):
+class SelectReport(Report):
     """kiss_hip_select_report"""
     _fields_ = [(k, ctypes.c_uint64) for k in ("Q", "V", "alignments", "candidates", "spanning", "redundant", "hits", "heads",
                                                "mapped")] + [
         ("max_candidates", ctypes.c_uint32), ("reserved_", ctypes.c_uint32), ("ms_total", ctypes.c_float),
         ("ms_sort", ctypes.c_float), ("ms_walk", ctypes.c_float), ("ms_emit", ctypes.c_float),
     ]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved_"}
 
 
 class PairParams(ctypes.Structure):
@@ -231,15 +221,12 @@ class Pair(ctypes.Structure):
     _fields_ = [(k, ctypes.c_uint32) for k in ("hit1", "hit2", "flags", "tlen", "score", "sub1", "sub2", "mapq1", "mapq2", "n_conc")]
 
 
-class PairReport(ctypes.Structure):
+class PairReport(Report):
     """kiss_hip_pair_report"""
     _fields_ = [(k, ctypes.c_uint64) for k in ("P", "eligible", "combinations", "concordant", "proper", "promoted", "lifted",
                                                "bad_input", "max_combinations")] + [
         ("ms_total", ctypes.c_float), ("ms_check", ctypes.c_float), ("ms_pair", ctypes.c_float), ("reserved_", ctypes.c_uint32),
     ]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved_"}
 
 
 class RescueParams(ctypes.Structure):
@@ -247,28 +234,22 @@ class RescueParams(ctypes.Structure):
     _fields_ = [(k, ctypes.c_uint32) for k in ("ins_min", "ins_max", "max_anchors", "min_anchor_score", "max_width")]
 
 
-class RescueReport(ctypes.Structure):
+class RescueReport(Report):
     """kiss_hip_rescue_report"""
     _fields_ = [(k, ctypes.c_uint64) for k in ("P", "pairs_planned", "anchors", "chains", "split", "empty", "bad_input",
                                                "max_chains")] + [
         ("ms_total", ctypes.c_float), ("ms_check", ctypes.c_float), ("ms_count", ctypes.c_float), ("ms_emit", ctypes.c_float),
     ]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class MergeReport(ctypes.Structure):
+class MergeReport(Report):
     """kiss_hip_merge_report"""
     _fields_ = [(k, ctypes.c_uint64) for k in ("V", "alignments_a", "alignments_b", "alignments", "cigar_ops")] + [
         ("ms_total", ctypes.c_float), ("ms_place", ctypes.c_float), ("ms_copy", ctypes.c_float), ("reserved_", ctypes.c_uint32),
     ]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved_"}
 
-
-class ReadsReport(ctypes.Structure):
+class ReadsReport(Report):
     """kiss_hip_reads_report (include/kiss_hip_reads.h)"""
     _fields_ = [(k, ctypes.c_uint64) for k in ("lines", "reads", "bases", "no_base", "empty_reads", "first_empty", "bad_records",
                                                "first_bad")] + [
@@ -276,18 +257,12 @@ class ReadsReport(ctypes.Structure):
         ("ms_total", ctypes.c_float), ("ms_lines", ctypes.c_float), ("ms_reads", ctypes.c_float), ("ms_copy", ctypes.c_float),
     ]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved_"}
 
-
-class MdReport(ctypes.Structure):
+class MdReport(Report):
     """kiss_hip_md_report (include/kiss_hip_md.h)"""
     _fields_ = [(k, ctypes.c_uint64) for k in ("items", "bad", "md_bytes", "mismatch_columns", "deleted_bases", "longest")] + [
         ("ms_total", ctypes.c_float), ("ms_count", ctypes.c_float), ("ms_emit", ctypes.c_float), ("reserved_", ctypes.c_uint32),
     ]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved_"}
 
 
 class InsertParams(ctypes.Structure):
@@ -295,15 +270,12 @@ class InsertParams(ctypes.Structure):
     _fields_ = [(k, ctypes.c_uint32) for k in ("min_mapq", "max_insert", "min_samples", "out_mult", "map_mult", "sd_mult")]
 
 
-class InsertReport(ctypes.Structure):
+class InsertReport(Report):
     """kiss_hip_insert_report (include/kiss_hip_insert.h)"""
     _fields_ = [(k, ctypes.c_uint64) for k in ("P", "unmapped", "bad_input", "low_mapq", "discordant", "too_long", "samples", "used")] + [
         (k, ctypes.c_uint32) for k in ("flags", "q25", "q50", "q75", "mean", "sd", "ins_min", "ins_max", "ins_mean")] + [
         ("ms_total", ctypes.c_float), ("ms_hist", ctypes.c_float), ("ms_stats", ctypes.c_float),
     ]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class Fmi8View(ctypes.Structure):
@@ -316,25 +288,19 @@ class Fmi8View(ctypes.Structure):
     ]
 
 
-class Fmi8Sizes(ctypes.Structure):
+class Fmi8Sizes(Report):
     """kiss_hip_fmi8_sizes"""
     _fields_ = [(k, ctypes.c_uint64) for k in ("n_sa", "bwt_bytes", "occ1_entries", "occ2_entries", "sa_entries", "b_words",
                                                "b_occ_entries")]
 
-    def as_dict(self):
-        return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
-
-class Fmi8Report(ctypes.Structure):
+class Fmi8Report(Report):
     """kiss_hip_fmi8_report"""
     _fields_ = [
         ("Q", ctypes.c_uint64), ("hits", ctypes.c_uint64), ("lf_pairs", ctypes.c_uint64), ("walk_failures", ctypes.c_uint64),
         ("checksum", ctypes.c_uint64), ("ms_total", ctypes.c_float), ("ms_search", ctypes.c_float),
         ("ms_locate", ctypes.c_float), ("ms_sort", ctypes.c_float),
     ]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class KissHipError(RuntimeError):

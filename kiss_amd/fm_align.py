@@ -10,6 +10,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from ._frame import addresses, make_params, read_batch, record_dtype, record_view, records, sized
 from .fm_chain import CHAIN_DTYPE
 from .sorter import _check
 
@@ -17,20 +18,14 @@ ALIGN_DEFAULTS = dict(match=1, mismatch=4, gap_open=6, gap_extend=1, band=32)
 ALIGN_MAX_BAND = 1024  # KISS_HIP_ALIGN_MAX_BAND
 ALIGN_CELLS_PER_N = 16  # KISS_HIP_ALIGN_CELLS_PER_N
 ALN_BAND_TOO_WIDE = 1
-ALN_FIELDS = ("score", "flags", "rbeg", "rend", "tbeg", "tend", "matches", "mismatches", "ins", "del", "gaps", "band")
-ALN_DTYPE = np.dtype([(k, np.uint32) for k in ALN_FIELDS])
+ALN_DTYPE = record_dtype(_lib.Aln)
+ALN_FIELDS = ALN_DTYPE.names
 CIGAR_OPS = "MID"
 
 
 def align_params(**params):
     """kiss_hip_align_params from keywords; the defaults are ALIGN_DEFAULTS"""
-    p = dict(ALIGN_DEFAULTS)
-    for k, v in params.items():
-        if k not in p:
-            raise TypeError("unknown align parameter %r (known: %s)" % (k, ", ".join(sorted(p))))
-        p[k] = int(v)
-    if min(p.values()) < 0 or max(p.values()) > 0xFFFFFFFF:
-        raise ValueError("the align parameters are u32")
+    p = make_params("align", ALIGN_DEFAULTS, params)
     if p["match"] < 1 or max(p["match"], p["mismatch"], p["gap_open"], p["gap_extend"]) > 65535 or p["band"] > 0x7FFFFFFF:
         raise ValueError("match is at least 1, the four scores at most 65535, band at most 2^31 - 1")
     return _lib.AlignParams(**p)
@@ -66,12 +61,8 @@ def align_dev(lib, ctx, device, d_text, n, d_reads, d_ridx, Q, both_strands, d_c
 
     d_cig = d_oidx = None
     if want_cigar:
-        d_cig = torch.zeros(1, dtype=torch.int32, device=dev)
         d_oidx = torch.zeros(C + 1, dtype=torch.int64, device=dev)
-        rc = call(d_cig, d_oidx, 0)
-        if rc == _lib.KISS_HIP_E_INVALID and rep.cigar_ops:  # the total is in the report
-            d_cig = torch.zeros(int(rep.cigar_ops), dtype=torch.int32, device=dev)
-            rc = call(d_cig, d_oidx, int(rep.cigar_ops))
+        rc, (d_cig, _, _) = sized(call, lambda m=0: (torch.zeros(max(m, 1), dtype=torch.int32, device=dev), d_oidx, m), rep, "cigar_ops")
     else:
         rc = call(None, None, 0)
     _raise(rc, rep, "kiss_hip_fmi_align_dev", ctx._ctx)
@@ -81,7 +72,7 @@ def align_dev(lib, ctx, device, d_text, n, d_reads, d_ridx, Q, both_strands, d_c
 def align_arrays(out, want_cigar):
     """the tensors of align_dev as numpy"""
     rep, C = out["rep"], out["C"]
-    res = {"alignments": np.ascontiguousarray(out["d_alns"][:C].cpu().numpy()).view(np.uint32).reshape(C, 12).view(ALN_DTYPE).reshape(C)}
+    res = {"alignments": record_view(out["d_alns"], C, ALN_DTYPE)}
     if want_cigar:
         m = int(rep.cigar_ops)
         res["cigar"] = out["d_cigar"][:m].cpu().numpy().view(np.uint32)
@@ -98,25 +89,8 @@ def align_chains(text, reads, chains, chain_index, both_strands=False, want_ciga
     want_cigar, cigar (u32 ops len << 4 | op, op 0 M, 1 I, 2 D) / cigar_index in CSR layout over the chains."""
     p = align_params(**params)
     text = np.ascontiguousarray(text, dtype=np.uint8).ravel()
-    if isinstance(reads, tuple):
-        cat = np.ascontiguousarray(reads[0], dtype=np.uint8)
-        ridx = np.ascontiguousarray(reads[1], dtype=np.uint64)
-    else:
-        arrs = [np.ascontiguousarray(r, dtype=np.uint8).ravel() for r in reads]
-        cat = np.concatenate(arrs) if arrs else np.zeros(0, np.uint8)
-        ridx = np.zeros(len(arrs) + 1, np.uint64)
-        np.cumsum([a.size for a in arrs], out=ridx[1:])
-    chains = np.asarray(chains)
-    if chains.dtype.names:
-        ch = np.zeros(chains.shape[0], CHAIN_DTYPE)
-        for k in CHAIN_DTYPE.names:
-            ch[k] = chains[k]
-    else:
-        quads = np.asarray(chains, np.int64).reshape(-1, 4)
-        if quads.size and (quads.min() < 0 or quads.max() > 0xFFFFFFFF):
-            raise ValueError("rbeg, rend, tbeg and tend are u32")
-        ch = np.zeros(quads.shape[0], CHAIN_DTYPE)
-        ch["rbeg"], ch["rend"], ch["tbeg"], ch["tend"] = quads[:, 0], quads[:, 1], quads[:, 2], quads[:, 3]
+    cat, ridx = read_batch(reads)
+    ch = records(chains, CHAIN_DTYPE, "rbeg, rend, tbeg and tend are u32", columns=("rbeg", "rend", "tbeg", "tend"), structured=CHAIN_DTYPE.names)
     cidx = np.ascontiguousarray(chain_index, dtype=np.uint64)
     if ridx.ndim != 1 or ridx.size < 1 or cidx.ndim != 1:
         raise ValueError("the read index has Q + 1 entries, chain_index V + 1")
@@ -131,12 +105,7 @@ def align_chains(text, reads, chains, chain_index, both_strands=False, want_ciga
     C = int(cidx[-1]) - int(cidx[0]) if int(cidx[-1]) >= int(cidx[0]) else 0
     alns = np.zeros(max(C, 1), ALN_DTYPE)
     oidx = np.zeros(C + 1, np.uint64)
-    if text.size == 0:
-        text = np.zeros(1, np.uint8)[:0]
-    keep = [np.zeros(1, np.uint8), np.zeros(1, CHAIN_DTYPE)]  # (pointers that are not NULL)
-    tp = text.ctypes.data if text.size else keep[0].ctypes.data
-    rp = cat.ctypes.data if cat.size else keep[0].ctypes.data
-    cp = ch.ctypes.data if ch.size else keep[1].ctypes.data
+    (tp, rp, cp), hold = addresses(text, cat, ch)
 
     def call(cig, ocap):
         return lib.kiss_hip_fmi_align_host(tp, text.size, rp, ridx.ctypes.data, Q, 1 if both_strands else 0, cp, cidx.ctypes.data,
@@ -145,11 +114,7 @@ def align_chains(text, reads, chains, chain_index, both_strands=False, want_ciga
 
     cig = None
     if want_cigar:
-        cig = np.zeros(1, np.uint32)
-        rc = call(cig, 0)
-        if rc == _lib.KISS_HIP_E_INVALID and rep.cigar_ops:  # the total is in the report
-            cig = np.zeros(int(rep.cigar_ops), np.uint32)
-            rc = call(cig, int(rep.cigar_ops))
+        rc, (cig, _) = sized(call, lambda m=0: (np.zeros(max(m, 1), np.uint32), m), rep, "cigar_ops")
     else:
         rc = call(None, 0)
     _raise(rc, rep, "kiss_hip_fmi_align_host")

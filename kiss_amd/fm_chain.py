@@ -9,23 +9,18 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from ._frame import addresses, make_params, record_dtype, record_view, records, sized
 from .sorter import _check
 
 CHAIN_DEFAULTS = dict(max_gap=5000, band=500, gap_cost=2, max_lookback=64, min_score=40)
-CHAIN_DTYPE = np.dtype([(k, np.uint32) for k in ("score", "anchors", "rbeg", "rend", "tbeg", "tend")])
-ANCHOR_DTYPE = np.dtype([(k, np.uint32) for k in ("rstart", "tpos", "len")])
-SEED_DTYPE = np.dtype([(k, np.uint32) for k in ("start", "len", "sa_beg", "sa_end")])
+CHAIN_DTYPE = record_dtype(_lib.Chain)
+ANCHOR_DTYPE = record_dtype(_lib.ChainAnchor)
+SEED_DTYPE = record_dtype(_lib.FmiSeed)
 
 
 def chain_params(**params):
     """kiss_hip_chain_params from keywords; the defaults are CHAIN_DEFAULTS"""
-    p = dict(CHAIN_DEFAULTS)
-    for k, v in params.items():
-        if k not in p:
-            raise TypeError("unknown chain parameter %r (known: %s)" % (k, ", ".join(sorted(p))))
-        p[k] = int(v)
-    if min(p.values()) < 0 or max(p.values()) > 0xFFFFFFFF:
-        raise ValueError("the chain parameters are u32")
+    p = make_params("chain", CHAIN_DEFAULTS, params)
     if p["max_gap"] > 0x7FFFFFFF or p["band"] > 0x7FFFFFFF or p["gap_cost"] > 65535:
         raise ValueError("max_gap and band are at most 2^31 - 1, gap_cost at most 65535")
     return _lib.ChainParams(**p)
@@ -52,17 +47,15 @@ def chain_dev(lib, ctx, device, d_seeds, d_sidx, V, d_pos, d_pidx, params, want_
                                           vp(d_cidx.data_ptr()), ccap, vp(d_anc.data_ptr()) if d_anc is not None else None,
                                           vp(d_aidx.data_ptr()) if d_aidx is not None else None, acap, ctypes.byref(rep), None)
 
-    d_chains = torch.zeros((1, 6), dtype=torch.int32, device=dev)
-    rc = call(d_chains, 0, None, None, 0)
-    d_anc = d_aidx = None
-    if rc == _lib.KISS_HIP_E_INVALID and rep.chains:  # the totals are in the report
-        n, m = int(rep.chains), int(rep.chain_anchors)
-        d_chains = torch.zeros((n, 6), dtype=torch.int32, device=dev)
-        if want_anchors:
-            d_anc = torch.zeros((max(m, 1), 3), dtype=torch.int32, device=dev)
-            d_aidx = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-        rc = call(d_chains, n, d_anc, d_aidx, m if want_anchors else 0)
-    elif rc == _lib.KISS_HIP_OK and want_anchors:  # no chains at all
+    def room(n=0, m=0):
+        d_chains = torch.zeros((max(n, 1), 6), dtype=torch.int32, device=dev)
+        if not (n and want_anchors):
+            return d_chains, n, None, None, 0
+        return (d_chains, n, torch.zeros((max(m, 1), 3), dtype=torch.int32, device=dev),
+                torch.zeros(n + 1, dtype=torch.int64, device=dev), m)
+
+    rc, (d_chains, n, d_anc, d_aidx, _) = sized(call, room, rep, "chains", "chain_anchors")
+    if rc == _lib.KISS_HIP_OK and want_anchors and not n:  # no chains at all
         d_anc = torch.zeros((1, 3), dtype=torch.int32, device=dev)
         d_aidx = torch.zeros(1, dtype=torch.int64, device=dev)
     _raise(rc, rep, "kiss_hip_fmi_chain_dev", ctx._ctx)
@@ -72,11 +65,9 @@ def chain_dev(lib, ctx, device, d_seeds, d_sidx, V, d_pos, d_pidx, params, want_
 def chain_arrays(out, want_anchors):
     """the tensors of chain_dev as numpy"""
     rep = out["rep"]
-    n, m = int(rep.chains), int(rep.chain_anchors)
-    res = {"chains": np.ascontiguousarray(out["d_chains"][:n].cpu().numpy()).view(np.uint32).reshape(n, 6).view(CHAIN_DTYPE).reshape(n),
-           "chain_index": out["d_cidx"].cpu().numpy().view(np.uint64)}
+    res = {"chains": record_view(out["d_chains"], int(rep.chains), CHAIN_DTYPE), "chain_index": out["d_cidx"].cpu().numpy().view(np.uint64)}
     if want_anchors:
-        res["anchors"] = np.ascontiguousarray(out["d_anc"][:m].cpu().numpy()).view(np.uint32).reshape(m, 3).view(ANCHOR_DTYPE).reshape(m)
+        res["anchors"] = record_view(out["d_anc"], int(rep.chain_anchors), ANCHOR_DTYPE)
         res["anchor_index"] = out["d_aidx"].cpu().numpy().view(np.uint64)
     res["report"] = rep.as_dict()
     return res
@@ -87,16 +78,7 @@ def chain_seeds(seeds, seed_index, positions, pos_index, want_anchors=True, devi
     sa_beg, sa_end) or an (n, 2) array of (start, len); seed_index has V + 1 entries, pos_index seeds + 1; params as in
     FMIndex.chains.  Returns dict(chains, chain_index, report) and, with want_anchors, anchors / anchor_index."""
     p = chain_params(**params)
-    seeds = np.asarray(seeds)
-    if seeds.dtype.names:
-        sd = np.zeros(seeds.shape[0], SEED_DTYPE)
-        sd["start"], sd["len"] = seeds["start"], seeds["len"]
-    else:
-        pairs = np.asarray(seeds, np.int64).reshape(-1, 2)
-        if pairs.size and (pairs.min() < 0 or pairs.max() > 0xFFFFFFFF):
-            raise ValueError("start and len are u32")
-        sd = np.zeros(pairs.shape[0], SEED_DTYPE)
-        sd["start"], sd["len"] = pairs[:, 0], pairs[:, 1]
+    sd = records(seeds, SEED_DTYPE, "start and len are u32", columns=("start", "len"))
     sidx = np.ascontiguousarray(seed_index, dtype=np.uint64)
     pidx = np.ascontiguousarray(pos_index, dtype=np.uint64)
     pos = np.ascontiguousarray(positions, dtype=np.uint32)
@@ -108,25 +90,20 @@ def chain_seeds(seeds, seed_index, positions, pos_index, want_anchors=True, devi
     lib = _lib.load(hooks)
     rep = _lib.ChainReport()
     cidx = np.zeros(V + 1, np.uint64)
-    if sd.size == 0:
-        sd = np.zeros(1, SEED_DTYPE)  # (a pointer that is not NULL)
-    if pos.size == 0:
-        pos = np.zeros(1, np.uint32)
+    (sp, pp), hold = addresses(sd, pos)
 
     def call(chains, ccap, anc, aidx, acap):
-        return lib.kiss_hip_fmi_chain_host(sd.ctypes.data, sidx.ctypes.data, V, pos.ctypes.data, pidx.ctypes.data, ctypes.byref(p),
+        return lib.kiss_hip_fmi_chain_host(sp, sidx.ctypes.data, V, pp, pidx.ctypes.data, ctypes.byref(p),
                                            chains.ctypes.data, cidx.ctypes.data, ccap, anc.ctypes.data if anc is not None else None,
                                            aidx.ctypes.data if aidx is not None else None, acap, ctypes.byref(rep), int(device))
 
-    chains = np.zeros(1, CHAIN_DTYPE)
-    anc = aidx = None
-    rc = call(chains, 0, None, None, 0)
-    if rc == _lib.KISS_HIP_E_INVALID and rep.chains:  # the totals are in the report
-        n, m = int(rep.chains), int(rep.chain_anchors)
-        chains = np.zeros(n, CHAIN_DTYPE)
-        if want_anchors:
-            anc, aidx = np.zeros(max(m, 1), ANCHOR_DTYPE), np.zeros(n + 1, np.uint64)
-        rc = call(chains, n, anc, aidx, m if want_anchors else 0)
+    def room(n=0, m=0):
+        chains = np.zeros(max(n, 1), CHAIN_DTYPE)
+        if not (n and want_anchors):
+            return chains, n, None, None, 0
+        return chains, n, np.zeros(max(m, 1), ANCHOR_DTYPE), np.zeros(n + 1, np.uint64), m
+
+    rc, (chains, _, anc, aidx, _) = sized(call, room, rep, "chains", "chain_anchors")
     _raise(rc, rep, "kiss_hip_fmi_chain_host")
     n, m = int(rep.chains), int(rep.chain_anchors)
     res = {"chains": chains[:n], "chain_index": cidx}

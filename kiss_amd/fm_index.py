@@ -13,10 +13,12 @@ There is no CPU path.
 """
 import ctypes
 import struct
+from dataclasses import dataclass
 
 import numpy as np
 
 from . import _lib
+from ._frame import read_batch, read_list, record_view
 from .sorter import Context, K_UNBOUNDED, _check
 
 SA_INTV = 4          # fmindex_build.hpp:27
@@ -38,6 +40,25 @@ def _check_params(sa_intv, lookup_len):
         raise ValueError("sa_intv must be in 1..%d, got %d" % (MAX_SA_INTV, sa_intv))
     if not 0 <= lookup_len <= MAX_LOOKUP_LEN:
         raise ValueError("lookup_len must be in 0..%d, got %d" % (MAX_LOOKUP_LEN, lookup_len))
+
+
+@dataclass
+class _Aligned:
+    """what _align_dev leaves on the device for the stages after it (select, insert, pair, rescue, MD)"""
+    lib: object          # the library that serves the index
+    ctx: object          # the context the align call ran on
+    d_text: object       # the text, its length n
+    n: int
+    d_reads: object      # the reads, their index (Q + 1) and, on the host, their lengths
+    d_ridx: object
+    Q: int
+    lens: object
+    d_cidx: object       # the chain index (V + 1) and the C alignments of the chains
+    d_alns: object
+    C: int
+    al: dict             # all of align_dev's output: the ops and their index, the report
+    align_params: object
+    keep: tuple          # the outputs of the seeds and the chain call, which the tensors above are part of
 
 
 class FMIndex:
@@ -98,6 +119,24 @@ class FMIndex:
                 self._ctx.close()
             self._ctx = Context(max_n=max(max_n, 1 << 20), device=self.device, hooks=self._hooks)
         return self._ctx
+
+    def _context_to_sort(self, ctx, count):
+        """ctx, or a context whose LMS arrays (0.32 max_n entries), where a call sorts its items, hold `count` of them"""
+        if count > 0.3 * ctx.max_n:
+            ctx = self._context(min(_lib.MAX_N, int(3.3 * count) + (1 << 20)))
+        return ctx
+
+    def _text_dev(self, text):
+        """the text, a uint8 array or a tensor, on the device (one element when it is empty: no NULL) -> tensor, length"""
+        torch = _torch()
+        dev = torch.device("cuda", self.device)
+        if isinstance(text, torch.Tensor):
+            d_text = text.to(device=dev, dtype=torch.uint8).contiguous().reshape(-1)
+        else:
+            arr = np.ascontiguousarray(text, dtype=np.uint8).ravel()
+            d_text = torch.from_numpy(arr).to(dev) if arr.size else torch.zeros(0, dtype=torch.uint8, device=dev)
+        n = int(d_text.numel())
+        return (d_text if n else torch.zeros(1, dtype=torch.uint8, device=dev)), n
 
     # ---- build (fm_index.hpp:379-451) ------------------------------------------------------------------
     def build(self, ref, sa=None, exact=False, exact_sa=False):
@@ -468,17 +507,14 @@ class FMIndex:
         max_len: 0 = no cap.  Seeds are defined for max_len <= the order of the build: 1..32 by default, any value after
         build(exact=True); positions only on an index built from the exact suffix array.  With positions the batch is
         searched twice, as the C interface has it: the first call sizes the output."""
+        from .fm_chain import SEED_DTYPE
         d = self._seeds_dev(reads, min_len, max_len, max_occ, both_strands, want_positions, want_ms)
         rep, nseeds = d["rep"], d["nseeds"]
         res = {}
         if want_positions:
             res["positions"] = d["d_pos"][:d["total"]].cpu().numpy().view(np.uint32)
             res["pos_index"] = d["d_pidx"].cpu().numpy().view(np.uint64)
-        raw = d["d_seeds"][:nseeds].cpu().numpy().view(np.uint32).reshape(nseeds, 4)
-        seeds = np.zeros(nseeds, dtype=[("start", np.uint32), ("len", np.uint32), ("sa_beg", np.uint32), ("sa_end", np.uint32)])
-        for j, name in enumerate(("start", "len", "sa_beg", "sa_end")):
-            seeds[name] = raw[:, j]
-        res["seeds"] = seeds
+        res["seeds"] = seeds = record_view(d["d_seeds"], nseeds, SEED_DTYPE)
         res["seed_index"] = d["d_sidx"].cpu().numpy().view(np.uint64)
         res["count"] = (seeds["sa_end"] - seeds["sa_beg"]).astype(np.uint32)
         if want_ms:
@@ -502,14 +538,7 @@ class FMIndex:
             if max_len == 0 or max_len > SORT_LEN:
                 raise ValueError("an index of a suffix array of order %d defines seeds for max_len in 1..%d only "
                                  "(build with exact=True for longer ones)" % (SORT_LEN, SORT_LEN))
-        if isinstance(reads, tuple):
-            cat = np.ascontiguousarray(reads[0], dtype=np.uint8)
-            index = np.ascontiguousarray(reads[1], dtype=np.uint64)
-        else:
-            arrs = [np.ascontiguousarray(r, dtype=np.uint8).ravel() for r in reads]
-            cat = np.concatenate(arrs) if arrs else np.zeros(0, np.uint8)
-            index = np.zeros(len(arrs) + 1, np.uint64)
-            np.cumsum([a.size for a in arrs], out=index[1:])
+        cat, index = read_batch(reads)
         if index.ndim != 1 or index.size < 1:
             raise ValueError("the read index has Q + 1 entries")
         Q = int(index.size) - 1
@@ -543,8 +572,7 @@ class FMIndex:
                "d_reads": d_reads, "d_ridx": d_index, "Q": Q}
         if want_positions:
             total, nseeds = int(rep.positions), int(rep.seeds)
-            if total > 0.3 * ctx.max_n:  # one call sorts its positions in the context's LMS arrays: a context sized for them
-                ctx = self._context(min(_lib.MAX_N, int(3.3 * total) + (1 << 20)))
+            ctx = self._context_to_sort(ctx, total)  # (the positions)
             d_pos = torch.zeros(max(total, 1), dtype=torch.int32, device=dev)
             d_pidx = torch.zeros(nseeds + 1, dtype=torch.int64, device=dev)
             rc = call(ctx, vp(d_pos.data_ptr()), vp(d_pidx.data_ptr()), total)
@@ -573,9 +601,7 @@ class FMIndex:
         from .fm_chain import chain_params, chain_dev, chain_arrays
         p = chain_params(**params)
         d = self._seeds_dev(reads, min_len, max_len, max_occ, both_strands, True, False)
-        ctx = d["ctx"]
-        if d["total"] > 0.3 * ctx.max_n:  # (the anchors are sorted where the positions were)
-            ctx = self._context(min(_lib.MAX_N, int(3.3 * d["total"]) + (1 << 20)))
+        ctx = self._context_to_sort(d["ctx"], d["total"])  # (the anchors are sorted where the positions were)
         out = chain_dev(_lib.load(self._hooks), ctx, self.device, d["d_seeds"], d["d_sidx"], d["V"], d["d_pos"], d["d_pidx"], p,
                         want_anchors)
         res = chain_arrays(out, want_anchors)
@@ -599,22 +625,12 @@ class FMIndex:
         """align(): -> (its result, the device tensors a later stage reads: reads, read index, chain index, alignments)"""
         from .fm_align import align_arrays, align_dev, align_params
         from .fm_chain import chain_params as make_chain_params, chain_dev, chain_arrays
-        torch = _torch()
+        _torch()  # (no device: said before anything else)
         p = align_params(**params)
         cp = make_chain_params(**(chain_params or {}))
-        dev = torch.device("cuda", self.device)
-        if isinstance(text, torch.Tensor):
-            d_text = text.to(device=dev, dtype=torch.uint8).contiguous().reshape(-1)
-        else:
-            arr = np.ascontiguousarray(text, dtype=np.uint8).ravel()
-            d_text = torch.from_numpy(arr).to(dev) if arr.size else torch.zeros(0, dtype=torch.uint8, device=dev)
-        n = int(d_text.numel())
-        if n == 0:
-            d_text = torch.zeros(1, dtype=torch.uint8, device=dev)
+        d_text, n = self._text_dev(text)
         d = self._seeds_dev(reads, min_len, max_len, max_occ, both_strands, True, False)
-        ctx = d["ctx"]
-        if d["total"] > 0.3 * ctx.max_n:  # (the anchors are sorted where the positions were)
-            ctx = self._context(min(_lib.MAX_N, int(3.3 * d["total"]) + (1 << 20)))
+        ctx = self._context_to_sort(d["ctx"], d["total"])  # (the anchors are sorted where the positions were)
         lib = _lib.load(self._hooks)
         out = chain_dev(lib, ctx, self.device, d["d_seeds"], d["d_sidx"], d["V"], d["d_pos"], d["d_pidx"], cp, False)
         res = chain_arrays(out, False)
@@ -626,9 +642,8 @@ class FMIndex:
         al = align_dev(lib, ctx, self.device, d_text, n, d["d_reads"], d["d_ridx"], d["Q"], both_strands, out["d_chains"],
                        out["d_cidx"], C, p, want_cigar)
         res.update(align_arrays(al, want_cigar))
-        return res, {"lib": lib, "ctx": ctx, "d_ridx": d["d_ridx"], "Q": d["Q"], "d_cidx": out["d_cidx"], "d_alns": al["d_alns"],
-                     "C": C, "keep": (d, out, al), "d_text": d_text, "n": n, "d_reads": d["d_reads"], "lens": lens, "align_params": p,
-                     "al": al}
+        return res, _Aligned(lib=lib, ctx=ctx, d_text=d_text, n=n, d_reads=d["d_reads"], d_ridx=d["d_ridx"], Q=d["Q"], lens=lens,
+                             d_cidx=out["d_cidx"], d_alns=al["d_alns"], C=C, al=al, align_params=p, keep=(d, out))
 
     def _context_for_cells(self, ctx, chains, chain_index, lens, both_strands, band):
         """the traceback store of an align call holds ALIGN_CELLS_PER_N cells per base of the context: ctx, or a context sized
@@ -656,25 +671,34 @@ class FMIndex:
         hit_index (Q + 1: the hits of read q are hits[hit_index[q]:hit_index[q + 1]], the primary first) and select_report.
         want_md (it needs want_cigar): also md, md_index, md_counts and md_report -- the MD:Z string of every hit, in the order
         of hits (kiss_hip_fmi_md_dev, include/kiss_hip_md.h; kiss_amd.fm_md.md_strings() splits the bytes)."""
-        from .fm_select import select_arrays, select_dev, select_params as make_select_params
+        from .fm_select import select_arrays, select_params as make_select_params
         sp = make_select_params(**select_params)
-        if want_md and not want_cigar:
-            raise ValueError("want_md needs the ops: want_cigar=True")
+        self._md_needs_ops(want_md, want_cigar)
         res, t = self._align_dev(reads, text, min_len, max_len, max_occ, both_strands, chain_params, want_cigar,
                                  align_params or {})
-        ctx = t["ctx"]
-        if t["C"] > 0.3 * ctx.max_n:  # (the alignments of a call are sorted in the context's LMS arrays)
-            ctx = self._context(min(_lib.MAX_N, int(3.3 * t["C"]) + (1 << 20)))
-        sel = select_dev(t["lib"], ctx, self.device, t["d_alns"], t["d_cidx"], t["d_ridx"], t["Q"], t["C"], both_strands, bounds, sp)
+        ctx, sel = self._select(t, t.ctx, t.d_alns, t.d_cidx, t.C, both_strands, bounds, sp)
         res.update(select_arrays(sel))
         if want_md:
-            res.update(self._md_of_hits(t, ctx, t["d_alns"], t["d_cidx"], t["C"], t["al"]["d_cigar"], t["al"]["d_oidx"], both_strands, sel))
+            res.update(self._md_of_hits(t, ctx, t.d_alns, t.d_cidx, t.C, t.al["d_cigar"], t.al["d_oidx"], both_strands, sel))
         return res
+
+    @staticmethod
+    def _md_needs_ops(want_md, want_cigar):
+        if want_md and not want_cigar:
+            raise ValueError("want_md needs the ops: want_cigar=True")
+
+    def _select(self, t, ctx, d_alns, d_cidx, C, both_strands, bounds, sp):
+        """the select stage over C alignments of the batch t -> the context it ran on (ctx, or one that sorts C alignments: a
+        call sorts them in the context's LMS arrays) and select_dev's output.  (What select_arrays makes of it the caller
+        merges into its result where it copies the rest: the rescue pass does so after its pair call.)"""
+        from .fm_select import select_dev
+        ctx = self._context_to_sort(ctx, C)
+        return ctx, select_dev(t.lib, ctx, self.device, d_alns, d_cidx, t.d_ridx, t.Q, C, both_strands, bounds, sp)
 
     def _md_of_hits(self, t, ctx, d_alns, d_cidx, C, d_cigar, d_oidx, both_strands, sel):
         """map(want_md=True): the MD strings of the hits of a select call, from the buffers that are on the device"""
         from .fm_md import md_arrays, md_dev
-        out = md_dev(t["lib"], ctx, self.device, t["d_text"], t["n"], t["d_reads"], t["d_ridx"], t["Q"], both_strands, d_alns, d_cidx, C,
+        out = md_dev(t.lib, ctx, self.device, t.d_text, t.n, t.d_reads, t.d_ridx, t.Q, both_strands, d_alns, d_cidx, C,
                      d_cigar, d_oidx, sel["d_hits"], int(sel["rep"].hits))
         return md_arrays(out)
 
@@ -710,47 +734,35 @@ class FMIndex:
         insert (report, hist, applied, ins_min, ins_max, ins_mean: the three values used).  With rescue both passes use the
         same values: the estimate is taken once, from the first pass."""
         from .fm_pair import pair_arrays, pair_dev, pair_params as make_pair_params
-        from .fm_select import select_arrays, select_dev, select_params as make_select_params
+        from .fm_select import select_arrays, select_params as make_select_params
         pp = make_pair_params(**pair_params)
         sp = make_select_params(**(select_params or {}))
-        if want_md and not want_cigar:
-            raise ValueError("want_md needs the ops: want_cigar=True")
+        self._md_needs_ops(want_md, want_cigar)
         ip = None
         if insert is not None and insert is not False:
             from .fm_insert import insert_params as make_insert_params
             ip = make_insert_params(**({} if insert is True or insert == "auto" else dict(insert)))
-
-        def as_list(reads):
-            if isinstance(reads, tuple):
-                cat = np.ascontiguousarray(reads[0], dtype=np.uint8)
-                index = np.ascontiguousarray(reads[1], dtype=np.uint64)
-                return [cat[int(index[q]):int(index[q + 1])] for q in range(index.size - 1)]
-            return [np.ascontiguousarray(r, dtype=np.uint8).ravel() for r in reads]
-
-        m1, m2 = as_list(reads1), as_list(reads2)
+        m1, m2 = read_list(reads1), read_list(reads2)
         if len(m1) != len(m2):
             raise ValueError("reads1 has %d reads, reads2 has %d: a pair has one of each" % (len(m1), len(m2)))
         batch = [r for pair in zip(m1, m2) for r in pair]
         res, t = self._align_dev(batch, text, min_len, max_len, max_occ, True, chain_params, want_cigar, align_params or {})
-        ctx = t["ctx"]
-        if t["C"] > 0.3 * ctx.max_n:  # (the alignments of a call are sorted in the context's LMS arrays)
-            ctx = self._context(min(_lib.MAX_N, int(3.3 * t["C"]) + (1 << 20)))
-        sel = select_dev(t["lib"], ctx, self.device, t["d_alns"], t["d_cidx"], t["d_ridx"], t["Q"], t["C"], True, bounds, sp)
+        ctx, sel = self._select(t, t.ctx, t.d_alns, t.d_cidx, t.C, True, bounds, sp)
         res.update(select_arrays(sel))
         if ip is not None:
             pp = self._insert_estimate(res, t, ctx, sel, pp, ip)
-        out = pair_dev(t["lib"], ctx, self.device, sel["d_hits"], sel["d_hidx"], t["Q"], t["d_alns"], t["C"], pp)
+        out = pair_dev(t.lib, ctx, self.device, sel["d_hits"], sel["d_hidx"], t.Q, t.d_alns, t.C, pp)
         res.update(pair_arrays(out))
         if rescue is None or rescue is False:
             if want_md:
-                res.update(self._md_of_hits(t, ctx, t["d_alns"], t["d_cidx"], t["C"], t["al"]["d_cigar"], t["al"]["d_oidx"], True, sel))
+                res.update(self._md_of_hits(t, ctx, t.d_alns, t.d_cidx, t.C, t.al["d_cigar"], t.al["d_oidx"], True, sel))
             return res
         return self._rescue_pass(res, t, ctx, sel, out, sp, pp, bounds, want_cigar, {} if rescue is True else dict(rescue), want_md)
 
     def _insert_estimate(self, res, t, ctx, sel, pp, ip):
         """map_pairs(insert=...): the estimate from the hits of the first select call -> the pair parameters to use"""
         from .fm_insert import INSERT_OK, insert_arrays, insert_dev
-        got = insert_arrays(insert_dev(t["lib"], ctx, self.device, sel["d_hits"], sel["d_hidx"], t["Q"], t["d_alns"], t["C"], ip))
+        got = insert_arrays(insert_dev(t.lib, ctx, self.device, sel["d_hits"], sel["d_hidx"], t.Q, t.d_alns, t.C, ip))
         rep = got["report"]
         applied = bool(rep["flags"] & INSERT_OK)
         if applied:
@@ -764,30 +776,28 @@ class FMIndex:
         from .fm_align import align_arrays, align_dev
         from .fm_pair import PAIR_PROPER, pair_arrays, pair_dev
         from .fm_rescue import merge_arrays, merge_dev, rescue_arrays, rescue_dev, rescue_params
-        from .fm_select import select_arrays, select_dev
+        from .fm_select import select_arrays
         rescue.setdefault("ins_min", pp.ins_min)
         rescue.setdefault("ins_max", pp.ins_max)
         rp = rescue_params(**rescue)
-        lib, Q, CA = t["lib"], t["Q"], t["C"]
+        lib, Q, CA = t.lib, t.Q, t.C
         first = {k: res[k] for k in ("pairs", "hits", "hit_index", "select_report", "pair_report")}
         first["alignments"] = CA
-        pl = rescue_dev(lib, ctx, self.device, out["d_pairs"], sel["d_hits"], sel["d_hidx"], Q, t["d_alns"], CA, t["d_ridx"], t["n"],
+        pl = rescue_dev(lib, ctx, self.device, out["d_pairs"], sel["d_hits"], sel["d_hidx"], Q, t.d_alns, CA, t.d_ridx, t.n,
                         bounds, rp, int(sel["rep"].hits))
         plan = rescue_arrays(pl)
         if pl["C"]:
-            ctx = self._context_for_cells(ctx, plan["chains"], plan["chain_index"], t["lens"], True, int(t["align_params"].band))
-        al2 = align_dev(lib, ctx, self.device, t["d_text"], t["n"], t["d_reads"], t["d_ridx"], Q, True, pl["d_chains"], pl["d_cidx"],
-                        pl["C"], t["align_params"], want_cigar)
-        al1 = t["al"]
-        a = {"d_alns": al1["d_alns"], "d_cidx": t["d_cidx"], "C": CA, "d_cigar": al1["d_cigar"], "d_oidx": al1["d_oidx"],
+            ctx = self._context_for_cells(ctx, plan["chains"], plan["chain_index"], t.lens, True, int(t.align_params.band))
+        al2 = align_dev(lib, ctx, self.device, t.d_text, t.n, t.d_reads, t.d_ridx, Q, True, pl["d_chains"], pl["d_cidx"],
+                        pl["C"], t.align_params, want_cigar)
+        al1 = t.al
+        a = {"d_alns": al1["d_alns"], "d_cidx": t.d_cidx, "C": CA, "d_cigar": al1["d_cigar"], "d_oidx": al1["d_oidx"],
              "ops": int(al1["rep"].cigar_ops)}
         b = {"d_alns": al2["d_alns"], "d_cidx": pl["d_cidx"], "C": pl["C"], "d_cigar": al2["d_cigar"], "d_oidx": al2["d_oidx"],
              "ops": int(al2["rep"].cigar_ops)}
         mg = merge_dev(lib, ctx, self.device, 2 * Q, a, b, want_cigar)
         C = mg["C"]
-        if C > 0.3 * ctx.max_n:  # (the alignments of a call are sorted in the context's LMS arrays)
-            ctx = self._context(min(_lib.MAX_N, int(3.3 * C) + (1 << 20)))
-        sel2 = select_dev(lib, ctx, self.device, mg["d_alns"], mg["d_cidx"], t["d_ridx"], Q, C, True, bounds, sp)
+        ctx, sel2 = self._select(t, ctx, mg["d_alns"], mg["d_cidx"], C, True, bounds, sp)
         out2 = pair_dev(lib, ctx, self.device, sel2["d_hits"], sel2["d_hidx"], Q, mg["d_alns"], C, pp)
         res.update(merge_arrays(mg, want_cigar))
         res.update(select_arrays(sel2))

@@ -11,9 +11,8 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .fm_align import ALN_DTYPE
-from .fm_pair import _records
-from .fm_select import HIT_DTYPE
+from ._frame import addresses, check_mates, make_params
+from .fm_pair import _mates_of
 from .sorter import _check
 
 INSERT_DEFAULTS = dict(min_mapq=20, max_insert=10000, min_samples=25, out_mult=2, map_mult=3, sd_mult=4)
@@ -24,16 +23,7 @@ INSERT_STATS = ("samples", "used", "q25", "q50", "q75", "mean", "sd", "ins_min",
 
 def insert_params(**params):
     """kiss_hip_insert_params from keywords; the defaults are INSERT_DEFAULTS"""
-    p = dict(INSERT_DEFAULTS)
-    for k, v in params.items():
-        if k not in p:
-            raise TypeError("unknown insert parameter %r (known: %s)" % (k, ", ".join(sorted(p))))
-        p[k] = int(v)
-    if min(p.values()) < 0 or max(p.values()) > 0xFFFFFFFF:
-        raise ValueError("the insert parameters are u32")
-    for k, top in INSERT_LIMITS.items():
-        if p[k] > top:
-            raise ValueError("%s is at most %d" % (k, top))
+    p = make_params("insert", INSERT_DEFAULTS, params, INSERT_LIMITS)
     if p["max_insert"] < 1:
         raise ValueError("max_insert is at least 1")
     return _lib.InsertParams(**p)
@@ -43,8 +33,7 @@ def insert_dev(lib, ctx, device, d_hits, d_hidx, Q, d_alns, aln_count, params, w
     """the device entry on torch tensors -> dict of the histogram tensor (max_insert + 1; None without want_hist: it then
     lives in the context's scratch) and the report"""
     import torch
-    if Q % 2:
-        raise ValueError("a batch of pairs has an even number of reads (2 p and 2 p + 1 are the mates of pair p), not %d" % Q)
+    check_mates(Q)
     vp = ctypes.c_void_p
     rep = _lib.InsertReport()
     d_hist = torch.zeros(params.max_insert + 1, dtype=torch.int32, device=torch.device("cuda", device)) if want_hist else None
@@ -68,22 +57,12 @@ def estimate_insert(hits, hit_index, alignments, device=0, hooks=None, **params)
     unless report["flags"] has INSERT_OK --, hist: max_insert + 1 counts of the samples by insert, report: every field of
     kiss_hip_insert_report)."""
     p = insert_params(**params)
-    ht = _records(hits, HIT_DTYPE, "a hit")
-    al = _records(alignments, ALN_DTYPE, "an alignment record")
-    hidx = np.ascontiguousarray(hit_index, dtype=np.uint64).ravel()
-    if hidx.size < 1:
-        raise ValueError("hit_index has Q + 1 entries")
-    Q = hidx.size - 1
-    if Q % 2:
-        raise ValueError("a batch of pairs has an even number of reads (2 p and 2 p + 1 are the mates of pair p), not %d" % Q)
-    if np.all(hidx[1:] >= hidx[:-1]) and int(hidx[-1]) > ht.size:
-        raise ValueError("hit_index spans %d hits, %d given" % (int(hidx[-1]), ht.size))
+    ht, al, hidx, Q = _mates_of(hits, hit_index, alignments)
     lib = _lib.load(hooks)
     rep = _lib.InsertReport()
     hist = np.zeros(p.max_insert + 1, np.uint32)
-    keep_h, keep_a = np.zeros(1, HIT_DTYPE), np.zeros(1, ALN_DTYPE)  # (pointers that are not NULL)
-    _check(lib.kiss_hip_fmi_insert_host(ht.ctypes.data if ht.size else keep_h.ctypes.data, hidx.ctypes.data, Q,
-                                        al.ctypes.data if al.size else keep_a.ctypes.data, al.size, ctypes.byref(p), hist.ctypes.data,
+    (hp, ap), hold = addresses(ht, al)
+    _check(lib.kiss_hip_fmi_insert_host(hp, hidx.ctypes.data, Q, ap, al.size, ctypes.byref(p), hist.ctypes.data,
                                         ctypes.byref(rep), int(device)), "kiss_hip_fmi_insert_host")
     r = rep.as_dict()
     return {"stats": {k: r[k] for k in INSERT_STATS}, "hist": hist, "report": r}

@@ -10,8 +10,8 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from ._frame import addresses, read_batch, records, sized
 from .fm_align import ALN_DTYPE
-from .fm_pair import _records
 from .fm_select import HIT_DTYPE
 from .sorter import _check
 
@@ -35,21 +35,17 @@ def md_dev(lib, ctx, device, d_text, n, d_reads, d_ridx, Q, both_strands, d_alns
         stream = torch.cuda.current_stream(dev).cuda_stream
     with_hits = d_hits is not None
     items = int(H) if with_hits else int(C)
+    d_midx = torch.zeros(items + 1, dtype=torch.int64, device=dev)
+    d_cnt = torch.zeros((max(items, 1), 2), dtype=torch.int32, device=dev)
 
-    def call(d_md, d_midx, d_cnt, cap):
+    def call(d_md, cap):
         return lib.kiss_hip_fmi_md_dev(ctx._ctx, vp(d_text.data_ptr()), n, vp(d_reads.data_ptr()), vp(d_ridx.data_ptr()), Q,
                                        1 if both_strands else 0, vp(d_alns.data_ptr()), vp(d_cidx.data_ptr()), vp(d_cigar.data_ptr()),
                                        vp(d_oidx.data_ptr()), vp(d_hits.data_ptr()) if with_hits else None, H if with_hits else 0,
                                        vp(d_md.data_ptr()) if d_md is not None else None, vp(d_midx.data_ptr()),
                                        vp(d_cnt.data_ptr()) if d_cnt is not None else None, cap, ctypes.byref(rep), vp(stream) if stream else None)
 
-    d_midx = torch.zeros(items + 1, dtype=torch.int64, device=dev)
-    d_cnt = torch.zeros((max(items, 1), 2), dtype=torch.int32, device=dev)
-    d_md = torch.zeros(1, dtype=torch.uint8, device=dev)
-    rc = call(d_md, d_midx, d_cnt, 0)
-    if rc == _lib.KISS_HIP_E_INVALID and rep.md_bytes:  # the total is in the report
-        d_md = torch.zeros(int(rep.md_bytes), dtype=torch.uint8, device=dev)
-        rc = call(d_md, d_midx, d_cnt, int(rep.md_bytes))
+    rc, (d_md, _) = sized(call, lambda m=0: (torch.zeros(max(m, 1), dtype=torch.uint8, device=dev), m), rep, "md_bytes")
     _check(rc, "kiss_hip_fmi_md_dev", ctx._ctx)
     return {"d_md": d_md, "d_midx": d_midx, "d_counts": d_cnt, "rep": rep, "items": items}
 
@@ -71,15 +67,8 @@ def md_tags(text, reads, alignments, chain_index, cigar, cigar_index, both_stran
     dict(md: the bytes, md_index: items + 1 u64, md_counts: (items, 2) u32 -- mismatch columns, deleted bases --, report).
     A bad item (see the header) has an empty string and is counted in report['bad']."""
     text = np.ascontiguousarray(text, dtype=np.uint8).ravel()
-    if isinstance(reads, tuple):
-        cat = np.ascontiguousarray(reads[0], dtype=np.uint8)
-        ridx = np.ascontiguousarray(reads[1], dtype=np.uint64)
-    else:
-        arrs = [np.ascontiguousarray(r, dtype=np.uint8).ravel() for r in reads]
-        cat = np.concatenate(arrs) if arrs else np.zeros(0, np.uint8)
-        ridx = np.zeros(len(arrs) + 1, np.uint64)
-        np.cumsum([a.size for a in arrs], out=ridx[1:])
-    al = _records(alignments, ALN_DTYPE, "an alignment record")
+    cat, ridx = read_batch(reads)
+    al = records(alignments, ALN_DTYPE, "the fields of an alignment record are u32")
     cidx = np.ascontiguousarray(chain_index, dtype=np.uint64).ravel()
     cig = np.ascontiguousarray(cigar, dtype=np.uint32).ravel()
     oidx = np.ascontiguousarray(cigar_index, dtype=np.uint64).ravel()
@@ -99,33 +88,21 @@ def md_tags(text, reads, alignments, chain_index, cigar, cigar_index, both_stran
     if hits is not None:
         h = np.asarray(hits)
         if h.dtype.names or h.ndim == 2:
-            ht = _records(h, HIT_DTYPE, "a hit")
+            ht = records(h, HIT_DTYPE, "the fields of a hit are u32")
         else:
-            alns_of = np.asarray(h, np.int64).ravel()
-            if alns_of.size and (alns_of.min() < 0 or alns_of.max() > 0xFFFFFFFF):
-                raise ValueError("an alignment number is u32")
-            ht = np.zeros(alns_of.size, HIT_DTYPE)
-            ht["aln"] = alns_of
+            ht = records(h.ravel(), HIT_DTYPE, "an alignment number is u32", columns=("aln",))
     items = ht.size if ht is not None else C
     lib = _lib.load(hooks)
     rep = _lib.MdReport()
     midx = np.zeros(items + 1, np.uint64)
     cnt = np.zeros((max(items, 1), 2), np.uint32)
-    keep = [np.zeros(1, np.uint8), np.zeros(1, ALN_DTYPE), np.zeros(1, np.uint32), np.zeros(1, HIT_DTYPE)]  # (pointers that are not NULL)
-
-    def ptr(a, k):
-        return a.ctypes.data if a.size else keep[k].ctypes.data
+    (tp, rp, ap, cp, hp), hold = addresses(text, cat, al, cig, ht)
 
     def call(md, cap):
-        return lib.kiss_hip_fmi_md_host(ptr(text, 0), text.size, ptr(cat, 0), ridx.ctypes.data, Q, 1 if both_strands else 0, ptr(al, 1),
-                                        cidx.ctypes.data, ptr(cig, 2), oidx.ctypes.data, ptr(ht, 3) if ht is not None else None,
-                                        ht.size if ht is not None else 0, md.ctypes.data, midx.ctypes.data, cnt.ctypes.data, cap,
-                                        ctypes.byref(rep), int(device))
+        return lib.kiss_hip_fmi_md_host(tp, text.size, rp, ridx.ctypes.data, Q, 1 if both_strands else 0, ap, cidx.ctypes.data, cp,
+                                        oidx.ctypes.data, hp, ht.size if ht is not None else 0, md.ctypes.data, midx.ctypes.data,
+                                        cnt.ctypes.data, cap, ctypes.byref(rep), int(device))
 
-    md = np.zeros(1, np.uint8)
-    rc = call(md, 0)
-    if rc == _lib.KISS_HIP_E_INVALID and rep.md_bytes:  # the total is in the report
-        md = np.zeros(int(rep.md_bytes), np.uint8)
-        rc = call(md, int(rep.md_bytes))
+    rc, (md, _) = sized(call, lambda m=0: (np.zeros(max(m, 1), np.uint8), m), rep, "md_bytes")
     _check(rc, "kiss_hip_fmi_md_host")
     return {"md": md[:int(rep.md_bytes)], "md_index": midx, "md_counts": cnt[:items], "report": rep.as_dict()}

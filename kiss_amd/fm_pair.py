@@ -10,6 +10,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from ._frame import addresses, check_mates, make_params, record_dtype, record_view, records
 from .fm_align import ALN_DTYPE
 from .fm_select import HIT_DTYPE
 from .sorter import _check
@@ -18,22 +19,13 @@ PAIR_DEFAULTS = dict(ins_min=0, ins_max=1000, ins_mean=400, pen_coef=8, pen_max=
 PAIR_LIMITS = dict(pen_coef=65535, pen_max=65535, mapq_coef=65535, mapq_max=255)
 PAIR_NONE = 0xFFFFFFFF
 PAIR_PROPER, PAIR_MATE1_MAPPED, PAIR_MATE2_MAPPED, PAIR_SAME_REF, PAIR_PROMOTED1, PAIR_PROMOTED2, PAIR_BAD_INPUT = 1, 2, 4, 8, 16, 32, 64
-PAIR_FIELDS = ("hit1", "hit2", "flags", "tlen", "score", "sub1", "sub2", "mapq1", "mapq2", "n_conc")
-PAIR_DTYPE = np.dtype([(k, np.uint32) for k in PAIR_FIELDS])
+PAIR_DTYPE = record_dtype(_lib.Pair)
+PAIR_FIELDS = PAIR_DTYPE.names
 
 
 def pair_params(**params):
     """kiss_hip_pair_params from keywords; the defaults are PAIR_DEFAULTS"""
-    p = dict(PAIR_DEFAULTS)
-    for k, v in params.items():
-        if k not in p:
-            raise TypeError("unknown pair parameter %r (known: %s)" % (k, ", ".join(sorted(p))))
-        p[k] = int(v)
-    if min(p.values()) < 0 or max(p.values()) > 0xFFFFFFFF:
-        raise ValueError("the pair parameters are u32")
-    for k, top in PAIR_LIMITS.items():
-        if p[k] > top:
-            raise ValueError("%s is at most %d" % (k, top))
+    p = make_params("pair", PAIR_DEFAULTS, params, PAIR_LIMITS)
     if p["ins_min"] > p["ins_max"]:
         raise ValueError("ins_min is at most ins_max")
     return _lib.PairParams(**p)
@@ -42,8 +34,7 @@ def pair_params(**params):
 def pair_dev(lib, ctx, device, d_hits, d_hidx, Q, d_alns, aln_count, params):
     """the device entry on torch tensors -> dict of the pairs tensor (P x 10) and the report"""
     import torch
-    if Q % 2:
-        raise ValueError("a batch of pairs has an even number of reads (2 p and 2 p + 1 are the mates of pair p), not %d" % Q)
+    check_mates(Q)
     dev = torch.device("cuda", device)
     vp = ctypes.c_void_p
     rep = _lib.PairReport()
@@ -56,24 +47,26 @@ def pair_dev(lib, ctx, device, d_hits, d_hidx, Q, d_alns, aln_count, params):
 
 def pair_arrays(out):
     """the tensors of pair_dev as numpy"""
-    n = int(out["rep"].P)
-    raw = np.ascontiguousarray(out["d_pairs"][:n].cpu().numpy()).view(np.uint32).reshape(n, 10)
-    return {"pairs": raw.view(PAIR_DTYPE).reshape(n), "pair_report": out["rep"].as_dict()}
+    return {"pairs": record_view(out["d_pairs"], int(out["rep"].P), PAIR_DTYPE), "pair_report": out["rep"].as_dict()}
 
 
 def _records(rows, dtype, what):
-    """a structured array with the fields of dtype, or an (n, fields) integer array in their order -> dtype array"""
-    arr = np.asarray(rows)
-    width = len(dtype.names)
-    if arr.dtype.names:
-        out = np.zeros(arr.shape[0], dtype)
-        for k in dtype.names:
-            out[k] = arr[k]
-        return out
-    ints = np.asarray(arr, np.int64).reshape(-1, width)
-    if ints.size and (ints.min() < 0 or ints.max() > 0xFFFFFFFF):
-        raise ValueError("the fields of %s are u32" % what)
-    return np.ascontiguousarray(ints.astype(np.uint32)).view(dtype).reshape(ints.shape[0])
+    """records() under the name and with the arguments it had here (tests/test_fm_rescue_gpu.py reaches it as fm_rescue._records)"""
+    return records(rows, dtype, "the fields of %s are u32" % what)
+
+
+def _mates_of(hits, hit_index, alignments):
+    """what pair_hits() and estimate_insert() take, checked -> the hits and alignment records, the hit index, Q"""
+    ht = records(hits, HIT_DTYPE, "the fields of a hit are u32")
+    al = records(alignments, ALN_DTYPE, "the fields of an alignment record are u32")
+    hidx = np.ascontiguousarray(hit_index, dtype=np.uint64).ravel()
+    if hidx.size < 1:
+        raise ValueError("hit_index has Q + 1 entries")
+    Q = hidx.size - 1
+    check_mates(Q)
+    if np.all(hidx[1:] >= hidx[:-1]) and int(hidx[-1]) > ht.size:
+        raise ValueError("hit_index spans %d hits, %d given" % (int(hidx[-1]), ht.size))
+    return ht, al, hidx, Q
 
 
 def pair_hits(hits, hit_index, alignments, device=0, hooks=None, **params):
@@ -84,21 +77,11 @@ def pair_hits(hits, hit_index, alignments, device=0, hooks=None, **params):
     mapq_coef (120), mapq_max (60).  Returns dict(pairs: structured array of the fields of kiss_hip_pair, one per pair,
     report)."""
     p = pair_params(**params)
-    ht = _records(hits, HIT_DTYPE, "a hit")
-    al = _records(alignments, ALN_DTYPE, "an alignment record")
-    hidx = np.ascontiguousarray(hit_index, dtype=np.uint64).ravel()
-    if hidx.size < 1:
-        raise ValueError("hit_index has Q + 1 entries")
-    Q = hidx.size - 1
-    if Q % 2:
-        raise ValueError("a batch of pairs has an even number of reads (2 p and 2 p + 1 are the mates of pair p), not %d" % Q)
-    if np.all(hidx[1:] >= hidx[:-1]) and int(hidx[-1]) > ht.size:
-        raise ValueError("hit_index spans %d hits, %d given" % (int(hidx[-1]), ht.size))
+    ht, al, hidx, Q = _mates_of(hits, hit_index, alignments)
     lib = _lib.load(hooks)
     rep = _lib.PairReport()
     pairs = np.zeros(max(Q // 2, 1), PAIR_DTYPE)
-    keep_h, keep_a = np.zeros(1, HIT_DTYPE), np.zeros(1, ALN_DTYPE)  # (pointers that are not NULL)
-    _check(lib.kiss_hip_fmi_pair_host(ht.ctypes.data if ht.size else keep_h.ctypes.data, hidx.ctypes.data, Q,
-                                      al.ctypes.data if al.size else keep_a.ctypes.data, al.size, ctypes.byref(p), pairs.ctypes.data,
+    (hp, ap), hold = addresses(ht, al)
+    _check(lib.kiss_hip_fmi_pair_host(hp, hidx.ctypes.data, Q, ap, al.size, ctypes.byref(p), pairs.ctypes.data,
                                       ctypes.byref(rep), int(device)), "kiss_hip_fmi_pair_host")
     return {"pairs": pairs[:Q // 2], "report": rep.as_dict()}

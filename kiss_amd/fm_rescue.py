@@ -11,9 +11,10 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from ._frame import addresses, check_mates, lengths_index, make_params, record_view, records, sized
 from .fm_align import ALIGN_MAX_BAND, ALN_DTYPE
 from .fm_chain import CHAIN_DTYPE
-from .fm_pair import PAIR_DTYPE, _records
+from .fm_pair import PAIR_DTYPE, _records  # noqa: F401
 from .fm_select import HIT_DTYPE, _bounds_array
 from .sorter import _check
 
@@ -23,13 +24,7 @@ RESCUE_LIMITS = dict(max_width=ALIGN_MAX_BAND)
 
 def rescue_params(**params):
     """kiss_hip_rescue_params from keywords; the defaults are RESCUE_DEFAULTS"""
-    p = dict(RESCUE_DEFAULTS)
-    for k, v in params.items():
-        if k not in p:
-            raise TypeError("unknown rescue parameter %r (known: %s)" % (k, ", ".join(sorted(p))))
-        p[k] = int(v)
-    if min(p.values()) < 0 or max(p.values()) > 0xFFFFFFFF:
-        raise ValueError("the rescue parameters are u32")
+    p = make_params("rescue", RESCUE_DEFAULTS, params)
     if p["ins_min"] > p["ins_max"]:
         raise ValueError("ins_min is at most ins_max")
     if p["max_anchors"] < 1:
@@ -65,14 +60,11 @@ def rescue_dev(lib, ctx, device, d_pairs, d_hits, d_hidx, Q, d_alns, aln_count, 
                                            vp(d_chains.data_ptr()), vp(d_cidx.data_ptr()), vp(d_origin.data_ptr()), cap,
                                            ctypes.byref(rep), None)
 
-    d_chains = torch.zeros((1, 6), dtype=torch.int32, device=dev)
-    d_origin = torch.zeros(1, dtype=torch.int32, device=dev)
-    rc = call(d_chains, d_origin, 0)
-    if rc == _lib.KISS_HIP_E_INVALID and rep.chains:  # the total is in the report
-        total = int(rep.chains)
-        d_chains = torch.zeros((total, 6), dtype=torch.int32, device=dev)
-        d_origin = torch.zeros(total, dtype=torch.int32, device=dev)
-        rc = call(d_chains, d_origin, total)
+    def room(total=0):
+        return (torch.zeros((max(total, 1), 6), dtype=torch.int32, device=dev),
+                torch.zeros(max(total, 1), dtype=torch.int32, device=dev), total)
+
+    rc, (d_chains, d_origin, _) = sized(call, room, rep, "chains")
     _check(rc, "kiss_hip_fmi_rescue_dev", ctx._ctx)
     return {"d_chains": d_chains, "d_cidx": d_cidx, "d_origin": d_origin, "rep": rep, "C": int(rep.chains)}
 
@@ -80,8 +72,7 @@ def rescue_dev(lib, ctx, device, d_pairs, d_hits, d_hidx, Q, d_alns, aln_count, 
 def rescue_arrays(out):
     """the tensors of rescue_dev as numpy"""
     C = out["C"]
-    raw = np.ascontiguousarray(out["d_chains"][:C].cpu().numpy()).view(np.uint32).reshape(C, 6)
-    return {"chains": raw.view(CHAIN_DTYPE).reshape(C), "chain_index": out["d_cidx"].cpu().numpy().view(np.uint64),
+    return {"chains": record_view(out["d_chains"], C, CHAIN_DTYPE), "chain_index": out["d_cidx"].cpu().numpy().view(np.uint64),
             "origin": out["d_origin"][:C].cpu().numpy().view(np.uint32), "report": out["rep"].as_dict()}
 
 
@@ -114,7 +105,7 @@ def merge_dev(lib, ctx, device, V, a, b, want_cigar):
 def merge_arrays(out, want_cigar):
     """the tensors of merge_dev as numpy"""
     C = out["C"]
-    res = {"alignments": np.ascontiguousarray(out["d_alns"][:C].cpu().numpy()).view(np.uint32).reshape(C, 12).view(ALN_DTYPE).reshape(C),
+    res = {"alignments": record_view(out["d_alns"], C, ALN_DTYPE),
            "chain_index": out["d_cidx"].cpu().numpy().view(np.uint64), "aln_source": out["d_source"][:C].cpu().numpy().view(np.uint32)}
     if want_cigar:
         res["cigar"] = out["d_cigar"][:int(out["rep"].cigar_ops)].cpu().numpy().view(np.uint32)
@@ -131,41 +122,32 @@ def plan_rescue(pairs, hits, hit_index, alignments, read_lengths, n, bounds=None
     align_chains() takes --, chain_index: 2 Q + 1 u64 over the virtual reads of both strands, origin: per chain the index of
     its anchor in hits, report)."""
     p = rescue_params(**params)
-    pr = _records(pairs, PAIR_DTYPE, "a pair")
-    ht = _records(hits, HIT_DTYPE, "a hit")
-    al = _records(alignments, ALN_DTYPE, "an alignment record")
+    pr = records(pairs, PAIR_DTYPE, "the fields of a pair are u32")
+    ht = records(hits, HIT_DTYPE, "the fields of a hit are u32")
+    al = records(alignments, ALN_DTYPE, "the fields of an alignment record are u32")
     hidx = np.ascontiguousarray(hit_index, dtype=np.uint64).ravel()
-    lens = np.ascontiguousarray(read_lengths, dtype=np.uint64).ravel()
-    Q = lens.size
+    ridx = lengths_index(read_lengths)
+    Q = ridx.size - 1
     if hidx.size != Q + 1:
         raise ValueError("hit_index has Q + 1 = %d entries" % (Q + 1))
-    if Q % 2:
-        raise ValueError("a batch of pairs has an even number of reads (2 p and 2 p + 1 are the mates of pair p), not %d" % Q)
+    check_mates(Q)
     if pr.size < Q // 2:
         raise ValueError("%d pairs, %d pair records given" % (Q // 2, pr.size))
     if np.all(hidx[1:] >= hidx[:-1]) and int(hidx[-1]) > ht.size:
         raise ValueError("hit_index spans %d hits, %d given" % (int(hidx[-1]), ht.size))
-    ridx = np.zeros(Q + 1, np.uint64)
-    np.cumsum(lens, out=ridx[1:])
     b = _bounds_array(bounds)
     lib = _lib.load(hooks)
     rep = _lib.RescueReport()
     cidx = np.zeros(2 * Q + 1, np.uint64)
-    keep = [np.zeros(1, PAIR_DTYPE), np.zeros(1, HIT_DTYPE), np.zeros(1, ALN_DTYPE)]  # (pointers that are not NULL)
+    (pp, hp, ap), hold = addresses(pr, ht, al)
 
     def call(chains, origin, cap):
-        return lib.kiss_hip_fmi_rescue_host(pr.ctypes.data if pr.size else keep[0].ctypes.data,
-                                            ht.ctypes.data if ht.size else keep[1].ctypes.data, hidx.ctypes.data, Q,
-                                            al.ctypes.data if al.size else keep[2].ctypes.data, al.size, ridx.ctypes.data, int(n),
-                                            b.ctypes.data if b is not None else None, b.size - 1 if b is not None else 0,
+        return lib.kiss_hip_fmi_rescue_host(pp, hp, hidx.ctypes.data, Q, ap, al.size,
+                                            ridx.ctypes.data, int(n), b.ctypes.data if b is not None else None, b.size - 1 if b is not None else 0,
                                             ctypes.byref(p), chains.ctypes.data, cidx.ctypes.data, origin.ctypes.data, cap,
                                             ctypes.byref(rep), int(device))
 
-    chains, origin = np.zeros(1, CHAIN_DTYPE), np.zeros(1, np.uint32)
-    rc = call(chains, origin, 0)
-    if rc == _lib.KISS_HIP_E_INVALID and rep.chains:  # the total is in the report
-        chains, origin = np.zeros(int(rep.chains), CHAIN_DTYPE), np.zeros(int(rep.chains), np.uint32)
-        rc = call(chains, origin, int(rep.chains))
+    rc, (chains, origin, _) = sized(call, lambda m=0: (np.zeros(max(m, 1), CHAIN_DTYPE), np.zeros(max(m, 1), np.uint32), m), rep, "chains")
     _check(rc, "kiss_hip_fmi_rescue_host")
     C = int(rep.chains)
     return {"chains": chains[:C], "chain_index": cidx, "origin": origin[:C], "report": rep.as_dict()}
@@ -178,8 +160,8 @@ def merge_alignments(alignments_a, chain_index_a, alignments_b, chain_index_b, c
     chain_index_*: V + 1 entries each; the ops of both sets (cigar_* with cigar_index_*) or of neither.  Returns
     dict(alignments, chain_index (from 0), source (i for alignments_a[i], C_A + j for alignments_b[j]), report) and, with the
     ops, cigar / cigar_index."""
-    A = _records(alignments_a, ALN_DTYPE, "an alignment record")
-    B = _records(alignments_b, ALN_DTYPE, "an alignment record")
+    A = records(alignments_a, ALN_DTYPE, "the fields of an alignment record are u32")
+    B = records(alignments_b, ALN_DTYPE, "the fields of an alignment record are u32")
     ia = np.ascontiguousarray(chain_index_a, dtype=np.uint64).ravel()
     ib = np.ascontiguousarray(chain_index_b, dtype=np.uint64).ravel()
     if ia.size < 1 or ia.size != ib.size:
@@ -206,10 +188,8 @@ def merge_alignments(alignments_a, chain_index_a, alignments_b, chain_index_b, c
             oi = np.ascontiguousarray(oi, dtype=np.uint64).ravel()
             if oi.size < cnt + 1 or (np.all(oi[1:] >= oi[:-1]) and int(oi[cnt]) > cig.size):
                 raise ValueError("a cigar index has C + 1 entries and points inside its ops")
-            if cig.size == 0:
-                cig = np.zeros(1, np.uint32)
-            hold += [cig, oi]
-            ptrs[2 * k], ptrs[2 * k + 1] = cig.ctypes.data, oi.ctypes.data
+            ptrs[2 * k:2 * k + 2], kept = addresses(cig, oi)
+            hold += kept
             ops += span(oi[:cnt + 1])
     lib = _lib.load(hooks)
     rep = _lib.MergeReport()
@@ -218,9 +198,8 @@ def merge_alignments(alignments_a, chain_index_a, alignments_b, chain_index_b, c
     src = np.zeros(max(C, 1), np.uint32)
     cig = np.zeros(max(ops, 1), np.uint32) if want else None
     oidx = np.zeros(C + 1, np.uint64) if want else None
-    keep = np.zeros(1, ALN_DTYPE)  # (a pointer that is not NULL)
-    _check(lib.kiss_hip_fmi_aln_merge_host(A.ctypes.data if A.size else keep.ctypes.data, ia.ctypes.data, ptrs[0], ptrs[1],
-                                           B.ctypes.data if B.size else keep.ctypes.data, ib.ctypes.data, ptrs[2], ptrs[3], V,
+    (pa, pb), kept = addresses(A, B)
+    _check(lib.kiss_hip_fmi_aln_merge_host(pa, ia.ctypes.data, ptrs[0], ptrs[1], pb, ib.ctypes.data, ptrs[2], ptrs[3], V,
                                            alns.ctypes.data, C, cidx.ctypes.data, src.ctypes.data,
                                            cig.ctypes.data if want else None, oidx.ctypes.data if want else None, ops,
                                            ctypes.byref(rep), int(device)), "kiss_hip_fmi_aln_merge_host")

@@ -10,29 +10,20 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from ._frame import addresses, make_params, read_index, record_dtype, record_view, records
 from .fm_align import ALN_DTYPE
 from .sorter import _check
 
 SELECT_DEFAULTS = dict(min_score=30, overlap=128, mapq_coef=120, mapq_max=60, max_hits=0)
 SELECT_LIMITS = dict(overlap=256, mapq_coef=65535, mapq_max=255)
 HIT_REVERSE, HIT_SECONDARY, HIT_SUPPLEMENTARY = 1, 2, 4
-HIT_FIELDS = ("aln", "flags", "mapq", "score", "sub", "n_sec", "head", "ref")
-HIT_DTYPE = np.dtype([(k, np.uint32) for k in HIT_FIELDS])
+HIT_DTYPE = record_dtype(_lib.Hit)
+HIT_FIELDS = HIT_DTYPE.names
 
 
 def select_params(**params):
     """kiss_hip_select_params from keywords; the defaults are SELECT_DEFAULTS"""
-    p = dict(SELECT_DEFAULTS)
-    for k, v in params.items():
-        if k not in p:
-            raise TypeError("unknown select parameter %r (known: %s)" % (k, ", ".join(sorted(p))))
-        p[k] = int(v)
-    if min(p.values()) < 0 or max(p.values()) > 0xFFFFFFFF:
-        raise ValueError("the select parameters are u32")
-    for k, top in SELECT_LIMITS.items():
-        if p[k] > top:
-            raise ValueError("%s is at most %d" % (k, top))
-    return _lib.SelectParams(**p)
+    return _lib.SelectParams(**make_params("select", SELECT_DEFAULTS, params, SELECT_LIMITS))
 
 
 def _bounds_array(bounds):
@@ -70,10 +61,8 @@ def select_dev(lib, ctx, device, d_alns, d_cidx, d_ridx, Q, C, both_strands, bou
 
 def select_arrays(out):
     """the tensors of select_dev as numpy"""
-    n = int(out["rep"].hits)
-    raw = np.ascontiguousarray(out["d_hits"][:n].cpu().numpy()).view(np.uint32).reshape(n, 8)
-    return {"hits": raw.view(HIT_DTYPE).reshape(n), "hit_index": out["d_hidx"].cpu().numpy().view(np.uint64),
-            "select_report": out["rep"].as_dict()}
+    return {"hits": record_view(out["d_hits"], int(out["rep"].hits), HIT_DTYPE),
+            "hit_index": out["d_hidx"].cpu().numpy().view(np.uint64), "select_report": out["rep"].as_dict()}
 
 
 def select_alignments(alignments, chain_index, read_lengths_or_index, both_strands=False, bounds=None, device=0, hooks=None,
@@ -86,24 +75,8 @@ def select_alignments(alignments, chain_index, read_lengths_or_index, both_stran
     (60), max_hits (0: all).  Returns dict(hits: structured array of the fields of kiss_hip_hit, hit_index: Q + 1 u64 over
     the reads, report)."""
     p = select_params(**params)
-    alns = np.asarray(alignments)
-    if alns.dtype.names:
-        al = np.zeros(alns.shape[0], ALN_DTYPE)
-        for k in ALN_DTYPE.names:
-            al[k] = alns[k]
-    else:
-        rows = np.asarray(alns, np.int64).reshape(-1, 12)
-        if rows.size and (rows.min() < 0 or rows.max() > 0xFFFFFFFF):
-            raise ValueError("the fields of an alignment record are u32")
-        al = np.ascontiguousarray(rows.astype(np.uint32)).view(ALN_DTYPE).reshape(rows.shape[0])
-    if isinstance(read_lengths_or_index, tuple):
-        if read_lengths_or_index[0] != "index":
-            raise ValueError('read_lengths_or_index is an array of lengths or ("index", offsets)')
-        ridx = np.ascontiguousarray(read_lengths_or_index[1], dtype=np.uint64).ravel()
-    else:
-        lens = np.ascontiguousarray(read_lengths_or_index, dtype=np.uint64).ravel()
-        ridx = np.zeros(lens.size + 1, np.uint64)
-        np.cumsum(lens, out=ridx[1:])
+    al = records(alignments, ALN_DTYPE, "the fields of an alignment record are u32")
+    ridx = read_index(read_lengths_or_index)
     cidx = np.ascontiguousarray(chain_index, dtype=np.uint64).ravel()
     if ridx.size < 1:
         raise ValueError("the read index has Q + 1 entries")
@@ -118,8 +91,7 @@ def select_alignments(alignments, chain_index, read_lengths_or_index, both_stran
     lib = _lib.load(hooks)
     rep = _lib.SelectReport()
     hidx = np.zeros(Q + 1, np.uint64)
-    keep = np.zeros(1, ALN_DTYPE)  # (a pointer that is not NULL)
-    ap = al.ctypes.data if al.size else keep.ctypes.data
+    (ap,), hold = addresses(al)
 
     def call(hits, cap):
         return lib.kiss_hip_fmi_select_host(ap, cidx.ctypes.data, ridx.ctypes.data, Q, 1 if both_strands else 0,

@@ -11,6 +11,7 @@ import os
 import numpy as np
 
 from . import _lib
+from ._frame import addresses
 from .sorter import _check
 
 FORMATS = {"auto": _lib.READS_AUTO, "lines": _lib.READS_LINES, "fastq": _lib.READS_FASTQ}
@@ -66,16 +67,14 @@ def parse_reads(source, format="auto", want_qual=True, want_names=True, ctx=None
         return _parse_on_ctx(raw, format, want_qual, want_names, ctx)
     lib = _lib.load(hooks)
     rep = _lib.ReadsReport()
-    keep = np.zeros(1, np.uint8)  # (a pointer that is not NULL)
-    ptr = lambda a: ctypes.c_void_p(a.ctypes.data if a.size else keep.ctypes.data)  # noqa: E731
 
     def call(codes, qual, bases_cap, index, noff, nlen, reads_cap):
-        return lib.kiss_hip_reads_parse_host(ptr(raw), raw.size, fmt, ptr(codes), ptr(qual) if qual is not None else None, bases_cap,
-                                             ptr(index), ptr(noff) if noff is not None else None, ptr(nlen) if nlen is not None else None,
-                                             reads_cap, ctypes.byref(rep), int(device))
+        p, hold = addresses(raw, codes, qual, index, noff, nlen)
+        return lib.kiss_hip_reads_parse_host(p[0], raw.size, fmt, p[1], p[2], bases_cap, p[3], p[4], p[5], reads_cap, ctypes.byref(rep),
+                                             int(device))
 
     index = np.zeros(1, np.uint64)
-    rc = call(keep, None, 0, index, None, None, 0)  # size ...
+    rc = call(np.zeros(0, np.uint8), None, 0, index, None, None, 0)  # size ...
     codes, qual, noff, nlen = np.zeros(0, np.uint8), None, None, None
     if rc == _lib.KISS_HIP_E_INVALID and not rep.bad_records and (rep.reads or rep.bases):  # ... then fill
         Q, B = int(rep.reads), int(rep.bases)
@@ -166,16 +165,13 @@ def interleave_reads(a, b, device=0, hooks=None):
     lib = _lib.load(hooks)
     total = int(ia[-1]) + int(ib[-1])
     codes, index = np.zeros(total, np.uint8), np.zeros(Pa + Pb + 1, np.uint64)
-    keep = np.zeros(1, np.uint8)
-    ptr = lambda x: ctypes.c_void_p(x.ctypes.data if x.size else keep.ctypes.data)  # noqa: E731
     qual = None
     if qa is not None:
         qa, qb, qual = np.ascontiguousarray(qa, np.uint8), np.ascontiguousarray(qb, np.uint8), np.zeros(total, np.uint8)
     got = ctypes.c_uint64()
-    _check(lib.kiss_hip_reads_interleave_host(ptr(ca), ptr(ia), ptr(qa) if qual is not None else None, Pa, ptr(cb), ptr(ib),
-                                              ptr(qb) if qual is not None else None, Pb, ptr(codes), ptr(index),
-                                              ptr(qual) if qual is not None else None, total, ctypes.byref(got), int(device)),
-           "kiss_hip_reads_interleave_host")
+    p, hold = addresses(ca, ia, qa, cb, ib, qb, codes, index, qual)
+    _check(lib.kiss_hip_reads_interleave_host(p[0], p[1], p[2], Pa, p[3], p[4], p[5], Pb, p[6], p[7], p[8], total, ctypes.byref(got),
+                                              int(device)), "kiss_hip_reads_interleave_host")
     res = {"reads": codes, "read_index": index, "qual": qual}
     if isinstance(a, dict) and isinstance(b, dict) and a.get("names") is not None and b.get("names") is not None:
         res["names"] = [n for pair in zip(a["names"], b["names"]) for n in pair]
