@@ -11,7 +11,7 @@
 //   key(p) = the first 7 characters of suffix p, each stored as c + 1 in 9 bits (0 = past the end, so a suffix that
 //            is a proper prefix of another sorts first), stable LSD radix sort of (key, p) over 63 bits;
 //   SA[0] = n, SA[1 + i] = sorted position i, group heads where the key changes;
-//   rank doubling from h = 7 on the tied suffixes (lms_sort.hip: kiss_exact_refine with the heads given).
+//   rank doubling from h = 7 on the tied suffixes (doubling.hip: kiss_exact_refine with the heads given).
 #include "fm_internal.hpp" // (FmStage: the arrays of the one-shot entry)
 #include <cstdlib>
 #include <cstring>

@@ -561,7 +561,7 @@ __global__ __launch_bounds__(IN_THREADS) void k_induce_scatter(const uint64_t *_
 // ranks its items by class), so a tile can find the items of each class in all EARLIER tiles by a decoupled look-back
 // instead: tiles take their number from an atomic ticket (every predecessor of a running tile is running or done),
 // publish their four class counts, and wave c of the workgroup sums class c over the predecessors, 64 descriptors per
-// round trip, until it meets a tile that has published its running total -- the scheme of k_fc0_onepass (lms_sort.hip)
+// round trip, until it meets a tile that has published its running total -- the scheme of k_fc0_onepass (flag_compact.hip)
 // with the descriptor of the radix passes: [status:2 | pass epoch:30 | value:32], one 64-bit word per (class, tile), never
 // cleared (the epoch keeps counting).  The count kernel, the three scan launches and their 4 bytes per item are gone
 // (round 3: 5.1 ms of 21 per sort); the wait is bounded (error flag, not a hung GPU).

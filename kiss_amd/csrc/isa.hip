@@ -9,7 +9,7 @@
 //   level 2: per level-1 bin (128 MiB of pairs, processed while it is still in the last-level cache):
 //            partition on the next 8 bits into a small scratch, then scatter into the bin's 64 MiB window of isa
 //            through 256 KiB sub-windows that live in L2, so isa lines leave the cache complete.
-// Used by the PREFIX_DOUBLING refinement (lms_sort.hip: kiss_exact_refine).
+// Used by the PREFIX_DOUBLING refinement (doubling.hip: kiss_exact_refine).
 #include "kiss_internal.hpp"
 #include <cstdlib>
 #include <vector>

@@ -415,14 +415,14 @@ constexpr int KISS_INTERNAL_TOO_DEEP = 1000; // never crosses the ABI
 // very deep ties).  Round 3 sweep at chm13 size, whole exact sort: h0 = 128 / 256 / 512 / 1024 -> 224 / 211 / 205 / 213 ms
 // (a deeper bounded phase costs pivot-round work, a shallower one leaves more tied suffixes to the doubling rounds).
 constexpr uint32_t KISS_EXACT_H0 = 512;
-// exact order from an h0-ordered SA by rank doubling over the full suffix array (lms_sort.hip)
+// exact order from an h0-ordered SA by rank doubling over the full suffix array (doubling.hip)
 int kiss_exact_refine(kiss_hip_ctx *ctx, uint64_t n, uint32_t h0, uint32_t *d_SA, uint8_t *heads_in = nullptr);
 // isa[SA[i]] = i for a permutation SA of [0, total) (isa.hip)
 int kiss_isa_build(kiss_hip_ctx *ctx, const uint32_t *SA, uint64_t total, uint32_t *isa);
 // rank[L[i] >> 1] = i for the m LMS positions of L (lms_asc: the same positions ascending); scratch from the caller (isa.hip)
 int kiss_rank_build_lms(kiss_hip_ctx *ctx, const uint32_t *L, const uint32_t *lms_asc, uint64_t m, uint64_t n,
                         uint32_t *rank, uint64_t *pairs1, uint64_t *pairs2, uint32_t *small, uint64_t small_words);
-// Exact order of the LMS suffixes BEFORE the induction (lms_sort.hip): the merged h0-ordered list ctx->lmsP / ctx->lmsC is
+// Exact order of the LMS suffixes BEFORE the induction (doubling.hip): the merged h0-ordered list ctx->lmsP / ctx->lmsC is
 // refined by rank doubling over the LMS suffixes alone.  `scratch`: the (n + 1)-word suffix array buffer (not yet written).
 // *resolved = false: the list is as kiss_merge_lms left it (still h0-ordered, taint bits intact) and kiss_exact_refine has
 // to finish the job on the suffix array.
@@ -541,5 +541,14 @@ __device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & 63u; }
 __device__ __forceinline__ uint64_t lanemask_lt()
 {
     return (1ull << (threadIdx.x & 63u)) - 1ull;
+}
+// four aligned 32-base keys starting at base q (five independent word loads)
+__device__ __forceinline__ void keys128(const uint64_t *__restrict__ pk, uint64_t q, uint64_t k[4])
+{
+    const uint32_t sh = 2u * (uint32_t)(q & 31u);
+    uint64_t x[5];
+    kiss_words5(pk, q >> 5, x);
+#pragma unroll
+    for (int t = 0; t < 4; t++) k[t] = (x[t] << sh) | ((x[t + 1] >> 1) >> (63u - sh));
 }
 #endif

@@ -1,7 +1,7 @@
 """k_fc0_onepass runs one 1024-thread workgroup per CU and every tile waits on its predecessors' descriptors: a register
 spill or a register count past 128 (the workgroup would no longer fit a CU) shows nowhere at run time but in the time.
 k_pair_finish is a chain of dependent text loads per lane and must not go through scratch either.  This test reads the
-figures from the code-object metadata of the built library (kiss_amd/csrc/lms_sort.hip).  No GPU needed."""
+figures from the code-object metadata of the built library (kiss_amd/csrc/flag_compact.hip).  No GPU needed."""
 import os
 import re
 import shutil

@@ -1,4 +1,4 @@
-"""Tied pairs decided from pair records (kiss_amd/csrc/lms_sort.hip: k_fc0_onepass<true>, k_pair_finish).
+"""Tied pairs decided from pair records (kiss_amd/csrc/flag_compact.hip: k_fc0_onepass<true>, lms_sort.hip: k_pair_finish).
 
 Round 0's one-pass flag + compact takes the tied segments of exactly two items out of the survivor stream and writes one
 record per pair; one lane per record decides it.  The result must be what the survivor stream's pair path gives

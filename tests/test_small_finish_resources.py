@@ -1,7 +1,7 @@
 """k_small_finish keeps a window of the survivor stream in LDS and its lanes walk pairs of suffixes through the text, chains
 of dependent loads: scratch, or fewer than four waves per SIMD to hide those loads behind, shows nowhere at run time but in
 the time.  This test reads the figures from the code-object metadata of the built library (kiss_amd/csrc/lms_sort.hip,
-DESIGN.md 4), as tests/test_fc0_resources.py does for k_fc0_onepass.  No GPU needed."""
+DESIGN.md 4), as tests/test_fc0_resources.py does for k_fc0_onepass (flag_compact.hip).  No GPU needed."""
 import os
 import re
 import shutil
