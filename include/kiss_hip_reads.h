@@ -37,7 +37,9 @@
  * one lane.
  * Report: format (the one parsed, never AUTO), lines (of the whole file), reads, bases, no_base (codes of 4), empty_reads and
  * first_empty (FASTQ; KISS_HIP_READS_NONE when there is none), has_qual (FASTQ: 1), bad_records, first_bad (or
- * KISS_HIP_READS_NONE), first_bad_kind (0: none), and the device times of the passes.  report may be NULL. */
+ * KISS_HIP_READS_NONE), first_bad_kind (0: none), and the device times of the passes.  report may be NULL.
+ * A file that does not fit one call goes through in batches: kiss_hip_reads_part.h, beside this header, parses the first whole
+ * records of a chunk and says where the next chunk starts. */
 #ifndef KISS_HIP_READS_H
 #define KISS_HIP_READS_H
 

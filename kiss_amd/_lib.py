@@ -258,6 +258,11 @@ class ReadsReport(Report):
     ]
 
 
+class ReadsPartReport(ctypes.Structure):
+    """kiss_hip_reads_part_report (include/kiss_hip_reads_part.h)"""
+    _fields_ = [("parsed", ReadsReport), ("records_complete", ctypes.c_uint64), ("records", ctypes.c_uint64), ("bytes_used", ctypes.c_uint64)]
+
+
 class MdReport(Report):
     """kiss_hip_md_report (include/kiss_hip_md.h)"""
     _fields_ = [(k, ctypes.c_uint64) for k in ("items", "bad", "md_bytes", "mismatch_columns", "deleted_bases", "longest")] + [
@@ -445,6 +450,10 @@ def load(hooks=None):
     lib.kiss_hip_fmi_aln_merge_dev.restype = lib.kiss_hip_fmi_aln_merge_host.restype = ctypes.c_int
     lib.kiss_hip_reads_parse_dev.argtypes = [vp, vp, u64, ctypes.c_int, vp, vp, u64, vp, vp, vp, u64, ctypes.POINTER(ReadsReport), vp]
     lib.kiss_hip_reads_parse_host.argtypes = [vp, u64, ctypes.c_int, vp, vp, u64, vp, vp, vp, u64, ctypes.POINTER(ReadsReport), ctypes.c_int]
+    lib.kiss_hip_reads_parse_part_dev.argtypes = [vp, vp, u64, ctypes.c_int, ctypes.c_int, u64, vp, vp, u64, vp, vp, vp, u64,
+                                                  ctypes.POINTER(ReadsPartReport), vp]
+    lib.kiss_hip_reads_parse_part_host.argtypes = [vp, u64, ctypes.c_int, ctypes.c_int, u64, vp, vp, u64, vp, vp, vp, u64,
+                                                   ctypes.POINTER(ReadsPartReport), ctypes.c_int]
     lib.kiss_hip_reads_interleave_dev.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, u64, vp, vp, vp, u64, ctypes.POINTER(u64), vp]
     lib.kiss_hip_reads_interleave_host.argtypes = [vp, vp, vp, u64, vp, vp, vp, u64, vp, vp, vp, u64, ctypes.POINTER(u64), ctypes.c_int]
     for name in READS_EXPORTED_SYMBOLS:
@@ -544,6 +553,8 @@ EXPORTED_SYMBOLS = [
 READS_EXPORTED_SYMBOLS = [
     "kiss_hip_reads_parse_dev", "kiss_hip_reads_parse_host", "kiss_hip_reads_interleave_dev", "kiss_hip_reads_interleave_host",
 ]
+# every symbol include/kiss_hip_reads_part.h declares (tests/test_reads_part_model.py)
+READS_PART_EXPORTED_SYMBOLS = ["kiss_hip_reads_parse_part_dev", "kiss_hip_reads_parse_part_host"]
 # every symbol include/kiss_hip_md.h declares (tests/test_fm_md_abi.py)
 MD_EXPORTED_SYMBOLS = ["kiss_hip_fmi_md_dev", "kiss_hip_fmi_md_host"]
 # every symbol include/kiss_hip_insert.h declares (tests/test_fm_insert_abi.py)

@@ -116,7 +116,18 @@ inline void usage_reads()
               << "                                 its quality string, reversed where SEQ is; of a read from lines it is *.\n"
               << "                                 With --mates both files have one format, and a FASTQ name that ends in /1 or\n"
               << "                                 /2 loses those two bytes.  A FASTQ read without bases stops the command.\n"
-              << "                                 The files are parsed on the device (line ends may be \\n or \\r\\n).\n";
+              << "                                 The files are parsed on the device (line ends may be \\n or \\r\\n).\n"
+              << "  --batch-reads NUM (=0)         with --sam: the file is mapped NUM reads (with --mates: NUM pairs) at a time, so a file\n"
+              << "                                 of any size goes through; 0: the whole file as one batch.  The SAM does not depend\n"
+              << "                                 on NUM: record, read and pair numbers in messages and the QNAMEs of reads without a\n"
+              << "                                 name count through the file.  The header is written once.  An error found in a\n"
+              << "                                 later batch (a bad FASTQ record, a read without bases, a mate file that runs out)\n"
+              << "                                 comes behind the SAM lines of the batches before it, with a non-zero exit status.\n"
+              << "                                 With --ins-auto the insert size is estimated once, from the first batch, and its\n"
+              << "                                 [insert] line is printed once; those values serve every later batch.\n"
+              << "  --batch-chunk BYTES (=67108864)  with --batch-reads: the file is read BYTES at a time, and on (twice as much each\n"
+              << "                                 time) until NUM records or the file's end are in memory; the records are cut on\n"
+              << "                                 the device.\n";
 }
 
 // The help of the SAM tags that are asked for (`kiss --help-sam`): apart from usage() for the same reason.
@@ -235,6 +246,8 @@ struct Args {
     kiss_hip_rescue_params rescue_params{0, 1000, 4, 0, 960}; // (ins_min / ins_max: the pair parameters' that are used, set in map_reads)
     bool ins_auto = false; // fmindex_query ... --mates READS2 --sam --ins-auto
     kiss_hip_insert_params insert_params{20, 10000, 25, 2, 3, 4};
+    size_t batch_reads = 0;          // fmindex_query ... --sam --batch-reads N (0: the whole file as one batch)
+    size_t batch_chunk = 64u << 20;  // --batch-chunk BYTES
 };
 
 inline bool given(const Args &a, const char *name) { return std::find(a.seen.begin(), a.seen.end(), name) != a.seen.end(); }
@@ -307,6 +320,8 @@ inline const Opt OPTIONS[] = {
     {"--ins-auto-min-mapq", nullptr, KISS_AT(insert_params.min_mapq), true, {"--ins-auto"}},
     {"--ins-auto-max", nullptr, KISS_AT(insert_params.max_insert), true, {"--ins-auto"}},
     {"--ins-auto-min-pairs", nullptr, KISS_AT(insert_params.min_samples), true, {"--ins-auto"}},
+    {"--batch-reads", nullptr, KISS_AT(batch_reads), true, {"--sam"}},
+    {"--batch-chunk", nullptr, KISS_AT(batch_chunk), true, {"--batch-reads"}},
 };
 #undef KISS_AT
 
@@ -372,6 +387,8 @@ inline Args parse(int argc, char **argv)
     goes_with_through("--ins-auto-min-pairs");
     if (a.insert_params.max_insert < 1 || a.insert_params.max_insert > KISS_HIP_INSERT_MAX)
         throw std::runtime_error("--ins-auto-max is in 1..65535");
+    goes_with_through("--batch-chunk");
+    if (a.batch_chunk < 1 || a.batch_chunk > (1ull << 30)) throw std::runtime_error("--batch-chunk is in 1..1073741824");
     if (given(a, "--mates")) { // the pair's MAPQ is on the scale of the reads'; the mates face each other
         a.both_strands = true;
         a.pair_params.mapq_coef = a.select_params.mapq_coef;

@@ -163,6 +163,7 @@ struct State {
     kiss_hip_fmi_view_ex index{}; // (of the caller's .fmi)
     ReadFile rd;                  // load_reads: Q reads, V virtual reads: with --both-strands two of each, strand + then -
     uint64_t Q = 0, V = 0;
+    uint64_t first = 0;           // --batch-reads: the number in the file of read 0 of this batch (mates: of the interleaved reads)
     std::vector<kiss_hip_fmi_seed> seeds; // find_seeds
     std::vector<uint64_t> sidx, pidx;
     std::vector<uint32_t> pos;
@@ -357,22 +358,43 @@ inline void sam_pair_lines(std::string &out, const State &m, uint64_t p, const k
     }
 }
 
-// SAM: the header, then the lines of every read, or when `paired` of every pair; rescued: --rescue has run
-inline int print_sam(const State &s, bool paired, bool rescued, const char *version)
+// the header: one @SQ per record of the reference
+inline void sam_header(std::string &out, const RefRecords &ref, const char *version)
 {
-    StdoutWriter w;
-    w.out = "@HD\tVN:1.6\tSO:unsorted\n";
-    for (size_t r = 0; r < s.ref.names.size(); r++)
-        w.out += "@SQ\tSN:" + s.ref.names[r] + "\tLN:" + std::to_string(s.ref.bounds[r + 1] - s.ref.bounds[r]) + '\n';
-    w.out += std::string("@PG\tID:kiss\tPN:kiss\tVN:") + version + '\n';
+    out += "@HD\tVN:1.6\tSO:unsorted\n";
+    for (size_t r = 0; r < ref.names.size(); r++)
+        out += "@SQ\tSN:" + ref.names[r] + "\tLN:" + std::to_string(ref.bounds[r + 1] - ref.bounds[r]) + '\n';
+    out += std::string("@PG\tID:kiss\tPN:kiss\tVN:") + version + '\n';
+}
+
+// the lines of every read of the State, or when `paired` of every pair
+inline void sam_lines(StdoutWriter &w, const State &s, bool paired)
+{
     for (uint64_t i = 0; i < (paired ? s.Q / 2 : s.Q); i++) {
         if (paired && (s.pairs[i].flags & KISS_HIP_PAIR_BAD_INPUT)) // (found here, behind the lines of the pairs before it)
-            throw std::runtime_error("kiss_hip_fmi_pair_host: pair " + std::to_string(i) + " is bad input");
+            throw std::runtime_error("kiss_hip_fmi_pair_host: pair " + std::to_string(s.first / 2 + i) + " is bad input");
         if (paired) sam_pair_lines(w.out, s, i, s.pairs[i]);
         else sam_read_lines(w.out, s, i);
         w.flush_if_full();
     }
+}
+
+inline void sam_info(const State &s, bool paired, bool rescued);
+
+// SAM: the header, then the lines, then the [info] lines; rescued: --rescue has run
+inline int print_sam(const State &s, bool paired, bool rescued, const char *version)
+{
+    StdoutWriter w;
+    sam_header(w.out, s.ref, version);
+    sam_lines(w, s, paired);
     w.finish();
+    sam_info(s, paired, rescued);
+    return 0;
+}
+
+// what the select, pair and rescue calls counted
+inline void sam_info(const State &s, bool paired, bool rescued)
+{
     const kiss_hip_select_report &r = s.select_rep;
     std::fprintf(stderr, "[info] reads: %llu, alignments: %llu, candidates: %llu, spanning: %llu, redundant: %llu, hits: %llu, heads: %llu, mapped: %llu, "
                          "most candidates of a read: %u\n",
@@ -391,7 +413,6 @@ inline int print_sam(const State &s, bool paired, bool rescued, const char *vers
                              "most chains of a pair: %llu, rescued: %llu\n",
                      (ull)s.plan.pairs_planned, (ull)s.plan.anchors, (ull)s.plan.chains, (ull)s.plan.split, (ull)s.plan.empty, (ull)s.plan.bad_input,
                      (ull)s.plan.max_chains, (ull)now_proper);
-    return 0;
 }
 
 } // namespace kiss_cli

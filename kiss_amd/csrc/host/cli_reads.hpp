@@ -5,6 +5,7 @@
 #pragma once
 #include "cli_common.hpp"
 #include "cli_format.hpp"
+#include "cli_batches.hpp"
 #include "../../../include/kiss_hip_reads.h"
 #include "../../../include/kiss_hip_md.h"
 #include "../../../include/kiss_hip_insert.h"
@@ -50,10 +51,8 @@ inline ReadFile parse_read_file(const Args &a, const std::string &path, bool wit
     int rc = call(0, 0);
     if (rc == KISS_HIP_E_INVALID && !rep.bad_records && (rep.reads || rep.bases)) rc = call(rep.bases, rep.reads);
     if (rc == KISS_HIP_E_INVALID && rep.bad_records) {
-        static const char *const kinds[] = {"", "its first line does not start with '@'", "its third line does not start with '+'",
-                                            "its sequence and its quality string differ in length", "the file ends inside it"};
         throw std::runtime_error("fmindex_query --seeds: " + path + " is no FASTQ file: " + std::to_string(rep.bad_records) +
-                                 " bad records, the first is record " + std::to_string(rep.first_bad) + ": " + kinds[rep.first_bad_kind % 5]);
+                                 " bad records, the first is record " + std::to_string(rep.first_bad) + ": " + fastq_bad_kind(rep.first_bad_kind));
     }
     check(rc, "kiss_hip_reads_parse_host");
     if (rep.empty_reads)
@@ -67,7 +66,39 @@ inline ReadFile parse_read_file(const Args &a, const std::string &path, bool wit
     return f;
 }
 
-// READS, with --mates READS2 interleaved with it (kiss_hip_reads_interleave_host)
+// Read p of `first` and read p of `second`, P of each, as reads 2 p and 2 p + 1 of one batch (kiss_hip_reads_interleave_host); with
+// names, those of FASTQ mates without /1 and /2
+inline ReadFile interleave_mates(const Args &a, ReadFile &first, ReadFile &second, int format)
+{
+    const uint64_t P = first.ridx.size() - 1;
+    ReadFile rd;
+    rd.has_qual = first.has_qual;
+    uint64_t bases = first.reads.size() + second.reads.size();
+    rd.reads.resize(bases + 1);
+    rd.qual.resize(bases + 1);
+    rd.ridx.assign(2 * P + 1, 0);
+    first.reads.reserve(1), second.reads.reserve(1), first.qual.reserve(1), second.qual.reserve(1);
+    check(kiss_hip_reads_interleave_host(first.reads.data(), first.ridx.data(), first.has_qual ? first.qual.data() : nullptr, P, second.reads.data(),
+                                         second.ridx.data(), first.has_qual ? second.qual.data() : nullptr, P, rd.reads.data(),
+                                         rd.ridx.data(), first.has_qual ? rd.qual.data() : nullptr, bases, &bases, a.device),
+          "kiss_hip_reads_interleave_host");
+    rd.reads.resize(bases);
+    rd.qual.resize(first.has_qual ? bases : 0);
+    for (uint64_t p = 0; p < P && a.sam; p++)
+        for (ReadFile *f : {&first, &second}) {
+            if (format == KISS_HIP_READS_FASTQ) strip_mate_suffix(f->names[p]);
+            rd.names.push_back(f->names[p]);
+        }
+    return rd;
+}
+
+[[noreturn]] inline void refuse_formats(const Args &a)
+{
+    throw std::runtime_error("fmindex_query --mates: " + a.seeds + " and " + a.mates + " differ in format (one is FASTQ, one has a read per line): "
+                             "name it with --reads-format");
+}
+
+// READS, with --mates READS2 interleaved with it
 inline void load_reads(const Args &a, State &s)
 {
     int format = 0;
@@ -79,27 +110,8 @@ inline void load_reads(const Args &a, State &s)
         if (second.ridx.size() - 1 != P)
             throw std::runtime_error("fmindex_query --mates: " + a.seeds + " has " + std::to_string(P) + " reads, " + a.mates + " has " +
                                      std::to_string(second.ridx.size() - 1) + " reads: a pair has one of each");
-        if (format != format2)
-            throw std::runtime_error("fmindex_query --mates: " + a.seeds + " and " + a.mates + " differ in format (one is FASTQ, one has a read per line): "
-                                     "name it with --reads-format");
-        s.rd = ReadFile();
-        s.rd.has_qual = first.has_qual;
-        uint64_t bases = first.reads.size() + second.reads.size();
-        s.rd.reads.resize(bases + 1);
-        s.rd.qual.resize(bases + 1);
-        s.rd.ridx.assign(2 * P + 1, 0);
-        first.reads.reserve(1), second.reads.reserve(1), first.qual.reserve(1), second.qual.reserve(1);
-        check(kiss_hip_reads_interleave_host(first.reads.data(), first.ridx.data(), first.has_qual ? first.qual.data() : nullptr, P, second.reads.data(),
-                                             second.ridx.data(), first.has_qual ? second.qual.data() : nullptr, P, s.rd.reads.data(),
-                                             s.rd.ridx.data(), first.has_qual ? s.rd.qual.data() : nullptr, bases, &bases, a.device),
-              "kiss_hip_reads_interleave_host");
-        s.rd.reads.resize(bases);
-        s.rd.qual.resize(first.has_qual ? bases : 0);
-        for (uint64_t p = 0; p < P && a.sam; p++)
-            for (ReadFile *f : {&first, &second}) {
-                if (format == KISS_HIP_READS_FASTQ) strip_mate_suffix(f->names[p]);
-                s.rd.names.push_back(f->names[p]);
-            }
+        if (format != format2) refuse_formats(a);
+        s.rd = interleave_mates(a, first, second, format);
     }
     s.Q = s.rd.ridx.size() - 1;
     s.V = a.both_strands ? 2 * s.Q : s.Q;
@@ -155,10 +167,14 @@ inline void align(const Args &a, const State &s, int both_strands, const Chains 
 }
 
 // --align: the text loaded as the index was built from it, every chain aligned to it
-inline void align_chains(const Args &a, State &s)
+inline void load_text(const Args &a, State &s)
 {
     s.S = DeviceText(a.fasta, a.device).to_host();
     s.S.reserve(1); // (a pointer that is not NULL)
+}
+inline void align_chains(const Args &a, State &s)
+{
+    load_text(a, s);
     align(a, s, a.both_strands, s.ch, s.ch.cidx[s.V], s.al, "--align");
 }
 
@@ -175,12 +191,16 @@ inline void select(const Args &a, State &s)
 }
 
 // --sam: the records of the reference, which must add up to the text, and the mappings of every read
-inline void select_hits(const Args &a, State &s)
+inline void load_records(const Args &a, State &s)
 {
     s.ref = scan_records(a.fasta);
     if (s.ref.bounds.back() != s.S.size())
         throw std::runtime_error("fmindex_query --sam: the records of " + a.fasta + " have " + std::to_string(s.ref.bounds.back()) +
                                  " bases, the parsed text has " + std::to_string(s.S.size()));
+}
+inline void select_hits(const Args &a, State &s)
+{
+    load_records(a, s);
     select(a, s);
 }
 
@@ -271,9 +291,85 @@ inline void pair_mates(const Args &a, State &s)
           "kiss_hip_fmi_pair_host");
 }
 
+// --batch-reads N: the text and the records of the reference loaded once, the header printed once; then every batch of N reads,
+// or of N pairs, cut from the files by a ChunkReader, gives a State, the stages above and its lines.  The stages are the _host
+// entries: each uploads the index or the text once more per batch (DESIGN.md 4.20 says what that costs).  --ins-auto: estimated
+// from batch 0, whose values serve every later batch.  An error of a later batch comes behind the lines of the earlier ones.
+inline int map_reads_in_batches(const Args &a, const kiss_hip_fmi_view_ex &index)
+{
+    const auto part = [&a](const uint8_t *raw, uint64_t bytes, int format, int final, uint64_t max_records, uint8_t *codes, uint8_t *qual,
+                           uint64_t bases_capacity, uint64_t *read_index, uint64_t *name_off, uint32_t *name_len, uint64_t reads_capacity,
+                           kiss_hip_reads_part_report *rep) {
+        const int rc = kiss_hip_reads_parse_part_host(raw, bytes, format, final, max_records, codes, qual, bases_capacity, read_index, name_off,
+                                                      name_len, reads_capacity, rep, a.device);
+        if (rc != KISS_HIP_E_INVALID) check(rc, "kiss_hip_reads_parse_part_host");
+        return rc;
+    };
+    typedef ChunkReader<decltype(part)> Reader;
+    const int wanted = a.reads_format == "lines" ? KISS_HIP_READS_LINES : a.reads_format == "fastq" ? KISS_HIP_READS_FASTQ : KISS_HIP_READS_AUTO;
+    const bool paired = !a.mates.empty();
+    std::vector<Reader> files;
+    files.reserve(2);
+    files.emplace_back(a.seeds, wanted, a.batch_chunk, true, part);
+    if (paired) files.emplace_back(a.mates, wanted, a.batch_chunk, true, part);
+    State keep; // the text and the records pass from batch to batch
+    load_text(a, keep);
+    load_records(a, keep);
+    kiss_hip_pair_params pair_params{};
+    kiss_hip_rescue_params rescue_params{};
+    StdoutWriter w;
+    uint64_t batches = 0, reads = 0, mapped = 0;
+    for (;; batches++) {
+        uint64_t K = files[0].ready(a.batch_reads);
+        if (paired) {
+            const uint64_t K2 = files[1].ready(a.batch_reads);
+            if (!K != !K2) {
+                const Reader &shorter = files[K ? 1 : 0];
+                throw std::runtime_error("fmindex_query --mates: " + shorter.path() + " ends after " + std::to_string(shorter.first()) +
+                                         " reads, " + files[K ? 0 : 1].path() + " has more: a pair has one of each");
+            }
+            K = std::min(K, K2);
+        }
+        if (!K) break;
+        State s;
+        s.index = index;
+        s.S = std::move(keep.S);
+        s.ref = std::move(keep.ref);
+        s.first = (paired ? 2 : 1) * files[0].first();
+        s.rd = files[0].take(K);
+        if (paired) {
+            ReadFile first = std::move(s.rd), second = files[1].take(K);
+            if (files[0].format() != files[1].format()) refuse_formats(a);
+            s.rd = interleave_mates(a, first, second, files[0].format());
+        }
+        s.Q = s.rd.ridx.size() - 1;
+        s.V = a.both_strands ? 2 * s.Q : s.Q;
+        find_seeds(a, s);
+        chain_seeds(a, s);
+        align(a, s, a.both_strands, s.ch, s.ch.cidx[s.V], s.al, "--align");
+        select(a, s);
+        if (paired && !batches) insert_size(a, s), pair_params = s.pair_params, rescue_params = s.rescue_params;
+        if (paired) s.pair_params = pair_params, s.rescue_params = rescue_params;
+        if (a.rescue) rescue_mates(a, s);
+        if (paired) pair_mates(a, s);
+        if (a.md) md_tags(a, s);
+        if (!batches) sam_header(w.out, s.ref, VERSION);
+        sam_lines(w, s, paired);
+        w.finish(); // (on stdout before the next batch can fail)
+        if (a.verbose) sam_info(s, paired, a.rescue);
+        reads += s.Q, mapped += s.select_rep.mapped;
+        keep.S = std::move(s.S);
+        keep.ref = std::move(s.ref);
+    }
+    if (!batches) sam_header(w.out, keep.ref, VERSION), w.finish();
+    std::fprintf(stderr, "[info] batches: %llu, reads: %llu, mapped: %llu\n", (ull)batches, (ull)reads, (ull)mapped);
+    return 0;
+}
+
 // fmindex_query --seeds: `index` is the view of the .fmi of a.fasta
 inline int map_reads(const Args &a, const kiss_hip_fmi_view_ex &index)
 {
+    if (a.batch_reads) return map_reads_in_batches(a, index);
     State s;
     s.index = index;
     load_reads(a, s);

@@ -20,8 +20,11 @@
 //                          sequence line is translated, one of a quality line copied, to where it belongs.  A read of 300 000
 //                          bases is the work of 18 750 lanes.
 //           k_rd_finish    one lane per read: read_index, the span of the name
+//   part  : kiss_hip_reads_parse_part_* (kiss_hip_reads_part.h): the lines passes over a chunk, the records its
+//           complete lines hold, the boundary picked (FASTQ: line start 4 * records; LINES: k_rd_cut_line), then the passes
+//           above over the prefix
 #include "fm_internal.hpp"
-#include "../../include/kiss_hip_reads.h"
+#include "../../include/kiss_hip_reads_part.h"
 
 namespace {
 
@@ -31,7 +34,7 @@ constexpr int RD_TILE = RD_THREADS * RD_PER; // 4096 bytes per workgroup
 
 // control block of a call (u64 words)
 enum { RD_FIRST = 0, RD_LAST = 1, RD_NL = 2, RD_READS = 3, RD_BASES = 4, RD_KEPT = 5, RD_BAD = 6, RD_FIRST_BAD = 7, RD_EMPTY = 8, RD_FIRST_EMPTY = 9,
-       RD_NOBASE = 10, IL_BAD = 11, IL_TOTAL_A = 12, IL_TOTAL_B = 13, RD_CTL_WORDS = 16 };
+       RD_NOBASE = 10, IL_BAD = 11, IL_TOTAL_A = 12, IL_TOTAL_B = 13, RD_CUT = 14, RD_CTL_WORDS = 16 };
 
 // Every load of an index or table entry starts at a multiple of its own size: relaxed loads of wavefront scope, as in
 // fm_pair.hip -- ordinary global_load_dword / _dwordx2 that the compiler does not merge with their neighbours (lstart[k] and
@@ -213,6 +216,15 @@ __global__ __launch_bounds__(RD_THREADS) void k_rd_line_reads(const uint8_t *__r
     line_of[q] = (uint32_t)k;
 }
 
+// LINES, the cut of a chunk: the byte behind read line number `records` >= 1 (rank = the scanned flags)
+__global__ __launch_bounds__(RD_THREADS) void k_rd_cut_line(const uint32_t *__restrict__ lstart, const uint32_t *__restrict__ rank, uint64_t lines,
+                                                           uint64_t records, unsigned long long *__restrict__ ctl)
+{
+    const uint64_t k = (uint64_t)blockIdx.x * RD_THREADS + threadIdx.x;
+    if (k >= lines) return;
+    if ((uint64_t)rd_ld32(rank + k) + 1 == records && (uint64_t)rd_ld32(rank + k + 1) == records) ctl[RD_CUT] = rd_ld32(lstart + k + 1);
+}
+
 // FASTQ: the number of lines up to the last one that is not empty
 __global__ __launch_bounds__(RD_THREADS) void k_rd_last_kept(const uint8_t *__restrict__ raw, const uint32_t *__restrict__ lstart, uint64_t lines,
                                                             unsigned long long *__restrict__ ctl)
@@ -381,6 +393,7 @@ struct ParseArgs {
     uint32_t *name_len;
     uint64_t reads_capacity;
     kiss_hip_reads_report *report;
+    bool no_drop = false; // FASTQ: the prefix of a chunk, every line of it a line of a record (kiss_hip_reads_part.h)
 };
 
 int parse_steps(kiss_hip_ctx *ctx, const ParseArgs &a, kiss_hip_reads_report &rep, FmEvents &ev)
@@ -429,7 +442,10 @@ int parse_steps(kiss_hip_ctx *ctx, const ParseArgs &a, kiss_hip_reads_report &re
 
     // ---- reads
     uint64_t reads = 0, used_lines = lines;
-    if (fastq) {
+    if (fastq && a.no_drop) {
+        if (lines % 4) return KINTERNAL();
+        reads = lines / 4;
+    } else if (fastq) {
         if (lines) hipLaunchKernelGGL(k_rd_last_kept, dim3(fm_grid(lines, RD_THREADS)), threads, 0, ctx->stream, raw, lstart, lines, d_ctl);
         KCHECK(hipGetLastError());
         KTRY(ctl.fetch_sync());
@@ -516,6 +532,84 @@ kiss_hip_reads_report empty_report(int format)
     r.has_qual = r.format == KISS_HIP_READS_FASTQ ? 1u : 0u;
     r.first_empty = r.first_bad = KISS_HIP_READS_NONE;
     return r;
+}
+
+// ---- the first whole records of a chunk (kiss_hip_reads_part.h) ----------------------------------------------------------------
+// The cut runs the line passes of the parse over the chunk, counts the records its complete lines hold and picks the byte behind
+// the last one it takes; the parse then runs on that prefix as on a file of its own (no_drop: without looking for empty lines at
+// its end).  The line passes run twice over the prefix so; DESIGN.md 4.20 has what that costs.
+struct Cut {
+    bool fastq = false, whole = false; // whole: the end of the file and every record taken -- the prefix is parsed as a file is
+    uint64_t complete = 0, records = 0, used = 0;
+};
+
+int cut_steps(kiss_hip_ctx *ctx, const uint8_t *raw, uint64_t bytes, int format, bool final, uint64_t max_records, Cut &cut)
+{
+    kiss_opts_refresh(ctx);
+    const uint32_t h = (uint32_t)((uintptr_t)raw & 15u);
+    const uint64_t tiles = div_up(bytes + h, RD_TILE);
+    const dim3 threads(RD_THREADS);
+    FmCtl<RD_CTL_WORDS> ctl;
+    KTRY(ctl.take(ctx, FM_SLOT_READS_CTL));
+    unsigned long long *const d_ctl = ctl.d, *const hc = ctl.h;
+    DevBuf tile_buf, line_buf;
+    KTRY(tile_buf.take(ctx, FM_SLOT_READS_TILES, (tiles + 1) * 4));
+    uint32_t *const nl_ex = (uint32_t *)tile_buf.p;
+    hipLaunchKernelGGL(k_rd_ctl_init, dim3(1), dim3(64), 0, ctx->stream, d_ctl);
+    {
+        KTimer t(ctx, KISS_HIP_K_PACK, bytes);
+        hipLaunchKernelGGL(k_rd_count, dim3((unsigned)(tiles + 1)), threads, 0, ctx->stream, raw, bytes, h, nl_ex, d_ctl);
+        KCHECK(hipGetLastError());
+    }
+    KTRY(kiss_scan_u32(ctx, nl_ex, nl_ex, tiles + 1));
+    KTRY(pick32(ctx, nl_ex, tiles, d_ctl, RD_NL));
+    KTRY(ctl.fetch_sync());
+    // the complete lines: a last piece without '\n' is one only at the end of the file
+    const int open_end = final && hc[RD_LAST] != (unsigned long long)'\n';
+    const uint64_t lines = hc[RD_NL] + (uint64_t)open_end;
+    cut.fastq = format == KISS_HIP_READS_FASTQ || (format == KISS_HIP_READS_AUTO && hc[RD_FIRST] == (unsigned long long)'@');
+    if (lines > bytes) return KINTERNAL();
+    FmSlab lay;
+    const uint64_t o_lstart = lay.carve((lines + 1) * 4), o_rank = lay.carve((lines + 1) * 4);
+    KTRY(line_buf.take(ctx, FM_SLOT_READS_LINES, lay.size));
+    uint32_t *const lstart = (uint32_t *)((char *)line_buf.p + o_lstart), *const rank = (uint32_t *)((char *)line_buf.p + o_rank);
+    {
+        KTimer t(ctx, KISS_HIP_K_PACK, bytes);
+        hipLaunchKernelGGL(k_rd_lines, dim3((unsigned)tiles), threads, 0, ctx->stream, raw, bytes, h, nl_ex, lines, open_end, lstart);
+        KCHECK(hipGetLastError());
+    }
+    if (cut.fastq) {
+        if (lines) hipLaunchKernelGGL(k_rd_last_kept, dim3(fm_grid(lines, RD_THREADS)), threads, 0, ctx->stream, raw, lstart, lines, d_ctl);
+        KCHECK(hipGetLastError());
+        KTRY(ctl.fetch_sync());
+        const uint64_t kept = hc[RD_KEPT];
+        if (kept > lines) return KINTERNAL();
+        cut.complete = final ? div_up(kept, 4) : kept / 4;
+    } else {
+        hipLaunchKernelGGL(k_rd_line_flags, dim3(fm_grid(lines + 1, RD_THREADS)), threads, 0, ctx->stream, raw, lstart, lines, rank);
+        KCHECK(hipGetLastError());
+        KTRY(kiss_scan_u32(ctx, rank, rank, lines + 1));
+        KTRY(pick32(ctx, rank, lines, d_ctl, RD_READS));
+        KTRY(ctl.fetch_sync());
+        cut.complete = hc[RD_READS];
+        if (cut.complete > lines) return KINTERNAL();
+    }
+    cut.records = max_records && max_records < cut.complete ? max_records : cut.complete;
+    cut.whole = final && cut.records == cut.complete;
+    cut.used = cut.whole ? bytes : 0;
+    if (cut.whole || !cut.records) return KISS_HIP_OK;
+    // the byte behind the '\n' of the last line taken (it has one: it is not the last line of the file's end, or not final)
+    if (cut.fastq) {
+        if (4 * cut.records > lines) return KINTERNAL();
+        KTRY(pick32(ctx, lstart, 4 * cut.records, d_ctl, RD_CUT));
+    } else {
+        hipLaunchKernelGGL(k_rd_cut_line, dim3(fm_grid(lines, RD_THREADS)), threads, 0, ctx->stream, lstart, rank, lines, cut.records, d_ctl);
+        KCHECK(hipGetLastError());
+    }
+    KTRY(ctl.fetch_sync());
+    cut.used = hc[RD_CUT];
+    if (cut.used == 0 || cut.used > bytes) return KINTERNAL();
+    return KISS_HIP_OK;
 }
 
 // ---- interleave ------------------------------------------------------------------------------------------------------------
@@ -674,6 +768,86 @@ int kiss_hip_reads_parse_host(const uint8_t *raw, uint64_t bytes, int format, ui
         st.down(read_index, didx, (r.reads + 1) * 8);
         if (names) st.down(name_off, dnoff, r.reads * 8);
         if (names) st.down(name_len, dnlen, r.reads * 4);
+        return st.rc;
+    });
+}
+
+int kiss_hip_reads_parse_part_dev(kiss_hip_ctx *ctx, const uint8_t *d_raw, uint64_t bytes, int format, int final, uint64_t max_records,
+                                  uint8_t *d_codes, uint8_t *d_qual, uint64_t bases_capacity, uint64_t *d_read_index, uint64_t *d_name_off,
+                                  uint32_t *d_name_len, uint64_t reads_capacity, kiss_hip_reads_part_report *report, void *stream)
+{
+    KissOwnStreamAtExit own_stream_at_exit(ctx);
+    kiss_hip_reads_part_report rep{};
+    rep.parsed = empty_report(format);
+    if (report) *report = rep;
+    ParseArgs a{d_raw, bytes, format, d_codes, d_qual, bases_capacity, d_read_index, d_name_off, d_name_len, reads_capacity, &rep.parsed};
+    KTRY(parse_args_check(a));
+    if (!ctx) return KISS_HIP_E_INVALID;
+    KTRY(fm_enter(ctx, stream));
+    if ((bytes + 2) / 4096 + 16 > ctx->scan_tmp_cap) return KISS_HIP_E_UNSUPPORTED; // more than the ctx can scan
+    FmEvents ev(ctx, report != nullptr);
+    Cut cut;
+    float ms_cut = 0.f;
+    bool parsed = false;
+    int rc = KISS_HIP_OK;
+    if (bytes) {
+        ev.mark(4);
+        rc = cut_steps(ctx, d_raw, bytes, format, final != 0, max_records, cut);
+        ev.mark(5);
+    }
+    if (rc == KISS_HIP_OK) {
+        if (bytes) rep.parsed = empty_report(cut.fastq ? KISS_HIP_READS_FASTQ : KISS_HIP_READS_LINES);
+        rep.records_complete = cut.complete;
+        rep.records = cut.records;
+        rep.bytes_used = cut.used;
+        a.bytes = cut.used;
+        a.format = (int)rep.parsed.format;
+        a.no_drop = !cut.whole;
+        if (cut.used == 0) { // no line, no read: the one entry of the index
+            rc = kiss_zero_u32(ctx, d_read_index, 2);
+            if (rc == KISS_HIP_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = KISS_HIP_E_HIP;
+        } else {
+            parsed = true;
+            rc = parse_steps(ctx, a, rep.parsed, ev);
+        }
+        if (bytes) ms_cut = ev.ms(4, 5);
+    }
+    rc = fm_leave(ctx, ev, rc, parsed ? &rep.parsed.ms_total : nullptr); // (events 0 .. 3 are the parse's)
+    rep.parsed.ms_total += ms_cut;
+    rep.parsed.ms_lines += ms_cut;
+    if (report) *report = rep;
+    return rc;
+}
+
+int kiss_hip_reads_parse_part_host(const uint8_t *raw, uint64_t bytes, int format, int final, uint64_t max_records, uint8_t *codes,
+                                   uint8_t *qual, uint64_t bases_capacity, uint64_t *read_index, uint64_t *name_off, uint32_t *name_len,
+                                   uint64_t reads_capacity, kiss_hip_reads_part_report *report, int device)
+{
+    if (report) {
+        *report = kiss_hip_reads_part_report{};
+        report->parsed = empty_report(format);
+    }
+    KTRY(parse_args_check(ParseArgs{raw, bytes, format, codes, qual, bases_capacity, read_index, name_off, name_len, reads_capacity, nullptr}));
+    return kiss_one_shot_cached(device, fm_host_max_n(0, bytes + 2), [&](kiss_hip_ctx *ctx) -> int {
+        const bool names = name_off != nullptr;
+        FmStage st(ctx);
+        const uint8_t *draw = st.up(raw, bytes);
+        uint8_t *dcodes = st.room<uint8_t>(true, bases_capacity);
+        uint8_t *dqual = st.room<uint8_t>(qual != nullptr, bases_capacity);
+        uint64_t *didx = st.room<uint64_t>(true, (reads_capacity + 1) * 8);
+        uint64_t *dnoff = st.room<uint64_t>(names, reads_capacity * 8);
+        uint32_t *dnlen = st.room<uint32_t>(names, reads_capacity * 4);
+        if (st.rc) return st.rc;
+        kiss_hip_reads_part_report r{};
+        const int rc = kiss_hip_reads_parse_part_dev(ctx, draw, bytes, format, final, max_records, dcodes, dqual, bases_capacity, didx, dnoff,
+                                                     dnlen, reads_capacity, &r, nullptr);
+        if (report) *report = r;
+        if (rc) return rc;
+        st.down(codes, dcodes, r.parsed.bases);
+        if (qual && r.parsed.has_qual) st.down(qual, dqual, r.parsed.bases);
+        st.down(read_index, didx, (r.parsed.reads + 1) * 8);
+        if (names) st.down(name_off, dnoff, r.parsed.reads * 8);
+        if (names) st.down(name_len, dnlen, r.parsed.reads * 4);
         return st.rc;
     });
 }

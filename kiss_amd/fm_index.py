@@ -746,6 +746,14 @@ class FMIndex:
         if len(m1) != len(m2):
             raise ValueError("reads1 has %d reads, reads2 has %d: a pair has one of each" % (len(m1), len(m2)))
         batch = [r for pair in zip(m1, m2) for r in pair]
+        return self._map_pair_batch(batch, text, min_len, max_len, max_occ, chain_params, align_params, sp, bounds, want_cigar, rescue,
+                                    want_md, ip, pp)
+
+    def _map_pair_batch(self, batch, text, min_len, max_len, max_occ, chain_params, align_params, sp, bounds, want_cigar, rescue, want_md,
+                        ip, pp):
+        """map_pairs() behind its arguments: batch holds the mates interleaved (reads 2 p and 2 p + 1), in either form"""
+        from .fm_pair import pair_arrays, pair_dev
+        from .fm_select import select_arrays
         res, t = self._align_dev(batch, text, min_len, max_len, max_occ, True, chain_params, want_cigar, align_params or {})
         ctx, sel = self._select(t, t.ctx, t.d_alns, t.d_cidx, t.C, True, bounds, sp)
         res.update(select_arrays(sel))
