@@ -357,6 +357,17 @@ int kiss_hip_stage_refine_exact(kiss_hip_ctx *ctx, uint64_t n, uint32_t h0, uint
 /* Test hooks (used by tests/ only): the library's stable LSD radix sort on bits [key_lo_bit, 64) of keys with a
  * 32-bit payload, and its exclusive u32 scan, run on caller data in host memory (count <= ctx LMS capacity). */
 int kiss_hip_debug_radix_sort(kiss_hip_ctx *ctx, uint64_t *keys, uint32_t *pos, uint64_t count, int key_lo_bit);
+/* The same sort in the form the tied-segment rounds and the stage partition call it: tuples (key, seg, pos), ordered by
+ * seg first, then by bits [key_lo_bit & ~7, 64) of key; key_lo_bit = 64 sorts by seg alone.  key_lo_bit 0..64, seg_bits
+ * 0..32, at most 12 passes of 8 bits in all (KISS_HIP_E_INVALID otherwise, and for count > ctx LMS capacity).
+ * Contract of the callers, not checked: every seg value is below 2^seg_bits (bits above the sorted ones of the last
+ * segment digit would take part in the order).  With seg_bits == 0 the sort never touches the segment column: `seg` may
+ * be NULL, and otherwise comes back as the column of buffer 0, i.e. as it went in, which is where the callers read it.
+ * flags bit 0: the positions go in through a buffer of their own that only the first pass reads (the sort's `first_pos`
+ * form) while the first position buffer holds a poison value; not with key_lo_bit = 64 and seg_bits = 0, where no pass
+ * runs that could read them (KISS_HIP_E_INVALID).  All three columns come back sorted, in host memory. */
+int kiss_hip_debug_radix_sort_seg(kiss_hip_ctx *ctx, uint64_t *keys, uint32_t *seg, uint32_t *pos, uint64_t count,
+                                  int key_lo_bit, int seg_bits, unsigned flags);
 int kiss_hip_debug_scan_u32(kiss_hip_ctx *ctx, uint32_t *data, uint64_t count);
 /* fault injection: from now on work-array allocations of this ctx above `bytes` fail with KISS_HIP_E_NOMEM (0 = off) */
 int kiss_hip_debug_fail_alloc_over(kiss_hip_ctx *ctx, uint64_t bytes);

@@ -383,6 +383,8 @@ def load(hooks=None):
     lib.kiss_hip_fnv1a64_host.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint64]
     lib.kiss_hip_fnv1a64_host.restype = ctypes.c_uint64
     lib.kiss_hip_debug_radix_sort.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_int]
+    lib.kiss_hip_debug_radix_sort_seg.argtypes = [vp, vp, vp, vp, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_uint]
+    lib.kiss_hip_debug_radix_sort_seg.restype = ctypes.c_int
     lib.kiss_hip_debug_scan_u32.argtypes = [vp, vp, ctypes.c_uint64]
     u64 = ctypes.c_uint64
     lib.kiss_hip_stage_classify.argtypes = [vp, vp, u64, ctypes.c_uint32, u64, u64, ctypes.POINTER(u64 * 13), vp]
@@ -528,7 +530,7 @@ EXPORTED_SYMBOLS = [
     "kiss_hip_suffix_sort_dna_u32", "kiss_hip_ctx_suffix_sort_dna_u32", "kiss_hip_ctx_suffix_sort_dna_u32_dev",
     "kiss_hip_ctx_get_stage_outputs", "kiss_hip_ctx_verify_sa_dev", "kiss_hip_sa_digest_host", "kiss_hip_fnv1a64_host",
     "kiss_hip_fmi_query_batch_dev", "kiss_hip_fmi_build_dev",
-    "kiss_hip_debug_radix_sort", "kiss_hip_debug_scan_u32",
+    "kiss_hip_debug_radix_sort", "kiss_hip_debug_radix_sort_seg", "kiss_hip_debug_scan_u32",
     "kiss_hip_stage_classify", "kiss_hip_stage_local_lms", "kiss_hip_stage_key_hist", "kiss_hip_stage_partition",
     "kiss_hip_stage_sort", "kiss_hip_stage_induce", "kiss_hip_stage_induce_exact", "kiss_hip_stage_refine_exact",
     "kiss_hip_fmi_sizes_for", "kiss_hip_fmi_build_host", "kiss_hip_fmi_query_batch_host",

@@ -952,6 +952,42 @@ int kiss_hip_debug_radix_sort(kiss_hip_ctx *ctx, uint64_t *keys, uint32_t *pos, 
     return KISS_HIP_OK;
 }
 
+// the sort in its full form: a segment column in the ctx scratch kiss_partition_by_splitters uses (stages.hip), and,
+// with flags bit 0, the positions of the first pass in a buffer of their own (RadixBufs::first_pos, as round 0 has them
+// in lms_pos) while pos[0] holds a poison value that no pass may read
+int kiss_hip_debug_radix_sort_seg(kiss_hip_ctx *ctx, uint64_t *keys, uint32_t *seg, uint32_t *pos, uint64_t count,
+                                  int key_lo_bit, int seg_bits, unsigned flags)
+{
+    if (!ctx || !keys || !pos || (!seg && seg_bits != 0)) return KISS_HIP_E_INVALID;
+    if (key_lo_bit < 0 || key_lo_bit > 64 || seg_bits < 0 || seg_bits > 32 || (flags & ~1u)) return KISS_HIP_E_INVALID;
+    const int passes = (64 - (key_lo_bit & ~7)) / 8 + (seg_bits + 7) / 8;
+    if (passes > RX_MAX_PASSES) return KISS_HIP_E_INVALID;
+    if ((flags & 1u) && passes == 0) return KISS_HIP_E_INVALID; // no pass: nothing would ever read first_pos
+    if (count > ctx->m_cap) return KISS_HIP_E_INVALID;
+    KCHECK(hipSetDevice(ctx->device));
+    RadixBufs rb = kiss_ctx_radix_bufs(ctx);
+    rb.seg[0] = ctx->lms_sorted_far;
+    rb.seg[1] = ctx->lms_ctx_far;
+    KCHECK(hipMemcpy(rb.key[0], keys, count * 8, hipMemcpyHostToDevice));
+    if (seg) KCHECK(hipMemcpy(rb.seg[0], seg, count * 4, hipMemcpyHostToDevice));
+    if (flags & 1u) {
+        KCHECK(hipMemcpy(ctx->lms_pos, pos, count * 4, hipMemcpyHostToDevice));
+        KTRY(kiss_fill_u32(ctx, rb.pos[0], 0xDEADBEEFu, count));
+        rb.first_pos = ctx->lms_pos;
+    } else {
+        KCHECK(hipMemcpy(rb.pos[0], pos, count * 4, hipMemcpyHostToDevice));
+    }
+    ctx->rx_ghist_count = 0; // no digit counts of an earlier classification belong to these keys
+    int res = 0;
+    KTRY(kiss_radix_sort(ctx, rb, count, key_lo_bit, seg_bits, &res));
+    KTRY(kiss_radix_check(ctx));
+    ktimer_collect(ctx);
+    KCHECK(hipMemcpy(keys, rb.key[res], count * 8, hipMemcpyDeviceToHost));
+    if (seg) KCHECK(hipMemcpy(seg, rb.seg[seg_bits ? res : 0], count * 4, hipMemcpyDeviceToHost));
+    KCHECK(hipMemcpy(pos, rb.pos[res], count * 4, hipMemcpyDeviceToHost));
+    return KISS_HIP_OK;
+}
+
 int kiss_hip_debug_fail_alloc_over(kiss_hip_ctx *ctx, uint64_t bytes)
 {
     if (!ctx) return KISS_HIP_E_INVALID;

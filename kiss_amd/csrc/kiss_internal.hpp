@@ -399,6 +399,7 @@ static inline RadixBufs kiss_ctx_radix_bufs(kiss_hip_ctx *ctx)
     b.pos[1] = ctx->posB;
     return b;
 }
+constexpr int RX_MAX_PASSES = 12; // most passes of one sort: 8 key digits + 4 segment digits (rx_ghist holds their bases)
 int kiss_radix_sort(kiss_hip_ctx *ctx, RadixBufs &b, uint64_t count, int key_lo_bit, int seg_bits, int *result_idx);
 int kiss_radix_check(kiss_hip_ctx *ctx); // synchronises; KISS_HIP_E_INTERNAL if a look-back wait ran out
 // stages.hip: pieces of the sharded form shared with multi.hip (all queued on ctx->stream, not synchronised)

@@ -92,7 +92,6 @@ __global__ __launch_bounds__(RX_THREADS) void k_radix_hist(const uint64_t *__res
 // [61:32] epoch of the pass (stale words of earlier passes read as "not there yet", no clearing), [31:0] value.
 // Forward progress: tiles take their number from an atomic ticket, so a tile only ever waits for tiles that started
 // before it; the wait is bounded (RX_SPIN_LIMIT polls) and flags an error instead of hanging.
-constexpr int RX_MAX_PASSES = 12;
 constexpr uint32_t RX_SPIN_LIMIT = 1u << 24;
 constexpr uint32_t RX_HIST_LDS_WORDS = 16384; // 64 KiB of histogram copies (the default dynamic-LDS limit)
 
