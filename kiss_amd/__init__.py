@@ -16,4 +16,5 @@ from .reads import interleave_reads, interleave_reads_dev, parse_reads, parse_re
 from .fm_md import md_strings, md_tags  # noqa: F401,E402
 from .fm_insert import INSERT_DEFAULTS, estimate_insert, insert_params  # noqa: F401,E402
 from .fm_sam import sam_header  # noqa: F401,E402
+from . import sam_writer  # noqa: F401,E402  (the SAM lines on the device: kiss_amd.sam_writer.sam_lines, sam_lines_dev)
 from . import batches  # noqa: F401,E402  (read files in batches: kiss_amd.batches.read_batches, map_file)

@@ -263,6 +263,20 @@ class ReadsPartReport(ctypes.Structure):
     _fields_ = [("parsed", ReadsReport), ("records_complete", ctypes.c_uint64), ("records", ctypes.c_uint64), ("bytes_used", ctypes.c_uint64)]
 
 
+class SamInput(ctypes.Structure):
+    """kiss_hip_sam_input (include/kiss_hip_sam.h): 18 pointers, then the counts"""
+    POINTERS = ("reads", "read_index", "qual", "names", "name_off", "name_len", "alns", "cigar", "cigar_index", "hits", "hit_index",
+                "pairs", "source", "md", "md_index", "ref_names", "ref_name_index", "bounds")
+    _fields_ = [(k, ctypes.c_void_p) for k in POINTERS] + [(k, ctypes.c_uint64) for k in ("Q", "C", "R", "first_alns")]
+
+
+class SamReport(Report):
+    """kiss_hip_sam_report (include/kiss_hip_sam.h)"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("lines", "sam_bytes", "unmapped_lines", "longest", "bad", "first_bad")] + [
+        ("ms_total", ctypes.c_float), ("ms_count", ctypes.c_float), ("ms_emit", ctypes.c_float), ("reserved_", ctypes.c_uint32),
+    ]
+
+
 class MdReport(Report):
     """kiss_hip_md_report (include/kiss_hip_md.h)"""
     _fields_ = [(k, ctypes.c_uint64) for k in ("items", "bad", "md_bytes", "mismatch_columns", "deleted_bases", "longest")] + [
@@ -466,6 +480,10 @@ def load(hooks=None):
                                          ctypes.POINTER(MdReport), ctypes.c_int]
     for name in MD_EXPORTED_SYMBOLS:
         getattr(lib, name).restype = ctypes.c_int
+    lib.kiss_hip_fmi_sam_dev.argtypes = [vp, ctypes.POINTER(SamInput), vp, u64, vp, u64, vp, ctypes.POINTER(SamReport), vp]
+    lib.kiss_hip_fmi_sam_host.argtypes = [ctypes.POINTER(SamInput), vp, u64, vp, u64, vp, ctypes.POINTER(SamReport), ctypes.c_int]
+    for name in SAM_EXPORTED_SYMBOLS:
+        getattr(lib, name).restype = ctypes.c_int
     lib.kiss_hip_fmi_insert_dev.argtypes = [vp, vp, vp, u64, vp, u64, ctypes.POINTER(InsertParams), vp, ctypes.POINTER(InsertReport), vp]
     lib.kiss_hip_fmi_insert_host.argtypes = [vp, vp, u64, vp, u64, ctypes.POINTER(InsertParams), vp, ctypes.POINTER(InsertReport),
                                              ctypes.c_int]
@@ -559,6 +577,8 @@ READS_EXPORTED_SYMBOLS = [
 READS_PART_EXPORTED_SYMBOLS = ["kiss_hip_reads_parse_part_dev", "kiss_hip_reads_parse_part_host"]
 # every symbol include/kiss_hip_md.h declares (tests/test_fm_md_abi.py)
 MD_EXPORTED_SYMBOLS = ["kiss_hip_fmi_md_dev", "kiss_hip_fmi_md_host"]
+# every symbol include/kiss_hip_sam.h declares (tests/test_fm_sam_abi.py)
+SAM_EXPORTED_SYMBOLS = ["kiss_hip_fmi_sam_dev", "kiss_hip_fmi_sam_host"]
 # every symbol include/kiss_hip_insert.h declares (tests/test_fm_insert_abi.py)
 INSERT_EXPORTED_SYMBOLS = ["kiss_hip_fmi_insert_dev", "kiss_hip_fmi_insert_host"]
 INSERT_MAX = 65535

@@ -266,7 +266,13 @@ def map_file(index, reads1, text, reads2=None, batch_reads=100000, chunk_bytes=6
     stage treats a read or a pair on its own: the mappings do not depend on how the file was cut.
     insert="auto" (or True, or a dict) with reads2: the insert size is estimated ONCE, from batch 0.  The three values it
     used -- the estimate, or the caller's or default values when batch 0 had too few samples -- serve every later batch,
-    whose result carries insert = dict(applied, ins_min, ins_max, ins_mean, from_batch=0), without report and histogram."""
+    whose result carries insert = dict(applied, ins_min, ins_max, ins_mean, from_batch=0), without report and histogram.
+    sam=True (with ref_names where bounds is given): every batch also carries its alignment lines (sam, sam_line_index,
+    sam_read_line, sam_report, as map(sam=True) gives them), with the names and the qualities of the parsed chunk -- FASTQ mate
+    names without their /1 and /2 --; the lines of the batches, one after the other, are the lines of the file."""
+    if "names" in params or "qual" in params:
+        raise ValueError("map_file takes names and qualities from the file")
+    sam, ref_names = bool(params.pop("sam", False)), params.pop("ref_names", None)
     from .fm_pair import pair_params as make_pair_params
     from .fm_select import select_params as make_select_params
     d_text, n = index._text_dev(text)
@@ -289,14 +295,16 @@ def map_file(index, reads1, text, reads2=None, batch_reads=100000, chunk_bytes=6
                                             hooks=index._hooks)):
         reads = (b["reads"], b["read_index"])
         if not paired:
-            res = index.map(reads, d_text, **params)
+            res = index.map(reads, d_text, **params, **(dict(sam=True, names=b["names"], qual=b["qual"], ref_names=ref_names) if sam else {}))
         else:
             if carried is not None:
                 pair_kw.update(ins_min=carried["ins_min"], ins_max=carried["ins_max"], ins_mean=carried["ins_mean"])
             res = index._map_pair_batch(reads, d_text, p.get("min_len", 19), p.get("max_len", 0), p.get("max_occ", 500),
                                         p.get("chain_params"), p.get("align_params"), sp, p.get("bounds"), p.get("want_cigar", True),
                                         p.get("rescue"), p.get("want_md", False), ip if carried is None else None,
-                                        make_pair_params(**pair_kw))
+                                        make_pair_params(**pair_kw),
+                                        index._sam_options(dict(sam=True, names=b["names"], qual=b["qual"], ref_names=ref_names) if sam else {},
+                                                           p.get("want_cigar", True), p.get("bounds")))
             if ip is not None:
                 if carried is None:
                     res["insert"]["from_batch"] = number

@@ -139,7 +139,16 @@ inline void usage_sam()
               << "                                 columns, the text's letter at a mismatch (a read letter that is no base never\n"
               << "                                 matches), ^ and the text's letters at a deletion; an insertion does not end a\n"
               << "                                 run of matches.  The strings are written on the device.  Unmapped lines carry\n"
-              << "                                 none.  Without --md every byte of the output is what it was.\n";
+              << "                                 none.  Without --md every byte of the output is what it was.\n"
+              << "Who writes the alignment lines:\n"
+              << "  --sam-writer host|device (=host)\n"
+              << "                                 with --sam: host builds every line on one thread of the host, from the arrays the\n"
+              << "                                 stages left behind; device writes the same bytes on the device\n"
+              << "                                 (kiss_hip_fmi_sam_host) and prints them batch by batch.  The header is the host's\n"
+              << "                                 in both.  A pair that is bad input ends the run with the same message and a\n"
+              << "                                 non-zero status under both writers; the host writer prints the lines of the pairs in\n"
+              << "                                 front of it first, the device writer the lines of the EARLIER BATCHES only: the\n"
+              << "                                 device call writes nothing for a batch that has a bad read.\n";
 }
 
 // The help of the options of --mates that `kiss -h` does not list (`kiss --help-pairs`): apart from usage() for the same reason.
@@ -248,6 +257,7 @@ struct Args {
     kiss_hip_insert_params insert_params{20, 10000, 25, 2, 3, 4};
     size_t batch_reads = 0;          // fmindex_query ... --sam --batch-reads N (0: the whole file as one batch)
     size_t batch_chunk = 64u << 20;  // --batch-chunk BYTES
+    std::string sam_writer = "host"; // fmindex_query ... --sam --sam-writer host|device
 };
 
 inline bool given(const Args &a, const char *name) { return std::find(a.seen.begin(), a.seen.end(), name) != a.seen.end(); }
@@ -322,6 +332,7 @@ inline const Opt OPTIONS[] = {
     {"--ins-auto-min-pairs", nullptr, KISS_AT(insert_params.min_samples), true, {"--ins-auto"}},
     {"--batch-reads", nullptr, KISS_AT(batch_reads), true, {"--sam"}},
     {"--batch-chunk", nullptr, KISS_AT(batch_chunk), true, {"--batch-reads"}},
+    {"--sam-writer", nullptr, KISS_AT(sam_writer), true, {"--sam"}},
 };
 #undef KISS_AT
 
@@ -389,6 +400,8 @@ inline Args parse(int argc, char **argv)
         throw std::runtime_error("--ins-auto-max is in 1..65535");
     goes_with_through("--batch-chunk");
     if (a.batch_chunk < 1 || a.batch_chunk > (1ull << 30)) throw std::runtime_error("--batch-chunk is in 1..1073741824");
+    goes_with_through("--sam-writer");
+    if (a.sam_writer != "host" && a.sam_writer != "device") throw std::runtime_error("--sam-writer is one of host, device (kiss --help-sam)");
     if (given(a, "--mates")) { // the pair's MAPQ is on the scale of the reads'; the mates face each other
         a.both_strands = true;
         a.pair_params.mapq_coef = a.select_params.mapq_coef;

@@ -9,6 +9,7 @@
 #include "../../../include/kiss_hip_reads.h"
 #include "../../../include/kiss_hip_md.h"
 #include "../../../include/kiss_hip_insert.h"
+#include "../../../include/kiss_hip_sam.h"
 #include <iterator>
 
 namespace kiss_cli {
@@ -291,6 +292,56 @@ inline void pair_mates(const Args &a, State &s)
           "kiss_hip_fmi_pair_host");
 }
 
+// --sam-writer device: the lines of the State written on the device, in the place of sam_lines.  The names of the reads and of
+// the records go up as byte arrays with their spans.  A pair that is bad input: the message of sam_lines, and no line of this
+// batch (the device call writes nothing for a batch that has a bad read).
+inline void sam_lines_device(StdoutWriter &w, const Args &a, const State &s, bool paired)
+{
+    const uint64_t Q = s.Q, R = s.ref.names.size();
+    if (!Q) return;
+    for (uint64_t p = 0; paired && p < Q / 2; p++)
+        if (s.pairs[p].flags & KISS_HIP_PAIR_BAD_INPUT)
+            throw std::runtime_error("kiss_hip_fmi_pair_host: pair " + std::to_string(s.first / 2 + p) + " is bad input");
+    std::vector<uint8_t> names, ref_names;
+    std::vector<uint64_t> name_off(Q), ref_name_index(R + 1, 0);
+    std::vector<uint32_t> name_len(Q);
+    for (uint64_t q = 0; q < Q; q++) {
+        name_off[q] = names.size();
+        name_len[q] = (uint32_t)s.rd.names[q].size();
+        names.insert(names.end(), s.rd.names[q].begin(), s.rd.names[q].end());
+    }
+    for (uint64_t r = 0; r < R; r++) {
+        ref_names.insert(ref_names.end(), s.ref.names[r].begin(), s.ref.names[r].end());
+        ref_name_index[r + 1] = ref_names.size();
+    }
+    names.push_back(0), ref_names.push_back(0); // (no NULL for reads without names)
+    static const uint32_t none = 0; // (no NULL for a batch without ops, alignments or hits)
+    static const kiss_hip_aln no_aln{};
+    static const kiss_hip_hit no_hit{};
+    kiss_hip_sam_input in{};
+    in.reads = s.rd.reads.data(), in.read_index = s.rd.ridx.data(), in.qual = s.rd.has_qual ? s.rd.qual.data() : nullptr;
+    in.names = names.data(), in.name_off = name_off.data(), in.name_len = name_len.data();
+    in.alns = s.al.alns.empty() ? &no_aln : s.al.alns.data(), in.cigar = s.al.cigar.empty() ? &none : s.al.cigar.data(), in.cigar_index = s.al.oidx.data();
+    in.hits = s.hits.empty() ? &no_hit : s.hits.data(), in.hit_index = s.hidx.data();
+    in.pairs = paired ? s.pairs.data() : nullptr;
+    in.source = s.source.empty() ? nullptr : s.source.data(), in.first_alns = s.first_alns;
+    in.md = s.midx.empty() ? nullptr : s.md.data(), in.md_index = s.midx.empty() ? nullptr : s.midx.data();
+    in.ref_names = ref_names.data(), in.ref_name_index = ref_name_index.data(), in.bounds = s.ref.bounds.data();
+    in.Q = Q, in.C = s.al.oidx.size() - 1, in.R = R;
+    std::vector<uint8_t> sam(1);
+    std::vector<uint64_t> read_line(Q + 1);
+    kiss_hip_sam_report rep{};
+    const int rc = sized_call(sam, rep.sam_bytes, [&](uint64_t capacity) {
+        return kiss_hip_fmi_sam_host(&in, sam.data(), capacity, nullptr, 0, read_line.data(), &rep, a.device);
+    });
+    if (rc == KISS_HIP_E_INVALID && rep.bad)
+        throw std::runtime_error("fmindex_query --sam-writer device: " + std::to_string(rep.bad) + " reads have hits that do not fit them, the first is read " +
+                                 std::to_string(s.first + rep.first_bad));
+    check(rc, "kiss_hip_fmi_sam_host");
+    w.write(); // (what is waiting, the header for one, goes first)
+    std::fwrite(sam.data(), 1, rep.sam_bytes, stdout);
+}
+
 // --batch-reads N: the text and the records of the reference loaded once, the header printed once; then every batch of N reads,
 // or of N pairs, cut from the files by a ChunkReader, gives a State, the stages above and its lines.  The stages are the _host
 // entries: each uploads the index or the text once more per batch (DESIGN.md 4.20 says what that costs).  --ins-auto: estimated
@@ -354,7 +405,8 @@ inline int map_reads_in_batches(const Args &a, const kiss_hip_fmi_view_ex &index
         if (paired) pair_mates(a, s);
         if (a.md) md_tags(a, s);
         if (!batches) sam_header(w.out, s.ref, VERSION);
-        sam_lines(w, s, paired);
+        if (a.sam_writer == "device") sam_lines_device(w, a, s, paired);
+        else sam_lines(w, s, paired);
         w.finish(); // (on stdout before the next batch can fail)
         if (a.verbose) sam_info(s, paired, a.rescue);
         reads += s.Q, mapped += s.select_rep.mapped;
@@ -384,7 +436,13 @@ inline int map_reads(const Args &a, const kiss_hip_fmi_view_ex &index)
     if (a.rescue) rescue_mates(a, s);
     if (!a.mates.empty()) pair_mates(a, s);
     if (a.md) md_tags(a, s);
-    return print_sam(s, !a.mates.empty(), a.rescue, VERSION);
+    if (a.sam_writer != "device") return print_sam(s, !a.mates.empty(), a.rescue, VERSION);
+    StdoutWriter w;
+    sam_header(w.out, s.ref, VERSION);
+    sam_lines_device(w, a, s, !a.mates.empty());
+    w.finish();
+    sam_info(s, !a.mates.empty(), a.rescue);
+    return 0;
 }
 
 } // namespace kiss_cli

@@ -25,6 +25,8 @@
 //       --md      MD:Z: behind NM:i: on the mapped lines, written on the device   kiss_hip_fmi_md_host (kiss --help-sam)
 //       --batch-reads N  with --sam: the file N reads (N pairs) at a time, cut on the device   kiss_hip_reads_parse_part_host
 //                 (cli_batches.hpp; kiss --help-reads)
+//       --sam-writer host|device  with --sam: the alignment lines built on the host (the default), or written on the device
+//                 kiss_hip_fmi_sam_host (kiss --help-sam)
 //   * -g / --generic with any of the three: the file is a text over the byte alphabet, byte for byte (no FASTA rule, no newline
 //     stripping, no % 4): kiss_hip_suffix_sort_u8 (-k, -s ignored), kiss_hip_lcp_u8, kiss_hip_fmi8_build_host -> <file>.fmi8
 //     (DESIGN.md 4.7), kiss_hip_fmi8_query_host.  One device, no lookup table, no mismatches.  The reference rejects -g.

@@ -179,6 +179,10 @@ enum FmSlot {
     // kiss_hip_fmi_insert_dev (fm_insert.hip)
     FM_SLOT_INSERT_CTL,
     FM_SLOT_INSERT_HIST, // the histogram, when the caller keeps none
+    // kiss_hip_fmi_sam_dev (fm_sam.hip)
+    FM_SLOT_SAM_CTL,
+    FM_SLOT_SAM_READS,   // per read: its lines, scanned
+    FM_SLOT_SAM_LINES,   // per line: its bytes, scanned
     FM_SLOT_COUNT
 };
 

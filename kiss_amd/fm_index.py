@@ -670,8 +670,15 @@ class FMIndex:
         (structured array: aln, flags, mapq, score, sub, n_sec, head, ref; flags 1 reverse, 2 secondary, 4 supplementary),
         hit_index (Q + 1: the hits of read q are hits[hit_index[q]:hit_index[q + 1]], the primary first) and select_report.
         want_md (it needs want_cigar): also md, md_index, md_counts and md_report -- the MD:Z string of every hit, in the order
-        of hits (kiss_hip_fmi_md_dev, include/kiss_hip_md.h; kiss_amd.fm_md.md_strings() splits the bytes)."""
+        of hits (kiss_hip_fmi_md_dev, include/kiss_hip_md.h; kiss_amd.fm_md.md_strings() splits the bytes).
+        Further keywords: sam (False; it needs want_cigar): also sam (bytes: the alignment lines of the batch, written from the buffers that are still on
+        the device by kiss_hip_fmi_sam_dev, include/kiss_hip_sam.h; kiss_amd.sam_header() gives the lines in front of them),
+        sam_line_index (lines + 1), sam_read_line (Q + 1: the first line of every read) and sam_report; with want_md the lines
+        carry MD:Z:.  names: the QNAMEs, a list of str or bytes or the (raw, name_off, name_len) triple of parse_reads; None: the
+        decimal read number.  qual: the quality bytes, a list with one entry per read or one array under the index of the reads;
+        None prints '*'.  ref_names: the names of the R records, needed when bounds is given; without either RNAME is '*'."""
         from .fm_select import select_arrays, select_params as make_select_params
+        so = self._sam_options(select_params, want_cigar, bounds)
         sp = make_select_params(**select_params)
         self._md_needs_ops(want_md, want_cigar)
         res, t = self._align_dev(reads, text, min_len, max_len, max_occ, both_strands, chain_params, want_cigar,
@@ -679,7 +686,9 @@ class FMIndex:
         ctx, sel = self._select(t, t.ctx, t.d_alns, t.d_cidx, t.C, both_strands, bounds, sp)
         res.update(select_arrays(sel))
         if want_md:
-            res.update(self._md_of_hits(t, ctx, t.d_alns, t.d_cidx, t.C, t.al["d_cigar"], t.al["d_oidx"], both_strands, sel))
+            res.update(self._md_of_hits(t, ctx, t.d_alns, t.d_cidx, t.C, t.al["d_cigar"], t.al["d_oidx"], both_strands, sel, so))
+        if so:
+            res.update(self._sam_lines(t, ctx, t.d_alns, t.C, t.al["d_cigar"], t.al["d_oidx"], sel, so))
         return res
 
     @staticmethod
@@ -695,12 +704,92 @@ class FMIndex:
         ctx = self._context_to_sort(ctx, C)
         return ctx, select_dev(t.lib, ctx, self.device, d_alns, d_cidx, t.d_ridx, t.Q, C, both_strands, bounds, sp)
 
-    def _md_of_hits(self, t, ctx, d_alns, d_cidx, C, d_cigar, d_oidx, both_strands, sel):
-        """map(want_md=True): the MD strings of the hits of a select call, from the buffers that are on the device"""
+    def _md_of_hits(self, t, ctx, d_alns, d_cidx, C, d_cigar, d_oidx, both_strands, sel, so=None):
+        """map(want_md=True): the MD strings of the hits of a select call, from the buffers that are on the device (so: the SAM
+        options, which keep the tensors for the lines)"""
         from .fm_md import md_arrays, md_dev
         out = md_dev(t.lib, ctx, self.device, t.d_text, t.n, t.d_reads, t.d_ridx, t.Q, both_strands, d_alns, d_cidx, C,
                      d_cigar, d_oidx, sel["d_hits"], int(sel["rep"].hits))
+        if so:
+            so["md"] = out
         return md_arrays(out)
+
+    @staticmethod
+    def _sam_options(given, want_cigar, bounds):
+        """map(sam=...): takes sam, names, qual and ref_names out of the keywords `given` -> None without sam, else the
+        arguments of the lines, held against each other before anything runs"""
+        sam, names, qual, ref_names = (given.pop(k, d) for k, d in (("sam", False), ("names", None), ("qual", None), ("ref_names", None)))
+        if not sam:
+            if names is not None or qual is not None or ref_names is not None:
+                raise ValueError("names, qual and ref_names belong to sam=True")
+            return None
+        if not want_cigar:
+            raise ValueError("sam needs the ops: want_cigar=True")
+        from .fm_select import _bounds_array
+        b = _bounds_array(bounds)
+        R = len(ref_names) if ref_names is not None else 0
+        if b is not None and R != b.size - 1:
+            raise ValueError("ref_names has one name per record: bounds has R + 1 = %d entries" % b.size)
+        if R > 1 and b is None:
+            raise ValueError("ref_names with more than one name needs bounds")
+        return {"names": names, "qual": qual, "ref_names": ref_names, "bounds": b, "md": None}
+
+    def _sam_lines(self, t, ctx, d_alns, C, d_cigar, d_oidx, sel, so, d_pairs=None, d_source=None, first_alns=0):
+        """map(sam=True): the lines of the hits of a select call (and the pairs of a pair call), from the buffers that are on the
+        device; names, qualities and record names go up beside them"""
+        from .sam_writer import default_names, name_index, pack_names, sam_arrays, sam_lines_dev
+        torch = _torch()
+        dev = torch.device("cuda", self.device)
+        Q, paired = t.Q, d_pairs is not None
+
+        def up(a, as_type=None):  # (one element when it is empty: no NULL)
+            a = np.ascontiguousarray(a)
+            a = a if a.size else np.zeros(1, a.dtype)
+            return torch.from_numpy(a.view(as_type) if as_type else a).to(dev)
+
+        names = so["names"]
+        if names is None:
+            names = default_names(Q, paired)
+        elif paired and not isinstance(names, tuple) and len(names) == Q // 2:
+            names = [x for x in names for _ in (0, 1)]  # (one name per pair: both mates carry it)
+        raw, noff, nlen = pack_names(names)
+        if noff.size != Q or nlen.size != Q:
+            raise ValueError("names has one entry per read (%d), or per pair" % Q)
+        if Q and int((noff + nlen).max()) > raw.size:
+            raise ValueError("a name span points past the name bytes")
+        bases = int(t.lens.sum())
+        qual = so["qual"]
+        d_qual = None
+        if qual is not None:
+            if isinstance(qual, torch.Tensor):
+                d_qual = qual.to(device=dev, dtype=torch.uint8).contiguous().reshape(-1)
+                n_qual = int(d_qual.numel())
+                d_qual = d_qual if n_qual else torch.zeros(1, dtype=torch.uint8, device=dev)
+            else:
+                if isinstance(qual, (list, tuple)):
+                    parts = [np.frombuffer(x, np.uint8) if isinstance(x, (bytes, bytearray)) else np.ascontiguousarray(x, dtype=np.uint8).ravel()
+                             for x in qual]
+                    if [p.size for p in parts] != [int(x) for x in t.lens]:
+                        raise ValueError("qual has one entry per read, as long as the read")
+                    qual = np.concatenate(parts) if parts else np.zeros(0, np.uint8)
+                qual = np.ascontiguousarray(qual, dtype=np.uint8).ravel()
+                n_qual, d_qual = qual.size, up(qual)
+            if n_qual < bases:
+                raise ValueError("qual covers %d bases, the reads have %d" % (n_qual, bases))
+        b, ref_names = so["bounds"], so["ref_names"]
+        R = len(ref_names) if ref_names is not None else 0
+        if R and b is None:
+            b = np.array([0, t.n], np.uint64)
+        rn, rnidx = name_index(ref_names)
+        md = so["md"]
+        H = int(sel["rep"].hits)
+        ctx = self._context_to_sort(ctx, Q + H + 1)
+        out = sam_lines_dev(t.lib, ctx, self.device, Q, C, R, first_alns, reads=t.d_reads, read_index=t.d_ridx, qual=d_qual, names=up(raw),
+                            name_off=up(noff, np.int64), name_len=up(nlen, np.int32), alns=d_alns, cigar=d_cigar, cigar_index=d_oidx,
+                            hits=sel["d_hits"], hit_index=sel["d_hidx"], pairs=d_pairs, source=d_source,
+                            md=md["d_md"] if md else None, md_index=md["d_midx"] if md else None, ref_names=up(rn) if R else None,
+                            ref_name_index=up(rnidx, np.int64) if R else None, bounds=up(b, np.int64) if R else None)
+        return sam_arrays(out)
 
     # ---- the mappings of two mates paired (kiss_hip_fmi_pair_dev; no reference counterpart) -----------------------------
     def map_pairs(self, reads1, reads2, text, min_len=19, max_len=0, max_occ=500, chain_params=None, align_params=None,
@@ -732,9 +821,14 @@ class FMIndex:
         ins_mean of the pair parameters are replaced by the estimate (every other pair parameter stays the caller's) and the
         rescue plan's ins_min / ins_max default to the estimated ones; otherwise the caller's or default values apply.  Added:
         insert (report, hist, applied, ins_min, ins_max, ins_mean: the three values used).  With rescue both passes use the
-        same values: the estimate is taken once, from the first pass."""
+        same values: the estimate is taken once, from the first pass.
+        Further keywords: sam (False; it needs want_cigar): also sam, sam_line_index, sam_read_line and sam_report as in map(), the paired lines of the
+        interleaved batch; with rescue they come from the second pass and YR:i:1 follows aln_source.  names: one per pair (both
+        mates carry it) or one per read of the interleaved batch; None: the decimal pair number.  qual: (qual1, qual2), each one
+        entry per read of its file; ref_names as in map()."""
         from .fm_pair import pair_arrays, pair_dev, pair_params as make_pair_params
         from .fm_select import select_arrays, select_params as make_select_params
+        so = self._sam_options(pair_params, want_cigar, bounds)
         pp = make_pair_params(**pair_params)
         sp = make_select_params(**(select_params or {}))
         self._md_needs_ops(want_md, want_cigar)
@@ -746,11 +840,16 @@ class FMIndex:
         if len(m1) != len(m2):
             raise ValueError("reads1 has %d reads, reads2 has %d: a pair has one of each" % (len(m1), len(m2)))
         batch = [r for pair in zip(m1, m2) for r in pair]
+        if so and so["qual"] is not None:
+            qual = so["qual"]
+            if not isinstance(qual, (list, tuple)) or len(qual) != 2 or len(qual[0]) != len(m1) or len(qual[1]) != len(m2):
+                raise ValueError("qual is (qual1, qual2), each with one entry per read of its file")
+            so["qual"] = [x for pair in zip(qual[0], qual[1]) for x in pair]
         return self._map_pair_batch(batch, text, min_len, max_len, max_occ, chain_params, align_params, sp, bounds, want_cigar, rescue,
-                                    want_md, ip, pp)
+                                    want_md, ip, pp, so)
 
     def _map_pair_batch(self, batch, text, min_len, max_len, max_occ, chain_params, align_params, sp, bounds, want_cigar, rescue, want_md,
-                        ip, pp):
+                        ip, pp, so=None):
         """map_pairs() behind its arguments: batch holds the mates interleaved (reads 2 p and 2 p + 1), in either form"""
         from .fm_pair import pair_arrays, pair_dev
         from .fm_select import select_arrays
@@ -763,9 +862,11 @@ class FMIndex:
         res.update(pair_arrays(out))
         if rescue is None or rescue is False:
             if want_md:
-                res.update(self._md_of_hits(t, ctx, t.d_alns, t.d_cidx, t.C, t.al["d_cigar"], t.al["d_oidx"], True, sel))
+                res.update(self._md_of_hits(t, ctx, t.d_alns, t.d_cidx, t.C, t.al["d_cigar"], t.al["d_oidx"], True, sel, so))
+            if so:
+                res.update(self._sam_lines(t, ctx, t.d_alns, t.C, t.al["d_cigar"], t.al["d_oidx"], sel, so, out["d_pairs"]))
             return res
-        return self._rescue_pass(res, t, ctx, sel, out, sp, pp, bounds, want_cigar, {} if rescue is True else dict(rescue), want_md)
+        return self._rescue_pass(res, t, ctx, sel, out, sp, pp, bounds, want_cigar, {} if rescue is True else dict(rescue), want_md, so)
 
     def _insert_estimate(self, res, t, ctx, sel, pp, ip):
         """map_pairs(insert=...): the estimate from the hits of the first select call -> the pair parameters to use"""
@@ -779,7 +880,7 @@ class FMIndex:
                              ins_mean=int(pp.ins_mean))
         return pp
 
-    def _rescue_pass(self, res, t, ctx, sel, out, sp, pp, bounds, want_cigar, rescue, want_md=False):
+    def _rescue_pass(self, res, t, ctx, sel, out, sp, pp, bounds, want_cigar, rescue, want_md=False, so=None):
         """map_pairs(rescue=...): plan, the rescue align call, merge, and select and pair again (res: the first pass's result)"""
         from .fm_align import align_arrays, align_dev
         from .fm_pair import PAIR_PROPER, pair_arrays, pair_dev
@@ -811,7 +912,9 @@ class FMIndex:
         res.update(select_arrays(sel2))
         res.update(pair_arrays(out2))
         if want_md:
-            res.update(self._md_of_hits(t, ctx, mg["d_alns"], mg["d_cidx"], C, mg["d_cigar"], mg["d_oidx"], True, sel2))
+            res.update(self._md_of_hits(t, ctx, mg["d_alns"], mg["d_cidx"], C, mg["d_cigar"], mg["d_oidx"], True, sel2, so))
+        if so:
+            res.update(self._sam_lines(t, ctx, mg["d_alns"], C, mg["d_cigar"], mg["d_oidx"], sel2, so, out2["d_pairs"], mg["d_source"], CA))
         proper1 = (first["pairs"]["flags"] & PAIR_PROPER) != 0
         proper2 = (res["pairs"]["flags"] & PAIR_PROPER) != 0
         plan.update(align_report=align_arrays(al2, False)["align_report"], merge_report=mg["rep"].as_dict(),
