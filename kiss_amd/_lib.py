@@ -284,6 +284,19 @@ class MdReport(Report):
     ]
 
 
+class PileupParams(ctypes.Structure):
+    """kiss_hip_pileup_params (include/kiss_hip_pileup.h)"""
+    _fields_ = [(k, ctypes.c_uint32) for k in ("min_mapq", "skip_flags", "proper_only", "reserved_")]
+
+
+class PileupReport(Report):
+    """kiss_hip_pileup_report (include/kiss_hip_pileup.h)"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("items", "bad", "filtered", "unmapped", "counted", "columns", "alt_columns",
+                                               "deleted_bases", "insertions", "clipped")] + [
+        ("ms_total", ctypes.c_float), ("ms_check", ctypes.c_float), ("ms_walk", ctypes.c_float), ("reserved_", ctypes.c_uint32),
+    ]
+
+
 class InsertParams(ctypes.Structure):
     """kiss_hip_insert_params (include/kiss_hip_insert.h)"""
     _fields_ = [(k, ctypes.c_uint32) for k in ("min_mapq", "max_insert", "min_samples", "out_mult", "map_mult", "sd_mult")]
@@ -480,6 +493,14 @@ def load(hooks=None):
                                          ctypes.POINTER(MdReport), ctypes.c_int]
     for name in MD_EXPORTED_SYMBOLS:
         getattr(lib, name).restype = ctypes.c_int
+    if hasattr(lib, "kiss_hip_fmi_pileup_dev"):  # (the parent commit's library under KISS_AMD_LIB_PATH, for an A-B of bench.py, has none)
+        lib.kiss_hip_fmi_pileup_dev.argtypes = [vp, vp, u64, vp, vp, u64, ctypes.c_int, vp, vp, vp, vp, vp, u64, vp, u64,
+                                                ctypes.POINTER(PileupParams), u64, u64, vp, ctypes.c_int, ctypes.POINTER(PileupReport), vp]
+        lib.kiss_hip_fmi_pileup_host.argtypes = [vp, u64, vp, vp, u64, ctypes.c_int, vp, vp, vp, vp, vp, u64, vp, u64,
+                                                 ctypes.POINTER(PileupParams), u64, u64, vp, ctypes.c_int, ctypes.c_int,
+                                                 ctypes.POINTER(PileupReport), ctypes.c_int]
+        for name in PILEUP_EXPORTED_SYMBOLS:
+            getattr(lib, name).restype = ctypes.c_int
     lib.kiss_hip_fmi_sam_dev.argtypes = [vp, ctypes.POINTER(SamInput), vp, u64, vp, u64, vp, ctypes.POINTER(SamReport), vp]
     lib.kiss_hip_fmi_sam_host.argtypes = [ctypes.POINTER(SamInput), vp, u64, vp, u64, vp, ctypes.POINTER(SamReport), ctypes.c_int]
     for name in SAM_EXPORTED_SYMBOLS:
@@ -577,6 +598,9 @@ READS_EXPORTED_SYMBOLS = [
 READS_PART_EXPORTED_SYMBOLS = ["kiss_hip_reads_parse_part_dev", "kiss_hip_reads_parse_part_host"]
 # every symbol include/kiss_hip_md.h declares (tests/test_fm_md_abi.py)
 MD_EXPORTED_SYMBOLS = ["kiss_hip_fmi_md_dev", "kiss_hip_fmi_md_host"]
+# every symbol include/kiss_hip_pileup.h declares (tests/test_fm_pileup_abi.py)
+PILEUP_EXPORTED_SYMBOLS = ["kiss_hip_fmi_pileup_dev", "kiss_hip_fmi_pileup_host"]
+PILEUP_PLANES = 8
 # every symbol include/kiss_hip_sam.h declares (tests/test_fm_sam_abi.py)
 SAM_EXPORTED_SYMBOLS = ["kiss_hip_fmi_sam_dev", "kiss_hip_fmi_sam_host"]
 # every symbol include/kiss_hip_insert.h declares (tests/test_fm_insert_abi.py)

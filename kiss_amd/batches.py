@@ -269,10 +269,15 @@ def map_file(index, reads1, text, reads2=None, batch_reads=100000, chunk_bytes=6
     whose result carries insert = dict(applied, ins_min, ins_max, ins_mean, from_batch=0), without report and histogram.
     sam=True (with ref_names where bounds is given): every batch also carries its alignment lines (sam, sam_line_index,
     sam_read_line, sam_report, as map(sam=True) gives them), with the names and the qualities of the parsed chunk -- FASTQ mate
-    names without their /1 and /2 --; the lines of the batches, one after the other, are the lines of the file."""
+    names without their /1 and /2 --; the lines of the batches, one after the other, are the lines of the file.
+    pileup=True (or a dict, or an (8, W) int32 device tensor to add to, as map(pileup=...) takes them): ONE tensor of counts,
+    allocated once, to which every batch adds (kiss_hip_fmi_pileup_dev with accumulate): its size depends on the text and not on
+    the file.  Every batch's result carries that tensor as pileup -- the sums up to and including the batch -- and
+    pileup_report, the sums of the report's fields so far; behind the last batch they are those of the file."""
     if "names" in params or "qual" in params:
         raise ValueError("map_file takes names and qualities from the file")
     sam, ref_names = bool(params.pop("sam", False)), params.pop("ref_names", None)
+    po = index._pileup_options({"pileup": params.pop("pileup", None)}, params.get("want_cigar", True))
     from .fm_pair import pair_params as make_pair_params
     from .fm_select import select_params as make_select_params
     d_text, n = index._text_dev(text)
@@ -289,13 +294,25 @@ def map_file(index, reads1, text, reads2=None, batch_reads=100000, chunk_bytes=6
             from .fm_insert import insert_params as make_insert_params
             ip = make_insert_params(**({} if insert is True or insert == "auto" else dict(insert)))
         make_pair_params(**pair_kw)  # (a wrong argument is said before a file is opened)
+    if po:
+        import torch
+        from .fm_pileup import add_reports, window
+        lo, hi = window(n, po["lo"] or 0, po["hi"])
+        dev = torch.device("cuda", index.device)
+        if po["counts"] is None:
+            po["counts"] = torch.zeros((8, hi - lo), dtype=torch.int32, device=dev)
+        elif not isinstance(po["counts"], torch.Tensor):
+            host = np.ascontiguousarray(po["counts"], dtype=np.uint32)
+            po["counts"] = torch.from_numpy(host.view(np.int32)).to(dev)
+        pileup_sums = {}
     carried = None
     lend = lambda nbytes: index._context(min(_lib.MAX_N, max(index.N, 4 * (nbytes + 2))))  # noqa: E731 (no second set of work arrays)
     for number, b in enumerate(read_batches(reads1, reads2, batch_reads, chunk_bytes, format, ctx=lend, device=index.device,
                                             hooks=index._hooks)):
         reads = (b["reads"], b["read_index"])
         if not paired:
-            res = index.map(reads, d_text, **params, **(dict(sam=True, names=b["names"], qual=b["qual"], ref_names=ref_names) if sam else {}))
+            res = index.map(reads, d_text, **params, **(dict(sam=True, names=b["names"], qual=b["qual"], ref_names=ref_names) if sam else {}),
+                            **(dict(pileup=dict(po["params"], lo=po["lo"], hi=po["hi"], counts=po["counts"])) if po else {}))
         else:
             if carried is not None:
                 pair_kw.update(ins_min=carried["ins_min"], ins_max=carried["ins_max"], ins_mean=carried["ins_mean"])
@@ -304,12 +321,14 @@ def map_file(index, reads1, text, reads2=None, batch_reads=100000, chunk_bytes=6
                                         p.get("rescue"), p.get("want_md", False), ip if carried is None else None,
                                         make_pair_params(**pair_kw),
                                         index._sam_options(dict(sam=True, names=b["names"], qual=b["qual"], ref_names=ref_names) if sam else {},
-                                                           p.get("want_cigar", True), p.get("bounds")))
+                                                           p.get("want_cigar", True), p.get("bounds")), po)
             if ip is not None:
                 if carried is None:
                     res["insert"]["from_batch"] = number
                     carried = {k: res["insert"][k] for k in ("applied", "ins_min", "ins_max", "ins_mean", "from_batch")}
                 else:
                     res["insert"] = dict(carried)
+        if po:
+            res["pileup_report"] = dict(add_reports(pileup_sums, res["pileup_report"]))
         res.update(names=b["names"], qual=b["qual"], first_read=b["first_read"])
         yield res

@@ -14,6 +14,7 @@
 
 #include "../../../include/kiss_hip.h"
 #include "../../../include/kiss_hip_insert.h"
+#include "../../../include/kiss_hip_pileup.h"
 
 namespace kiss_cli {
 
@@ -172,6 +173,25 @@ inline void usage_pairs()
               << "  --ins-auto-min-pairs NUM (=25) fewest such pairs for an estimate\n";
 }
 
+// The help of the pileup file (`kiss --help-pileup`): apart from usage() for the same reason.
+inline void usage_pileup()
+{
+    std::cerr << "The pileup of ./kiss fmindex_query --seeds READS [--mates READS2] --chain --align --sam:\n"
+              << "  --pileup FILE                  with --sam: what the mappings say at every position of the text, counted on the\n"
+              << "                                 device and summed over the batches of --batch-reads in one array of 32 bytes per\n"
+              << "                                 base of the text, which is allocated before a read is mapped.  FILE gets one line\n"
+              << "                                 per position that a read covers, deletes or inserts behind, tab-separated:\n"
+              << "                                 RNAME POS REF COV A C G T N DEL INS -- the record and the 1-based position in it,\n"
+              << "                                 the text's letter, the aligned read bases over it, those bases by letter (N: no\n"
+              << "                                 base), the reads that delete the position, the insertions directly behind it.\n"
+              << "                                 The depth in samtools' sense is COV + DEL.  Counted are the primary and the\n"
+              << "                                 supplementary lines of a read; with --mates the one line of either mate that the\n"
+              << "                                 pair chose, with the pair's MAPQ.  Mates that overlap are counted twice.  The SAM\n"
+              << "                                 on stdout is what it is without the option.\n"
+              << "  --pileup-min-mapq NUM (=0)     lowest MAPQ of a line that is counted (0..255)\n"
+              << "  --pileup-proper                with --mates: only the mates of proper pairs are counted\n";
+}
+
 inline void check(int rc, const char *where)
 {
     if (rc != KISS_HIP_OK) throw std::runtime_error(std::string(where) + ": " + kiss_hip_strerror(rc));
@@ -258,6 +278,9 @@ struct Args {
     size_t batch_reads = 0;          // fmindex_query ... --sam --batch-reads N (0: the whole file as one batch)
     size_t batch_chunk = 64u << 20;  // --batch-chunk BYTES
     std::string sam_writer = "host"; // fmindex_query ... --sam --sam-writer host|device
+    std::string pileup;              // fmindex_query ... --sam --pileup FILE
+    kiss_hip_pileup_params pileup_params{0, KISS_HIP_HIT_SECONDARY, 0, 0};
+    bool pileup_proper = false;      // --pileup-proper
 };
 
 inline bool given(const Args &a, const char *name) { return std::find(a.seen.begin(), a.seen.end(), name) != a.seen.end(); }
@@ -333,6 +356,9 @@ inline const Opt OPTIONS[] = {
     {"--batch-reads", nullptr, KISS_AT(batch_reads), true, {"--sam"}},
     {"--batch-chunk", nullptr, KISS_AT(batch_chunk), true, {"--batch-reads"}},
     {"--sam-writer", nullptr, KISS_AT(sam_writer), true, {"--sam"}},
+    {"--pileup", nullptr, KISS_AT(pileup), true, {"--sam"}},
+    {"--pileup-min-mapq", nullptr, KISS_AT(pileup_params.min_mapq), true, {"--pileup"}},
+    {"--pileup-proper", nullptr, KISS_AT(pileup_proper), true, {"--pileup", "--mates"}},
 };
 #undef KISS_AT
 
@@ -347,6 +373,7 @@ inline Args parse(int argc, char **argv)
         if (s == "--help-reads") { usage_reads(); std::exit(1); }
         if (s == "--help-sam") { usage_sam(); std::exit(1); }
         if (s == "--help-pairs") { usage_pairs(); std::exit(1); }
+        if (s == "--help-pileup") { usage_pileup(); std::exit(1); }
         const Opt *o = std::find_if(std::begin(OPTIONS), std::end(OPTIONS), [&](const Opt &x) { return s == x.name || (x.alias && s == x.alias); });
         if (o == std::end(OPTIONS)) {
             if (!s.empty() && s[0] == '-' && s.size() > 1) throw std::runtime_error("unrecognised option '" + s + "'");
@@ -402,6 +429,9 @@ inline Args parse(int argc, char **argv)
     if (a.batch_chunk < 1 || a.batch_chunk > (1ull << 30)) throw std::runtime_error("--batch-chunk is in 1..1073741824");
     goes_with_through("--sam-writer");
     if (a.sam_writer != "host" && a.sam_writer != "device") throw std::runtime_error("--sam-writer is one of host, device (kiss --help-sam)");
+    goes_with_through("--pileup-proper");
+    if (a.pileup_params.min_mapq > 255u) throw std::runtime_error("--pileup-min-mapq is at most 255 (kiss --help-pileup)");
+    a.pileup_params.proper_only = a.pileup_proper ? 1u : 0u;
     if (given(a, "--mates")) { // the pair's MAPQ is on the scale of the reads'; the mates face each other
         a.both_strands = true;
         a.pair_params.mapq_coef = a.select_params.mapq_coef;

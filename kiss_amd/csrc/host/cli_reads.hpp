@@ -6,6 +6,7 @@
 #include "cli_common.hpp"
 #include "cli_format.hpp"
 #include "cli_batches.hpp"
+#include "cli_pileup.hpp"
 #include "../../../include/kiss_hip_reads.h"
 #include "../../../include/kiss_hip_md.h"
 #include "../../../include/kiss_hip_insert.h"
@@ -342,6 +343,62 @@ inline void sam_lines_device(StdoutWriter &w, const Args &a, const State &s, boo
     std::fwrite(sam.data(), 1, rep.sam_bytes, stdout);
 }
 
+// --pileup FILE: ONE device array of 8 planes of n u32 (32 n bytes) to which every batch adds -- kiss_hip_fmi_pileup_host with
+// counts_on_device, accumulate from the second call on --, fetched once behind the last batch and written as lines
+// (cli_pileup.hpp).  The array is allocated and FILE opened before a read is mapped.
+struct PileupSums {
+    std::string path;
+    std::FILE *file = nullptr;
+    uint32_t *d = nullptr;
+    uint64_t n = 0, calls = 0;
+    kiss_hip_pileup_report total{};
+    PileupSums() = default;
+    PileupSums(const PileupSums &) = delete;
+    PileupSums &operator=(const PileupSums &) = delete;
+    ~PileupSums()
+    {
+        if (d) kiss_hip_free_dev(d);
+        if (file) std::fclose(file);
+    }
+    bool on() const { return file != nullptr; }
+    // (behind load_text: its context has made a.device the current one)
+    void open(const Args &a, uint64_t bases)
+    {
+        path = a.pileup, n = bases;
+        void *p = nullptr;
+        if (n && kiss_hip_alloc_dev(&p, 32 * n) != KISS_HIP_OK)
+            throw std::runtime_error("fmindex_query --pileup: cannot allocate the " + std::to_string(32 * n) + " bytes of the counts on the device (32 per base of the text)");
+        d = static_cast<uint32_t *>(p);
+        file = std::fopen(path.c_str(), "wb");
+        if (!file) throw std::runtime_error("cannot open " + path);
+    }
+    // the hits of the last select call (paired: the pairs of the last pair call) added
+    void add(const Args &a, const State &s, bool paired)
+    {
+        kiss_hip_pileup_report rep{};
+        check(kiss_hip_fmi_pileup_host(s.S.data(), s.S.size(), s.rd.reads.data(), s.rd.ridx.data(), s.Q, a.both_strands, s.al.alns.data(),
+                                       s.ch.cidx.data(), s.al.cigar.data(), s.al.oidx.data(), s.hits.data(), s.select_rep.hits,
+                                       paired ? s.pairs.data() : nullptr, paired ? s.Q / 2 : 0, &a.pileup_params, 0, n, d, 1, calls ? 1 : 0, &rep,
+                                       a.device),
+              "kiss_hip_fmi_pileup_host");
+        calls++;
+        total.items += rep.items, total.bad += rep.bad, total.filtered += rep.filtered, total.unmapped += rep.unmapped, total.counted += rep.counted;
+        total.columns += rep.columns, total.alt_columns += rep.alt_columns, total.deleted_bases += rep.deleted_bases;
+        total.insertions += rep.insertions, total.clipped += rep.clipped;
+    }
+    // the sums fetched once and written; S and ref: the text and its records
+    void write(const std::vector<uint8_t> &S, const RefRecords &ref)
+    {
+        std::vector<uint32_t> planes(8 * n + 1, 0);
+        if (n && calls) check(kiss_hip_copy_to_host(planes.data(), d, 32 * n), "kiss_hip_copy_to_host");
+        write_pileup(file, path, planes.data(), n, S.data(), ref.names, ref.bounds);
+        std::fprintf(stderr, "[info] pileup: items: %llu, counted: %llu, filtered: %llu, unmapped: %llu, bad: %llu, columns: %llu, differing: %llu, "
+                             "deleted bases: %llu, insertions: %llu\n",
+                     (ull)total.items, (ull)total.counted, (ull)total.filtered, (ull)total.unmapped, (ull)total.bad, (ull)total.columns,
+                     (ull)total.alt_columns, (ull)total.deleted_bases, (ull)total.insertions);
+    }
+};
+
 // --batch-reads N: the text and the records of the reference loaded once, the header printed once; then every batch of N reads,
 // or of N pairs, cut from the files by a ChunkReader, gives a State, the stages above and its lines.  The stages are the _host
 // entries: each uploads the index or the text once more per batch (DESIGN.md 4.20 says what that costs).  --ins-auto: estimated
@@ -366,6 +423,8 @@ inline int map_reads_in_batches(const Args &a, const kiss_hip_fmi_view_ex &index
     State keep; // the text and the records pass from batch to batch
     load_text(a, keep);
     load_records(a, keep);
+    PileupSums pile;
+    if (!a.pileup.empty()) pile.open(a, keep.S.size());
     kiss_hip_pair_params pair_params{};
     kiss_hip_rescue_params rescue_params{};
     StdoutWriter w;
@@ -404,6 +463,7 @@ inline int map_reads_in_batches(const Args &a, const kiss_hip_fmi_view_ex &index
         if (a.rescue) rescue_mates(a, s);
         if (paired) pair_mates(a, s);
         if (a.md) md_tags(a, s);
+        if (pile.on()) pile.add(a, s, paired);
         if (!batches) sam_header(w.out, s.ref, VERSION);
         if (a.sam_writer == "device") sam_lines_device(w, a, s, paired);
         else sam_lines(w, s, paired);
@@ -414,6 +474,7 @@ inline int map_reads_in_batches(const Args &a, const kiss_hip_fmi_view_ex &index
         keep.ref = std::move(s.ref);
     }
     if (!batches) sam_header(w.out, keep.ref, VERSION), w.finish();
+    if (pile.on()) pile.write(keep.S, keep.ref);
     std::fprintf(stderr, "[info] batches: %llu, reads: %llu, mapped: %llu\n", (ull)batches, (ull)reads, (ull)mapped);
     return 0;
 }
@@ -424,24 +485,32 @@ inline int map_reads(const Args &a, const kiss_hip_fmi_view_ex &index)
     if (a.batch_reads) return map_reads_in_batches(a, index);
     State s;
     s.index = index;
+    PileupSums pile;
+    if (!a.pileup.empty()) load_text(a, s), pile.open(a, s.S.size()); // (before a read is mapped)
     load_reads(a, s);
     find_seeds(a, s);
     if (!a.chain) return print_seeds(s, a.both_strands);
     chain_seeds(a, s);
     if (!a.align) return print_chains(s, a.both_strands);
-    align_chains(a, s);
+    if (pile.on()) align(a, s, a.both_strands, s.ch, s.ch.cidx[s.V], s.al, "--align");
+    else align_chains(a, s);
     if (!a.sam) return print_alignments(s, a.both_strands);
     select_hits(a, s);
     if (!a.mates.empty()) insert_size(a, s);
     if (a.rescue) rescue_mates(a, s);
     if (!a.mates.empty()) pair_mates(a, s);
     if (a.md) md_tags(a, s);
-    if (a.sam_writer != "device") return print_sam(s, !a.mates.empty(), a.rescue, VERSION);
-    StdoutWriter w;
-    sam_header(w.out, s.ref, VERSION);
-    sam_lines_device(w, a, s, !a.mates.empty());
-    w.finish();
-    sam_info(s, !a.mates.empty(), a.rescue);
+    if (pile.on()) pile.add(a, s, !a.mates.empty());
+    if (a.sam_writer != "device") {
+        print_sam(s, !a.mates.empty(), a.rescue, VERSION);
+    } else {
+        StdoutWriter w;
+        sam_header(w.out, s.ref, VERSION);
+        sam_lines_device(w, a, s, !a.mates.empty());
+        w.finish();
+        sam_info(s, !a.mates.empty(), a.rescue);
+    }
+    if (pile.on()) pile.write(s.S, s.ref);
     return 0;
 }
 

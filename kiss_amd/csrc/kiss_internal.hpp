@@ -183,6 +183,8 @@ enum FmSlot {
     FM_SLOT_SAM_CTL,
     FM_SLOT_SAM_READS,   // per read: its lines, scanned
     FM_SLOT_SAM_LINES,   // per line: its bytes, scanned
+    // kiss_hip_fmi_pileup_dev (fm_pileup.hip)
+    FM_SLOT_PILEUP_CTL,
     FM_SLOT_COUNT
 };
 

@@ -676,9 +676,15 @@ class FMIndex:
         sam_line_index (lines + 1), sam_read_line (Q + 1: the first line of every read) and sam_report; with want_md the lines
         carry MD:Z:.  names: the QNAMEs, a list of str or bytes or the (raw, name_off, name_len) triple of parse_reads; None: the
         decimal read number.  qual: the quality bytes, a list with one entry per read or one array under the index of the reads;
-        None prints '*'.  ref_names: the names of the R records, needed when bounds is given; without either RNAME is '*'."""
+        None prints '*'.  ref_names: the names of the R records, needed when bounds is given; without either RNAME is '*'.
+        pileup (None; it needs want_cigar): True, a dict of lo, hi, counts and the pileup parameters min_mapq (0), skip_flags (2:
+        secondary hits) and proper_only (0), or an (8, W) int32 device tensor to add to (the dict's counts: such a tensor, or an
+        (8, W) u32 array): also pileup -- the eight planes of kiss_amd.fm_pileup.PLANES over the text positions [lo, hi), default
+        the whole text, counted from the hits by kiss_hip_fmi_pileup_dev (include/kiss_hip_pileup.h) from the buffers that are
+        still on the device; a u32 array, or the tensor that was given, now holding the sums -- and pileup_report."""
         from .fm_select import select_arrays, select_params as make_select_params
         so = self._sam_options(select_params, want_cigar, bounds)
+        po = self._pileup_options(select_params, want_cigar)
         sp = make_select_params(**select_params)
         self._md_needs_ops(want_md, want_cigar)
         res, t = self._align_dev(reads, text, min_len, max_len, max_occ, both_strands, chain_params, want_cigar,
@@ -689,6 +695,8 @@ class FMIndex:
             res.update(self._md_of_hits(t, ctx, t.d_alns, t.d_cidx, t.C, t.al["d_cigar"], t.al["d_oidx"], both_strands, sel, so))
         if so:
             res.update(self._sam_lines(t, ctx, t.d_alns, t.C, t.al["d_cigar"], t.al["d_oidx"], sel, so))
+        if po:
+            res.update(self._pileup_counts(t, ctx, t.d_alns, t.d_cidx, t.al["d_cigar"], t.al["d_oidx"], both_strands, sel, po))
         return res
 
     @staticmethod
@@ -713,6 +721,40 @@ class FMIndex:
         if so:
             so["md"] = out
         return md_arrays(out)
+
+    @staticmethod
+    def _pileup_options(given, want_cigar):
+        """map(pileup=...): takes pileup out of the keywords `given` -> None without it, else lo, hi, counts and the parameters,
+        held against their limits before anything runs"""
+        from .fm_pileup import WINDOW_KEYS, pileup_params
+        what = given.pop("pileup", None)
+        if what is None or what is False:
+            return None
+        if not want_cigar:
+            raise ValueError("pileup needs the ops: want_cigar=True")
+        opts = dict(what) if isinstance(what, dict) else ({} if what is True else {"counts": what})
+        po = {k: opts.pop(k, None) for k in WINDOW_KEYS}
+        pileup_params(**opts)
+        po["params"] = opts
+        return po
+
+    def _pileup_counts(self, t, ctx, d_alns, d_cidx, d_cigar, d_oidx, both_strands, sel, po, out=None):
+        """map(pileup=...): the counts of the hits of a select call (out: and the pairs of a pair call), from the buffers that are
+        on the device"""
+        from .fm_pileup import pileup_dev, planes_of, window
+        torch = _torch()
+        lo, hi = window(t.n, po["lo"] or 0, po["hi"])
+        counts = po["counts"]
+        on_device = isinstance(counts, torch.Tensor)
+        if counts is not None and not on_device:
+            host = np.ascontiguousarray(counts, dtype=np.uint32)
+            if host.shape != (8, hi - lo):
+                raise ValueError("the counts of a pileup have the shape (8, %d)" % (hi - lo))
+            counts = torch.from_numpy(host.view(np.int32)).to(torch.device("cuda", self.device))
+        got = pileup_dev(t.lib, ctx, self.device, t.d_text, t.n, t.d_reads, t.d_ridx, t.Q, both_strands, d_alns, d_cidx, d_cigar, d_oidx,
+                         sel["d_hits"], int(sel["rep"].hits), out["d_pairs"] if out else None, int(out["rep"].P) if out else 0, lo, hi,
+                         counts, **po["params"])
+        return {"pileup": got["d_counts"] if on_device else planes_of(got["d_counts"]), "pileup_report": got["rep"].as_dict()}
 
     @staticmethod
     def _sam_options(given, want_cigar, bounds):
@@ -825,10 +867,12 @@ class FMIndex:
         Further keywords: sam (False; it needs want_cigar): also sam, sam_line_index, sam_read_line and sam_report as in map(), the paired lines of the
         interleaved batch; with rescue they come from the second pass and YR:i:1 follows aln_source.  names: one per pair (both
         mates carry it) or one per read of the interleaved batch; None: the decimal pair number.  qual: (qual1, qual2), each one
-        entry per read of its file; ref_names as in map()."""
+        entry per read of its file; ref_names as in map().  pileup as in map(), counted from the pairs (the chosen hit of every
+        mate with the pair's MAPQ; proper_only: proper pairs alone); with rescue from the second pass's records and pairs."""
         from .fm_pair import pair_arrays, pair_dev, pair_params as make_pair_params
         from .fm_select import select_arrays, select_params as make_select_params
         so = self._sam_options(pair_params, want_cigar, bounds)
+        po = self._pileup_options(pair_params, want_cigar)
         pp = make_pair_params(**pair_params)
         sp = make_select_params(**(select_params or {}))
         self._md_needs_ops(want_md, want_cigar)
@@ -846,10 +890,10 @@ class FMIndex:
                 raise ValueError("qual is (qual1, qual2), each with one entry per read of its file")
             so["qual"] = [x for pair in zip(qual[0], qual[1]) for x in pair]
         return self._map_pair_batch(batch, text, min_len, max_len, max_occ, chain_params, align_params, sp, bounds, want_cigar, rescue,
-                                    want_md, ip, pp, so)
+                                    want_md, ip, pp, so, po)
 
     def _map_pair_batch(self, batch, text, min_len, max_len, max_occ, chain_params, align_params, sp, bounds, want_cigar, rescue, want_md,
-                        ip, pp, so=None):
+                        ip, pp, so=None, po=None):
         """map_pairs() behind its arguments: batch holds the mates interleaved (reads 2 p and 2 p + 1), in either form"""
         from .fm_pair import pair_arrays, pair_dev
         from .fm_select import select_arrays
@@ -865,8 +909,10 @@ class FMIndex:
                 res.update(self._md_of_hits(t, ctx, t.d_alns, t.d_cidx, t.C, t.al["d_cigar"], t.al["d_oidx"], True, sel, so))
             if so:
                 res.update(self._sam_lines(t, ctx, t.d_alns, t.C, t.al["d_cigar"], t.al["d_oidx"], sel, so, out["d_pairs"]))
+            if po:
+                res.update(self._pileup_counts(t, ctx, t.d_alns, t.d_cidx, t.al["d_cigar"], t.al["d_oidx"], True, sel, po, out))
             return res
-        return self._rescue_pass(res, t, ctx, sel, out, sp, pp, bounds, want_cigar, {} if rescue is True else dict(rescue), want_md, so)
+        return self._rescue_pass(res, t, ctx, sel, out, sp, pp, bounds, want_cigar, {} if rescue is True else dict(rescue), want_md, so, po)
 
     def _insert_estimate(self, res, t, ctx, sel, pp, ip):
         """map_pairs(insert=...): the estimate from the hits of the first select call -> the pair parameters to use"""
@@ -880,7 +926,7 @@ class FMIndex:
                              ins_mean=int(pp.ins_mean))
         return pp
 
-    def _rescue_pass(self, res, t, ctx, sel, out, sp, pp, bounds, want_cigar, rescue, want_md=False, so=None):
+    def _rescue_pass(self, res, t, ctx, sel, out, sp, pp, bounds, want_cigar, rescue, want_md=False, so=None, po=None):
         """map_pairs(rescue=...): plan, the rescue align call, merge, and select and pair again (res: the first pass's result)"""
         from .fm_align import align_arrays, align_dev
         from .fm_pair import PAIR_PROPER, pair_arrays, pair_dev
@@ -915,6 +961,8 @@ class FMIndex:
             res.update(self._md_of_hits(t, ctx, mg["d_alns"], mg["d_cidx"], C, mg["d_cigar"], mg["d_oidx"], True, sel2, so))
         if so:
             res.update(self._sam_lines(t, ctx, mg["d_alns"], C, mg["d_cigar"], mg["d_oidx"], sel2, so, out2["d_pairs"], mg["d_source"], CA))
+        if po:
+            res.update(self._pileup_counts(t, ctx, mg["d_alns"], mg["d_cidx"], mg["d_cigar"], mg["d_oidx"], True, sel2, po, out2))
         proper1 = (first["pairs"]["flags"] & PAIR_PROPER) != 0
         proper2 = (res["pairs"]["flags"] & PAIR_PROPER) != 0
         plan.update(align_report=align_arrays(al2, False)["align_report"], merge_report=mg["rep"].as_dict(),
