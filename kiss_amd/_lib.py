@@ -277,6 +277,18 @@ class SamReport(Report):
     ]
 
 
+class BamReport(Report):
+    """kiss_hip_bam_report (include/kiss_hip_bam.h)"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("records", "bam_bytes", "unmapped_records", "longest", "bad", "first_bad")] + [
+        ("ms_total", ctypes.c_float), ("ms_count", ctypes.c_float), ("ms_emit", ctypes.c_float), ("reserved_", ctypes.c_uint32),
+    ]
+
+
+class BgzfReport(Report):
+    """kiss_hip_bgzf_report (include/kiss_hip_bam.h)"""
+    _fields_ = [("blocks", ctypes.c_uint64), ("out_bytes", ctypes.c_uint64), ("ms_total", ctypes.c_float), ("reserved_", ctypes.c_uint32)]
+
+
 class MdReport(Report):
     """kiss_hip_md_report (include/kiss_hip_md.h)"""
     _fields_ = [(k, ctypes.c_uint64) for k in ("items", "bad", "md_bytes", "mismatch_columns", "deleted_bases", "longest")] + [
@@ -505,6 +517,13 @@ def load(hooks=None):
     lib.kiss_hip_fmi_sam_host.argtypes = [ctypes.POINTER(SamInput), vp, u64, vp, u64, vp, ctypes.POINTER(SamReport), ctypes.c_int]
     for name in SAM_EXPORTED_SYMBOLS:
         getattr(lib, name).restype = ctypes.c_int
+    if hasattr(lib, "kiss_hip_fmi_bam_dev"):  # (as the pileup call: an older library under KISS_AMD_LIB_PATH has none)
+        lib.kiss_hip_fmi_bam_dev.argtypes = [vp, ctypes.POINTER(SamInput), vp, u64, vp, u64, vp, ctypes.POINTER(BamReport), vp]
+        lib.kiss_hip_fmi_bam_host.argtypes = [ctypes.POINTER(SamInput), vp, u64, vp, u64, vp, ctypes.POINTER(BamReport), ctypes.c_int]
+        lib.kiss_hip_bgzf_dev.argtypes = [vp, vp, u64, u32, ctypes.c_int, vp, u64, ctypes.POINTER(BgzfReport), vp]
+        lib.kiss_hip_bgzf_host.argtypes = [vp, u64, u32, ctypes.c_int, vp, u64, ctypes.POINTER(BgzfReport), ctypes.c_int]
+        for name in BAM_EXPORTED_SYMBOLS:
+            getattr(lib, name).restype = ctypes.c_int
     lib.kiss_hip_fmi_insert_dev.argtypes = [vp, vp, vp, u64, vp, u64, ctypes.POINTER(InsertParams), vp, ctypes.POINTER(InsertReport), vp]
     lib.kiss_hip_fmi_insert_host.argtypes = [vp, vp, u64, vp, u64, ctypes.POINTER(InsertParams), vp, ctypes.POINTER(InsertReport),
                                              ctypes.c_int]
@@ -603,6 +622,9 @@ PILEUP_EXPORTED_SYMBOLS = ["kiss_hip_fmi_pileup_dev", "kiss_hip_fmi_pileup_host"
 PILEUP_PLANES = 8
 # every symbol include/kiss_hip_sam.h declares (tests/test_fm_sam_abi.py)
 SAM_EXPORTED_SYMBOLS = ["kiss_hip_fmi_sam_dev", "kiss_hip_fmi_sam_host"]
+# every symbol include/kiss_hip_bam.h declares (tests/test_fm_bam_abi.py)
+BAM_EXPORTED_SYMBOLS = ["kiss_hip_fmi_bam_dev", "kiss_hip_fmi_bam_host", "kiss_hip_bgzf_dev", "kiss_hip_bgzf_host"]
+BGZF_BLOCK_DEFAULT, BGZF_BLOCK_MAX, BGZF_OVERHEAD, BGZF_EOF_BYTES = 65280, 65505, 31, 28
 # every symbol include/kiss_hip_insert.h declares (tests/test_fm_insert_abi.py)
 INSERT_EXPORTED_SYMBOLS = ["kiss_hip_fmi_insert_dev", "kiss_hip_fmi_insert_host"]
 INSERT_MAX = 65535

@@ -1,0 +1,173 @@
+"""BAM output written on the device (include/kiss_hip_bam.h has the definition): the alignment records of a batch
+(kiss_hip_fmi_bam_dev / _host) from the arrays the SAM lines are written from, and the BGZF framing of any bytes in stored blocks
+with the CRC-32 of every block computed on the device (kiss_hip_bgzf_dev / _host).  bam_records() and bgzf() take numpy arrays
+and run the host entries; FMIndex.map(bam=True), map_pairs(bam=True) and map_file(bam=True) keep everything on the device
+(bam_records_dev, then bgzf_dev, no round trip between them); write_bam() writes a whole file.  The blocks are not compressed:
+`samtools sort` and every other BAM reader take them as they are.  All arithmetic runs in libkiss_hip.so; there is no CPU path."""
+import ctypes
+import struct
+
+import numpy as np
+
+from . import _lib
+from ._frame import sized
+from .fm_sam import _bytes, sam_header
+from .sam_writer import _host_input, sam_input
+from .sorter import _check
+
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+
+
+def bam_header(ref_names, bounds, version):
+    """the BAM header, unframed: the magic, the text of sam_header, and the records with their lengths bounds[r + 1] - bounds[r]"""
+    text = sam_header(ref_names, bounds, version)
+    text = text if isinstance(text, bytes) else str(text).encode()
+    names = [_bytes(x) for x in ref_names]
+    b = np.ascontiguousarray(bounds, dtype=np.uint64).ravel()
+    if b.size != len(names) + 1:
+        raise ValueError("bounds has R + 1 = %d entries" % (len(names) + 1))
+    out = [b"BAM\1", struct.pack("<i", len(text)), text, struct.pack("<i", len(names))]
+    for r, nm in enumerate(names):
+        l_ref = int(b[r + 1]) - int(b[r])
+        if l_ref < 0 or l_ref >= 1 << 31:
+            raise ValueError("record %d has %d bases: a BAM header holds fewer than 2^31" % (r, l_ref))
+        out += [struct.pack("<i", len(nm) + 1), nm, b"\0", struct.pack("<i", l_ref)]
+    return b"".join(out)
+
+
+def _refuse_bad(rc, rep, entry):
+    if rc == _lib.KISS_HIP_E_INVALID and rep.bad:
+        err = _lib.KissHipError(rc, entry, "%d bad read(s), the first one read %d" % (rep.bad, rep.first_bad))
+        err.report = rep.as_dict()
+        raise err
+
+
+def bam_records(reads, read_index, names, alns, cigar, cigar_index, hits, hit_index, qual=None, pairs=None, source=None, first_alns=0, md=None,
+                md_index=None, ref_names=None, bounds=None, device=0, hooks=None):
+    """The BAM records of a batch given as arrays (numpy in, numpy out), through the host entry; the arguments are those of
+    sam_writer.sam_lines, and ref_names with bounds is required.  Returns dict(bam: the records as uint8, rec_index, read_rec,
+    report).  A batch with a bad read (see the header) raises KissHipError; its report is the exception's `report`."""
+    inp, Q, hold = _host_input(reads, read_index, names, alns, cigar, cigar_index, hits, hit_index, qual, pairs, source, first_alns, md, md_index,
+                               ref_names, bounds)
+    lib = _lib.load(hooks)
+    rep = _lib.BamReport()
+    rr = np.zeros(Q + 1, np.uint64)
+
+    def call(bam, cap, ri, rcap):
+        return lib.kiss_hip_fmi_bam_host(ctypes.byref(inp), bam.ctypes.data, cap, ri.ctypes.data, rcap, rr.ctypes.data, ctypes.byref(rep), int(device))
+
+    rc, (bam, _, ri, _) = sized(call, lambda m=0, recs=0: (np.zeros(max(m, 1), np.uint8), m, np.zeros(recs + 1, np.uint64), recs), rep,
+                               "bam_bytes", "records")
+    del hold
+    _refuse_bad(rc, rep, "kiss_hip_fmi_bam_host")
+    _check(rc, "kiss_hip_fmi_bam_host")
+    return {"bam": bam[:int(rep.bam_bytes)], "rec_index": ri, "read_rec": rr, "report": rep.as_dict()}
+
+
+def bam_records_dev(lib, ctx, device, Q, C, R, first_alns=0, want_rec_index=True, stream=None, **tensors):
+    """the device entry on torch tensors -> dict of torch tensors (d_bam, d_rec_index, d_read_rec) and the report; two calls, the
+    first one sizes the bytes and the records.  tensors: the arrays of kiss_hip_sam_input by their names (None: NULL).  stream:
+    None, the current stream of torch"""
+    import torch
+    dev = torch.device("cuda", device)
+    vp = ctypes.c_void_p
+    rep = _lib.BamReport()
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    inp = sam_input({k: (None if t is None else t.data_ptr()) for k, t in tensors.items()}, Q, C, R, first_alns)
+    d_rr = torch.zeros(Q + 1, dtype=torch.int64, device=dev)
+
+    def call(d_bam, cap, d_ri, rcap):
+        return lib.kiss_hip_fmi_bam_dev(ctx._ctx, ctypes.byref(inp), vp(d_bam.data_ptr()), cap, vp(d_ri.data_ptr()) if d_ri is not None else None,
+                                        rcap, vp(d_rr.data_ptr()), ctypes.byref(rep), vp(stream) if stream else None)
+
+    def room(m=0, recs=0):
+        return (torch.zeros(max(m, 1), dtype=torch.uint8, device=dev), m,
+                torch.zeros(recs + 1, dtype=torch.int64, device=dev) if want_rec_index else None, recs)
+
+    rc, (d_bam, _, d_ri, _) = sized(call, room, rep, "bam_bytes", "records")
+    _refuse_bad(rc, rep, "kiss_hip_fmi_bam_dev")
+    _check(rc, "kiss_hip_fmi_bam_dev", ctx._ctx)
+    return {"d_bam": d_bam, "d_rec_index": d_ri, "d_read_rec": d_rr, "rep": rep, "keep": tensors}
+
+
+def _block_bytes(block_bytes):
+    bb = int(block_bytes)
+    if not 0 <= bb <= _lib.BGZF_BLOCK_MAX:
+        raise ValueError("block_bytes is 1 .. %d (0: %d)" % (_lib.BGZF_BLOCK_MAX, _lib.BGZF_BLOCK_DEFAULT))
+    return bb
+
+
+def bgzf_bytes(n, block_bytes=65280, eof=False):
+    """the bytes bgzf() makes of n"""
+    bb = _block_bytes(block_bytes) or _lib.BGZF_BLOCK_DEFAULT
+    return n + _lib.BGZF_OVERHEAD * (-(-n // bb)) + (_lib.BGZF_EOF_BYTES if eof else 0)
+
+
+def bgzf(data, block_bytes=65280, eof=False, device=0, hooks=None, want_report=False):
+    """data (bytes or a uint8 array) cut into BGZF blocks of block_bytes payload bytes, stored, each with its CRC-32, through the host
+    entry -> bytes (want_report: and the report); eof: the end-of-file block behind them"""
+    raw = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8).ravel()
+    bb = _block_bytes(block_bytes)
+    out = np.zeros(max(bgzf_bytes(raw.size, bb, eof), 1), np.uint8)
+    rep = _lib.BgzfReport()
+    rc = _lib.load(hooks).kiss_hip_bgzf_host(raw.ctypes.data if raw.size else None, raw.size, bb, int(bool(eof)), out.ctypes.data, out.size,
+                                            ctypes.byref(rep), int(device))
+    _check(rc, "kiss_hip_bgzf_host")
+    got = out[:int(rep.out_bytes)].tobytes()
+    return (got, rep.as_dict()) if want_report else got
+
+
+def bgzf_dev(lib, ctx, device, d_data, n, block_bytes=65280, eof=False, stream=None):
+    """the device entry: the first n bytes of the uint8 tensor d_data -> (a uint8 tensor of exactly the blocks, the report)"""
+    import torch
+    dev = torch.device("cuda", device)
+    vp = ctypes.c_void_p
+    bb = _block_bytes(block_bytes)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    total = bgzf_bytes(int(n), bb, eof)
+    d_out = torch.zeros(max(total, 1), dtype=torch.uint8, device=dev)
+    rep = _lib.BgzfReport()
+    rc = lib.kiss_hip_bgzf_dev(ctx._ctx, vp(d_data.data_ptr()) if n else None, int(n), bb, int(bool(eof)), vp(d_out.data_ptr()), total,
+                               ctypes.byref(rep), vp(stream) if stream else None)
+    _check(rc, "kiss_hip_bgzf_dev", ctx._ctx)
+    return d_out[:int(rep.out_bytes)], rep
+
+
+def bam_arrays(lib, ctx, device, out, block_bytes=65280):
+    """the tensors of bam_records_dev framed on the device, as what map(bam=True) adds to its result"""
+    total = int(out["rep"].bam_bytes)
+    d_blocks, frep = bgzf_dev(lib, ctx, device, out["d_bam"], total, block_bytes)
+    ri = out["d_rec_index"]
+    rep = out["rep"].as_dict()
+    rep.update(blocks=int(frep.blocks), out_bytes=int(frep.out_bytes), ms_frame=float(frep.ms_total))
+    return {"bam": d_blocks.cpu().numpy().tobytes(), "bam_rec_index": None if ri is None else ri.cpu().numpy().view(np.uint64),
+            "bam_read_rec": out["d_read_rec"].cpu().numpy().view(np.uint64), "bam_report": rep}
+
+
+def write_bam(path, index, reads1, text, reads2=None, ref_names=None, bounds=None, version=None, **params):
+    """A whole BAM file of the read file(s) mapped by `index` (batches.map_file, which has the other arguments): the framed header,
+    the blocks of every batch, the end-of-file block.  path: a file name, or a binary file object.  -> the batches, records and bytes
+    written"""
+    from .batches import map_file
+    if ref_names is None or bounds is None:
+        raise ValueError("a BAM file needs ref_names and bounds")
+    if version is None:  # (@PG VN: the library's version number, as kiss_hip_version() gives it)
+        version = str(_lib.load(index._hooks).kiss_hip_version())
+    head = bgzf(bam_header(ref_names, bounds, version), device=index.device, hooks=index._hooks)
+    f = open(path, "wb") if isinstance(path, (str, bytes)) or hasattr(path, "__fspath__") else path
+    done = {"batches": 0, "records": 0, "bytes": len(head)}
+    try:
+        f.write(head)
+        for res in map_file(index, reads1, text, reads2, bam=True, ref_names=ref_names, bounds=bounds, **params):
+            f.write(res["bam"])
+            done["batches"] += 1
+            done["records"] += int(res["bam_report"]["records"])
+            done["bytes"] += len(res["bam"])
+        f.write(BGZF_EOF)
+        done["bytes"] += len(BGZF_EOF)
+    finally:
+        if f is not path:
+            f.close()
+    return done

@@ -270,13 +270,17 @@ def map_file(index, reads1, text, reads2=None, batch_reads=100000, chunk_bytes=6
     sam=True (with ref_names where bounds is given): every batch also carries its alignment lines (sam, sam_line_index,
     sam_read_line, sam_report, as map(sam=True) gives them), with the names and the qualities of the parsed chunk -- FASTQ mate
     names without their /1 and /2 --; the lines of the batches, one after the other, are the lines of the file.
+    bam=True (with ref_names and bounds; it may stand beside sam=True): every batch also carries bam, the BGZF blocks of its BAM
+    records (bam_rec_index, bam_read_rec, bam_report, as map(bam=True) gives them); the blocks of the batches, one after the other
+    behind the framed header and in front of the end-of-file block, are the file (kiss_amd.bam_writer.write_bam does that).
     pileup=True (or a dict, or an (8, W) int32 device tensor to add to, as map(pileup=...) takes them): ONE tensor of counts,
     allocated once, to which every batch adds (kiss_hip_fmi_pileup_dev with accumulate): its size depends on the text and not on
     the file.  Every batch's result carries that tensor as pileup -- the sums up to and including the batch -- and
     pileup_report, the sums of the report's fields so far; behind the last batch they are those of the file."""
     if "names" in params or "qual" in params:
         raise ValueError("map_file takes names and qualities from the file")
-    sam, ref_names = bool(params.pop("sam", False)), params.pop("ref_names", None)
+    sam, bam, ref_names = bool(params.pop("sam", False)), bool(params.pop("bam", False)), params.pop("ref_names", None)
+    lines = lambda b: dict(sam=sam, bam=bam, names=b["names"], qual=b["qual"], ref_names=ref_names) if sam or bam else {}  # noqa: E731
     po = index._pileup_options({"pileup": params.pop("pileup", None)}, params.get("want_cigar", True))
     from .fm_pair import pair_params as make_pair_params
     from .fm_select import select_params as make_select_params
@@ -311,7 +315,7 @@ def map_file(index, reads1, text, reads2=None, batch_reads=100000, chunk_bytes=6
                                             hooks=index._hooks)):
         reads = (b["reads"], b["read_index"])
         if not paired:
-            res = index.map(reads, d_text, **params, **(dict(sam=True, names=b["names"], qual=b["qual"], ref_names=ref_names) if sam else {}),
+            res = index.map(reads, d_text, **params, **lines(b),
                             **(dict(pileup=dict(po["params"], lo=po["lo"], hi=po["hi"], counts=po["counts"])) if po else {}))
         else:
             if carried is not None:
@@ -320,7 +324,7 @@ def map_file(index, reads1, text, reads2=None, batch_reads=100000, chunk_bytes=6
                                         p.get("chain_params"), p.get("align_params"), sp, p.get("bounds"), p.get("want_cigar", True),
                                         p.get("rescue"), p.get("want_md", False), ip if carried is None else None,
                                         make_pair_params(**pair_kw),
-                                        index._sam_options(dict(sam=True, names=b["names"], qual=b["qual"], ref_names=ref_names) if sam else {},
+                                        index._sam_options(lines(b),
                                                            p.get("want_cigar", True), p.get("bounds")), po)
             if ip is not None:
                 if carried is None:

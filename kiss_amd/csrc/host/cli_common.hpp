@@ -192,6 +192,23 @@ inline void usage_pileup()
               << "  --pileup-proper                with --mates: only the mates of proper pairs are counted\n";
 }
 
+// The help of the BAM output (`kiss --help-bam`): apart from usage() for the same reason.
+inline void usage_bam()
+{
+    std::cerr << "BAM in the place of SAM, ./kiss fmindex_query --seeds READS [--mates READS2] --chain --align --sam --bam FILE:\n"
+              << "  --bam FILE                     with --sam: the mappings go to FILE as BAM ('-': stdout) and no SAM line is\n"
+              << "                                 printed.  One SAM line is one BAM record: the same reads, flags, places and\n"
+              << "                                 tags (NM, MD with --md, AS, XS, YS, YT, YR), the tag values as unsigned 32-bit\n"
+              << "                                 integers.  The records and the BGZF blocks around them, with the CRC-32 of every\n"
+              << "                                 block, are written on the device (kiss_hip_fmi_bam_host, kiss_hip_bgzf_host).\n"
+              << "                                 The blocks are NOT compressed (stored deflate blocks), which every BAM reader\n"
+              << "                                 accepts: `samtools sort` writes the compressed file.  Works with --mates,\n"
+              << "                                 --rescue, --md, --ins-auto, --batch-reads and --pileup.  A read name of more than\n"
+              << "                                 254 bytes, more than 65535 CIGAR operations on a line or a position of 2^31 or\n"
+              << "                                 more in its record cannot be written as BAM and ends the run.  Without --bam every\n"
+              << "                                 byte of the output is what it was.\n";
+}
+
 inline void check(int rc, const char *where)
 {
     if (rc != KISS_HIP_OK) throw std::runtime_error(std::string(where) + ": " + kiss_hip_strerror(rc));
@@ -281,6 +298,7 @@ struct Args {
     std::string pileup;              // fmindex_query ... --sam --pileup FILE
     kiss_hip_pileup_params pileup_params{0, KISS_HIP_HIT_SECONDARY, 0, 0};
     bool pileup_proper = false;      // --pileup-proper
+    std::string bam;                 // fmindex_query ... --sam --bam FILE ('-': stdout)
 };
 
 inline bool given(const Args &a, const char *name) { return std::find(a.seen.begin(), a.seen.end(), name) != a.seen.end(); }
@@ -359,6 +377,7 @@ inline const Opt OPTIONS[] = {
     {"--pileup", nullptr, KISS_AT(pileup), true, {"--sam"}},
     {"--pileup-min-mapq", nullptr, KISS_AT(pileup_params.min_mapq), true, {"--pileup"}},
     {"--pileup-proper", nullptr, KISS_AT(pileup_proper), true, {"--pileup", "--mates"}},
+    {"--bam", nullptr, KISS_AT(bam), true, {"--sam"}},
 };
 #undef KISS_AT
 
@@ -374,6 +393,7 @@ inline Args parse(int argc, char **argv)
         if (s == "--help-sam") { usage_sam(); std::exit(1); }
         if (s == "--help-pairs") { usage_pairs(); std::exit(1); }
         if (s == "--help-pileup") { usage_pileup(); std::exit(1); }
+        if (s == "--help-bam") { usage_bam(); std::exit(1); }
         const Opt *o = std::find_if(std::begin(OPTIONS), std::end(OPTIONS), [&](const Opt &x) { return s == x.name || (x.alias && s == x.alias); });
         if (o == std::end(OPTIONS)) {
             if (!s.empty() && s[0] == '-' && s.size() > 1) throw std::runtime_error("unrecognised option '" + s + "'");
@@ -432,6 +452,8 @@ inline Args parse(int argc, char **argv)
     goes_with_through("--pileup-proper");
     if (a.pileup_params.min_mapq > 255u) throw std::runtime_error("--pileup-min-mapq is at most 255 (kiss --help-pileup)");
     a.pileup_params.proper_only = a.pileup_proper ? 1u : 0u;
+    goes_with_through("--bam");
+    if (given(a, "--bam") && a.bam.empty()) throw std::runtime_error("--bam needs a file name, or - for stdout (kiss --help-bam)");
     if (given(a, "--mates")) { // the pair's MAPQ is on the scale of the reads'; the mates face each other
         a.both_strands = true;
         a.pair_params.mapq_coef = a.select_params.mapq_coef;

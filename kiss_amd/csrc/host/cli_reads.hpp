@@ -7,10 +7,12 @@
 #include "cli_format.hpp"
 #include "cli_batches.hpp"
 #include "cli_pileup.hpp"
+#include "cli_bam.hpp"
 #include "../../../include/kiss_hip_reads.h"
 #include "../../../include/kiss_hip_md.h"
 #include "../../../include/kiss_hip_insert.h"
 #include "../../../include/kiss_hip_sam.h"
+#include "../../../include/kiss_hip_bam.h"
 #include <iterator>
 
 namespace kiss_cli {
@@ -293,47 +295,58 @@ inline void pair_mates(const Args &a, State &s)
           "kiss_hip_fmi_pair_host");
 }
 
-// --sam-writer device: the lines of the State written on the device, in the place of sam_lines.  The names of the reads and of
-// the records go up as byte arrays with their spans.  A pair that is bad input: the message of sam_lines, and no line of this
-// batch (the device call writes nothing for a batch that has a bad read).
+// The State as the input of the device writers (include/kiss_hip_sam.h): the names of the reads and of the records go up as byte
+// arrays with their spans.  A pair that is bad input: the message of sam_lines.
+struct DeviceLinesInput {
+    std::vector<uint8_t> names, ref_names;
+    std::vector<uint64_t> name_off, ref_name_index;
+    std::vector<uint32_t> name_len;
+    kiss_hip_sam_input in{};
+    DeviceLinesInput(const DeviceLinesInput &) = delete;
+    DeviceLinesInput &operator=(const DeviceLinesInput &) = delete;
+    DeviceLinesInput(const State &s, bool paired) : name_off(s.Q), ref_name_index(s.ref.names.size() + 1, 0), name_len(s.Q)
+    {
+        const uint64_t Q = s.Q, R = s.ref.names.size();
+        for (uint64_t p = 0; paired && p < Q / 2; p++)
+            if (s.pairs[p].flags & KISS_HIP_PAIR_BAD_INPUT)
+                throw std::runtime_error("kiss_hip_fmi_pair_host: pair " + std::to_string(s.first / 2 + p) + " is bad input");
+        for (uint64_t q = 0; q < Q; q++) {
+            name_off[q] = names.size();
+            name_len[q] = (uint32_t)s.rd.names[q].size();
+            names.insert(names.end(), s.rd.names[q].begin(), s.rd.names[q].end());
+        }
+        for (uint64_t r = 0; r < R; r++) {
+            ref_names.insert(ref_names.end(), s.ref.names[r].begin(), s.ref.names[r].end());
+            ref_name_index[r + 1] = ref_names.size();
+        }
+        names.push_back(0), ref_names.push_back(0); // (no NULL for reads without names)
+        static const uint32_t none = 0; // (no NULL for a batch without ops, alignments or hits)
+        static const kiss_hip_aln no_aln{};
+        static const kiss_hip_hit no_hit{};
+        in.reads = s.rd.reads.data(), in.read_index = s.rd.ridx.data(), in.qual = s.rd.has_qual ? s.rd.qual.data() : nullptr;
+        in.names = names.data(), in.name_off = name_off.data(), in.name_len = name_len.data();
+        in.alns = s.al.alns.empty() ? &no_aln : s.al.alns.data(), in.cigar = s.al.cigar.empty() ? &none : s.al.cigar.data(), in.cigar_index = s.al.oidx.data();
+        in.hits = s.hits.empty() ? &no_hit : s.hits.data(), in.hit_index = s.hidx.data();
+        in.pairs = paired ? s.pairs.data() : nullptr;
+        in.source = s.source.empty() ? nullptr : s.source.data(), in.first_alns = s.first_alns;
+        in.md = s.midx.empty() ? nullptr : s.md.data(), in.md_index = s.midx.empty() ? nullptr : s.midx.data();
+        in.ref_names = ref_names.data(), in.ref_name_index = ref_name_index.data(), in.bounds = s.ref.bounds.data();
+        in.Q = Q, in.C = s.al.oidx.size() - 1, in.R = R;
+    }
+};
+
+// --sam-writer device: the lines of the State written on the device, in the place of sam_lines.  A pair that is bad input: no
+// line of this batch (the device call writes nothing for a batch that has a bad read).
 inline void sam_lines_device(StdoutWriter &w, const Args &a, const State &s, bool paired)
 {
-    const uint64_t Q = s.Q, R = s.ref.names.size();
+    const uint64_t Q = s.Q;
     if (!Q) return;
-    for (uint64_t p = 0; paired && p < Q / 2; p++)
-        if (s.pairs[p].flags & KISS_HIP_PAIR_BAD_INPUT)
-            throw std::runtime_error("kiss_hip_fmi_pair_host: pair " + std::to_string(s.first / 2 + p) + " is bad input");
-    std::vector<uint8_t> names, ref_names;
-    std::vector<uint64_t> name_off(Q), ref_name_index(R + 1, 0);
-    std::vector<uint32_t> name_len(Q);
-    for (uint64_t q = 0; q < Q; q++) {
-        name_off[q] = names.size();
-        name_len[q] = (uint32_t)s.rd.names[q].size();
-        names.insert(names.end(), s.rd.names[q].begin(), s.rd.names[q].end());
-    }
-    for (uint64_t r = 0; r < R; r++) {
-        ref_names.insert(ref_names.end(), s.ref.names[r].begin(), s.ref.names[r].end());
-        ref_name_index[r + 1] = ref_names.size();
-    }
-    names.push_back(0), ref_names.push_back(0); // (no NULL for reads without names)
-    static const uint32_t none = 0; // (no NULL for a batch without ops, alignments or hits)
-    static const kiss_hip_aln no_aln{};
-    static const kiss_hip_hit no_hit{};
-    kiss_hip_sam_input in{};
-    in.reads = s.rd.reads.data(), in.read_index = s.rd.ridx.data(), in.qual = s.rd.has_qual ? s.rd.qual.data() : nullptr;
-    in.names = names.data(), in.name_off = name_off.data(), in.name_len = name_len.data();
-    in.alns = s.al.alns.empty() ? &no_aln : s.al.alns.data(), in.cigar = s.al.cigar.empty() ? &none : s.al.cigar.data(), in.cigar_index = s.al.oidx.data();
-    in.hits = s.hits.empty() ? &no_hit : s.hits.data(), in.hit_index = s.hidx.data();
-    in.pairs = paired ? s.pairs.data() : nullptr;
-    in.source = s.source.empty() ? nullptr : s.source.data(), in.first_alns = s.first_alns;
-    in.md = s.midx.empty() ? nullptr : s.md.data(), in.md_index = s.midx.empty() ? nullptr : s.midx.data();
-    in.ref_names = ref_names.data(), in.ref_name_index = ref_name_index.data(), in.bounds = s.ref.bounds.data();
-    in.Q = Q, in.C = s.al.oidx.size() - 1, in.R = R;
+    const DeviceLinesInput d(s, paired);
     std::vector<uint8_t> sam(1);
     std::vector<uint64_t> read_line(Q + 1);
     kiss_hip_sam_report rep{};
     const int rc = sized_call(sam, rep.sam_bytes, [&](uint64_t capacity) {
-        return kiss_hip_fmi_sam_host(&in, sam.data(), capacity, nullptr, 0, read_line.data(), &rep, a.device);
+        return kiss_hip_fmi_sam_host(&d.in, sam.data(), capacity, nullptr, 0, read_line.data(), &rep, a.device);
     });
     if (rc == KISS_HIP_E_INVALID && rep.bad)
         throw std::runtime_error("fmindex_query --sam-writer device: " + std::to_string(rep.bad) + " reads have hits that do not fit them, the first is read " +
@@ -342,6 +355,71 @@ inline void sam_lines_device(StdoutWriter &w, const Args &a, const State &s, boo
     w.write(); // (what is waiting, the header for one, goes first)
     std::fwrite(sam.data(), 1, rep.sam_bytes, stdout);
 }
+
+// --bam FILE: the header (cli_bam.hpp), the records of every batch (kiss_hip_fmi_bam_host) and the end-of-file block, each framed
+// as BGZF blocks on the device (kiss_hip_bgzf_host) and written as it comes.  FILE is opened before a read is mapped.
+struct BamOut {
+    std::string path;
+    std::FILE *file = nullptr;
+    int device = 0;
+    uint64_t records = 0, bytes = 0;
+    BamOut() = default;
+    BamOut(const BamOut &) = delete;
+    BamOut &operator=(const BamOut &) = delete;
+    ~BamOut()
+    {
+        if (file && file != stdout) std::fclose(file);
+    }
+    bool on() const { return file != nullptr; }
+    void open(const Args &a)
+    {
+        path = a.bam, device = a.device;
+        file = path == "-" ? stdout : std::fopen(path.c_str(), "wb");
+        if (!file) throw std::runtime_error("cannot open " + path);
+    }
+    // data[0, n) as BGZF blocks; eof: the end-of-file block behind them
+    void framed(const uint8_t *data, uint64_t n, int eof)
+    {
+        const uint64_t total = n + (uint64_t)KISS_HIP_BGZF_OVERHEAD * ((n + KISS_HIP_BGZF_BLOCK_DEFAULT - 1) / KISS_HIP_BGZF_BLOCK_DEFAULT) +
+                               (eof ? KISS_HIP_BGZF_EOF_BYTES : 0u);
+        std::vector<uint8_t> out(total + 1);
+        kiss_hip_bgzf_report rep{};
+        check(kiss_hip_bgzf_host(n ? data : nullptr, n, 0, eof, out.data(), total, &rep, device), "kiss_hip_bgzf_host");
+        if (std::fwrite(out.data(), 1, rep.out_bytes, file) != rep.out_bytes) throw std::runtime_error("cannot write " + path);
+        bytes += rep.out_bytes;
+    }
+    void header(const RefRecords &ref, const char *version)
+    {
+        std::string text;
+        sam_header(text, ref, version);
+        const std::string h = bam_header(text, ref.names, ref.bounds);
+        framed(reinterpret_cast<const uint8_t *>(h.data()), h.size(), 0);
+    }
+    // the records of the State, in the place of its lines
+    void add(const State &s, bool paired)
+    {
+        if (!s.Q) return;
+        const DeviceLinesInput d(s, paired);
+        std::vector<uint8_t> bam(1);
+        std::vector<uint64_t> read_rec(s.Q + 1);
+        kiss_hip_bam_report rep{};
+        const int rc = sized_call(bam, rep.bam_bytes, [&](uint64_t capacity) {
+            return kiss_hip_fmi_bam_host(&d.in, bam.data(), capacity, nullptr, 0, read_rec.data(), &rep, device);
+        });
+        if (rc == KISS_HIP_E_INVALID && rep.bad)
+            throw std::runtime_error("fmindex_query --bam: " + std::to_string(rep.bad) + " reads cannot be written as BAM (kiss --help-bam), the first is read " +
+                                     std::to_string(s.first + rep.first_bad));
+        check(rc, "kiss_hip_fmi_bam_host");
+        framed(bam.data(), rep.bam_bytes, 0);
+        records += rep.records;
+    }
+    void close()
+    {
+        framed(nullptr, 0, 1);
+        if (std::fflush(file) != 0) throw std::runtime_error("cannot write " + path);
+        std::fprintf(stderr, "[info] bam: records: %llu, bytes: %llu\n", (ull)records, (ull)bytes);
+    }
+};
 
 // --pileup FILE: ONE device array of 8 planes of n u32 (32 n bytes) to which every batch adds -- kiss_hip_fmi_pileup_host with
 // counts_on_device, accumulate from the second call on --, fetched once behind the last batch and written as lines
@@ -425,6 +503,8 @@ inline int map_reads_in_batches(const Args &a, const kiss_hip_fmi_view_ex &index
     load_records(a, keep);
     PileupSums pile;
     if (!a.pileup.empty()) pile.open(a, keep.S.size());
+    BamOut bam;
+    if (!a.bam.empty()) bam.open(a);
     kiss_hip_pair_params pair_params{};
     kiss_hip_rescue_params rescue_params{};
     StdoutWriter w;
@@ -464,16 +544,23 @@ inline int map_reads_in_batches(const Args &a, const kiss_hip_fmi_view_ex &index
         if (paired) pair_mates(a, s);
         if (a.md) md_tags(a, s);
         if (pile.on()) pile.add(a, s, paired);
-        if (!batches) sam_header(w.out, s.ref, VERSION);
-        if (a.sam_writer == "device") sam_lines_device(w, a, s, paired);
-        else sam_lines(w, s, paired);
-        w.finish(); // (on stdout before the next batch can fail)
+        if (bam.on()) {
+            if (!batches) bam.header(s.ref, VERSION);
+            bam.add(s, paired);
+        } else {
+            if (!batches) sam_header(w.out, s.ref, VERSION);
+            if (a.sam_writer == "device") sam_lines_device(w, a, s, paired);
+            else sam_lines(w, s, paired);
+            w.finish(); // (on stdout before the next batch can fail)
+        }
         if (a.verbose) sam_info(s, paired, a.rescue);
         reads += s.Q, mapped += s.select_rep.mapped;
         keep.S = std::move(s.S);
         keep.ref = std::move(s.ref);
     }
-    if (!batches) sam_header(w.out, keep.ref, VERSION), w.finish();
+    if (!batches && bam.on()) bam.header(keep.ref, VERSION);
+    if (!batches && !bam.on()) sam_header(w.out, keep.ref, VERSION), w.finish();
+    if (bam.on()) bam.close();
     if (pile.on()) pile.write(keep.S, keep.ref);
     std::fprintf(stderr, "[info] batches: %llu, reads: %llu, mapped: %llu\n", (ull)batches, (ull)reads, (ull)mapped);
     return 0;
@@ -487,6 +574,8 @@ inline int map_reads(const Args &a, const kiss_hip_fmi_view_ex &index)
     s.index = index;
     PileupSums pile;
     if (!a.pileup.empty()) load_text(a, s), pile.open(a, s.S.size()); // (before a read is mapped)
+    BamOut bam;
+    if (!a.bam.empty()) bam.open(a);
     load_reads(a, s);
     find_seeds(a, s);
     if (!a.chain) return print_seeds(s, a.both_strands);
@@ -501,7 +590,12 @@ inline int map_reads(const Args &a, const kiss_hip_fmi_view_ex &index)
     if (!a.mates.empty()) pair_mates(a, s);
     if (a.md) md_tags(a, s);
     if (pile.on()) pile.add(a, s, !a.mates.empty());
-    if (a.sam_writer != "device") {
+    if (bam.on()) {
+        bam.header(s.ref, VERSION);
+        bam.add(s, !a.mates.empty());
+        bam.close();
+        sam_info(s, !a.mates.empty(), a.rescue);
+    } else if (a.sam_writer != "device") {
         print_sam(s, !a.mates.empty(), a.rescue, VERSION);
     } else {
         StdoutWriter w;

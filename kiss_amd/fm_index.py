@@ -677,6 +677,10 @@ class FMIndex:
         carry MD:Z:.  names: the QNAMEs, a list of str or bytes or the (raw, name_off, name_len) triple of parse_reads; None: the
         decimal read number.  qual: the quality bytes, a list with one entry per read or one array under the index of the reads;
         None prints '*'.  ref_names: the names of the R records, needed when bounds is given; without either RNAME is '*'.
+        bam (False; it needs want_cigar, ref_names and bounds; names and qual as for sam, and both may be given): also bam (bytes: the
+        BGZF blocks of the batch's BAM records, ready to append to a file behind the framed kiss_amd.bam_writer.bam_header(); written and
+        framed on the device by kiss_hip_fmi_bam_dev and kiss_hip_bgzf_dev, include/kiss_hip_bam.h), bam_rec_index (records + 1, over
+        the unframed records), bam_read_rec (Q + 1) and bam_report.
         pileup (None; it needs want_cigar): True, a dict of lo, hi, counts and the pileup parameters min_mapq (0), skip_flags (2:
         secondary hits) and proper_only (0), or an (8, W) int32 device tensor to add to (the dict's counts: such a tensor, or an
         (8, W) u32 array): also pileup -- the eight planes of kiss_amd.fm_pileup.PLANES over the text positions [lo, hi), default
@@ -758,15 +762,18 @@ class FMIndex:
 
     @staticmethod
     def _sam_options(given, want_cigar, bounds):
-        """map(sam=...): takes sam, names, qual and ref_names out of the keywords `given` -> None without sam, else the
+        """map(sam=..., bam=...): takes sam, bam, names, qual and ref_names out of the keywords `given` -> None without both, else the
         arguments of the lines, held against each other before anything runs"""
         sam, names, qual, ref_names = (given.pop(k, d) for k, d in (("sam", False), ("names", None), ("qual", None), ("ref_names", None)))
-        if not sam:
+        bam = given.pop("bam", False)
+        if not sam and not bam:
             if names is not None or qual is not None or ref_names is not None:
                 raise ValueError("names, qual and ref_names belong to sam=True")
             return None
         if not want_cigar:
-            raise ValueError("sam needs the ops: want_cigar=True")
+            raise ValueError("%s needs the ops: want_cigar=True" % ("sam" if sam else "bam"))
+        if bam and (not ref_names or bounds is None):
+            raise ValueError("bam needs the records: ref_names and bounds")
         from .fm_select import _bounds_array
         b = _bounds_array(bounds)
         R = len(ref_names) if ref_names is not None else 0
@@ -774,7 +781,7 @@ class FMIndex:
             raise ValueError("ref_names has one name per record: bounds has R + 1 = %d entries" % b.size)
         if R > 1 and b is None:
             raise ValueError("ref_names with more than one name needs bounds")
-        return {"names": names, "qual": qual, "ref_names": ref_names, "bounds": b, "md": None}
+        return {"names": names, "qual": qual, "ref_names": ref_names, "bounds": b, "md": None, "sam": bool(sam), "bam": bool(bam)}
 
     def _sam_lines(self, t, ctx, d_alns, C, d_cigar, d_oidx, sel, so, d_pairs=None, d_source=None, first_alns=0):
         """map(sam=True): the lines of the hits of a select call (and the pairs of a pair call), from the buffers that are on the
@@ -826,12 +833,17 @@ class FMIndex:
         md = so["md"]
         H = int(sel["rep"].hits)
         ctx = self._context_to_sort(ctx, Q + H + 1)
-        out = sam_lines_dev(t.lib, ctx, self.device, Q, C, R, first_alns, reads=t.d_reads, read_index=t.d_ridx, qual=d_qual, names=up(raw),
-                            name_off=up(noff, np.int64), name_len=up(nlen, np.int32), alns=d_alns, cigar=d_cigar, cigar_index=d_oidx,
-                            hits=sel["d_hits"], hit_index=sel["d_hidx"], pairs=d_pairs, source=d_source,
-                            md=md["d_md"] if md else None, md_index=md["d_midx"] if md else None, ref_names=up(rn) if R else None,
-                            ref_name_index=up(rnidx, np.int64) if R else None, bounds=up(b, np.int64) if R else None)
-        return sam_arrays(out)
+        arrays = dict(reads=t.d_reads, read_index=t.d_ridx, qual=d_qual, names=up(raw), name_off=up(noff, np.int64), name_len=up(nlen, np.int32),
+                      alns=d_alns, cigar=d_cigar, cigar_index=d_oidx, hits=sel["d_hits"], hit_index=sel["d_hidx"], pairs=d_pairs, source=d_source,
+                      md=md["d_md"] if md else None, md_index=md["d_midx"] if md else None, ref_names=up(rn) if R else None,
+                      ref_name_index=up(rnidx, np.int64) if R else None, bounds=up(b, np.int64) if R else None)
+        res = {}
+        if so["sam"]:
+            res.update(sam_arrays(sam_lines_dev(t.lib, ctx, self.device, Q, C, R, first_alns, **arrays)))
+        if so["bam"]:  # (the records, then their blocks: both from the buffers on the device)
+            from .bam_writer import bam_arrays, bam_records_dev
+            res.update(bam_arrays(t.lib, ctx, self.device, bam_records_dev(t.lib, ctx, self.device, Q, C, R, first_alns, **arrays)))
+        return res
 
     # ---- the mappings of two mates paired (kiss_hip_fmi_pair_dev; no reference counterpart) -----------------------------
     def map_pairs(self, reads1, reads2, text, min_len=19, max_len=0, max_occ=500, chain_params=None, align_params=None,

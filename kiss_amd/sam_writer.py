@@ -88,13 +88,10 @@ def default_names(Q, paired=False):
     return [str(q // 2 if paired else q).encode() for q in range(Q)]
 
 
-def sam_lines(reads, read_index, names, alns, cigar, cigar_index, hits, hit_index, qual=None, pairs=None, source=None, first_alns=0, md=None,
-              md_index=None, ref_names=None, bounds=None, device=0, hooks=None):
-    """The alignment lines of a batch given as arrays (numpy in, numpy out), through the host entry.  The arrays are those of
-    include/kiss_hip_sam.h: alns / hits / pairs the structured arrays of the calls or (n, 12) / (n, 8) / (n, 10) integer arrays in
-    the order of their fields; names a list of str or bytes or the (raw, name_off, name_len) triple of parse_reads; ref_names a
-    list of R names with bounds (R + 1), or None.  Returns dict(sam: the bytes as uint8, line_index, read_line, report).  A batch
-    with a bad read (see the header) raises KissHipError; its report is the exception's `report`."""
+def _host_input(reads, read_index, names, alns, cigar, cigar_index, hits, hit_index, qual=None, pairs=None, source=None, first_alns=0, md=None,
+                md_index=None, ref_names=None, bounds=None):
+    """the arrays of a batch, as sam_lines takes them, held against each other -> (kiss_hip_sam_input over host pointers, Q, what
+    keeps the arrays alive)"""
     from .fm_align import ALN_DTYPE
     from .fm_pair import PAIR_DTYPE
     from .fm_select import HIT_DTYPE
@@ -140,6 +137,18 @@ def sam_lines(reads, read_index, names, alns, cigar, cigar_index, hits, hit_inde
              md_index=None if midx is None else midx.ctypes.data, ref_name_index=rnidx.ctypes.data if R else None,
              bounds=bnd.ctypes.data if R else None)
     inp = sam_input(p, Q, C, R, first_alns)
+    return inp, Q, (hold, hold2, cat, ridx, ql, raw, noff, nlen, al, cig, oidx, ht, hidx, pr, src, mdb, midx, rn, rnidx, bnd)
+
+
+def sam_lines(reads, read_index, names, alns, cigar, cigar_index, hits, hit_index, qual=None, pairs=None, source=None, first_alns=0, md=None,
+              md_index=None, ref_names=None, bounds=None, device=0, hooks=None):
+    """The alignment lines of a batch given as arrays (numpy in, numpy out), through the host entry.  The arrays are those of
+    include/kiss_hip_sam.h: alns / hits / pairs the structured arrays of the calls or (n, 12) / (n, 8) / (n, 10) integer arrays in
+    the order of their fields; names a list of str or bytes or the (raw, name_off, name_len) triple of parse_reads; ref_names a
+    list of R names with bounds (R + 1), or None.  Returns dict(sam: the bytes as uint8, line_index, read_line, report).  A batch
+    with a bad read (see the header) raises KissHipError; its report is the exception's `report`."""
+    inp, Q, hold = _host_input(reads, read_index, names, alns, cigar, cigar_index, hits, hit_index, qual, pairs, source, first_alns, md, md_index,
+                               ref_names, bounds)
     lib = _lib.load(hooks)
     rep = _lib.SamReport()
     rl = np.zeros(Q + 1, np.uint64)
@@ -149,7 +158,7 @@ def sam_lines(reads, read_index, names, alns, cigar, cigar_index, hits, hit_inde
 
     rc, (sam, _, li, _) = sized(call, lambda m=0, lines=0: (np.zeros(max(m, 1), np.uint8), m, np.zeros(lines + 1, np.uint64), lines), rep,
                                "sam_bytes", "lines")
-    del hold, hold2
+    del hold
     if rc == _lib.KISS_HIP_E_INVALID and rep.bad:
         err = _lib.KissHipError(rc, "kiss_hip_fmi_sam_host", "%d bad read(s), the first one read %d" % (rep.bad, rep.first_bad))
         err.report = rep.as_dict()
