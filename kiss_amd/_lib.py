@@ -289,6 +289,12 @@ class BgzfReport(Report):
     _fields_ = [("blocks", ctypes.c_uint64), ("out_bytes", ctypes.c_uint64), ("ms_total", ctypes.c_float), ("reserved_", ctypes.c_uint32)]
 
 
+class BgzfDeflateReport(Report):
+    """kiss_hip_bgzf_deflate_report (include/kiss_hip_deflate.h)"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("blocks", "out_bytes", "stored_blocks", "fixed_blocks", "dynamic_blocks", "literals", "matches",
+                                               "match_bytes")] + [(k, ctypes.c_float) for k in ("ms_total", "ms_block", "ms_scan", "ms_copy")]
+
+
 class MdReport(Report):
     """kiss_hip_md_report (include/kiss_hip_md.h)"""
     _fields_ = [(k, ctypes.c_uint64) for k in ("items", "bad", "md_bytes", "mismatch_columns", "deleted_bases", "longest")] + [
@@ -524,6 +530,11 @@ def load(hooks=None):
         lib.kiss_hip_bgzf_host.argtypes = [vp, u64, u32, ctypes.c_int, vp, u64, ctypes.POINTER(BgzfReport), ctypes.c_int]
         for name in BAM_EXPORTED_SYMBOLS:
             getattr(lib, name).restype = ctypes.c_int
+    if hasattr(lib, "kiss_hip_bgzf_deflate_dev"):  # (as the BAM calls)
+        lib.kiss_hip_bgzf_deflate_dev.argtypes = [vp, vp, u64, u32, ctypes.c_int, vp, u64, vp, u64, ctypes.POINTER(BgzfDeflateReport), vp]
+        lib.kiss_hip_bgzf_deflate_host.argtypes = [vp, u64, u32, ctypes.c_int, vp, u64, vp, u64, ctypes.POINTER(BgzfDeflateReport), ctypes.c_int]
+        for name in DEFLATE_EXPORTED_SYMBOLS:
+            getattr(lib, name).restype = ctypes.c_int
     lib.kiss_hip_fmi_insert_dev.argtypes = [vp, vp, vp, u64, vp, u64, ctypes.POINTER(InsertParams), vp, ctypes.POINTER(InsertReport), vp]
     lib.kiss_hip_fmi_insert_host.argtypes = [vp, vp, u64, vp, u64, ctypes.POINTER(InsertParams), vp, ctypes.POINTER(InsertReport),
                                              ctypes.c_int]
@@ -625,6 +636,8 @@ SAM_EXPORTED_SYMBOLS = ["kiss_hip_fmi_sam_dev", "kiss_hip_fmi_sam_host"]
 # every symbol include/kiss_hip_bam.h declares (tests/test_fm_bam_abi.py)
 BAM_EXPORTED_SYMBOLS = ["kiss_hip_fmi_bam_dev", "kiss_hip_fmi_bam_host", "kiss_hip_bgzf_dev", "kiss_hip_bgzf_host"]
 BGZF_BLOCK_DEFAULT, BGZF_BLOCK_MAX, BGZF_OVERHEAD, BGZF_EOF_BYTES = 65280, 65505, 31, 28
+# every symbol include/kiss_hip_deflate.h declares (tests/test_deflate_abi.py)
+DEFLATE_EXPORTED_SYMBOLS = ["kiss_hip_bgzf_deflate_dev", "kiss_hip_bgzf_deflate_host"]
 # every symbol include/kiss_hip_insert.h declares (tests/test_fm_insert_abi.py)
 INSERT_EXPORTED_SYMBOLS = ["kiss_hip_fmi_insert_dev", "kiss_hip_fmi_insert_host"]
 INSERT_MAX = 65535

@@ -2,8 +2,9 @@
 (kiss_hip_fmi_bam_dev / _host) from the arrays the SAM lines are written from, and the BGZF framing of any bytes in stored blocks
 with the CRC-32 of every block computed on the device (kiss_hip_bgzf_dev / _host).  bam_records() and bgzf() take numpy arrays
 and run the host entries; FMIndex.map(bam=True), map_pairs(bam=True) and map_file(bam=True) keep everything on the device
-(bam_records_dev, then bgzf_dev, no round trip between them); write_bam() writes a whole file.  The blocks are not compressed:
-`samtools sort` and every other BAM reader take them as they are.  All arithmetic runs in libkiss_hip.so; there is no CPU path."""
+(bam_records_dev, then bgzf_dev, no round trip between them); write_bam() writes a whole file.  The blocks are stored unless
+compression is asked for (bgzf_deflate / bgzf_deflate_dev, map(bam_compress=True), write_bam(compress=True): DEFLATE on the device,
+include/kiss_hip_deflate.h); `samtools sort` and every other BAM reader take either kind as it is.  All arithmetic runs in libkiss_hip.so; there is no CPU path."""
 import ctypes
 import struct
 
@@ -135,27 +136,71 @@ def bgzf_dev(lib, ctx, device, d_data, n, block_bytes=65280, eof=False, stream=N
     return d_out[:int(rep.out_bytes)], rep
 
 
-def bam_arrays(lib, ctx, device, out, block_bytes=65280):
-    """the tensors of bam_records_dev framed on the device, as what map(bam=True) adds to its result"""
+def bgzf_deflate(data, block_bytes=65280, eof=False, device=0, hooks=None, want_report=False, want_index=False):
+    """bgzf() with the blocks compressed on the device (DEFLATE; include/kiss_hip_deflate.h), through the host entry -> bytes
+    (want_index: and block_index, blocks + 1 uint64 over those bytes; want_report: and the report, in that order)"""
+    raw = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8).ravel()
+    bb = _block_bytes(block_bytes)
+    out = np.zeros(max(bgzf_bytes(raw.size, bb, eof), 1), np.uint8)
+    index = np.zeros(-(-raw.size // (bb or _lib.BGZF_BLOCK_DEFAULT)) + 1, np.uint64)
+    rep = _lib.BgzfDeflateReport()
+    rc = _lib.load(hooks).kiss_hip_bgzf_deflate_host(raw.ctypes.data if raw.size else None, raw.size, bb, int(bool(eof)), out.ctypes.data, out.size,
+                                                    index.ctypes.data, index.size, ctypes.byref(rep), int(device))
+    _check(rc, "kiss_hip_bgzf_deflate_host")
+    got = (out[:int(rep.out_bytes)].tobytes(),) + ((index,) if want_index else ()) + ((rep.as_dict(),) if want_report else ())
+    return got if len(got) > 1 else got[0]
+
+
+def bgzf_deflate_dev(lib, ctx, device, d_data, n, block_bytes=65280, eof=False, stream=None):
+    """the device entry: the first n bytes of the uint8 tensor d_data -> (a uint8 tensor of exactly the blocks, block_index as an
+    int64 tensor of blocks + 1, the report)"""
+    import torch
+    dev = torch.device("cuda", device)
+    vp = ctypes.c_void_p
+    bb = _block_bytes(block_bytes)
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    bound = bgzf_bytes(int(n), bb, eof)
+    blocks = -(-int(n) // (bb or _lib.BGZF_BLOCK_DEFAULT))
+    d_out = torch.zeros(max(bound, 1), dtype=torch.uint8, device=dev)
+    d_index = torch.zeros(blocks + 1, dtype=torch.int64, device=dev)
+    rep = _lib.BgzfDeflateReport()
+    rc = lib.kiss_hip_bgzf_deflate_dev(ctx._ctx, vp(d_data.data_ptr()) if n else None, int(n), bb, int(bool(eof)), vp(d_out.data_ptr()), bound,
+                                       vp(d_index.data_ptr()), blocks + 1, ctypes.byref(rep), vp(stream) if stream else None)
+    _check(rc, "kiss_hip_bgzf_deflate_dev", ctx._ctx)
+    return d_out[:int(rep.out_bytes)], d_index, rep
+
+
+def bam_arrays(lib, ctx, device, out, block_bytes=65280, compress=False):
+    """the tensors of bam_records_dev framed on the device, as what map(bam=True) adds to its result; compress: the blocks are
+    compressed (bam_block_index and the counts of the coding beside them)"""
     total = int(out["rep"].bam_bytes)
-    d_blocks, frep = bgzf_dev(lib, ctx, device, out["d_bam"], total, block_bytes)
     ri = out["d_rec_index"]
     rep = out["rep"].as_dict()
+    more = {}
+    if compress:
+        d_blocks, d_index, frep = bgzf_deflate_dev(lib, ctx, device, out["d_bam"], total, block_bytes)
+        rep.update({k: int(getattr(frep, k)) for k in ("stored_blocks", "fixed_blocks", "dynamic_blocks", "literals", "matches", "match_bytes")})
+        more["bam_block_index"] = d_index.cpu().numpy().view(np.uint64)
+    else:
+        d_blocks, frep = bgzf_dev(lib, ctx, device, out["d_bam"], total, block_bytes)
     rep.update(blocks=int(frep.blocks), out_bytes=int(frep.out_bytes), ms_frame=float(frep.ms_total))
     return {"bam": d_blocks.cpu().numpy().tobytes(), "bam_rec_index": None if ri is None else ri.cpu().numpy().view(np.uint64),
-            "bam_read_rec": out["d_read_rec"].cpu().numpy().view(np.uint64), "bam_report": rep}
+            "bam_read_rec": out["d_read_rec"].cpu().numpy().view(np.uint64), "bam_report": rep, **more}
 
 
-def write_bam(path, index, reads1, text, reads2=None, ref_names=None, bounds=None, version=None, **params):
+def write_bam(path, index, reads1, text, reads2=None, ref_names=None, bounds=None, version=None, compress=False, **params):
     """A whole BAM file of the read file(s) mapped by `index` (batches.map_file, which has the other arguments): the framed header,
-    the blocks of every batch, the end-of-file block.  path: a file name, or a binary file object.  -> the batches, records and bytes
-    written"""
+    the blocks of every batch, the end-of-file block.  path: a file name, or a binary file object.  compress: the header and the
+    batches in compressed blocks (bgzf_deflate, map_file(bam_compress=True)).  -> the batches, records and bytes written"""
     from .batches import map_file
     if ref_names is None or bounds is None:
         raise ValueError("a BAM file needs ref_names and bounds")
     if version is None:  # (@PG VN: the library's version number, as kiss_hip_version() gives it)
         version = str(_lib.load(index._hooks).kiss_hip_version())
-    head = bgzf(bam_header(ref_names, bounds, version), device=index.device, hooks=index._hooks)
+    head = (bgzf_deflate if compress else bgzf)(bam_header(ref_names, bounds, version), device=index.device, hooks=index._hooks)
+    if compress:
+        params["bam_compress"] = True
     f = open(path, "wb") if isinstance(path, (str, bytes)) or hasattr(path, "__fspath__") else path
     done = {"batches": 0, "records": 0, "bytes": len(head)}
     try:

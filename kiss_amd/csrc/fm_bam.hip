@@ -283,74 +283,8 @@ __global__ __launch_bounds__(SAM_THREADS) void k_bam_emit(SamIn in, const uint64
 }
 
 // ---- BGZF ------------------------------------------------------------------------------------------------------------------
-constexpr int BGZF_THREADS = 256;
+#include "bgzf_block.hpp"
 constexpr unsigned BGZF_MAX_BLOCKS = 2048;
-constexpr uint32_t BGZF_PAY_WORDS = 16384; // 65505 payload bytes and 3 of phase, rounded up
-constexpr uint32_t CRC_POLY = 0xEDB88320u;
-
-// a * b modulo the CRC-32 polynomial, reflected: bit 31 is x^0
-__host__ __device__ constexpr uint32_t crc_mul(uint32_t a, uint32_t b)
-{
-    uint32_t p = 0;
-    for (int k = 0; k < 32; k++) {
-        if (a & (0x80000000u >> k)) p ^= b;
-        b = (b >> 1) ^ ((b & 1u) ? CRC_POLY : 0u);
-    }
-    return p;
-}
-// x^(8 * 2^j) modulo the polynomial, j = 0 .. 15
-struct CrcPowers {
-    uint32_t x[16];
-    constexpr CrcPowers() : x{}
-    {
-        uint32_t v = 0x40000000u; // x^1
-        for (int k = 0; k < 3; k++) v = crc_mul(v, v);
-        for (int j = 0; j < 16; j++) {
-            x[j] = v;
-            v = crc_mul(v, v);
-        }
-    }
-};
-// x^(8 m) modulo the polynomial, m < 2^16
-__device__ __forceinline__ uint32_t crc_x8n(uint32_t m)
-{
-    constexpr CrcPowers P;
-    uint32_t p = 0x80000000u; // x^0
-#pragma unroll
-    for (int j = 0; j < 16; j++)
-        if (m >> j & 1u) p = crc_mul(p, P.x[j]);
-    return p;
-}
-
-// the fixed bytes of a block in front of its payload (18 of BGZF, 5 of the stored deflate block); total = the bytes of the block
-__device__ __forceinline__ uint8_t bgzf_head_byte(uint32_t k, uint32_t len)
-{
-    const uint32_t bsize = len + KISS_HIP_BGZF_OVERHEAD - 1u;
-    switch (k) {
-    case 0: return 0x1f;
-    case 1: return 0x8b;
-    case 2: return 8;
-    case 3: return 4;
-    case 9: return 0xff;
-    case 10: return 6;
-    case 12: return 'B';
-    case 13: return 'C';
-    case 14: return 2;
-    case 16: return (uint8_t)bsize;
-    case 17: return (uint8_t)(bsize >> 8);
-    case 18: return 1;
-    case 19: return (uint8_t)len;
-    case 20: return (uint8_t)(len >> 8);
-    case 21: return (uint8_t)~len;
-    case 22: return (uint8_t)(~len >> 8);
-    default: return 0;
-    }
-}
-__device__ __forceinline__ uint8_t bgzf_eof_byte(uint32_t k)
-{
-    if (k < 16) return bgzf_head_byte(k, 0);
-    return k == 16 ? 0x1b : (k == 18 ? 0x03 : 0);
-}
 
 // One workgroup per block (a workgroup takes blocks b, b + gridDim.x, ...); the end-of-file block by workgroup 0.
 __global__ __launch_bounds__(BGZF_THREADS) void k_bgzf(const uint8_t *__restrict__ data, uint64_t n, uint32_t bb, uint64_t blocks, int eof,
@@ -360,12 +294,7 @@ __global__ __launch_bounds__(BGZF_THREADS) void k_bgzf(const uint8_t *__restrict
     __shared__ uint32_t s_pay[BGZF_PAY_WORDS];
     __shared__ uint32_t s_acc;
     const uint32_t t = threadIdx.x;
-    {
-        uint32_t c = t;
-#pragma unroll
-        for (int k = 0; k < 8; k++) c = (c >> 1) ^ ((c & 1u) ? CRC_POLY : 0u);
-        s_tab[t] = c;
-    }
+    s_tab[t] = crc_table_entry(t);
     if (eof && blockIdx.x == 0 && t < KISS_HIP_BGZF_EOF_BYTES) out[n + (uint64_t)KISS_HIP_BGZF_OVERHEAD * blocks + t] = bgzf_eof_byte(t);
     const uint8_t *const pb = (const uint8_t *)s_pay;
     for (uint64_t b = blockIdx.x; b < blocks; b += gridDim.x) {
@@ -406,14 +335,7 @@ __global__ __launch_bounds__(BGZF_THREADS) void k_bgzf(const uint8_t *__restrict
         }
         // the CRC: lane t over its piece, then times x^(8 * the bytes behind the piece)
         {
-            const uint32_t piece = (len + BGZF_THREADS - 1u) / BGZF_THREADS;
-            const uint32_t beg = t * piece < len ? t * piece : len;
-            const uint32_t end = beg + piece < len ? beg + piece : len;
-            uint32_t c = t == 0 ? 0xFFFFFFFFu : 0u;
-            for (uint32_t k = beg; k < end; k++) c = s_tab[(c ^ pb[sh + k]) & 0xFFu] ^ (c >> 8);
-            if (end > beg && end < len) c = crc_mul(c, crc_x8n(len - end));
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) c ^= (uint32_t)__shfl_xor((unsigned int)c, o, 64);
+            const uint32_t c = crc_wave_of_pieces(s_tab, pb + sh, len, t);
             if ((t & 63u) == 0) atomicXor(&s_acc, c);
         }
         __syncthreads();

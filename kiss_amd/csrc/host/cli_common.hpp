@@ -206,7 +206,12 @@ inline void usage_bam()
               << "                                 --rescue, --md, --ins-auto, --batch-reads and --pileup.  A read name of more than\n"
               << "                                 254 bytes, more than 65535 CIGAR operations on a line or a position of 2^31 or\n"
               << "                                 more in its record cannot be written as BAM and ends the run.  Without --bam every\n"
-              << "                                 byte of the output is what it was.\n";
+              << "                                 byte of the output is what it was.\n"
+              << "  --bam-compress                 with --bam: the header, every batch and the end-of-file block go out in COMPRESSED\n"
+              << "                                 BGZF blocks: DEFLATE (LZ77 matches, fixed or dynamic Huffman codes, whichever is\n"
+              << "                                 smallest for the block; a block that does not shrink stays stored), computed on the\n"
+              << "                                 device, one block per workgroup (kiss_hip_bgzf_deflate_host).  The file decompresses\n"
+              << "                                 to exactly what --bam alone writes and is smaller; no `samtools` pass is needed.\n";
 }
 
 inline void check(int rc, const char *where)
@@ -299,6 +304,7 @@ struct Args {
     kiss_hip_pileup_params pileup_params{0, KISS_HIP_HIT_SECONDARY, 0, 0};
     bool pileup_proper = false;      // --pileup-proper
     std::string bam;                 // fmindex_query ... --sam --bam FILE ('-': stdout)
+    bool bam_compress = false;       // --bam-compress: the BGZF blocks compressed on the device
 };
 
 inline bool given(const Args &a, const char *name) { return std::find(a.seen.begin(), a.seen.end(), name) != a.seen.end(); }
@@ -378,6 +384,7 @@ inline const Opt OPTIONS[] = {
     {"--pileup-min-mapq", nullptr, KISS_AT(pileup_params.min_mapq), true, {"--pileup"}},
     {"--pileup-proper", nullptr, KISS_AT(pileup_proper), true, {"--pileup", "--mates"}},
     {"--bam", nullptr, KISS_AT(bam), true, {"--sam"}},
+    {"--bam-compress", nullptr, KISS_AT(bam_compress), true, {"--bam"}},
 };
 #undef KISS_AT
 
@@ -454,6 +461,7 @@ inline Args parse(int argc, char **argv)
     a.pileup_params.proper_only = a.pileup_proper ? 1u : 0u;
     goes_with_through("--bam");
     if (given(a, "--bam") && a.bam.empty()) throw std::runtime_error("--bam needs a file name, or - for stdout (kiss --help-bam)");
+    goes_with_through("--bam-compress");
     if (given(a, "--mates")) { // the pair's MAPQ is on the scale of the reads'; the mates face each other
         a.both_strands = true;
         a.pair_params.mapq_coef = a.select_params.mapq_coef;

@@ -13,6 +13,7 @@
 #include "../../../include/kiss_hip_insert.h"
 #include "../../../include/kiss_hip_sam.h"
 #include "../../../include/kiss_hip_bam.h"
+#include "../../../include/kiss_hip_deflate.h"
 #include <iterator>
 
 namespace kiss_cli {
@@ -357,11 +358,13 @@ inline void sam_lines_device(StdoutWriter &w, const Args &a, const State &s, boo
 }
 
 // --bam FILE: the header (cli_bam.hpp), the records of every batch (kiss_hip_fmi_bam_host) and the end-of-file block, each framed
-// as BGZF blocks on the device (kiss_hip_bgzf_host) and written as it comes.  FILE is opened before a read is mapped.
+// as BGZF blocks on the device (kiss_hip_bgzf_host; with --bam-compress kiss_hip_bgzf_deflate_host, which compresses them) and
+// written as it comes.  FILE is opened before a read is mapped.
 struct BamOut {
     std::string path;
     std::FILE *file = nullptr;
     int device = 0;
+    bool compress = false;
     uint64_t records = 0, bytes = 0;
     BamOut() = default;
     BamOut(const BamOut &) = delete;
@@ -373,7 +376,7 @@ struct BamOut {
     bool on() const { return file != nullptr; }
     void open(const Args &a)
     {
-        path = a.bam, device = a.device;
+        path = a.bam, device = a.device, compress = a.bam_compress;
         file = path == "-" ? stdout : std::fopen(path.c_str(), "wb");
         if (!file) throw std::runtime_error("cannot open " + path);
     }
@@ -383,10 +386,18 @@ struct BamOut {
         const uint64_t total = n + (uint64_t)KISS_HIP_BGZF_OVERHEAD * ((n + KISS_HIP_BGZF_BLOCK_DEFAULT - 1) / KISS_HIP_BGZF_BLOCK_DEFAULT) +
                                (eof ? KISS_HIP_BGZF_EOF_BYTES : 0u);
         std::vector<uint8_t> out(total + 1);
-        kiss_hip_bgzf_report rep{};
-        check(kiss_hip_bgzf_host(n ? data : nullptr, n, 0, eof, out.data(), total, &rep, device), "kiss_hip_bgzf_host");
-        if (std::fwrite(out.data(), 1, rep.out_bytes, file) != rep.out_bytes) throw std::runtime_error("cannot write " + path);
-        bytes += rep.out_bytes;
+        uint64_t out_bytes = 0;
+        if (compress) { // (total is the worst case: every block stored)
+            kiss_hip_bgzf_deflate_report rep{};
+            check(kiss_hip_bgzf_deflate_host(n ? data : nullptr, n, 0, eof, out.data(), total, nullptr, 0, &rep, device), "kiss_hip_bgzf_deflate_host");
+            out_bytes = rep.out_bytes;
+        } else {
+            kiss_hip_bgzf_report rep{};
+            check(kiss_hip_bgzf_host(n ? data : nullptr, n, 0, eof, out.data(), total, &rep, device), "kiss_hip_bgzf_host");
+            out_bytes = rep.out_bytes;
+        }
+        if (std::fwrite(out.data(), 1, out_bytes, file) != out_bytes) throw std::runtime_error("cannot write " + path);
+        bytes += out_bytes;
     }
     void header(const RefRecords &ref, const char *version)
     {

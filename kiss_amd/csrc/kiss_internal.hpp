@@ -185,6 +185,10 @@ enum FmSlot {
     FM_SLOT_SAM_LINES,   // per line: its bytes, scanned
     // kiss_hip_fmi_pileup_dev (fm_pileup.hip)
     FM_SLOT_PILEUP_CTL,
+    // kiss_hip_bgzf_deflate_dev (bgzf_deflate.hip)
+    FM_SLOT_DEFLATE_TOKENS, // per resident workgroup: the tokens of the block it works on
+    FM_SLOT_DEFLATE_STAGE,  // the blocks at a fixed stride, before they are packed
+    FM_SLOT_DEFLATE_SIZES,  // per block: its bytes, scanned; the counters of the call
     FM_SLOT_COUNT
 };
 
@@ -276,6 +280,7 @@ struct kiss_hip_ctx {
     // scratch of the FM-index batch calls, kept between calls: one buffer per FmSlot
     void *fm_pool[FM_SLOT_COUNT] = {};
     uint64_t fm_pool_cap[FM_SLOT_COUNT] = {};
+    int cu_count = 0;         // the compute units of the device, asked for once (bgzf_deflate.hip: its persistent grid)
     hipEvent_t fm_ev[6] = {}; // the times of the FM-index reports (fm_internal.hpp: FmEvents; created by the first call that wants one)
     // near-end
     uint32_t *near_idx = nullptr, *near_fin = nullptr, *near_pos = nullptr, *near_tmp = nullptr, *near_tmp2 = nullptr; // place.hip: near_reserve

@@ -681,6 +681,8 @@ class FMIndex:
         BGZF blocks of the batch's BAM records, ready to append to a file behind the framed kiss_amd.bam_writer.bam_header(); written and
         framed on the device by kiss_hip_fmi_bam_dev and kiss_hip_bgzf_dev, include/kiss_hip_bam.h), bam_rec_index (records + 1, over
         the unframed records), bam_read_rec (Q + 1) and bam_report.
+        bam_compress (False; it needs bam): the blocks are compressed on the device (DEFLATE, kiss_hip_bgzf_deflate_dev,
+        include/kiss_hip_deflate.h); the result also has bam_block_index (blocks + 1, over bam) and bam_report the counts of the coding.
         pileup (None; it needs want_cigar): True, a dict of lo, hi, counts and the pileup parameters min_mapq (0), skip_flags (2:
         secondary hits) and proper_only (0), or an (8, W) int32 device tensor to add to (the dict's counts: such a tensor, or an
         (8, W) u32 array): also pileup -- the eight planes of kiss_amd.fm_pileup.PLANES over the text positions [lo, hi), default
@@ -766,6 +768,9 @@ class FMIndex:
         arguments of the lines, held against each other before anything runs"""
         sam, names, qual, ref_names = (given.pop(k, d) for k, d in (("sam", False), ("names", None), ("qual", None), ("ref_names", None)))
         bam = given.pop("bam", False)
+        bam_compress = given.pop("bam_compress", False)
+        if bam_compress and not bam:
+            raise ValueError("bam_compress belongs to bam=True")
         if not sam and not bam:
             if names is not None or qual is not None or ref_names is not None:
                 raise ValueError("names, qual and ref_names belong to sam=True")
@@ -781,7 +786,8 @@ class FMIndex:
             raise ValueError("ref_names has one name per record: bounds has R + 1 = %d entries" % b.size)
         if R > 1 and b is None:
             raise ValueError("ref_names with more than one name needs bounds")
-        return {"names": names, "qual": qual, "ref_names": ref_names, "bounds": b, "md": None, "sam": bool(sam), "bam": bool(bam)}
+        return {"names": names, "qual": qual, "ref_names": ref_names, "bounds": b, "md": None, "sam": bool(sam), "bam": bool(bam),
+                "bam_compress": bool(bam_compress)}
 
     def _sam_lines(self, t, ctx, d_alns, C, d_cigar, d_oidx, sel, so, d_pairs=None, d_source=None, first_alns=0):
         """map(sam=True): the lines of the hits of a select call (and the pairs of a pair call), from the buffers that are on the
@@ -842,7 +848,8 @@ class FMIndex:
             res.update(sam_arrays(sam_lines_dev(t.lib, ctx, self.device, Q, C, R, first_alns, **arrays)))
         if so["bam"]:  # (the records, then their blocks: both from the buffers on the device)
             from .bam_writer import bam_arrays, bam_records_dev
-            res.update(bam_arrays(t.lib, ctx, self.device, bam_records_dev(t.lib, ctx, self.device, Q, C, R, first_alns, **arrays)))
+            res.update(bam_arrays(t.lib, ctx, self.device, bam_records_dev(t.lib, ctx, self.device, Q, C, R, first_alns, **arrays),
+                                  compress=so["bam_compress"]))
         return res
 
     # ---- the mappings of two mates paired (kiss_hip_fmi_pair_dev; no reference counterpart) -----------------------------
