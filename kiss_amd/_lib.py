@@ -295,6 +295,12 @@ class BgzfDeflateReport(Report):
                                                "match_bytes")] + [(k, ctypes.c_float) for k in ("ms_total", "ms_block", "ms_scan", "ms_copy")]
 
 
+class BamSortReport(Report):
+    """kiss_hip_bam_sort_report (include/kiss_hip_bam_sort.h)"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("records", "bam_bytes", "unplaced", "longest", "bad", "first_bad")] + [
+        (k, ctypes.c_float) for k in ("ms_total", "ms_key", "ms_sort", "ms_copy")]
+
+
 class MdReport(Report):
     """kiss_hip_md_report (include/kiss_hip_md.h)"""
     _fields_ = [(k, ctypes.c_uint64) for k in ("items", "bad", "md_bytes", "mismatch_columns", "deleted_bases", "longest")] + [
@@ -535,6 +541,11 @@ def load(hooks=None):
         lib.kiss_hip_bgzf_deflate_host.argtypes = [vp, u64, u32, ctypes.c_int, vp, u64, vp, u64, ctypes.POINTER(BgzfDeflateReport), ctypes.c_int]
         for name in DEFLATE_EXPORTED_SYMBOLS:
             getattr(lib, name).restype = ctypes.c_int
+    if hasattr(lib, "kiss_hip_bam_sort_dev"):  # (as the BAM calls)
+        lib.kiss_hip_bam_sort_dev.argtypes = [vp, vp, u64, vp, u64, u32, vp, u64, vp, vp, ctypes.POINTER(BamSortReport), vp]
+        lib.kiss_hip_bam_sort_host.argtypes = [vp, u64, vp, u64, u32, vp, u64, vp, vp, ctypes.POINTER(BamSortReport), ctypes.c_int]
+        for name in BAM_SORT_EXPORTED_SYMBOLS:
+            getattr(lib, name).restype = ctypes.c_int
     lib.kiss_hip_fmi_insert_dev.argtypes = [vp, vp, vp, u64, vp, u64, ctypes.POINTER(InsertParams), vp, ctypes.POINTER(InsertReport), vp]
     lib.kiss_hip_fmi_insert_host.argtypes = [vp, vp, u64, vp, u64, ctypes.POINTER(InsertParams), vp, ctypes.POINTER(InsertReport),
                                              ctypes.c_int]
@@ -638,6 +649,9 @@ BAM_EXPORTED_SYMBOLS = ["kiss_hip_fmi_bam_dev", "kiss_hip_fmi_bam_host", "kiss_h
 BGZF_BLOCK_DEFAULT, BGZF_BLOCK_MAX, BGZF_OVERHEAD, BGZF_EOF_BYTES = 65280, 65505, 31, 28
 # every symbol include/kiss_hip_deflate.h declares (tests/test_deflate_abi.py)
 DEFLATE_EXPORTED_SYMBOLS = ["kiss_hip_bgzf_deflate_dev", "kiss_hip_bgzf_deflate_host"]
+# every symbol include/kiss_hip_bam_sort.h declares (tests/test_bam_sort_abi.py)
+BAM_SORT_EXPORTED_SYMBOLS = ["kiss_hip_bam_sort_dev", "kiss_hip_bam_sort_host"]
+BAM_RECORD_MIN = 36
 # every symbol include/kiss_hip_insert.h declares (tests/test_fm_insert_abi.py)
 INSERT_EXPORTED_SYMBOLS = ["kiss_hip_fmi_insert_dev", "kiss_hip_fmi_insert_host"]
 INSERT_MAX = 65535

@@ -4,7 +4,10 @@ with the CRC-32 of every block computed on the device (kiss_hip_bgzf_dev / _host
 and run the host entries; FMIndex.map(bam=True), map_pairs(bam=True) and map_file(bam=True) keep everything on the device
 (bam_records_dev, then bgzf_dev, no round trip between them); write_bam() writes a whole file.  The blocks are stored unless
 compression is asked for (bgzf_deflate / bgzf_deflate_dev, map(bam_compress=True), write_bam(compress=True): DEFLATE on the device,
-include/kiss_hip_deflate.h); `samtools sort` and every other BAM reader take either kind as it is.  All arithmetic runs in libkiss_hip.so; there is no CPU path."""
+include/kiss_hip_deflate.h); `samtools sort` and every other BAM reader take either kind as it is.  The records
+come out in read order unless they are sorted: bam_sort / bam_sort_dev put unframed records into coordinate order on the device
+(kiss_hip_bam_sort_host / _dev, include/kiss_hip_bam_sort.h), map(bam_sort=True) does so for a batch and
+write_bam(sort=True) for a whole file, whose header then says SO:coordinate.  All arithmetic runs in libkiss_hip.so; there is no CPU path."""
 import ctypes
 import struct
 
@@ -12,16 +15,31 @@ import numpy as np
 
 from . import _lib
 from ._frame import sized
-from .fm_sam import _bytes, sam_header
+from .fm_sam import _bytes, sam_header as _sam_header
 from .sam_writer import _host_input, sam_input
 from .sorter import _check
 
 BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
 
 
-def bam_header(ref_names, bounds, version):
-    """the BAM header, unframed: the magic, the text of sam_header, and the records with their lengths bounds[r + 1] - bounds[r]"""
-    text = sam_header(ref_names, bounds, version)
+SORT_ORDERS = ("unsorted", "coordinate")
+
+
+def sam_header(ref_names, bounds, version, sort_order="unsorted"):
+    """kiss_amd.sam_header -- @HD, one @SQ per record, @PG, as bytes -- with the SO: word of the @HD line chosen: "coordinate" for
+    records that bam_sort has put in order.  Only that word changes; the default is kiss_amd.sam_header byte for byte"""
+    if sort_order not in SORT_ORDERS:
+        raise ValueError("sort_order is one of %s" % ", ".join(SORT_ORDERS))
+    text = _sam_header(ref_names, bounds, version)
+    first, rest = text.split(b"\n", 1)
+    assert first.endswith(b"\tSO:unsorted")
+    return first[:-len(b"unsorted")] + sort_order.encode() + b"\n" + rest
+
+
+def bam_header(ref_names, bounds, version, sort_order="unsorted"):
+    """the BAM header, unframed: the magic, the text of sam_header (sort_order: its SO: word), and the records with their lengths
+    bounds[r + 1] - bounds[r]"""
+    text = sam_header(ref_names, bounds, version, sort_order)
     text = text if isinstance(text, bytes) else str(text).encode()
     names = [_bytes(x) for x in ref_names]
     b = np.ascontiguousarray(bounds, dtype=np.uint64).ravel()
@@ -90,6 +108,81 @@ def bam_records_dev(lib, ctx, device, Q, C, R, first_alns=0, want_rec_index=True
     _refuse_bad(rc, rep, "kiss_hip_fmi_bam_dev")
     _check(rc, "kiss_hip_fmi_bam_dev", ctx._ctx)
     return {"d_bam": d_bam, "d_rec_index": d_ri, "d_read_rec": d_rr, "rep": rep, "keep": tensors}
+
+
+def _refuse_unsortable(rc, rep, entry):
+    if rc == _lib.KISS_HIP_E_INVALID and rep.bad:
+        err = _lib.KissHipError(rc, entry, "%d bad record(s), the first one record %d" % (rep.bad, rep.first_bad))
+        err.report = rep.as_dict()
+        raise err
+
+
+def bam_sort(bam, rec_index, n_ref, device=0, hooks=None):
+    """Unframed BAM records (bam: bytes or a uint8 array; rec_index: records + 1, the CSR over them, as bam_records gives both) in
+    coordinate order -- reference, then position, the records without a place last, equal places in input order --, sorted on the
+    device through the host entry.  n_ref: the references of the header.  Returns dict(bam: the sorted records as uint8, rec_index:
+    their CSR, order: order[s] is the input index of the record in slot s, report).  Input that is not such records (see the
+    header) raises KissHipError; its report is the exception's `report`."""
+    raw = np.frombuffer(bam, np.uint8) if isinstance(bam, (bytes, bytearray, memoryview)) else np.ascontiguousarray(bam, dtype=np.uint8).ravel()
+    ri = np.ascontiguousarray(rec_index, dtype=np.uint64).ravel()
+    if ri.size < 1:
+        raise ValueError("rec_index has records + 1 entries")
+    records = ri.size - 1
+    out = np.zeros(max(raw.size, 1), np.uint8)
+    out_index = np.zeros(records + 1, np.uint64)
+    order = np.zeros(max(records, 1), np.uint32)
+    rep = _lib.BamSortReport()
+    rc = _lib.load(hooks).kiss_hip_bam_sort_host(raw.ctypes.data if raw.size else None, raw.size, ri.ctypes.data, records, int(n_ref), out.ctypes.data,
+                                                raw.size, out_index.ctypes.data, order.ctypes.data, ctypes.byref(rep), int(device))
+    _refuse_unsortable(rc, rep, "kiss_hip_bam_sort_host")
+    _check(rc, "kiss_hip_bam_sort_host")
+    return {"bam": out[:raw.size], "rec_index": out_index, "order": order[:records], "report": rep.as_dict()}
+
+
+def bam_sort_dev(lib, ctx, device, d_bam, n, d_rec_index, records, n_ref, want_order=True, stream=None):
+    """the device entry on torch tensors: the first n bytes of the uint8 tensor d_bam and the int64 tensor d_rec_index (records + 1)
+    -> dict of d_bam (n sorted bytes), d_rec_index (records + 1), d_order (records, int32 holding u32; None without want_order) and
+    rep.  ctx sorts the records in its work arrays: one made for max_n >= 3.3 * records holds them.  stream: None, the current
+    stream of torch"""
+    import torch
+    dev = torch.device("cuda", device)
+    vp = ctypes.c_void_p
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    n, records = int(n), int(records)
+    d_out = torch.zeros(max(n, 1), dtype=torch.uint8, device=dev)
+    d_index = torch.zeros(records + 1, dtype=torch.int64, device=dev)
+    d_order = torch.zeros(max(records, 1), dtype=torch.int32, device=dev) if want_order else None
+    rep = _lib.BamSortReport()
+    rc = lib.kiss_hip_bam_sort_dev(ctx._ctx, vp(d_bam.data_ptr()) if n else None, n, vp(d_rec_index.data_ptr()), records, int(n_ref),
+                                   vp(d_out.data_ptr()), n, vp(d_index.data_ptr()), vp(d_order.data_ptr()) if want_order else None,
+                                   ctypes.byref(rep), vp(stream) if stream else None)
+    _refuse_unsortable(rc, rep, "kiss_hip_bam_sort_dev")
+    _check(rc, "kiss_hip_bam_sort_dev", ctx._ctx)
+    return {"d_bam": d_out[:n] if n else d_out, "d_rec_index": d_index, "d_order": d_order[:records] if want_order else None, "rep": rep}
+
+
+def bam_sorted(lib, ctx, device, out, n_ref):
+    """the tensors of bam_records_dev with the records sorted (map(bam_sort=True)): the same dict with d_bam and d_rec_index
+    replaced, d_order and sort_rep added.  It asks bam_records_dev for the record index it may have left out."""
+    if out["d_rec_index"] is None:
+        raise ValueError("bam_sort needs the record index: bam_records_dev(want_rec_index=True)")
+    got = bam_sort_dev(lib, ctx, device, out["d_bam"], int(out["rep"].bam_bytes), out["d_rec_index"], int(out["rep"].records), n_ref)
+    return dict(out, d_bam=got["d_bam"], d_rec_index=got["d_rec_index"], d_order=got["d_order"], sort_rep=got["rep"])
+
+
+def _sort_counts(rep):
+    return dict(unplaced=int(rep.unplaced), ms_sort_total=float(rep.ms_total), ms_sort_key=float(rep.ms_key), ms_sort=float(rep.ms_sort),
+                ms_sort_copy=float(rep.ms_copy))
+
+
+def bam_unframed(out):
+    """the tensors of bam_records_dev as they are, for a caller that frames them later (write_bam(sort=True)): bam_dev = (the uint8
+    tensor of the records, bytes, the int64 tensor of the record index, records), on the device; bam_read_rec and bam_report as
+    bam_arrays gives them"""
+    rep = out["rep"]
+    return {"bam_dev": (out["d_bam"], int(rep.bam_bytes), out["d_rec_index"], int(rep.records)),
+            "bam_read_rec": out["d_read_rec"].cpu().numpy().view(np.uint64), "bam_report": rep.as_dict()}
 
 
 def _block_bytes(block_bytes):
@@ -173,11 +266,14 @@ def bgzf_deflate_dev(lib, ctx, device, d_data, n, block_bytes=65280, eof=False, 
 
 def bam_arrays(lib, ctx, device, out, block_bytes=65280, compress=False):
     """the tensors of bam_records_dev framed on the device, as what map(bam=True) adds to its result; compress: the blocks are
-    compressed (bam_block_index and the counts of the coding beside them)"""
+    compressed (bam_block_index and the counts of the coding beside them); after bam_sorted: bam_order and the sort's counts"""
     total = int(out["rep"].bam_bytes)
     ri = out["d_rec_index"]
     rep = out["rep"].as_dict()
     more = {}
+    if out.get("sort_rep") is not None:
+        rep.update(_sort_counts(out["sort_rep"]))
+        more["bam_order"] = out["d_order"].cpu().numpy().view(np.uint32)
     if compress:
         d_blocks, d_index, frep = bgzf_deflate_dev(lib, ctx, device, out["d_bam"], total, block_bytes)
         rep.update({k: int(getattr(frep, k)) for k in ("stored_blocks", "fixed_blocks", "dynamic_blocks", "literals", "matches", "match_bytes")})
@@ -189,30 +285,82 @@ def bam_arrays(lib, ctx, device, out, block_bytes=65280, compress=False):
             "bam_read_rec": out["d_read_rec"].cpu().numpy().view(np.uint64), "bam_report": rep, **more}
 
 
-def write_bam(path, index, reads1, text, reads2=None, ref_names=None, bounds=None, version=None, compress=False, **params):
+def write_bam(path, index, reads1, text, reads2=None, ref_names=None, bounds=None, version=None, compress=False, sort=False, **params):
     """A whole BAM file of the read file(s) mapped by `index` (batches.map_file, which has the other arguments): the framed header,
     the blocks of every batch, the end-of-file block.  path: a file name, or a binary file object.  compress: the header and the
-    batches in compressed blocks (bgzf_deflate, map_file(bam_compress=True)).  -> the batches, records and bytes written"""
+    batches in compressed blocks (bgzf_deflate, map_file(bam_compress=True)).  -> the batches, records and bytes written.
+    sort: the records of the WHOLE file in coordinate order and SO:coordinate in the header.  The unframed records and the record
+    index of every batch then stay on the device; behind the last batch they are concatenated, sorted once (bam_sort_dev) and
+    framed once, and only then is anything written to path.  Device memory: about twice the file's uncompressed record bytes (the
+    records and their sorted copy; while the batches are concatenated, or the blocks framed, one of the two is held a second time)
+    plus 12 bytes per record (the index and the permutation), beside the sort's work arrays.  When that memory is not there
+    MemoryError names the bytes asked for and nothing has been written.  The result also carries sort_report."""
     from .batches import map_file
     if ref_names is None or bounds is None:
         raise ValueError("a BAM file needs ref_names and bounds")
     if version is None:  # (@PG VN: the library's version number, as kiss_hip_version() gives it)
         version = str(_lib.load(index._hooks).kiss_hip_version())
-    head = (bgzf_deflate if compress else bgzf)(bam_header(ref_names, bounds, version), device=index.device, hooks=index._hooks)
-    if compress:
+    frame = bgzf_deflate if compress else bgzf
+    head = frame(bam_header(ref_names, bounds, version, "coordinate" if sort else "unsorted"), device=index.device, hooks=index._hooks)
+    if compress and not sort:
         params["bam_compress"] = True
-    f = open(path, "wb") if isinstance(path, (str, bytes)) or hasattr(path, "__fspath__") else path
     done = {"batches": 0, "records": 0, "bytes": len(head)}
+    if sort:
+        blocks, done["sort_report"] = _sorted_file(index, len(ref_names), compress,
+                                                   map_file(index, reads1, text, reads2, bam=True, _bam_unframed=True, ref_names=ref_names, bounds=bounds,
+                                                            **params), done)
+    f = open(path, "wb") if isinstance(path, (str, bytes)) or hasattr(path, "__fspath__") else path
     try:
         f.write(head)
-        for res in map_file(index, reads1, text, reads2, bam=True, ref_names=ref_names, bounds=bounds, **params):
-            f.write(res["bam"])
-            done["batches"] += 1
-            done["records"] += int(res["bam_report"]["records"])
-            done["bytes"] += len(res["bam"])
+        if sort:
+            f.write(blocks)
+            done["bytes"] += len(blocks)
+        else:
+            for res in map_file(index, reads1, text, reads2, bam=True, ref_names=ref_names, bounds=bounds, **params):
+                f.write(res["bam"])
+                done["batches"] += 1
+                done["records"] += int(res["bam_report"]["records"])
+                done["bytes"] += len(res["bam"])
         f.write(BGZF_EOF)
         done["bytes"] += len(BGZF_EOF)
     finally:
         if f is not path:
             f.close()
     return done
+
+
+def _sorted_file(index, n_ref, compress, batches, done):
+    """write_bam(sort=True): the records of all `batches` (results of map_file(_bam_unframed=True)) sorted and framed on the device
+    -> (the blocks as bytes, the sort's report); done: the counts so far"""
+    import torch
+    dev = torch.device("cuda", index.device)
+    parts, total, records = [], 0, 0
+    for res in batches:
+        d_bam, n, d_ri, recs = res["bam_dev"]
+        done["batches"] += 1
+        if recs:
+            parts.append((d_bam[:n], d_ri[1:recs + 1] + total))  # (the index of the batch rebased onto the bytes in front of it)
+            total += n
+            records += recs
+    done["records"] = records
+    asked = 2 * total + 12 * records + 8
+    lib = _lib.load(index._hooks)
+    try:
+        d_all = torch.cat([p[0] for p in parts]) if parts else torch.zeros(1, dtype=torch.uint8, device=dev)
+        d_index = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev)] + [p[1] for p in parts])
+        del parts
+        ctx = index._context_to_sort(index._context(1 << 20), records)
+        got = bam_sort_dev(lib, ctx, index.device, d_all, total, d_index, records, n_ref, want_order=False)
+        del d_all, d_index
+        if compress:
+            d_blocks, _, _ = bgzf_deflate_dev(lib, ctx, index.device, got["d_bam"], total)
+        else:
+            d_blocks, _ = bgzf_dev(lib, ctx, index.device, got["d_bam"], total)
+    except torch.cuda.OutOfMemoryError:
+        raise MemoryError("write_bam(sort=True): the device does not hold the %d bytes the sort asks for (%d record bytes twice, 12 bytes for "
+                          "each of %d records)" % (asked, total, records)) from None
+    except _lib.KissHipError as e:
+        if e.status == _lib.KISS_HIP_E_NOMEM:
+            raise MemoryError("write_bam(sort=True): the device does not hold the %d bytes the sort asks for" % asked) from None
+        raise
+    return d_blocks.cpu().numpy().tobytes(), dict(got["rep"].as_dict())

@@ -274,6 +274,8 @@ def map_file(index, reads1, text, reads2=None, batch_reads=100000, chunk_bytes=6
     records (bam_rec_index, bam_read_rec, bam_report, as map(bam=True) gives them); the blocks of the batches, one after the other
     behind the framed header and in front of the end-of-file block, are the file (kiss_amd.bam_writer.write_bam does that).
     bam_compress=True (with bam=True): the blocks are compressed on the device, as map(bam_compress=True) does it.
+    bam_sort=True is a ValueError: batches sorted one by one do not concatenate into a sorted file.  A sorted file is written by
+    kiss_amd.bam_writer.write_bam(sort=True), which keeps the records of every batch on the device and sorts them once.
     pileup=True (or a dict, or an (8, W) int32 device tensor to add to, as map(pileup=...) takes them): ONE tensor of counts,
     allocated once, to which every batch adds (kiss_hip_fmi_pileup_dev with accumulate): its size depends on the text and not on
     the file.  Every batch's result carries that tensor as pileup -- the sums up to and including the batch -- and
@@ -281,9 +283,14 @@ def map_file(index, reads1, text, reads2=None, batch_reads=100000, chunk_bytes=6
     if "names" in params or "qual" in params:
         raise ValueError("map_file takes names and qualities from the file")
     sam, bam, ref_names = bool(params.pop("sam", False)), bool(params.pop("bam", False)), params.pop("ref_names", None)
+    if params.pop("bam_sort", False):
+        raise ValueError("map_file(bam_sort=True): batches sorted one by one are not a sorted file; kiss_amd.bam_writer.write_bam(sort=True) "
+                         "sorts the whole file")
     packed = {"bam_compress": True} if params.pop("bam_compress", False) else {}
     if packed and not bam:
         raise ValueError("bam_compress belongs to bam=True")
+    if params.pop("_bam_unframed", False):  # (write_bam(sort=True): the records of every batch stay on the device, unframed)
+        packed["_bam_unframed"] = True
     lines = lambda b: dict(sam=sam, bam=bam, names=b["names"], qual=b["qual"], ref_names=ref_names, **packed) if sam or bam else {}  # noqa: E731
     po = index._pileup_options({"pileup": params.pop("pileup", None)}, params.get("want_cigar", True))
     from .fm_pair import pair_params as make_pair_params

@@ -211,7 +211,14 @@ inline void usage_bam()
               << "                                 BGZF blocks: DEFLATE (LZ77 matches, fixed or dynamic Huffman codes, whichever is\n"
               << "                                 smallest for the block; a block that does not shrink stays stored), computed on the\n"
               << "                                 device, one block per workgroup (kiss_hip_bgzf_deflate_host).  The file decompresses\n"
-              << "                                 to exactly what --bam alone writes and is smaller; no `samtools` pass is needed.\n";
+              << "                                 to exactly what --bam alone writes and is smaller; no `samtools` pass is needed.\n"
+              << "  --bam-sort                     with --bam: the records of the WHOLE file in coordinate order (reference, then\n"
+              << "                                 position; records without a place last; equal places in the order of the reads),\n"
+              << "                                 sorted on the device (kiss_hip_bam_sort_host), and SO:coordinate in the @HD line:\n"
+              << "                                 `samtools index` takes the file as it is and no `samtools sort` pass is needed.\n"
+              << "                                 The unframed records of every batch are kept in host memory until the last one,\n"
+              << "                                 then sorted once, framed and written: nothing reaches FILE before that.  Works\n"
+              << "                                 with --batch-reads, --bam-compress and --bam -.\n";
 }
 
 inline void check(int rc, const char *where)
@@ -305,6 +312,7 @@ struct Args {
     bool pileup_proper = false;      // --pileup-proper
     std::string bam;                 // fmindex_query ... --sam --bam FILE ('-': stdout)
     bool bam_compress = false;       // --bam-compress: the BGZF blocks compressed on the device
+    bool bam_sort = false;           // --bam-sort: the records of the whole file in coordinate order, sorted on the device
 };
 
 inline bool given(const Args &a, const char *name) { return std::find(a.seen.begin(), a.seen.end(), name) != a.seen.end(); }
@@ -385,6 +393,7 @@ inline const Opt OPTIONS[] = {
     {"--pileup-proper", nullptr, KISS_AT(pileup_proper), true, {"--pileup", "--mates"}},
     {"--bam", nullptr, KISS_AT(bam), true, {"--sam"}},
     {"--bam-compress", nullptr, KISS_AT(bam_compress), true, {"--bam"}},
+    {"--bam-sort", nullptr, KISS_AT(bam_sort), true, {"--bam"}},
 };
 #undef KISS_AT
 
@@ -461,7 +470,7 @@ inline Args parse(int argc, char **argv)
     a.pileup_params.proper_only = a.pileup_proper ? 1u : 0u;
     goes_with_through("--bam");
     if (given(a, "--bam") && a.bam.empty()) throw std::runtime_error("--bam needs a file name, or - for stdout (kiss --help-bam)");
-    goes_with_through("--bam-compress");
+    goes_with_through("--bam-sort");
     if (given(a, "--mates")) { // the pair's MAPQ is on the scale of the reads'; the mates face each other
         a.both_strands = true;
         a.pair_params.mapq_coef = a.select_params.mapq_coef;

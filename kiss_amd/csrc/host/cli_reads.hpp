@@ -8,11 +8,13 @@
 #include "cli_batches.hpp"
 #include "cli_pileup.hpp"
 #include "cli_bam.hpp"
+#include "cli_bam_sort.hpp"
 #include "../../../include/kiss_hip_reads.h"
 #include "../../../include/kiss_hip_md.h"
 #include "../../../include/kiss_hip_insert.h"
 #include "../../../include/kiss_hip_sam.h"
 #include "../../../include/kiss_hip_bam.h"
+#include "../../../include/kiss_hip_bam_sort.h"
 #include "../../../include/kiss_hip_deflate.h"
 #include <iterator>
 
@@ -360,12 +362,18 @@ inline void sam_lines_device(StdoutWriter &w, const Args &a, const State &s, boo
 // --bam FILE: the header (cli_bam.hpp), the records of every batch (kiss_hip_fmi_bam_host) and the end-of-file block, each framed
 // as BGZF blocks on the device (kiss_hip_bgzf_host; with --bam-compress kiss_hip_bgzf_deflate_host, which compresses them) and
 // written as it comes.  FILE is opened before a read is mapped.
+// --bam-sort: the header and the unframed records of every batch are kept (cli_bam_sort.hpp) until close(), which sorts the records
+// of the whole file on the device (kiss_hip_bam_sort_host) and only then frames and writes the header, with SO:coordinate, the
+// records and the end-of-file block.
 struct BamOut {
     std::string path;
     std::FILE *file = nullptr;
     int device = 0;
-    bool compress = false;
+    bool compress = false, sort = false;
     uint64_t records = 0, bytes = 0;
+    BamSortRecords kept;     // --bam-sort: the records so far
+    std::string kept_header; // ... and the header, unframed
+    uint32_t n_ref = 0;
     BamOut() = default;
     BamOut(const BamOut &) = delete;
     BamOut &operator=(const BamOut &) = delete;
@@ -376,7 +384,7 @@ struct BamOut {
     bool on() const { return file != nullptr; }
     void open(const Args &a)
     {
-        path = a.bam, device = a.device, compress = a.bam_compress;
+        path = a.bam, device = a.device, compress = a.bam_compress, sort = a.bam_sort;
         file = path == "-" ? stdout : std::fopen(path.c_str(), "wb");
         if (!file) throw std::runtime_error("cannot open " + path);
     }
@@ -403,6 +411,11 @@ struct BamOut {
     {
         std::string text;
         sam_header(text, ref, version);
+        if (sort) {
+            kept_header = bam_header(sam_header_coordinate(text), ref.names, ref.bounds);
+            n_ref = (uint32_t)ref.names.size();
+            return;
+        }
         const std::string h = bam_header(text, ref.names, ref.bounds);
         framed(reinterpret_cast<const uint8_t *>(h.data()), h.size(), 0);
     }
@@ -412,20 +425,41 @@ struct BamOut {
         if (!s.Q) return;
         const DeviceLinesInput d(s, paired);
         std::vector<uint8_t> bam(1);
-        std::vector<uint64_t> read_rec(s.Q + 1);
+        std::vector<uint64_t> read_rec(s.Q + 1), rec_index(1);
         kiss_hip_bam_report rep{};
         const int rc = sized_call(bam, rep.bam_bytes, [&](uint64_t capacity) {
-            return kiss_hip_fmi_bam_host(&d.in, bam.data(), capacity, nullptr, 0, read_rec.data(), &rep, device);
+            if (!sort) return kiss_hip_fmi_bam_host(&d.in, bam.data(), capacity, nullptr, 0, read_rec.data(), &rep, device);
+            if (rec_index.size() < rep.records + 1) rec_index.resize(rep.records + 1); // (the sizing call has left the count)
+            return kiss_hip_fmi_bam_host(&d.in, bam.data(), capacity, rec_index.data(), rec_index.size() - 1, read_rec.data(), &rep, device);
         });
         if (rc == KISS_HIP_E_INVALID && rep.bad)
             throw std::runtime_error("fmindex_query --bam: " + std::to_string(rep.bad) + " reads cannot be written as BAM (kiss --help-bam), the first is read " +
                                      std::to_string(s.first + rep.first_bad));
         check(rc, "kiss_hip_fmi_bam_host");
-        framed(bam.data(), rep.bam_bytes, 0);
+        if (sort) kept.add(bam.data(), rep.bam_bytes, rec_index.data(), rep.records);
+        else framed(bam.data(), rep.bam_bytes, 0);
         records += rep.records;
+    }
+    // --bam-sort: the whole file, once
+    void sorted()
+    {
+        const uint64_t n = kept.bytes.size();
+        std::vector<uint8_t> out(n + 1);
+        kiss_hip_bam_sort_report rep{};
+        const int rc = kiss_hip_bam_sort_host(n ? kept.bytes.data() : nullptr, n, kept.index.data(), kept.records(), n_ref, out.data(), n, nullptr, nullptr,
+                                              &rep, device);
+        if (rc == KISS_HIP_E_INVALID && rep.bad)
+            throw std::runtime_error("fmindex_query --bam-sort: " + std::to_string(rep.bad) + " records cannot be sorted, the first is record " +
+                                     std::to_string(rep.first_bad));
+        check(rc, "kiss_hip_bam_sort_host");
+        BamSortRecords().bytes.swap(kept.bytes); // (the unsorted copy is not needed any more)
+        framed(reinterpret_cast<const uint8_t *>(kept_header.data()), kept_header.size(), 0);
+        framed(out.data(), n, 0);
+        std::fprintf(stderr, "[info] bam sort: records: %llu, unplaced: %llu, longest record: %llu\n", (ull)rep.records, (ull)rep.unplaced, (ull)rep.longest);
     }
     void close()
     {
+        if (sort) sorted();
         framed(nullptr, 0, 1);
         if (std::fflush(file) != 0) throw std::runtime_error("cannot write " + path);
         std::fprintf(stderr, "[info] bam: records: %llu, bytes: %llu\n", (ull)records, (ull)bytes);

@@ -30,6 +30,8 @@
 //       --bam FILE  with --sam: BAM to FILE ('-': stdout) in the place of the SAM lines; records and BGZF blocks written on the
 //                 device   kiss_hip_fmi_bam_host, kiss_hip_bgzf_host (cli_bam.hpp; kiss --help-bam)
 //       --bam-compress  with --bam: the BGZF blocks compressed on the device (DEFLATE)   kiss_hip_bgzf_deflate_host
+//       --bam-sort  with --bam: the records of the whole file in coordinate order, sorted once on the device behind the last
+//                 batch, SO:coordinate in the header   kiss_hip_bam_sort_host (cli_bam_sort.hpp; kiss --help-bam)
 //   * -g / --generic with any of the three: the file is a text over the byte alphabet, byte for byte (no FASTA rule, no newline
 //     stripping, no % 4): kiss_hip_suffix_sort_u8 (-k, -s ignored), kiss_hip_lcp_u8, kiss_hip_fmi8_build_host -> <file>.fmi8
 //     (DESIGN.md 4.7), kiss_hip_fmi8_query_host.  One device, no lookup table, no mismatches.  The reference rejects -g.

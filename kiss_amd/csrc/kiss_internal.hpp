@@ -189,6 +189,9 @@ enum FmSlot {
     FM_SLOT_DEFLATE_TOKENS, // per resident workgroup: the tokens of the block it works on
     FM_SLOT_DEFLATE_STAGE,  // the blocks at a fixed stride, before they are packed
     FM_SLOT_DEFLATE_SIZES,  // per block: its bytes, scanned; the counters of the call
+    // kiss_hip_bam_sort_dev (bam_sort.hip)
+    FM_SLOT_BAM_SORT_CTL,
+    FM_SLOT_BAM_SORT_INDEX, // per sorted slot: the bytes of its record, scanned
     FM_SLOT_COUNT
 };
 

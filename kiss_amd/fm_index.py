@@ -683,6 +683,12 @@ class FMIndex:
         the unframed records), bam_read_rec (Q + 1) and bam_report.
         bam_compress (False; it needs bam): the blocks are compressed on the device (DEFLATE, kiss_hip_bgzf_deflate_dev,
         include/kiss_hip_deflate.h); the result also has bam_block_index (blocks + 1, over bam) and bam_report the counts of the coding.
+        bam_sort (False; it needs bam, and goes with bam_compress): the records of the batch are put into coordinate order on the
+        device between the record call and the framing (kiss_hip_bam_sort_dev, include/kiss_hip_bam_sort.h): bam holds the sorted
+        records and bam_rec_index is their CSR; the new bam_order (records, u32) says which record stands in every slot --
+        bam_read_rec keeps counting the records as they were written, so record bam_read_rec[q] of read q is in the slot s with
+        bam_order[s] == bam_read_rec[q] --, and bam_report gains unplaced and the times of the sort.  (A FILE is sorted as a whole
+        by kiss_amd.bam_writer.write_bam(sort=True): sorted batches do not concatenate into a sorted file.)
         pileup (None; it needs want_cigar): True, a dict of lo, hi, counts and the pileup parameters min_mapq (0), skip_flags (2:
         secondary hits) and proper_only (0), or an (8, W) int32 device tensor to add to (the dict's counts: such a tensor, or an
         (8, W) u32 array): also pileup -- the eight planes of kiss_amd.fm_pileup.PLANES over the text positions [lo, hi), default
@@ -769,8 +775,12 @@ class FMIndex:
         sam, names, qual, ref_names = (given.pop(k, d) for k, d in (("sam", False), ("names", None), ("qual", None), ("ref_names", None)))
         bam = given.pop("bam", False)
         bam_compress = given.pop("bam_compress", False)
+        bam_sort = given.pop("bam_sort", False)
+        bam_unframed = given.pop("_bam_unframed", False)  # (write_bam(sort=True): the records stay on the device, unframed)
         if bam_compress and not bam:
             raise ValueError("bam_compress belongs to bam=True")
+        if (bam_sort or bam_unframed) and not bam:
+            raise ValueError("bam_sort belongs to bam=True")
         if not sam and not bam:
             if names is not None or qual is not None or ref_names is not None:
                 raise ValueError("names, qual and ref_names belong to sam=True")
@@ -787,7 +797,7 @@ class FMIndex:
         if R > 1 and b is None:
             raise ValueError("ref_names with more than one name needs bounds")
         return {"names": names, "qual": qual, "ref_names": ref_names, "bounds": b, "md": None, "sam": bool(sam), "bam": bool(bam),
-                "bam_compress": bool(bam_compress)}
+                "bam_compress": bool(bam_compress), "bam_sort": bool(bam_sort), "bam_unframed": bool(bam_unframed)}
 
     def _sam_lines(self, t, ctx, d_alns, C, d_cigar, d_oidx, sel, so, d_pairs=None, d_source=None, first_alns=0):
         """map(sam=True): the lines of the hits of a select call (and the pairs of a pair call), from the buffers that are on the
@@ -847,9 +857,15 @@ class FMIndex:
         if so["sam"]:
             res.update(sam_arrays(sam_lines_dev(t.lib, ctx, self.device, Q, C, R, first_alns, **arrays)))
         if so["bam"]:  # (the records, then their blocks: both from the buffers on the device)
-            from .bam_writer import bam_arrays, bam_records_dev
-            res.update(bam_arrays(t.lib, ctx, self.device, bam_records_dev(t.lib, ctx, self.device, Q, C, R, first_alns, **arrays),
-                                  compress=so["bam_compress"]))
+            from .bam_writer import bam_arrays, bam_records_dev, bam_sorted, bam_unframed
+            out = bam_records_dev(t.lib, ctx, self.device, Q, C, R, first_alns, **arrays)
+            if so["bam_unframed"]:
+                res.update(bam_unframed(out))
+            else:
+                if so["bam_sort"]:
+                    ctx = self._context_to_sort(ctx, int(out["rep"].records))
+                    out = bam_sorted(t.lib, ctx, self.device, out, R)
+                res.update(bam_arrays(t.lib, ctx, self.device, out, compress=so["bam_compress"]))
         return res
 
     # ---- the mappings of two mates paired (kiss_hip_fmi_pair_dev; no reference counterpart) -----------------------------
