@@ -301,6 +301,13 @@ class BamSortReport(Report):
         (k, ctypes.c_float) for k in ("ms_total", "ms_key", "ms_sort", "ms_copy")]
 
 
+class BaiReport(Report):
+    """kiss_hip_bai_report (include/kiss_hip_bai.h)"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("records", "bam_bytes", "bai_bytes", "chunks", "bins", "windows", "mapped", "unmapped_placed",
+                                                "no_coor", "bad", "first_bad")] + [
+        (k, ctypes.c_float) for k in ("ms_total", "ms_record", "ms_window", "ms_sort", "ms_emit")]
+
+
 class MdReport(Report):
     """kiss_hip_md_report (include/kiss_hip_md.h)"""
     _fields_ = [(k, ctypes.c_uint64) for k in ("items", "bad", "md_bytes", "mismatch_columns", "deleted_bases", "longest")] + [
@@ -546,6 +553,11 @@ def load(hooks=None):
         lib.kiss_hip_bam_sort_host.argtypes = [vp, u64, vp, u64, u32, vp, u64, vp, vp, ctypes.POINTER(BamSortReport), ctypes.c_int]
         for name in BAM_SORT_EXPORTED_SYMBOLS:
             getattr(lib, name).restype = ctypes.c_int
+    if hasattr(lib, "kiss_hip_bai_dev"):  # (as the BAM calls)
+        lib.kiss_hip_bai_dev.argtypes = [vp, vp, u64, vp, u64, u32, u32, vp, u64, vp, u64, ctypes.POINTER(BaiReport), vp]
+        lib.kiss_hip_bai_host.argtypes = [vp, u64, vp, u64, u32, u32, vp, u64, vp, u64, ctypes.POINTER(BaiReport), ctypes.c_int]
+        for name in BAI_EXPORTED_SYMBOLS:
+            getattr(lib, name).restype = ctypes.c_int
     lib.kiss_hip_fmi_insert_dev.argtypes = [vp, vp, vp, u64, vp, u64, ctypes.POINTER(InsertParams), vp, ctypes.POINTER(InsertReport), vp]
     lib.kiss_hip_fmi_insert_host.argtypes = [vp, vp, u64, vp, u64, ctypes.POINTER(InsertParams), vp, ctypes.POINTER(InsertReport),
                                              ctypes.c_int]
@@ -652,6 +664,9 @@ DEFLATE_EXPORTED_SYMBOLS = ["kiss_hip_bgzf_deflate_dev", "kiss_hip_bgzf_deflate_
 # every symbol include/kiss_hip_bam_sort.h declares (tests/test_bam_sort_abi.py)
 BAM_SORT_EXPORTED_SYMBOLS = ["kiss_hip_bam_sort_dev", "kiss_hip_bam_sort_host"]
 BAM_RECORD_MIN = 36
+# every symbol include/kiss_hip_bai.h declares (tests/test_bai_abi.py)
+BAI_EXPORTED_SYMBOLS = ["kiss_hip_bai_dev", "kiss_hip_bai_host"]
+BAI_PSEUDO_BIN, BAI_MAX_END = 37450, 1 << 29
 # every symbol include/kiss_hip_insert.h declares (tests/test_fm_insert_abi.py)
 INSERT_EXPORTED_SYMBOLS = ["kiss_hip_fmi_insert_dev", "kiss_hip_fmi_insert_host"]
 INSERT_MAX = 65535

@@ -7,8 +7,11 @@ compression is asked for (bgzf_deflate / bgzf_deflate_dev, map(bam_compress=True
 include/kiss_hip_deflate.h); `samtools sort` and every other BAM reader take either kind as it is.  The records
 come out in read order unless they are sorted: bam_sort / bam_sort_dev put unframed records into coordinate order on the device
 (kiss_hip_bam_sort_host / _dev, include/kiss_hip_bam_sort.h), map(bam_sort=True) does so for a batch and
-write_bam(sort=True) for a whole file, whose header then says SO:coordinate.  All arithmetic runs in libkiss_hip.so; there is no CPU path."""
+write_bam(sort=True) for a whole file, whose header then says SO:coordinate.  A sorted file gets its BAI index from bam_index /
+bam_index_dev (kiss_hip_bai_host / _dev, include/kiss_hip_bai.h): write_bam(sort=True, bai=True) writes FILE.bai
+beside the file, built on the device from the sorted records and the offsets of their blocks.  All arithmetic runs in libkiss_hip.so; there is no CPU path."""
 import ctypes
+import os
 import struct
 
 import numpy as np
@@ -162,6 +165,69 @@ def bam_sort_dev(lib, ctx, device, d_bam, n, d_rec_index, records, n_ref, want_o
     return {"d_bam": d_out[:n] if n else d_out, "d_rec_index": d_index, "d_order": d_order[:records] if want_order else None, "rep": rep}
 
 
+def _refuse_unindexable(rc, rep, entry):
+    if rc == _lib.KISS_HIP_E_INVALID and rep.bad:
+        err = _lib.KissHipError(rc, entry, "%d record(s) that an index cannot hold or that are out of order, the first one record %d" % (rep.bad, rep.first_bad))
+        err.report = rep.as_dict()
+        raise err
+
+
+def bam_index(bam, rec_index, n_ref, block_bytes=65280, block_index=None, file_base=0, device=0, hooks=None):
+    """The BAI index of unframed BAM records in coordinate order (bam, rec_index: as bam_sort gives both), built on the device
+    through the host entry (kiss_hip_bai_host, include/kiss_hip_bai.h).  block_bytes: the payload bytes with which the records are
+    framed; block_index: the compressed offset of every block as bgzf_deflate(want_index=True) gives it (None: stored blocks);
+    file_base: the bytes of the file in front of the first record block, the framed header.  Returns dict(bai: the bytes of
+    FILE.bai, report).  The chunks are not merged beyond runs of one bin, so the bytes are a valid index and need not be those of
+    `samtools index`.  Records that are out of order or that BAI cannot hold (see the header) raise KissHipError; its report is the
+    exception's `report`."""
+    raw = np.frombuffer(bam, np.uint8) if isinstance(bam, (bytes, bytearray, memoryview)) else np.ascontiguousarray(bam, dtype=np.uint8).ravel()
+    ri = np.ascontiguousarray(rec_index, dtype=np.uint64).ravel()
+    if ri.size < 1:
+        raise ValueError("rec_index has records + 1 entries")
+    bb = _block_bytes(block_bytes)
+    bi = None
+    if block_index is not None:
+        bi = np.ascontiguousarray(block_index, dtype=np.uint64).ravel()
+        if bi.size != -(-raw.size // (bb or _lib.BGZF_BLOCK_DEFAULT)) + 1:
+            raise ValueError("block_index has blocks + 1 entries")
+    records = ri.size - 1
+    lib = _lib.load(hooks)
+    rep = _lib.BaiReport()
+
+    def call(bai, cap):
+        return lib.kiss_hip_bai_host(raw.ctypes.data if raw.size else None, raw.size, ri.ctypes.data, records, int(n_ref), bb,
+                                     None if bi is None else bi.ctypes.data, int(file_base), None if bai is None else bai.ctypes.data, cap,
+                                     ctypes.byref(rep), int(device))
+
+    rc, (bai, _) = sized(call, lambda m=0: (np.zeros(m, np.uint8) if m else None, m), rep, "bai_bytes")
+    _refuse_unindexable(rc, rep, "kiss_hip_bai_host")
+    _check(rc, "kiss_hip_bai_host")
+    return {"bai": bai[:int(rep.bai_bytes)].tobytes(), "report": rep.as_dict()}
+
+
+def bam_index_dev(lib, ctx, device, d_bam, n, d_rec_index, records, n_ref, block_bytes, d_block_index, file_base, stream=None):
+    """the device entry on torch tensors: the first n bytes of the uint8 tensor d_bam (sorted records), the int64 tensor d_rec_index
+    (records + 1), d_block_index (int64, blocks + 1, or None for stored blocks) -> (a uint8 tensor of exactly the bytes of FILE.bai,
+    the report); two calls, the first one sizes the bytes.  stream: None, the current stream of torch"""
+    import torch
+    dev = torch.device("cuda", device)
+    vp = ctypes.c_void_p
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    n, records, bb = int(n), int(records), _block_bytes(block_bytes)
+    rep = _lib.BaiReport()
+
+    def call(d_bai, cap):
+        return lib.kiss_hip_bai_dev(ctx._ctx, vp(d_bam.data_ptr()) if n else None, n, vp(d_rec_index.data_ptr()), records, int(n_ref), bb,
+                                    None if d_block_index is None else vp(d_block_index.data_ptr()), int(file_base),
+                                    None if d_bai is None else vp(d_bai.data_ptr()), cap, ctypes.byref(rep), vp(stream) if stream else None)
+
+    rc, (d_bai, _) = sized(call, lambda m=0: (torch.zeros(m, dtype=torch.uint8, device=dev) if m else None, m), rep, "bai_bytes")
+    _refuse_unindexable(rc, rep, "kiss_hip_bai_dev")
+    _check(rc, "kiss_hip_bai_dev", ctx._ctx)
+    return d_bai[:int(rep.bai_bytes)], rep
+
+
 def bam_sorted(lib, ctx, device, out, n_ref):
     """the tensors of bam_records_dev with the records sorted (map(bam_sort=True)): the same dict with d_bam and d_rec_index
     replaced, d_order and sort_rep added.  It asks bam_records_dev for the record index it may have left out."""
@@ -285,7 +351,7 @@ def bam_arrays(lib, ctx, device, out, block_bytes=65280, compress=False):
             "bam_read_rec": out["d_read_rec"].cpu().numpy().view(np.uint64), "bam_report": rep, **more}
 
 
-def write_bam(path, index, reads1, text, reads2=None, ref_names=None, bounds=None, version=None, compress=False, sort=False, **params):
+def write_bam(path, index, reads1, text, reads2=None, ref_names=None, bounds=None, version=None, compress=False, sort=False, bai=None, **params):
     """A whole BAM file of the read file(s) mapped by `index` (batches.map_file, which has the other arguments): the framed header,
     the blocks of every batch, the end-of-file block.  path: a file name, or a binary file object.  compress: the header and the
     batches in compressed blocks (bgzf_deflate, map_file(bam_compress=True)).  -> the batches, records and bytes written.
@@ -294,10 +360,23 @@ def write_bam(path, index, reads1, text, reads2=None, ref_names=None, bounds=Non
     framed once, and only then is anything written to path.  Device memory: about twice the file's uncompressed record bytes (the
     records and their sorted copy; while the batches are concatenated, or the blocks framed, one of the two is held a second time)
     plus 12 bytes per record (the index and the permutation), beside the sort's work arrays.  When that memory is not there
-    MemoryError names the bytes asked for and nothing has been written.  The result also carries sort_report."""
+    MemoryError names the bytes asked for and nothing has been written.  The result also carries sort_report.
+    bai (with sort=True): the BAI index of the file, built on the device from the sorted records, their index and the offsets of
+    the blocks (bam_index_dev; include/kiss_hip_bai.h) before anything is written.  True: written to str(path) + ".bai", which needs
+    path to be a file name; a file name; or a binary file object.  The result then carries bai_bytes and bai_report.  The index is
+    valid per the specification; its bytes need not be those of `samtools index`, which merges more chunks."""
     from .batches import map_file
     if ref_names is None or bounds is None:
         raise ValueError("a BAM file needs ref_names and bounds")
+    named = isinstance(path, (str, bytes)) or hasattr(path, "__fspath__")
+    if bai is False:
+        bai = None
+    if bai is not None and not sort:
+        raise ValueError("write_bam(bai=...) indexes a sorted file: it goes with sort=True")
+    if bai is True:
+        if not named:
+            raise ValueError("write_bam(bai=True) writes the index beside the file: path must be a file name (or give bai a name or a file object)")
+        bai = os.fsdecode(path) + ".bai"
     if version is None:  # (@PG VN: the library's version number, as kiss_hip_version() gives it)
         version = str(_lib.load(index._hooks).kiss_hip_version())
     frame = bgzf_deflate if compress else bgzf
@@ -306,10 +385,10 @@ def write_bam(path, index, reads1, text, reads2=None, ref_names=None, bounds=Non
         params["bam_compress"] = True
     done = {"batches": 0, "records": 0, "bytes": len(head)}
     if sort:
-        blocks, done["sort_report"] = _sorted_file(index, len(ref_names), compress,
-                                                   map_file(index, reads1, text, reads2, bam=True, _bam_unframed=True, ref_names=ref_names, bounds=bounds,
-                                                            **params), done)
-    f = open(path, "wb") if isinstance(path, (str, bytes)) or hasattr(path, "__fspath__") else path
+        blocks, done["sort_report"], index_bytes = _sorted_file(index, len(ref_names), compress,
+                                                                map_file(index, reads1, text, reads2, bam=True, _bam_unframed=True, ref_names=ref_names,
+                                                                         bounds=bounds, **params), done, len(head) if bai is not None else None)
+    f = open(path, "wb") if named else path
     try:
         f.write(head)
         if sort:
@@ -326,12 +405,19 @@ def write_bam(path, index, reads1, text, reads2=None, ref_names=None, bounds=Non
     finally:
         if f is not path:
             f.close()
+    if bai is not None:  # (behind the file it indexes)
+        if isinstance(bai, (str, bytes)) or hasattr(bai, "__fspath__"):
+            with open(bai, "wb") as g:
+                g.write(index_bytes)
+        else:
+            bai.write(index_bytes)
     return done
 
 
-def _sorted_file(index, n_ref, compress, batches, done):
+def _sorted_file(index, n_ref, compress, batches, done, file_base=None):
     """write_bam(sort=True): the records of all `batches` (results of map_file(_bam_unframed=True)) sorted and framed on the device
-    -> (the blocks as bytes, the sort's report); done: the counts so far"""
+    -> (the blocks as bytes, the sort's report, the bytes of the index or None); done: the counts so far; file_base: the bytes of the
+    framed header when the index is wanted (done then gains bai_bytes and bai_report)"""
     import torch
     dev = torch.device("cuda", index.device)
     parts, total, records = [], 0, 0
@@ -352,10 +438,16 @@ def _sorted_file(index, n_ref, compress, batches, done):
         ctx = index._context_to_sort(index._context(1 << 20), records)
         got = bam_sort_dev(lib, ctx, index.device, d_all, total, d_index, records, n_ref, want_order=False)
         del d_all, d_index
+        d_block_index = None
         if compress:
-            d_blocks, _, _ = bgzf_deflate_dev(lib, ctx, index.device, got["d_bam"], total)
+            d_blocks, d_block_index, _ = bgzf_deflate_dev(lib, ctx, index.device, got["d_bam"], total)
         else:
             d_blocks, _ = bgzf_dev(lib, ctx, index.device, got["d_bam"], total)
+        index_bytes = None
+        if file_base is not None:
+            d_bai, brep = bam_index_dev(lib, ctx, index.device, got["d_bam"], total, got["d_rec_index"], records, n_ref, 65280, d_block_index, file_base)
+            index_bytes = d_bai.cpu().numpy().tobytes()
+            done["bai_bytes"], done["bai_report"] = len(index_bytes), brep.as_dict()
     except torch.cuda.OutOfMemoryError:
         raise MemoryError("write_bam(sort=True): the device does not hold the %d bytes the sort asks for (%d record bytes twice, 12 bytes for "
                           "each of %d records)" % (asked, total, records)) from None
@@ -363,4 +455,4 @@ def _sorted_file(index, n_ref, compress, batches, done):
         if e.status == _lib.KISS_HIP_E_NOMEM:
             raise MemoryError("write_bam(sort=True): the device does not hold the %d bytes the sort asks for" % asked) from None
         raise
-    return d_blocks.cpu().numpy().tobytes(), dict(got["rep"].as_dict())
+    return d_blocks.cpu().numpy().tobytes(), dict(got["rep"].as_dict()), index_bytes

@@ -18,8 +18,7 @@
 //
 // ADDRESSING.  As fm_bam.hip: every address is a kernel-argument base pointer plus a 64-bit offset, and 64-bit values cross lanes
 // as two unsigned halves.  Every load and store is naturally aligned.  No LDS, no scratch.
-#include "fm_internal.hpp"
-#include "../../include/kiss_hip_bam_sort.h"
+#include "bam_record.hpp" // the word reads and the check of a record's head, shared with bai.hip
 
 namespace {
 
@@ -31,32 +30,6 @@ static_assert(BS_GRANULE / KISS_HIP_BAM_RECORD_MIN + 2 + 1 <= 64, "the boundarie
 // control block of a call (u64 words); BS_NFIRST holds the largest ~r of a bad record r (the words start at 0)
 enum { BS_BAD = 0, BS_NFIRST = 1, BS_UNPLACED = 2, BS_LONGEST = 3, BS_CTL_WORDS = 4 };
 
-__device__ __forceinline__ uint32_t bs_ld32(const uint32_t *p)
-{
-    return __hip_atomic_load(const_cast<uint32_t *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-}
-__device__ __forceinline__ uint64_t bs_ld64(const uint64_t *p)
-{
-    return __hip_atomic_load(const_cast<uint64_t *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-}
-// v of lane `from`, as two unsigned halves (fm_sam_line.hpp has the pitfall this avoids)
-__device__ __forceinline__ uint64_t bs_lane64(uint64_t v, int from)
-{
-    const uint32_t lo = (uint32_t)__shfl((unsigned int)(v & 0xFFFFFFFFull), from, 64);
-    const uint32_t hi = (uint32_t)__shfl((unsigned int)(v >> 32), from, 64);
-    return (uint64_t)hi << 32 | (uint64_t)lo;
-}
-// the four bytes at base + off (any byte offset, any base) from the aligned words that hold them: one word, or two funnelled
-__device__ __forceinline__ uint32_t bs_word_at(const uint8_t *__restrict__ base, uint64_t off)
-{
-    const uintptr_t a = (uintptr_t)(base + off);
-    const uint32_t *w = (const uint32_t *)(a & ~(uintptr_t)3);
-    const uint32_t sh = (uint32_t)(a & 3u) * 8u;
-    const uint32_t lo = bs_ld32(w);
-    const uint32_t hi = sh ? bs_ld32(w + 1) : 0u; // (an aligned word is never read unless one of its bytes is wanted)
-    return __funnelshift_r(lo, hi, sh);
-}
-
 // One lane per record: the checks, the key.  size[] is not kept: the sizes are read again in sorted order.
 __global__ __launch_bounds__(BS_THREADS) void k_bam_sort_key(const uint8_t *__restrict__ bam, uint64_t bam_bytes, const uint64_t *__restrict__ rec_index,
                                                            uint64_t records, uint32_t n_ref, int key_shift, uint64_t *__restrict__ key,
@@ -66,21 +39,14 @@ __global__ __launch_bounds__(BS_THREADS) void k_bam_sort_key(const uint8_t *__re
     bool bad = false, unplaced = false;
     uint64_t size = 0;
     if (r < records) {
-        const uint64_t a = bs_ld64(rec_index + r), b = bs_ld64(rec_index + r + 1);
-        if (r == 0 && a != 0) bad = true;
-        if (r == records - 1 && b != bam_bytes) bad = true;
-        if (b <= a || b > bam_bytes) bad = true;
-        else if (b - a < KISS_HIP_BAM_RECORD_MIN) bad = true;
+        const BsHead h = bs_head(bam, bam_bytes, rec_index, records, n_ref, r);
+        bad = h.bad;
         uint64_t k = ~0ull;
-        if (b > a && b <= bam_bytes && b - a >= KISS_HIP_BAM_RECORD_MIN) { // (only then are the twelve bytes there to be read)
-            size = b - a;
-            const int32_t block_size = (int32_t)bs_word_at(bam, a), ref = (int32_t)bs_word_at(bam, a + 4), p = (int32_t)bs_word_at(bam, a + 8);
-            if (block_size < 0 || (uint64_t)block_size != size - 4) bad = true;
-            if (ref < -1 || (int64_t)ref >= (int64_t)n_ref) bad = true;
-            if (p < -1) bad = true;
-            unplaced = ref == -1;
-            const uint64_t rk = unplaced ? (uint64_t)n_ref : (uint64_t)(uint32_t)ref;
-            k = (rk << 32 | (uint64_t)(uint32_t)(p + 1)) << key_shift;
+        if (h.read) {
+            size = h.size;
+            unplaced = h.ref == -1;
+            const uint64_t rk = unplaced ? (uint64_t)n_ref : (uint64_t)(uint32_t)h.ref;
+            k = (rk << 32 | (uint64_t)(uint32_t)(h.pos + 1)) << key_shift;
         }
         key[r] = k;
         pos[r] = (uint32_t)r;

@@ -12,6 +12,7 @@
 #include <variant>
 #include <vector>
 
+#include "cli_bam_index.hpp"
 #include "../../../include/kiss_hip.h"
 #include "../../../include/kiss_hip_insert.h"
 #include "../../../include/kiss_hip_pileup.h"
@@ -218,7 +219,16 @@ inline void usage_bam()
               << "                                 `samtools index` takes the file as it is and no `samtools sort` pass is needed.\n"
               << "                                 The unframed records of every batch are kept in host memory until the last one,\n"
               << "                                 then sorted once, framed and written: nothing reaches FILE before that.  Works\n"
-              << "                                 with --batch-reads, --bam-compress and --bam -.\n";
+              << "                                 with --batch-reads, --bam-compress and --bam -.\n"
+              << "  --bam-index                    with --bam FILE --bam-sort: FILE.bai, the BAI index of the sorted file, built on the\n"
+              << "                                 device (kiss_hip_bai_host) from the sorted records and the offsets of their blocks\n"
+              << "                                 and written behind FILE: region queries (`samtools view FILE chr:beg-end`, IGV)\n"
+              << "                                 need no `samtools index` pass.  One chunk per run of records that share a bin: a\n"
+              << "                                 valid index per the specification, not byte for byte the one `samtools index`\n"
+              << "                                 writes.  References or alignments beyond 2^29 are refused: the CSI index is not\n"
+              << "                                 built, and since the index is complete in memory before the first byte of FILE is\n"
+              << "                                 written, such a run ends with FILE empty.  Not with --bam -: an index of what goes\n"
+              << "                                 to stdout has no name.\n";
 }
 
 inline void check(int rc, const char *where)
@@ -313,6 +323,7 @@ struct Args {
     std::string bam;                 // fmindex_query ... --sam --bam FILE ('-': stdout)
     bool bam_compress = false;       // --bam-compress: the BGZF blocks compressed on the device
     bool bam_sort = false;           // --bam-sort: the records of the whole file in coordinate order, sorted on the device
+    bool bam_index = false;          // --bam-index: FILE.bai beside the sorted FILE, built on the device
 };
 
 inline bool given(const Args &a, const char *name) { return std::find(a.seen.begin(), a.seen.end(), name) != a.seen.end(); }
@@ -394,6 +405,7 @@ inline const Opt OPTIONS[] = {
     {"--bam", nullptr, KISS_AT(bam), true, {"--sam"}},
     {"--bam-compress", nullptr, KISS_AT(bam_compress), true, {"--bam"}},
     {"--bam-sort", nullptr, KISS_AT(bam_sort), true, {"--bam"}},
+    {"--bam-index", nullptr, KISS_AT(bam_index), true, {"--bam-sort"}},
 };
 #undef KISS_AT
 
@@ -470,7 +482,8 @@ inline Args parse(int argc, char **argv)
     a.pileup_params.proper_only = a.pileup_proper ? 1u : 0u;
     goes_with_through("--bam");
     if (given(a, "--bam") && a.bam.empty()) throw std::runtime_error("--bam needs a file name, or - for stdout (kiss --help-bam)");
-    goes_with_through("--bam-sort");
+    goes_with_through("--bam-index");
+    bam_index_options(a.bam_index, a.bam);
     if (given(a, "--mates")) { // the pair's MAPQ is on the scale of the reads'; the mates face each other
         a.both_strands = true;
         a.pair_params.mapq_coef = a.select_params.mapq_coef;

@@ -9,12 +9,14 @@
 #include "cli_pileup.hpp"
 #include "cli_bam.hpp"
 #include "cli_bam_sort.hpp"
+#include "cli_bam_index.hpp"
 #include "../../../include/kiss_hip_reads.h"
 #include "../../../include/kiss_hip_md.h"
 #include "../../../include/kiss_hip_insert.h"
 #include "../../../include/kiss_hip_sam.h"
 #include "../../../include/kiss_hip_bam.h"
 #include "../../../include/kiss_hip_bam_sort.h"
+#include "../../../include/kiss_hip_bai.h"
 #include "../../../include/kiss_hip_deflate.h"
 #include <iterator>
 
@@ -365,11 +367,14 @@ inline void sam_lines_device(StdoutWriter &w, const Args &a, const State &s, boo
 // --bam-sort: the header and the unframed records of every batch are kept (cli_bam_sort.hpp) until close(), which sorts the records
 // of the whole file on the device (kiss_hip_bam_sort_host) and only then frames and writes the header, with SO:coordinate, the
 // records and the end-of-file block.
+// --bam-index: the sort also gives the CSR of the sorted records and the framing of the records the offsets of its blocks
+// (cli_bam_index.hpp); kiss_hip_bai_host builds the index from both and the framed header's length, and FILE.bai is written
+// behind FILE.
 struct BamOut {
     std::string path;
     std::FILE *file = nullptr;
     int device = 0;
-    bool compress = false, sort = false;
+    bool compress = false, sort = false, index = false;
     uint64_t records = 0, bytes = 0;
     BamSortRecords kept;     // --bam-sort: the records so far
     std::string kept_header; // ... and the header, unframed
@@ -384,12 +389,13 @@ struct BamOut {
     bool on() const { return file != nullptr; }
     void open(const Args &a)
     {
-        path = a.bam, device = a.device, compress = a.bam_compress, sort = a.bam_sort;
+        path = a.bam, device = a.device, compress = a.bam_compress, sort = a.bam_sort, index = a.bam_index;
         file = path == "-" ? stdout : std::fopen(path.c_str(), "wb");
         if (!file) throw std::runtime_error("cannot open " + path);
     }
-    // data[0, n) as BGZF blocks; eof: the end-of-file block behind them
-    void framed(const uint8_t *data, uint64_t n, int eof)
+    // data[0, n) as BGZF blocks; eof: the end-of-file block behind them; keep: what the index needs of the framing, or null; hold:
+    // the blocks go behind what it holds, not to FILE (they count as written: `bytes` is where they will stand), or null
+    void framed(const uint8_t *data, uint64_t n, int eof, BamIndexFrame *keep = nullptr, std::vector<uint8_t> *hold = nullptr)
     {
         const uint64_t total = n + (uint64_t)KISS_HIP_BGZF_OVERHEAD * ((n + KISS_HIP_BGZF_BLOCK_DEFAULT - 1) / KISS_HIP_BGZF_BLOCK_DEFAULT) +
                                (eof ? KISS_HIP_BGZF_EOF_BYTES : 0u);
@@ -397,14 +403,18 @@ struct BamOut {
         uint64_t out_bytes = 0;
         if (compress) { // (total is the worst case: every block stored)
             kiss_hip_bgzf_deflate_report rep{};
-            check(kiss_hip_bgzf_deflate_host(n ? data : nullptr, n, 0, eof, out.data(), total, nullptr, 0, &rep, device), "kiss_hip_bgzf_deflate_host");
+            const uint64_t entries = keep ? keep->room(n, KISS_HIP_BGZF_BLOCK_DEFAULT) : 0;
+            check(kiss_hip_bgzf_deflate_host(n ? data : nullptr, n, 0, eof, out.data(), total, keep ? keep->block_index.data() : nullptr, entries, &rep, device),
+                  "kiss_hip_bgzf_deflate_host");
             out_bytes = rep.out_bytes;
+            if (keep) keep->check(out_bytes);
         } else {
             kiss_hip_bgzf_report rep{};
             check(kiss_hip_bgzf_host(n ? data : nullptr, n, 0, eof, out.data(), total, &rep, device), "kiss_hip_bgzf_host");
             out_bytes = rep.out_bytes;
         }
-        if (std::fwrite(out.data(), 1, out_bytes, file) != out_bytes) throw std::runtime_error("cannot write " + path);
+        if (hold) hold->insert(hold->end(), out.begin(), out.begin() + (std::ptrdiff_t)out_bytes);
+        else if (std::fwrite(out.data(), 1, out_bytes, file) != out_bytes) throw std::runtime_error("cannot write " + path);
         bytes += out_bytes;
     }
     void header(const RefRecords &ref, const char *version)
@@ -445,23 +455,63 @@ struct BamOut {
     {
         const uint64_t n = kept.bytes.size();
         std::vector<uint8_t> out(n + 1);
+        std::vector<uint64_t> sorted_index(index ? kept.records() + 1 : 0);
         kiss_hip_bam_sort_report rep{};
-        const int rc = kiss_hip_bam_sort_host(n ? kept.bytes.data() : nullptr, n, kept.index.data(), kept.records(), n_ref, out.data(), n, nullptr, nullptr,
-                                              &rep, device);
+        const int rc = kiss_hip_bam_sort_host(n ? kept.bytes.data() : nullptr, n, kept.index.data(), kept.records(), n_ref, out.data(), n,
+                                              index ? sorted_index.data() : nullptr, nullptr, &rep, device);
         if (rc == KISS_HIP_E_INVALID && rep.bad)
             throw std::runtime_error("fmindex_query --bam-sort: " + std::to_string(rep.bad) + " records cannot be sorted, the first is record " +
                                      std::to_string(rep.first_bad));
         check(rc, "kiss_hip_bam_sort_host");
         BamSortRecords().bytes.swap(kept.bytes); // (the unsorted copy is not needed any more)
-        framed(reinterpret_cast<const uint8_t *>(kept_header.data()), kept_header.size(), 0);
-        framed(out.data(), n, 0);
         std::fprintf(stderr, "[info] bam sort: records: %llu, unplaced: %llu, longest record: %llu\n", (ull)rep.records, (ull)rep.unplaced, (ull)rep.longest);
+        if (!index) {
+            framed(reinterpret_cast<const uint8_t *>(kept_header.data()), kept_header.size(), 0);
+            framed(out.data(), n, 0);
+            return;
+        }
+        // with the index nothing reaches FILE before FILE.bai is complete in memory: an index that refuses the records (an end
+        // beyond 2^29, say) ends the run with FILE empty, not cut off behind its last record block
+        std::vector<uint8_t> blocks;
+        framed(reinterpret_cast<const uint8_t *>(kept_header.data()), kept_header.size(), 0, nullptr, &blocks);
+        BamIndexFrame frame;
+        frame.file_base = bytes; // (nothing but the framed header stands in front of the record blocks)
+        framed(out.data(), n, 0, &frame, &blocks);
+        indexed(out.data(), n, sorted_index, frame);
+        if (std::fwrite(blocks.data(), 1, blocks.size(), file) != blocks.size()) throw std::runtime_error("cannot write " + path);
+    }
+    // --bam-index: the bytes of FILE.bai, kept until FILE is complete
+    std::vector<uint8_t> bai;
+    void indexed(const uint8_t *bam, uint64_t n, const std::vector<uint64_t> &rec_index, const BamIndexFrame &frame)
+    {
+        kiss_hip_bai_report rep{};
+        bai.assign(1, 0);
+        const int rc = sized_call(bai, rep.bai_bytes, [&](uint64_t capacity) {
+            return kiss_hip_bai_host(n ? bam : nullptr, n, rec_index.data(), rec_index.size() - 1, n_ref, KISS_HIP_BGZF_BLOCK_DEFAULT, frame.offsets(),
+                                     frame.file_base, bai.data(), capacity, &rep, device);
+        });
+        if (rc == KISS_HIP_E_INVALID && rep.bad)
+            throw std::runtime_error("fmindex_query --bam-index: " + std::to_string(rep.bad) + " records cannot be indexed (kiss --help-bam), the first is record " +
+                                     std::to_string(rep.first_bad));
+        check(rc, "kiss_hip_bai_host");
+        bai.resize(rep.bai_bytes);
+        std::fprintf(stderr, "[info] bam index: bytes: %llu, bins: %llu, chunks: %llu, windows: %llu, no_coor: %llu\n", (ull)rep.bai_bytes, (ull)rep.bins,
+                     (ull)rep.chunks, (ull)rep.windows, (ull)rep.no_coor);
+    }
+    void write_index()
+    {
+        const std::string to = bam_index_path(path);
+        std::FILE *f = std::fopen(to.c_str(), "wb");
+        if (!f) throw std::runtime_error("cannot open " + to);
+        const bool ok = std::fwrite(bai.data(), 1, bai.size(), f) == bai.size();
+        if (std::fclose(f) != 0 || !ok) throw std::runtime_error("cannot write " + to);
     }
     void close()
     {
         if (sort) sorted();
         framed(nullptr, 0, 1);
         if (std::fflush(file) != 0) throw std::runtime_error("cannot write " + path);
+        if (index) write_index(); // (FILE.bai after FILE)
         std::fprintf(stderr, "[info] bam: records: %llu, bytes: %llu\n", (ull)records, (ull)bytes);
     }
 };

@@ -32,6 +32,8 @@
 //       --bam-compress  with --bam: the BGZF blocks compressed on the device (DEFLATE)   kiss_hip_bgzf_deflate_host
 //       --bam-sort  with --bam: the records of the whole file in coordinate order, sorted once on the device behind the last
 //                 batch, SO:coordinate in the header   kiss_hip_bam_sort_host (cli_bam_sort.hpp; kiss --help-bam)
+//       --bam-index  with --bam FILE --bam-sort: FILE.bai, the BAI index of the sorted file, built on the device and written
+//                 behind FILE   kiss_hip_bai_host (cli_bam_index.hpp; kiss --help-bam)
 //   * -g / --generic with any of the three: the file is a text over the byte alphabet, byte for byte (no FASTA rule, no newline
 //     stripping, no % 4): kiss_hip_suffix_sort_u8 (-k, -s ignored), kiss_hip_lcp_u8, kiss_hip_fmi8_build_host -> <file>.fmi8
 //     (DESIGN.md 4.7), kiss_hip_fmi8_query_host.  One device, no lookup table, no mismatches.  The reference rejects -g.

@@ -192,6 +192,12 @@ enum FmSlot {
     // kiss_hip_bam_sort_dev (bam_sort.hip)
     FM_SLOT_BAM_SORT_CTL,
     FM_SLOT_BAM_SORT_INDEX, // per sorted slot: the bytes of its record, scanned
+    // kiss_hip_bai_dev (bai.hip)
+    FM_SLOT_BAI_CTL,
+    FM_SLOT_BAI_REC,   // per record: key, end, the run flags scanned, the first record of every chunk
+    FM_SLOT_BAI_REF,   // per reference: windows (scanned), unmapped records, first record, first chunk, where its ioffsets stand
+    FM_SLOT_BAI_WIN,   // per window: the lowest record that covers it
+    FM_SLOT_BAI_ITEMS, // per piece of the file (reference heads and tails, chunks): its bytes, scanned
     FM_SLOT_COUNT
 };
 
