@@ -308,6 +308,13 @@ class BaiReport(Report):
         (k, ctypes.c_float) for k in ("ms_total", "ms_record", "ms_window", "ms_sort", "ms_emit")]
 
 
+class MarkdupReport(Report):
+    """kiss_hip_markdup_report (include/kiss_hip_markdup.h)"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("records", "templates", "pairs", "fragments", "unmapped_templates", "ambiguous", "dup_pairs",
+                                                "dup_fragments", "dup_records", "bad", "first_bad")] + [
+        (k, ctypes.c_float) for k in ("ms_total", "ms_record", "ms_class", "ms_sort", "ms_mark")]
+
+
 class MdReport(Report):
     """kiss_hip_md_report (include/kiss_hip_md.h)"""
     _fields_ = [(k, ctypes.c_uint64) for k in ("items", "bad", "md_bytes", "mismatch_columns", "deleted_bases", "longest")] + [
@@ -558,6 +565,11 @@ def load(hooks=None):
         lib.kiss_hip_bai_host.argtypes = [vp, u64, vp, u64, u32, u32, vp, u64, vp, u64, ctypes.POINTER(BaiReport), ctypes.c_int]
         for name in BAI_EXPORTED_SYMBOLS:
             getattr(lib, name).restype = ctypes.c_int
+    if hasattr(lib, "kiss_hip_bam_markdup_dev"):  # (as the BAM calls)
+        lib.kiss_hip_bam_markdup_dev.argtypes = [vp, vp, u64, vp, u64, u32, u32, vp, ctypes.POINTER(MarkdupReport), vp]
+        lib.kiss_hip_bam_markdup_host.argtypes = [vp, u64, vp, u64, u32, u32, vp, ctypes.POINTER(MarkdupReport), ctypes.c_int]
+        for name in MARKDUP_EXPORTED_SYMBOLS:
+            getattr(lib, name).restype = ctypes.c_int
     lib.kiss_hip_fmi_insert_dev.argtypes = [vp, vp, vp, u64, vp, u64, ctypes.POINTER(InsertParams), vp, ctypes.POINTER(InsertReport), vp]
     lib.kiss_hip_fmi_insert_host.argtypes = [vp, vp, u64, vp, u64, ctypes.POINTER(InsertParams), vp, ctypes.POINTER(InsertReport),
                                              ctypes.c_int]
@@ -667,6 +679,9 @@ BAM_RECORD_MIN = 36
 # every symbol include/kiss_hip_bai.h declares (tests/test_bai_abi.py)
 BAI_EXPORTED_SYMBOLS = ["kiss_hip_bai_dev", "kiss_hip_bai_host"]
 BAI_PSEUDO_BIN, BAI_MAX_END = 37450, 1 << 29
+# every symbol include/kiss_hip_markdup.h declares (tests/test_markdup_abi.py)
+MARKDUP_EXPORTED_SYMBOLS = ["kiss_hip_bam_markdup_dev", "kiss_hip_bam_markdup_host"]
+MARKDUP_MIN_QUAL_DEFAULT, MARKDUP_MAX_N_REF, BAM_FLAG_DUP = 15, (1 << 30) - 1, 0x400
 # every symbol include/kiss_hip_insert.h declares (tests/test_fm_insert_abi.py)
 INSERT_EXPORTED_SYMBOLS = ["kiss_hip_fmi_insert_dev", "kiss_hip_fmi_insert_host"]
 INSERT_MAX = 65535

@@ -9,7 +9,10 @@ come out in read order unless they are sorted: bam_sort / bam_sort_dev put unfra
 (kiss_hip_bam_sort_host / _dev, include/kiss_hip_bam_sort.h), map(bam_sort=True) does so for a batch and
 write_bam(sort=True) for a whole file, whose header then says SO:coordinate.  A sorted file gets its BAI index from bam_index /
 bam_index_dev (kiss_hip_bai_host / _dev, include/kiss_hip_bai.h): write_bam(sort=True, bai=True) writes FILE.bai
-beside the file, built on the device from the sorted records and the offsets of their blocks.  All arithmetic runs in libkiss_hip.so; there is no CPU path."""
+beside the file, built on the device from the sorted records and the offsets of their blocks.  Duplicate templates get FLAG 0x400
+from bam_markdup / bam_markdup_dev (kiss_hip_bam_markdup_host / _dev, include/kiss_hip_markdup.h) while the records
+are still in the order they were written: map(bam_markdup=True) for a batch, write_bam(sort=True, markdup=True) for a whole file.
+All arithmetic runs in libkiss_hip.so; there is no CPU path."""
 import ctypes
 import os
 import struct
@@ -165,6 +168,83 @@ def bam_sort_dev(lib, ctx, device, d_bam, n, d_rec_index, records, n_ref, want_o
     return {"d_bam": d_out[:n] if n else d_out, "d_rec_index": d_index, "d_order": d_order[:records] if want_order else None, "rep": rep}
 
 
+def _refuse_unmarkable(rc, rep, entry):
+    if rc == _lib.KISS_HIP_E_INVALID and rep.bad:
+        err = _lib.KissHipError(rc, entry, "%d bad record(s), the first one record %d" % (rep.bad, rep.first_bad))
+        err.report = rep.as_dict()
+        raise err
+
+
+def _min_qual(min_qual):
+    q = int(min_qual)
+    if not 0 <= q < 1 << 32:
+        raise ValueError("min_qual is 0 .. 2^32 - 1 (above 255 no quality counts)")
+    return q
+
+
+def bam_markdup(bam, rec_index, n_ref, min_qual=15, device=0, hooks=None):
+    """The duplicate templates of unframed BAM records marked with FLAG 0x400 on the device, through the host entry
+    (kiss_hip_bam_markdup_host; include/kiss_hip_markdup.h has the definition).  bam, rec_index: as bam_records gives both, IN THAT
+    ORDER -- the records of a read together, the mates of a pair adjacent -- and not sorted.  min_qual: a quality counts towards a
+    template's score from here (15: Picard's SUM_OF_BASE_QUALITIES).  Returns dict(bam: the marked records as uint8, dup: one byte
+    per record, 1 for a record of a duplicate template, report).  Input that is not such records raises KissHipError; its report
+    is the exception's `report`."""
+    raw = np.array(np.frombuffer(bam, np.uint8) if isinstance(bam, (bytes, bytearray, memoryview)) else np.asarray(bam, dtype=np.uint8).ravel())
+    ri = np.ascontiguousarray(rec_index, dtype=np.uint64).ravel()
+    if ri.size < 1:
+        raise ValueError("rec_index has records + 1 entries")
+    records = ri.size - 1
+    dup = np.zeros(max(records, 1), np.uint8)
+    rep = _lib.MarkdupReport()
+    rc = _lib.load(hooks).kiss_hip_bam_markdup_host(raw.ctypes.data if raw.size else None, raw.size, ri.ctypes.data, records, int(n_ref),
+                                                   _min_qual(min_qual), dup.ctypes.data, ctypes.byref(rep), int(device))
+    _refuse_unmarkable(rc, rep, "kiss_hip_bam_markdup_host")
+    _check(rc, "kiss_hip_bam_markdup_host")
+    return {"bam": raw, "dup": dup[:records], "report": rep.as_dict()}
+
+
+def bam_markdup_dev(lib, ctx, device, d_bam, n, d_rec_index, records, n_ref, min_qual=15, want_dup=True, stream=None):
+    """the device entry on torch tensors: the first n bytes of the uint8 tensor d_bam are marked IN PLACE; d_rec_index: int64,
+    records + 1 -> dict of d_dup (records, uint8; None without want_dup) and rep.  ctx sorts the items in its work arrays, as
+    bam_sort_dev has it.  stream: None, the current stream of torch"""
+    import torch
+    dev = torch.device("cuda", device)
+    vp = ctypes.c_void_p
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    n, records = int(n), int(records)
+    d_dup = torch.zeros(max(records, 1), dtype=torch.uint8, device=dev) if want_dup else None
+    rep = _lib.MarkdupReport()
+    rc = lib.kiss_hip_bam_markdup_dev(ctx._ctx, vp(d_bam.data_ptr()) if n else None, n, vp(d_rec_index.data_ptr()), records, int(n_ref),
+                                      _min_qual(min_qual), vp(d_dup.data_ptr()) if want_dup else None, ctypes.byref(rep),
+                                      vp(stream) if stream else None)
+    _refuse_unmarkable(rc, rep, "kiss_hip_bam_markdup_dev")
+    _check(rc, "kiss_hip_bam_markdup_dev", ctx._ctx)
+    return {"d_dup": d_dup[:records] if want_dup else None, "rep": rep}
+
+
+def markdup_options(markdup):
+    """markdup=True | dict(min_qual=...) -> the keyword arguments of bam_markdup_dev; False or None -> None"""
+    if markdup is None or markdup is False:
+        return None
+    if markdup is True:
+        return {"min_qual": _lib.MARKDUP_MIN_QUAL_DEFAULT}
+    opts = dict(markdup)
+    unknown = sorted(set(opts) - {"min_qual"})
+    if unknown:
+        raise ValueError("markdup takes min_qual, not %s" % ", ".join(unknown))
+    return {"min_qual": _min_qual(opts.get("min_qual", _lib.MARKDUP_MIN_QUAL_DEFAULT))}
+
+
+def bam_marked(lib, ctx, device, out, n_ref, min_qual=15):
+    """the tensors of bam_records_dev with the duplicates of the batch marked in place (map(bam_markdup=True)): the same dict with
+    d_dup and markdup_rep added"""
+    if out["d_rec_index"] is None:
+        raise ValueError("bam_markdup needs the record index: bam_records_dev(want_rec_index=True)")
+    got = bam_markdup_dev(lib, ctx, device, out["d_bam"], int(out["rep"].bam_bytes), out["d_rec_index"], int(out["rep"].records), n_ref, min_qual)
+    return dict(out, d_dup=got["d_dup"], markdup_rep=got["rep"])
+
+
 def _refuse_unindexable(rc, rep, entry):
     if rc == _lib.KISS_HIP_E_INVALID and rep.bad:
         err = _lib.KissHipError(rc, entry, "%d record(s) that an index cannot hold or that are out of order, the first one record %d" % (rep.bad, rep.first_bad))
@@ -247,8 +327,11 @@ def bam_unframed(out):
     tensor of the records, bytes, the int64 tensor of the record index, records), on the device; bam_read_rec and bam_report as
     bam_arrays gives them"""
     rep = out["rep"]
+    more = {}
+    if out.get("markdup_rep") is not None:
+        more = {"bam_dup": out["d_dup"].cpu().numpy(), "bam_markdup_report": out["markdup_rep"].as_dict()}
     return {"bam_dev": (out["d_bam"], int(rep.bam_bytes), out["d_rec_index"], int(rep.records)),
-            "bam_read_rec": out["d_read_rec"].cpu().numpy().view(np.uint64), "bam_report": rep.as_dict()}
+            "bam_read_rec": out["d_read_rec"].cpu().numpy().view(np.uint64), "bam_report": rep.as_dict(), **more}
 
 
 def _block_bytes(block_bytes):
@@ -332,11 +415,15 @@ def bgzf_deflate_dev(lib, ctx, device, d_data, n, block_bytes=65280, eof=False, 
 
 def bam_arrays(lib, ctx, device, out, block_bytes=65280, compress=False):
     """the tensors of bam_records_dev framed on the device, as what map(bam=True) adds to its result; compress: the blocks are
-    compressed (bam_block_index and the counts of the coding beside them); after bam_sorted: bam_order and the sort's counts"""
+    compressed (bam_block_index and the counts of the coding beside them); after bam_sorted: bam_order and the sort's counts; after
+    bam_marked: bam_dup and bam_markdup_report"""
     total = int(out["rep"].bam_bytes)
     ri = out["d_rec_index"]
     rep = out["rep"].as_dict()
     more = {}
+    if out.get("markdup_rep") is not None:
+        more["bam_dup"] = out["d_dup"].cpu().numpy()
+        more["bam_markdup_report"] = out["markdup_rep"].as_dict()
     if out.get("sort_rep") is not None:
         rep.update(_sort_counts(out["sort_rep"]))
         more["bam_order"] = out["d_order"].cpu().numpy().view(np.uint32)
@@ -351,7 +438,8 @@ def bam_arrays(lib, ctx, device, out, block_bytes=65280, compress=False):
             "bam_read_rec": out["d_read_rec"].cpu().numpy().view(np.uint64), "bam_report": rep, **more}
 
 
-def write_bam(path, index, reads1, text, reads2=None, ref_names=None, bounds=None, version=None, compress=False, sort=False, bai=None, **params):
+def write_bam(path, index, reads1, text, reads2=None, ref_names=None, bounds=None, version=None, compress=False, sort=False, bai=None, markdup=None,
+              **params):
     """A whole BAM file of the read file(s) mapped by `index` (batches.map_file, which has the other arguments): the framed header,
     the blocks of every batch, the end-of-file block.  path: a file name, or a binary file object.  compress: the header and the
     batches in compressed blocks (bgzf_deflate, map_file(bam_compress=True)).  -> the batches, records and bytes written.
@@ -364,7 +452,12 @@ def write_bam(path, index, reads1, text, reads2=None, ref_names=None, bounds=Non
     bai (with sort=True): the BAI index of the file, built on the device from the sorted records, their index and the offsets of
     the blocks (bam_index_dev; include/kiss_hip_bai.h) before anything is written.  True: written to str(path) + ".bai", which needs
     path to be a file name; a file name; or a binary file object.  The result then carries bai_bytes and bai_report.  The index is
-    valid per the specification; its bytes need not be those of `samtools index`, which merges more chunks."""
+    valid per the specification; its bytes need not be those of `samtools index`, which merges more chunks.
+    markdup (with sort=True): True or dict(min_qual=15): the duplicate templates of the WHOLE file get FLAG 0x400 on the device
+    (bam_markdup_dev; include/kiss_hip_markdup.h has the definition), on the concatenated records directly before they are sorted:
+    the batches are cut at read or pair boundaries, so the records of a template are still together there.  Only bytes 18 - 19 of
+    records change: the blocks of a stored file and the index are what they are without it.  The result then carries
+    markdup_report.  Without sort=True it is a ValueError: the unsorted path does not hold the file on the device."""
     from .batches import map_file
     if ref_names is None or bounds is None:
         raise ValueError("a BAM file needs ref_names and bounds")
@@ -373,6 +466,10 @@ def write_bam(path, index, reads1, text, reads2=None, ref_names=None, bounds=Non
         bai = None
     if bai is not None and not sort:
         raise ValueError("write_bam(bai=...) indexes a sorted file: it goes with sort=True")
+    mark = markdup_options(markdup)
+    if mark is not None and not sort:
+        raise ValueError("write_bam(markdup=...) marks the duplicates of the whole file, which only the sorted path holds on the device: it goes "
+                         "with sort=True")
     if bai is True:
         if not named:
             raise ValueError("write_bam(bai=True) writes the index beside the file: path must be a file name (or give bai a name or a file object)")
@@ -387,7 +484,8 @@ def write_bam(path, index, reads1, text, reads2=None, ref_names=None, bounds=Non
     if sort:
         blocks, done["sort_report"], index_bytes = _sorted_file(index, len(ref_names), compress,
                                                                 map_file(index, reads1, text, reads2, bam=True, _bam_unframed=True, ref_names=ref_names,
-                                                                         bounds=bounds, **params), done, len(head) if bai is not None else None)
+                                                                         bounds=bounds, **params), done, len(head) if bai is not None else None,
+                                                                mark)
     f = open(path, "wb") if named else path
     try:
         f.write(head)
@@ -414,10 +512,11 @@ def write_bam(path, index, reads1, text, reads2=None, ref_names=None, bounds=Non
     return done
 
 
-def _sorted_file(index, n_ref, compress, batches, done, file_base=None):
+def _sorted_file(index, n_ref, compress, batches, done, file_base=None, mark=None):
     """write_bam(sort=True): the records of all `batches` (results of map_file(_bam_unframed=True)) sorted and framed on the device
     -> (the blocks as bytes, the sort's report, the bytes of the index or None); done: the counts so far; file_base: the bytes of the
-    framed header when the index is wanted (done then gains bai_bytes and bai_report)"""
+    framed header when the index is wanted (done then gains bai_bytes and bai_report); mark: the keyword arguments of
+    bam_markdup_dev when the duplicates are to be marked (done then gains markdup_report)"""
     import torch
     dev = torch.device("cuda", index.device)
     parts, total, records = [], 0, 0
@@ -436,6 +535,8 @@ def _sorted_file(index, n_ref, compress, batches, done, file_base=None):
         d_index = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev)] + [p[1] for p in parts])
         del parts
         ctx = index._context_to_sort(index._context(1 << 20), records)
+        if mark is not None:  # (in place, while the records are in the order they were written)
+            done["markdup_report"] = bam_markdup_dev(lib, ctx, index.device, d_all, total, d_index, records, n_ref, want_dup=False, **mark)["rep"].as_dict()
         got = bam_sort_dev(lib, ctx, index.device, d_all, total, d_index, records, n_ref, want_order=False)
         del d_all, d_index
         d_block_index = None

@@ -276,6 +276,8 @@ def map_file(index, reads1, text, reads2=None, batch_reads=100000, chunk_bytes=6
     bam_compress=True (with bam=True): the blocks are compressed on the device, as map(bam_compress=True) does it.
     bam_sort=True is a ValueError: batches sorted one by one do not concatenate into a sorted file.  A sorted file is written by
     kiss_amd.bam_writer.write_bam(sort=True), which keeps the records of every batch on the device and sorts them once.
+    bam_markdup=True is a ValueError for the same reason: duplicates are a property of the file, and
+    kiss_amd.bam_writer.write_bam(sort=True, markdup=True) marks them once, on all its records.
     pileup=True (or a dict, or an (8, W) int32 device tensor to add to, as map(pileup=...) takes them): ONE tensor of counts,
     allocated once, to which every batch adds (kiss_hip_fmi_pileup_dev with accumulate): its size depends on the text and not on
     the file.  Every batch's result carries that tensor as pileup -- the sums up to and including the batch -- and
@@ -286,6 +288,9 @@ def map_file(index, reads1, text, reads2=None, batch_reads=100000, chunk_bytes=6
     if params.pop("bam_sort", False):
         raise ValueError("map_file(bam_sort=True): batches sorted one by one are not a sorted file; kiss_amd.bam_writer.write_bam(sort=True) "
                          "sorts the whole file")
+    if params.pop("bam_markdup", False):
+        raise ValueError("map_file(bam_markdup=True): duplicates marked batch by batch are not the duplicates of the file; "
+                         "kiss_amd.bam_writer.write_bam(sort=True, markdup=True) marks the whole file")
     packed = {"bam_compress": True} if params.pop("bam_compress", False) else {}
     if packed and not bam:
         raise ValueError("bam_compress belongs to bam=True")

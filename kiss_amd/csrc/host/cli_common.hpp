@@ -228,7 +228,22 @@ inline void usage_bam()
               << "                                 writes.  References or alignments beyond 2^29 are refused: the CSI index is not\n"
               << "                                 built, and since the index is complete in memory before the first byte of FILE is\n"
               << "                                 written, such a run ends with FILE empty.  Not with --bam -: an index of what goes\n"
-              << "                                 to stdout has no name.\n";
+              << "                                 to stdout has no name.\n"
+              << "  --bam-markdup                  with --bam FILE --bam-sort: the duplicate templates of the WHOLE file get FLAG 0x400\n"
+              << "                                 on the device (kiss_hip_bam_markdup_host), directly before the sort, while the\n"
+              << "                                 records of a read are still together: no `samtools fixmate` / `samtools markdup`\n"
+              << "                                 or Picard pass is needed.  A template is the records of one read name; its ends\n"
+              << "                                 are the unclipped 5' ends of its mapped primary records with their strands.  Of\n"
+              << "                                 the pairs with the same two ends the one with the highest sum of base qualities\n"
+              << "                                 stays unmarked (ties: the first in the file); a single mapped read is marked when\n"
+              << "                                 a pair has its end, else all but the best of an end.  Every record of a marked\n"
+              << "                                 template is marked, secondary, supplementary and an unmapped mate included.  Only\n"
+              << "                                 the FLAG of records changes, no size and no place: stdout is what it is without\n"
+              << "                                 the option, and so is FILE.bai (with --bam-compress as long as the compressed\n"
+              << "                                 blocks keep their sizes: a block that packs differently moves those behind it).\n"
+              << "                                 One line of counts goes to stderr.\n"
+              << "  --bam-markdup-min-qual Q       with --bam-markdup: a base quality counts towards the sum from Q (15, Picard's\n"
+              << "                                 SUM_OF_BASE_QUALITIES; 0: every quality).\n";
 }
 
 inline void check(int rc, const char *where)
@@ -324,6 +339,8 @@ struct Args {
     bool bam_compress = false;       // --bam-compress: the BGZF blocks compressed on the device
     bool bam_sort = false;           // --bam-sort: the records of the whole file in coordinate order, sorted on the device
     bool bam_index = false;          // --bam-index: FILE.bai beside the sorted FILE, built on the device
+    bool bam_markdup = false;        // --bam-markdup: FLAG 0x400 on the duplicate templates of the whole file, marked on the device
+    uint32_t bam_markdup_min_qual = 15; // --bam-markdup-min-qual Q
 };
 
 inline bool given(const Args &a, const char *name) { return std::find(a.seen.begin(), a.seen.end(), name) != a.seen.end(); }
@@ -406,6 +423,8 @@ inline const Opt OPTIONS[] = {
     {"--bam-compress", nullptr, KISS_AT(bam_compress), true, {"--bam"}},
     {"--bam-sort", nullptr, KISS_AT(bam_sort), true, {"--bam"}},
     {"--bam-index", nullptr, KISS_AT(bam_index), true, {"--bam-sort"}},
+    {"--bam-markdup", nullptr, KISS_AT(bam_markdup), true, {"--bam-sort"}},
+    {"--bam-markdup-min-qual", nullptr, KISS_AT(bam_markdup_min_qual), true, {"--bam-markdup"}},
 };
 #undef KISS_AT
 
@@ -484,6 +503,7 @@ inline Args parse(int argc, char **argv)
     if (given(a, "--bam") && a.bam.empty()) throw std::runtime_error("--bam needs a file name, or - for stdout (kiss --help-bam)");
     goes_with_through("--bam-index");
     bam_index_options(a.bam_index, a.bam);
+    goes_with_through("--bam-markdup-min-qual");
     if (given(a, "--mates")) { // the pair's MAPQ is on the scale of the reads'; the mates face each other
         a.both_strands = true;
         a.pair_params.mapq_coef = a.select_params.mapq_coef;

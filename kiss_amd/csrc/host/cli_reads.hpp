@@ -16,6 +16,7 @@
 #include "../../../include/kiss_hip_sam.h"
 #include "../../../include/kiss_hip_bam.h"
 #include "../../../include/kiss_hip_bam_sort.h"
+#include "../../../include/kiss_hip_markdup.h"
 #include "../../../include/kiss_hip_bai.h"
 #include "../../../include/kiss_hip_deflate.h"
 #include <iterator>
@@ -370,11 +371,14 @@ inline void sam_lines_device(StdoutWriter &w, const Args &a, const State &s, boo
 // --bam-index: the sort also gives the CSR of the sorted records and the framing of the records the offsets of its blocks
 // (cli_bam_index.hpp); kiss_hip_bai_host builds the index from both and the framed header's length, and FILE.bai is written
 // behind FILE.
+// --bam-markdup: directly before the sort, kiss_hip_bam_markdup_host sets FLAG 0x400 in the kept records of the duplicate
+// templates, in place: the records of a read are still together there.
 struct BamOut {
     std::string path;
     std::FILE *file = nullptr;
     int device = 0;
-    bool compress = false, sort = false, index = false;
+    bool compress = false, sort = false, index = false, markdup = false;
+    uint32_t markdup_min_qual = KISS_HIP_MARKDUP_MIN_QUAL_DEFAULT;
     uint64_t records = 0, bytes = 0;
     BamSortRecords kept;     // --bam-sort: the records so far
     std::string kept_header; // ... and the header, unframed
@@ -390,6 +394,7 @@ struct BamOut {
     void open(const Args &a)
     {
         path = a.bam, device = a.device, compress = a.bam_compress, sort = a.bam_sort, index = a.bam_index;
+        markdup = a.bam_markdup, markdup_min_qual = a.bam_markdup_min_qual;
         file = path == "-" ? stdout : std::fopen(path.c_str(), "wb");
         if (!file) throw std::runtime_error("cannot open " + path);
     }
@@ -450,9 +455,24 @@ struct BamOut {
         else framed(bam.data(), rep.bam_bytes, 0);
         records += rep.records;
     }
+    // --bam-markdup: the kept records of the whole file, in the order they were written, marked in place
+    void marked()
+    {
+        const uint64_t n = kept.bytes.size();
+        kiss_hip_markdup_report rep{};
+        const int rc = kiss_hip_bam_markdup_host(n ? kept.bytes.data() : nullptr, n, kept.index.data(), kept.records(), n_ref, markdup_min_qual, nullptr,
+                                                 &rep, device);
+        if (rc == KISS_HIP_E_INVALID && rep.bad)
+            throw std::runtime_error("fmindex_query --bam-markdup: " + std::to_string(rep.bad) + " records cannot be read, the first is record " +
+                                     std::to_string(rep.first_bad));
+        check(rc, "kiss_hip_bam_markdup_host");
+        std::fprintf(stderr, "[info] bam markdup: templates: %llu, duplicate pairs: %llu, duplicate fragments: %llu, duplicate records: %llu\n",
+                     (ull)rep.templates, (ull)rep.dup_pairs, (ull)rep.dup_fragments, (ull)rep.dup_records);
+    }
     // --bam-sort: the whole file, once
     void sorted()
     {
+        if (markdup) marked();
         const uint64_t n = kept.bytes.size();
         std::vector<uint8_t> out(n + 1);
         std::vector<uint64_t> sorted_index(index ? kept.records() + 1 : 0);

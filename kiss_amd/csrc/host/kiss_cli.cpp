@@ -34,6 +34,8 @@
 //                 batch, SO:coordinate in the header   kiss_hip_bam_sort_host (cli_bam_sort.hpp; kiss --help-bam)
 //       --bam-index  with --bam FILE --bam-sort: FILE.bai, the BAI index of the sorted file, built on the device and written
 //                 behind FILE   kiss_hip_bai_host (cli_bam_index.hpp; kiss --help-bam)
+//       --bam-markdup  with --bam FILE --bam-sort: FLAG 0x400 on the duplicate templates of the whole file, marked on the device
+//                 directly before the sort   kiss_hip_bam_markdup_host (kiss --help-bam); --bam-markdup-min-qual Q
 //   * -g / --generic with any of the three: the file is a text over the byte alphabet, byte for byte (no FASTA rule, no newline
 //     stripping, no % 4): kiss_hip_suffix_sort_u8 (-k, -s ignored), kiss_hip_lcp_u8, kiss_hip_fmi8_build_host -> <file>.fmi8
 //     (DESIGN.md 4.7), kiss_hip_fmi8_query_host.  One device, no lookup table, no mismatches.  The reference rejects -g.

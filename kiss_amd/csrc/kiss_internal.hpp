@@ -198,6 +198,10 @@ enum FmSlot {
     FM_SLOT_BAI_REF,   // per reference: windows (scanned), unmapped records, first record, first chunk, where its ioffsets stand
     FM_SLOT_BAI_WIN,   // per window: the lowest record that covers it
     FM_SLOT_BAI_ITEMS, // per piece of the file (reference heads and tails, chunks): its bytes, scanned
+    // kiss_hip_bam_markdup_dev (bam_markdup.hip)
+    FM_SLOT_MARKDUP_CTL,
+    FM_SLOT_MARKDUP_REC,   // per record: end, score, bits, template; per template (at its first record): class, ends, score, verdict
+    FM_SLOT_MARKDUP_ITEMS, // per end item and per pair item: its key words and its template
     FM_SLOT_COUNT
 };
 

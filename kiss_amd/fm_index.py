@@ -689,6 +689,11 @@ class FMIndex:
         bam_read_rec keeps counting the records as they were written, so record bam_read_rec[q] of read q is in the slot s with
         bam_order[s] == bam_read_rec[q] --, and bam_report gains unplaced and the times of the sort.  (A FILE is sorted as a whole
         by kiss_amd.bam_writer.write_bam(sort=True): sorted batches do not concatenate into a sorted file.)
+        bam_markdup (False; it needs bam): True or dict(min_qual=15): the duplicate templates of the batch get FLAG 0x400 on the
+        device between the record call and the sort or the framing (kiss_hip_bam_markdup_dev, include/kiss_hip_markdup.h, which has
+        the definition); the new bam_dup (records, u8) says which records, numbered as they were written (as bam_read_rec counts
+        them, with or without bam_sort), belong to one, and bam_markdup_report holds the counts.  (The duplicates of a FILE are
+        marked by kiss_amd.bam_writer.write_bam(sort=True, markdup=True): they are a property of the file, not of a batch.)
         pileup (None; it needs want_cigar): True, a dict of lo, hi, counts and the pileup parameters min_mapq (0), skip_flags (2:
         secondary hits) and proper_only (0), or an (8, W) int32 device tensor to add to (the dict's counts: such a tensor, or an
         (8, W) u32 array): also pileup -- the eight planes of kiss_amd.fm_pileup.PLANES over the text positions [lo, hi), default
@@ -777,6 +782,12 @@ class FMIndex:
         bam_compress = given.pop("bam_compress", False)
         bam_sort = given.pop("bam_sort", False)
         bam_unframed = given.pop("_bam_unframed", False)  # (write_bam(sort=True): the records stay on the device, unframed)
+        bam_markdup = given.pop("bam_markdup", False)
+        if bam_markdup and not bam:
+            raise ValueError("bam_markdup belongs to bam=True")
+        if bam_markdup:
+            from .bam_writer import markdup_options
+            bam_markdup = markdup_options(bam_markdup)
         if bam_compress and not bam:
             raise ValueError("bam_compress belongs to bam=True")
         if (bam_sort or bam_unframed) and not bam:
@@ -797,7 +808,7 @@ class FMIndex:
         if R > 1 and b is None:
             raise ValueError("ref_names with more than one name needs bounds")
         return {"names": names, "qual": qual, "ref_names": ref_names, "bounds": b, "md": None, "sam": bool(sam), "bam": bool(bam),
-                "bam_compress": bool(bam_compress), "bam_sort": bool(bam_sort), "bam_unframed": bool(bam_unframed)}
+                "bam_compress": bool(bam_compress), "bam_sort": bool(bam_sort), "bam_unframed": bool(bam_unframed), "bam_markdup": bam_markdup or None}
 
     def _sam_lines(self, t, ctx, d_alns, C, d_cigar, d_oidx, sel, so, d_pairs=None, d_source=None, first_alns=0):
         """map(sam=True): the lines of the hits of a select call (and the pairs of a pair call), from the buffers that are on the
@@ -857,8 +868,11 @@ class FMIndex:
         if so["sam"]:
             res.update(sam_arrays(sam_lines_dev(t.lib, ctx, self.device, Q, C, R, first_alns, **arrays)))
         if so["bam"]:  # (the records, then their blocks: both from the buffers on the device)
-            from .bam_writer import bam_arrays, bam_records_dev, bam_sorted, bam_unframed
+            from .bam_writer import bam_arrays, bam_marked, bam_records_dev, bam_sorted, bam_unframed
             out = bam_records_dev(t.lib, ctx, self.device, Q, C, R, first_alns, **arrays)
+            if so["bam_markdup"]:  # (in place, in the order the records were written: before any sort)
+                ctx = self._context_to_sort(ctx, int(out["rep"].records))
+                out = bam_marked(t.lib, ctx, self.device, out, R, **so["bam_markdup"])
             if so["bam_unframed"]:
                 res.update(bam_unframed(out))
             else:
